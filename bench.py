@@ -27,6 +27,14 @@ stream around the K timed launches (average launch duration = elapsed / K); a se
 its own pair of events, gives `roofline.median_ms / min_ms / max_ms` (BASELINE.md section 3 asks for the median; a pair
 per launch adds event handling to every launch, so that pass is not the headline).  `cpu_baseline` is the CPU oracle timed
 on this box's host cores (N = 1 only), one frame per call through its single-frame entry.
+
+`--dump-outputs DIR` writes what the last timed step computed, straight after the K timed steps and before any other launch
+reuses the buffers, as DIR/<name>.npy (float32, or float64 where an integer can pass 2**24): every per-launch output of the
+mode (frame records field by field, RTP info, lengths, PCM / codes / payload / file bytes) and the launch aggregate.  An output
+larger than its budget is sampled at fixed positions drawn from a fixed seed, stored next to it as <name>_index.npy, so two
+builds run with the same arguments can be compared array for array.  Channel state that accumulates over every launch of
+the run, pre-warm included (the hold's counters, the silence probe), is left out; the hold's peak / level max / min are kept.
+Rank 0 writes its own shard.
 """
 from __future__ import annotations
 
@@ -51,6 +59,10 @@ BYTES_PER_SAMPLE = {"meter": (160 + 1 + 16) / 160.0, "store": (160 + 1 + 16 + 32
                     "wav": (160 + 320) / 160.0,                  # 8(f) rank 2: payload in, [b, 0x00] file images out (+ 44 B per channel)
                     "encode": (320 + 1 + 160) / 160.0}           # a2: int16 in, code out    # 8(f) rank 1: 180 B packet in, dense payload + len + info out
 HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured float4 copy)
+DUMP_SEED = 0x5EED         # --dump-outputs: the sampled positions are drawn from this seed
+DUMP_RECORDS = 1 << 19     # records (frame stats, RTP info, lengths) kept per output
+DUMP_BULK = 1 << 21        # elements kept per bulk output (PCM, codes, payload bytes, file images)
+DUMP_MAX_BYTES = 64 << 20
 
 
 def parse():
@@ -83,6 +95,9 @@ def parse():
     ap.add_argument("--placement", choices=["both", "abi", "plain"], default="both",
                     help="both: headline on igdsp_io_alloc buffers + the plain-allocation figures (cold and pre-warmed) on igdsp_dev_alloc buffers; "
                          "abi / plain: only that one (plain = the headline itself runs on plain buffers)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (float32 / float64, a fixed seeded "
+                         "sample of the larger ones, at most 64 MB in all)")
     ap.add_argument("--force-collective", action="store_true",
                     help="N = 1 only: bring up a 1-rank nccl (= RCCL) group and run the N > 1 step sequence (kernel -> event -> "
                          "side-stream all_reduce(int64[112]) -> next launch); reports the per-launch cost against the plain step")
@@ -120,6 +135,71 @@ def cpu_baseline(seconds: float):
         "reference_loop_byte_mean_value": round(samples / tb / 1e6, 2),
         "cpu_model": _cpu_model(), "compiler_flags": "gcc -O2 -funsigned-char (oracle/Makefile; -O2 as the reference's .pro:88)",
     }
+
+
+def _dump_index(total: int, k: int):
+    """Positions of an output that --dump-outputs keeps: all of them up to k, else k sorted ones drawn from DUMP_SEED."""
+    import numpy as np
+
+    if total <= k:
+        return np.arange(total, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(total, k, replace=False))
+
+
+def capture_outputs(t: dict, agg=None) -> dict:
+    """--dump-outputs: the outputs in a step's buffers `t` (the names of main()'s buffer spec, inputs skipped) and its launch
+    aggregate `agg` (int64 words, or None), as float32 (integers below 2**24) / float64 host arrays."""
+    import numpy as np
+    import torch
+
+    from igate4xsoftphonedsp_amd import capi
+
+    res = {}
+
+    def records(prefix, name, dtype, fields):
+        rec = t[name].view(-1, dtype.itemsize // 8)           # int64 words, one row per record
+        idx = _dump_index(rec.shape[0], DUMP_RECORDS)
+        sel = rec.index_select(0, torch.from_numpy(idx).to(rec.device)).cpu().numpy().view(dtype).reshape(-1)
+        for f in fields:
+            wide = sel[f].dtype.kind in "iu" and sel[f].dtype.itemsize >= 4
+            res[f"{prefix}_{f}"] = sel[f].astype(np.float64 if wide else np.float32)
+        res[f"{prefix}_index"] = idx.astype(np.float64)
+
+    def bulk(prefix, flat, k=DUMP_BULK):
+        idx = _dump_index(flat.numel(), k)
+        res[prefix] = flat.index_select(0, torch.from_numpy(idx).to(flat.device)).cpu().numpy().astype(np.float32)
+        res[f"{prefix}_index"] = idx.astype(np.float64)
+
+    if "st" in t:
+        records("stats", "st", capi.FRAME_STATS, capi.FRAME_STATS.names)
+    if "info" in t:
+        records("info", "info", capi.RTP_INFO, capi.RTP_INFO.names)
+    if "hold" in t:                              # the fields that every launch over the same input leaves the same
+        records("hold", "hold", capi.CHAN_HOLD, ("peak_hold", "level_max", "level_min"))
+    if "len" in t:                               # one per frame: the records' positions
+        bulk("len", t["len"].reshape(-1), DUMP_RECORDS)
+    for name, prefix in (("pcm", "pcm"), ("out", "codes"), ("dense", "payload"), ("files", "wav")):
+        if name in t:
+            bulk(prefix, t[name].reshape(-1))
+    if agg is not None:
+        a = agg.cpu().numpy().view(capi.AGGREGATE)[0]
+        # sumsq, samples, frames, n_silent, n_clipped, byte_mean_sum, peak_slot[8]; sumsq again as two exact 32-bit halves
+        res["aggregate"] = np.array([a[f] for f in capi.AGGREGATE.names[:6]] + list(a["peak_slot"]), dtype=np.float64)
+        res["aggregate_sumsq_words"] = np.array([a["sumsq"] >> np.uint64(32), a["sumsq"] & np.uint64(0xFFFFFFFF)], dtype=np.float64)
+    return res
+
+
+def write_outputs(outdir: str, arrays: dict) -> dict:
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte budget")
+    import numpy as np
+
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    return {"dir": outdir, "bytes": total, "arrays": {name: list(a.shape) for name, a in arrays.items()}}
 
 
 def _cpu_model() -> str:
@@ -424,6 +504,14 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    # the median pass and the calibration kernels below reuse OUT's buffers: the outputs are taken here
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        outs = {name: OUT.t[name] for name, _, _, role in spec if role != capi.IO_INPUT and name not in ("probe", "work")}
+        if "files" in outs:                      # the file images: the bytes before and after them are never written
+            outs["files"] = outs["files"][args.wav_offset:args.wav_offset + C_ * wav_stride]
+        uses_agg = MODE in ("rtp", "packets", "window") or (MODE in ("meter", "store") and not args.no_agg)
+        dumped = write_outputs(args.dump_outputs, capture_outputs(outs, agg_ring[n_steps_total - 1] if uses_agg else None))
 
     # average launch duration: the K launches run back to back on `hs`, bracketed by ONE pair of HIP events on that
     # stream (bracketing every launch with its own pair adds ~10 us of event handling to each 0.25 ms launch)
@@ -557,6 +645,8 @@ def main():
     out["placement_setup_ms"] = None if not OUT.report else OUT.report.get("setup_ms")     # start-up cost of the placed set (not in any step)
     if coll_info:
         out["collective"] = coll_info
+    if dumped:
+        out["dump_outputs"] = dumped
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
     elif rank == 0:

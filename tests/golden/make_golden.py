@@ -11,6 +11,10 @@ Sources of truth (none of them is our own oracle):
     oracle/Makefile into oracle/_ref/ (SURVEY.md 8c): a 4 ch x 50 frame recording.
   * SURVEY.md 8(c) known answers (SHA-256 of the decode tables, spot values).
 
+The parts that need the reference objects can be regenerated alone:
+
+    python tests/golden/make_golden.py wavwriter_uniform audiometer_fifo
+
 Inputs fed to the reference recorder come from the oracle's D-speech generator;
 they are stored in the fixture too, so the fixture is self-contained data.
 """
@@ -107,10 +111,74 @@ def main():
     sm = {"splitmix64(0)": str(orc.lib().orc_splitmix64(0)), "first16_uniform_seed": orc.gen_uniform(16).tolist()}
     with open(os.path.join(HERE, "prng.json"), "w") as fh:
         json.dump(sm, fh, indent=1, sort_keys=True)
+    wavwriter_uniform()
+    audiometer_fifo()
+    listing()
+
+
+def wavwriter_uniform():
+    """The REAL WavWriter over 7 frames of D-uniform (seed 99): pins the recorder restatement on input other than config #1."""
+    if not orc.ref_wavwriter_available():
+        raise SystemExit("oracle/_ref/libref_wavwriter.so missing: run `make -C oracle` with the reference sources present")
+    payload = orc.gen_uniform(7 * 160, seed=99).reshape(7, 160)
+    with tempfile.TemporaryDirectory() as td:
+        wav = np.frombuffer(orc.ref_wav_record(td, payload), dtype=np.uint8)
+    np.savez_compressed(os.path.join(HERE, "wavwriter_uniform_7f.npz"), payload=payload, wav=wav)
+
+
+def audiometer_fifo():
+    """The host mirror's meter-FIFO records for a set of levels, and what the REAL AudioMeter::getAudioLevel() emitted when
+    it consumed exactly those bytes (written into the FIFO it creates itself, one 32-byte record per read)."""
+    import ctypes as C
+    import threading
+    import time
+
+    from tests import host_util as hu
+
+    if not orc.ref_audiometer_available():
+        raise SystemExit("oracle/_ref/libref_audiometer.so missing: run `make -C oracle` (needs Qt5 moc)")
+    levels = [0, 150, 300, 10138, 29999, 30000, 32124, 32256]
+    records = hu.capture_meter_fifo(hu.load(), f"igdspg{os.getpid()}".encode(), levels)
+    assert len(records) == 32 * len(levels)
+    R = C.CDLL(orc._REF_METER_PATH)
+    R.ref_audiometer_consume.restype = C.c_int
+    card = f"igdspr{os.getpid()}"
+    path = "/tmp/capturefifo" + card
+    out = (C.c_int * 64)()
+    res = {}
+    t = threading.Thread(target=lambda: res.setdefault("n", R.ref_audiometer_consume(card.encode(), 64, out)))
+    t.start()
+    fd = -1
+    for _ in range(5000):                     # the class mkfifo()s and opens the FIFO itself
+        try:
+            fd = os.open(path, os.O_WRONLY | os.O_NONBLOCK)
+            break
+        except OSError:
+            time.sleep(0.001)
+    if fd < 0:
+        raise SystemExit("the reference AudioMeter never opened its FIFO")
+    os.set_blocking(fd, True)
+    for i in range(0, len(records), 32):
+        os.write(fd, records[i:i + 32])
+        time.sleep(0.002)
+    os.close(fd)
+    t.join()
+    os.unlink(path)
+    with open(os.path.join(HERE, "audiometer_fifo.json"), "w") as fh:
+        json.dump({"source": "igdsp_meter_fifo_write records, consumed by the REAL AudioMeter::getAudioLevel() (audiometer.cpp)",
+                   "levels": levels, "records_hex": records.hex(), "percent": list(out[:res["n"]])}, fh, indent=1)
+
+
+def listing():
     print("golden fixtures written to", HERE)
     for fn in sorted(os.listdir(HERE)):
         print("  ", fn, os.path.getsize(os.path.join(HERE, fn)))
 
 
 if __name__ == "__main__":
-    main()
+    if len(sys.argv) > 1:
+        for part in sys.argv[1:]:
+            {"wavwriter_uniform": wavwriter_uniform, "audiometer_fifo": audiometer_fifo}[part]()
+        listing()
+    else:
+        main()

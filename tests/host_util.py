@@ -77,3 +77,31 @@ def rtp_packet(pt: int, seq: int, payload: bytes, radio: bool, ed137_word: int =
     if radio:
         hdr += struct.pack("!HHI", 0x0167, 1, ed137_word & 0xFFFFFFFF)
     return hdr + payload
+
+
+def capture_meter_fifo(L, card: bytes, levels) -> bytes:
+    """Play the reader side of the meter FIFO (/tmp/capturefifo<card>, created 0666 as the reference's AudioMeter does): run the
+    host mirror's igdsp_meter_fifo_open / _write / _close over `levels` and return every byte it wrote, read 32 at a time.
+    The reader end is opened non-blocking first, so the writer finds it at once and nothing can wait on a missing partner."""
+    path = f"/tmp/capturefifo{card.decode()}"
+    if os.path.exists(path):
+        os.unlink(path)
+    os.mkfifo(path, 0o666)
+    try:
+        rfd = os.open(path, os.O_RDONLY | os.O_NONBLOCK)
+        try:
+            fd = L.igdsp_meter_fifo_open(card, 5000)
+            assert fd >= 0, fd
+            for v in levels:
+                assert L.igdsp_meter_fifo_write(fd, v) == 0
+            assert L.igdsp_meter_fifo_close(fd) == 0
+            got = b""
+            while True:                               # the writer has closed: the pipe drains, then reads return 0
+                rec = os.read(rfd, 32)
+                if not rec:
+                    return got
+                got += rec
+        finally:
+            os.close(rfd)
+    finally:
+        os.unlink(path)

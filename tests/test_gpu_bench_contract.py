@@ -55,6 +55,29 @@ def test_bench_json_contract_small(orc):
     assert abs(d["aggregate"]["node_rms"] - float(np.sqrt(int(agg["sumsq"]) / int(agg["samples"])))) < 1e-3
 
 
+@pytest.mark.parametrize("mode", ["meter", "store"])
+def test_bench_dump_outputs_match_the_oracle(orc, tmp_path, mode):
+    """--dump-outputs: what the last timed step computed, every frame record and the aggregate (and the PCM in store mode),
+    equals the oracle's on the same generator; the files are float32 / float64."""
+    C_, F_ = 256, 8
+    out = tmp_path / "dump"
+    d = _run(["--channels", str(C_), "--frames", str(F_), "--mode", mode, "--no-cpu-baseline", "--dump-outputs", str(out)])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0
+    got = {name: np.load(out / f"{name}.npy") for name in d["dump_outputs"]["arrays"]}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    payload = orc.gen_uniform(F_ * C_ * 160).reshape(F_, C_, 160)
+    st, pcm, agg = orc.decode_meter(payload, np.zeros((C_,), np.uint8), want_pcm=True, want_agg=True)
+    assert np.array_equal(got["stats_index"], np.arange(F_ * C_))
+    for f in ("sumsq", "peak", "byte_mean", "flags"):
+        assert np.array_equal(got[f"stats_{f}"], st[f].reshape(-1)), f
+    ref = np.sqrt(st["sumsq"].reshape(-1).astype(np.float64) / 160)
+    assert np.all(np.abs(got["stats_rms"] - ref) <= 1e-5 * ref + 1e-30)
+    assert got["aggregate"][:3].tolist() == [int(agg["sumsq"]), int(agg["samples"]), int(agg["frames"])]
+    assert got["aggregate"][6] == int(st["peak"].max())
+    if mode == "store":
+        assert np.array_equal(got["pcm"], pcm.reshape(-1))
+
+
 @pytest.mark.parametrize("mode", ["store", "roundtrip", "rtp", "packets", "window", "depayload", "encode"])
 def test_bench_secondary_modes_run(mode):
     d = _run(["--channels", "1024", "--frames", "16", "--mode", mode, "--no-cpu-baseline"])

@@ -95,24 +95,28 @@ def test_transport_rtp_cb_fuzz_against_depayload_oracle(orc):
         L.igdsp_host_adapter_free(a)
 
 
-def test_fifo_writer_drives_the_real_reference_audiometer(orc):
-    """The product's FIFO producer (igdsp_meter_fifo_*) feeding the REAL reference AudioMeter::getAudioLevel()
-    (oracle/_ref, built from audiometer.cpp + moc): the reference's own consumer code emits exactly
-    int(float(v*100.0/30000.0)) for every level we write."""
+def test_fifo_writer_drives_the_real_reference_audiometer(orc, golden_dir):
+    """The product's FIFO producer (igdsp_meter_fifo_*) feeding the REAL reference AudioMeter::getAudioLevel(): the fixture
+    holds the records this writer produced and the percents the reference's own consumer code emitted on exactly those bytes
+    (int(float(v*100.0/30000.0)) for every level).  The writer must still produce those bytes; when oracle/_ref is present
+    (built from audiometer.cpp + moc) the reference consumer also runs live."""
     import ctypes as C
     import threading
     import time
 
-    import pytest
-
-    if not orc.ref_audiometer_available():
-        pytest.skip("oracle/_ref/libref_audiometer.so not built (reference / Qt not present)")
     L = hu.load()
+    with open(os.path.join(golden_dir, "audiometer_fifo.json")) as fh:
+        g = json.load(fh)
+    levels = g["levels"]
+    assert g["percent"] == [orc.percent(v) for v in levels]
+    assert L.igdsp_meter_fifo_open(b"nobody-listens", 5) == -2          # no reader: IGDSP_ENOENT after the timeout
+    records = hu.capture_meter_fifo(L, f"igdspc{os.getpid()}".encode(), levels)
+    assert records.hex() == g["records_hex"]
+    if not orc.ref_audiometer_available():
+        return
     R = C.CDLL(os.path.join(os.path.dirname(orc.__file__), "_ref", "libref_audiometer.so"))
     R.ref_audiometer_consume.restype = C.c_int
     card = f"igdspw{os.getpid()}".encode()
-    levels = [0, 150, 300, 10138, 29999, 30000, 32124, 32256]
-    assert L.igdsp_meter_fifo_open(b"nobody-listens", 5) == -2          # no reader: IGDSP_ENOENT after the timeout
 
     def produce():
         fd = L.igdsp_meter_fifo_open(card, 5000)
@@ -129,4 +133,4 @@ def test_fifo_writer_drives_the_real_reference_audiometer(orc):
     t.join()
     os.unlink(f"/tmp/capturefifo{card.decode()}")
     assert n == len(levels)
-    assert list(out[:n]) == [orc.percent(v) for v in levels]
+    assert list(out[:n]) == g["percent"]

@@ -153,16 +153,18 @@ def test_config1_against_real_wavwriter_and_audioop(orc, golden_dir):
         assert hashlib.sha256(mine.tobytes()).hexdigest() == meta["wav_sha256"][c]
 
 
-def test_real_wavwriter_live_if_built(orc, tmp_path):
-    """When oracle/_ref is present (it travels to the GPU box as a built .so), run the
-    REAL reference recorder again and compare with the restatement on fresh input."""
-    if not orc.ref_wavwriter_available():
-        pytest.skip("oracle/_ref not built (reference not mounted)")
+def test_real_wavwriter_live_if_built(orc, golden_dir, tmp_path):
+    """The restatement against the REAL reference recorder on input other than config #1: the bytes it wrote for
+    7 frames of D-uniform (seed 99) are stored in the fixture; when oracle/_ref is present, the recorder runs again live."""
+    g = np.load(os.path.join(golden_dir, "wavwriter_uniform_7f.npz"))
     payload = orc.gen_uniform(7 * 160, seed=99).reshape(7, 160)
-    ref = np.frombuffer(orc.ref_wav_record(str(tmp_path), payload), dtype=np.uint8)
+    assert np.array_equal(payload, g["payload"])
     body = orc.wav_expand(payload)
     mine = np.concatenate([np.frombuffer(orc.wav_header(8000, body.size), dtype=np.uint8), body])
-    assert np.array_equal(mine, ref)
+    assert np.array_equal(mine, g["wav"])
+    if orc.ref_wavwriter_available():
+        ref = np.frombuffer(orc.ref_wav_record(str(tmp_path), payload), dtype=np.uint8)
+        assert np.array_equal(mine, ref)
 
 
 def test_prng_fixture(orc, golden_dir):
