@@ -47,6 +47,19 @@ GATE_ALWAYS, GATE_SQU, GATE_PTT, GATE_SQU_OR_PTT = 0, 1, 2, 3
 PKT_SLOTS, PKT_PACKED, PKT_MIXED = 0, 1, 2
 PROBE_ALARM = 500
 RTP_V2, RTP_X, RTP_MARKER, RTP_ED137_OK, RTP_KEEPALIVE, RTP_METERED, RTP_RUNT, RTP_OVERSIZE = 1, 2, 4, 8, 16, 32, 64, 128
+# ED-137 TX packetizer (igdsp_tx_packetize)
+TX_CHAN = np.dtype(
+    [("r2s_send_ms", "<u8"), ("ts", "<u4"), ("ssrc", "<u4"), ("keepalive_ms", "<i4"), ("packet_cnt", "<i4"), ("seq", "<u2"), ("pt", "u1"),
+     ("first_r2s", "u1"), ("tx_slave", "u1"), ("rx_slave", "u1"), ("tx_slave_changed", "u1"), ("rx_slave_changed", "u1"),
+     ("slave_count", "<i4"), ("ptt", "u1"), ("sql", "u1"), ("call_in", "u1"), ("call_recorder", "u1"), ("pttid", "u1"),
+     ("pttpriority", "u1"), ("bssi", "u1"), ("calltype", "u1"), ("tx_run", "<i2"), ("level", "u1"), ("reserved0", "u1"),
+     ("reserved", "<u4", (4,))],
+    align=True,
+)
+TX_INFO = np.dtype([("ed137", "<u4"), ("size", "<u2"), ("flags", "u1"), ("level", "u1")], align=True)
+TX_CT_IDLE, TX_CT_RX, TX_CT_TX = 1, 2, 4
+TX_SENT, TX_KEEPALIVE_PT, TX_MARKER, TX_STALE_PAYLOAD, TX_LEVEL_VALID = 1, 2, 4, 8, 16
+TX_CTL_PTT, TX_CTL_SQL, TX_CTL_MARK, TX_CTL_SET = 1, 2, 4, 0x80
 AGGREGATE = np.dtype({      # one 128-byte line per counter (include/igdsp.h); the padding is not exposed as fields
     "names": ["sumsq", "samples", "frames", "n_silent", "n_clipped", "byte_mean_sum", "peak_slot"],
     "formats": ["<u8", "<u8", "<u8", "<u8", "<u8", "<u8", ("<u8", (AGG_MAX_RANKS,))],
@@ -128,6 +141,9 @@ PROTOTYPES = [
     ("igdsp_window_update", _int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, C.POINTER(Window), _vp]),
     ("igdsp_decode_meter_window", _int, [_vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _u32, C.POINTER(Window), _vp]),
     ("igdsp_wav_expand", _int, [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _u64, _vp]),
+    ("igdsp_tx_chan_init", _int, [_vp, C.c_char_p, _int, C.c_uint8, _u32, C.c_uint16, _u32, _i32, _u64]),
+    ("igdsp_tx_calltype_bits", _int, [C.c_char_p]),
+    ("igdsp_tx_packetize", _int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _u64, _u32, _vp, _vp, _vp, _u32, _vp, _vp, _int, _vp]),
     ("igdsp_g726_reorder", _int, [_vp, _vp, _vp, _u64, _int, _vp]),
     ("igdsp_gen_uniform", _int, [_vp, _vp, _u64, _u64, _u64, _vp]),
     ("igdsp_dev_alloc", _int, [_vp, C.POINTER(_vp), C.c_size_t]),
@@ -177,6 +193,21 @@ def load() -> C.CDLL:
             raise ImportError(f"libigdsp ABI {L.igdsp_abi_version()} != binding {ABI_VERSION}")
         _lib = L
     return _lib
+
+
+def tx_calltype_bits(calltype: str) -> int:
+    """IGDSP_TX_CT_* bits of a calltype (host only, no GPU)."""
+    return load().igdsp_tx_calltype_bits(calltype.encode())
+
+
+def tx_chan_init(calltype: str, call_in: bool, pt: int, ssrc: int, seq0: int, ts0: int, keepalive_ms: int = 200, now_ms: int = 0) -> np.ndarray:
+    """One igdsp_tx_chan with transport_adapter_create's defaults (host only, no GPU); a TX_CHAN record."""
+    out = np.zeros((), dtype=TX_CHAN)
+    rc = load().igdsp_tx_chan_init(out.ctypes.data_as(_vp), calltype.encode(), 1 if call_in else 0, pt, ssrc & 0xFFFFFFFF, seq0 & 0xFFFF,
+                                   ts0 & 0xFFFFFFFF, keepalive_ms, now_ms)
+    if rc != 0:
+        raise IgdspError(rc, "igdsp_tx_chan_init")
+    return out
 
 
 def _ptr(x) -> int | None:
@@ -324,6 +355,13 @@ class Context:
     def decode_meter_packets_mixed(self, packets, sizes, codec, radio, C_, F_, stride, stats, info=None, agg=None, rank=0, stream=None):
         self._ck(self.L.igdsp_decode_meter_packets_mixed(self.h, _ptr(packets), _ptr(sizes), _ptr(codec), _ptr(radio), C_, F_, stride,
                                                          _ptr(stats), _ptr(info), _ptr(agg), rank, stream), "igdsp_decode_meter_packets_mixed")
+
+    def tx_packetize(self, state, last_payload, packets, stride, sizes, info, C_, F_, n, t0_ms, frame_ms=20, pcm=None, g711=None,
+                     ctl=None, variant=ENC_G191, stream=None):
+        """igdsp_tx_packetize: exactly one of pcm [F][C][n] int16 / g711 [F][C][n] u8 (device)."""
+        self._ck(self.L.igdsp_tx_packetize(self.h, _ptr(pcm), _ptr(g711), _ptr(ctl), C_, F_, n, t0_ms, frame_ms, _ptr(state),
+                                           _ptr(last_payload), _ptr(packets), stride, _ptr(sizes), _ptr(info), variant, stream),
+                 "igdsp_tx_packetize")
 
     # -- ED-137 gated window
     @staticmethod

@@ -542,6 +542,23 @@ int igdsp_decode_meter(igdsp_ctx *ctx, const uint8_t *d_payload, const uint8_t *
     return IGDSP_OK;
 }
 
+// The context's 16-bit compressor table of one lineage (tab[law << 16 | uint16(v)]), built on the device the first time a large
+// batch asks for it; nullptr if that failed (the kernels then evaluate the table themselves).
+static const uint8_t *enc_table(igdsp_ctx *ctx, int variant)
+{
+    const int v = variant == IGDSP_ENC_G191 ? 1 : 0;
+    std::call_once(ctx->enc_once[v], [&]() {
+        uint8_t *t = nullptr;
+        hipStream_t bs = nullptr;
+        bool ok = hipMalloc((void **)&t, 2u * 65536u) == hipSuccess && hipStreamCreateWithFlags(&bs, hipStreamNonBlocking) == hipSuccess;
+        ok = ok && igdsp::launch_build_enc_table(variant, t, bs) == hipSuccess && hipStreamSynchronize(bs) == hipSuccess;
+        if (bs) (void)hipStreamDestroy(bs);
+        if (ok) ctx->d_enc_tab[v] = t;                          // complete before any launch that reads it is enqueued
+        else { if (t) (void)hipFree(t); (void)hipGetLastError(); }   // the kernel evaluates the table itself, as before
+    });
+    return ctx->d_enc_tab[v];
+}
+
 int igdsp_encode(igdsp_ctx *ctx, const int16_t *d_pcm, const uint8_t *d_codec, uint32_t C, uint32_t F, uint32_t n,
                  uint8_t *d_out, int variant, void *stream)
 {
@@ -552,19 +569,7 @@ int igdsp_encode(igdsp_ctx *ctx, const int16_t *d_pcm, const uint8_t *d_codec, u
     if (int rc = check_shape(C, F, n)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     igdsp::LaunchCfg cfg = cfg_of(ctx, pick(ctx, stream));
-    if ((uint64_t)C * F * n >= (1ull << 25)) {                     // the batches k_encode_lut16 serves: its table, built once per context and lineage
-        const int v = variant == IGDSP_ENC_G191 ? 1 : 0;
-        std::call_once(ctx->enc_once[v], [&]() {
-            uint8_t *t = nullptr;
-            hipStream_t bs = nullptr;
-            bool ok = hipMalloc((void **)&t, 2u * 65536u) == hipSuccess && hipStreamCreateWithFlags(&bs, hipStreamNonBlocking) == hipSuccess;
-            ok = ok && igdsp::launch_build_enc_table(variant, t, bs) == hipSuccess && hipStreamSynchronize(bs) == hipSuccess;
-            if (bs) (void)hipStreamDestroy(bs);
-            if (ok) ctx->d_enc_tab[v] = t;                          // complete before any launch that reads it is enqueued
-            else { if (t) (void)hipFree(t); (void)hipGetLastError(); }   // the kernel evaluates the table itself, as before
-        });
-        cfg.enc_tab = ctx->d_enc_tab[v];
-    }
+    if ((uint64_t)C * F * n >= (1ull << 25)) cfg.enc_tab = enc_table(ctx, variant);   // the batches k_encode_lut16 serves
     HIP_TRY(ctx, launch_encode(cfg, d_pcm, d_codec, C, F, n, d_out, variant, pick(ctx, stream)));
     return IGDSP_OK;
 }
@@ -818,6 +823,57 @@ int igdsp_wav_expand(igdsp_ctx *ctx, const uint8_t *d_payload, uint32_t C, uint3
     return IGDSP_OK;
 }
 
+// ---- ED-137 TX packetizer (transport_send_rtp, TransportAdapter.cpp:635-874) ----
+int igdsp_tx_calltype_bits(const char *ct)
+{
+    if (!ct) return 0;
+    int b = 0;
+    if (std::strstr(ct, "Idle")) b |= IGDSP_TX_CT_IDLE;                                   // :675
+    if (std::strstr(ct, "Rxonly") || std::strcmp(ct, "Rx") == 0) b |= IGDSP_TX_CT_RX;     // :795, :811
+    if (std::strstr(ct, "Tx") || std::strstr(ct, "TRx")) b |= IGDSP_TX_CT_TX;             // :816, :821
+    return b;
+}
+
+int igdsp_tx_chan_init(igdsp_tx_chan *h, const char *calltype, int call_in, uint8_t pt, uint32_t ssrc, uint16_t seq0, uint32_t ts0,
+                       int32_t keepalive_ms, uint64_t now_ms)
+{
+    if (!h || pt > 127u) return IGDSP_EINVAL;
+    std::memset(h, 0, sizeof *h);                          // PJ_POOL_ZALLOC_T (TransportAdapter.cpp:97)
+    h->seq = seq0;
+    h->ts = ts0;
+    h->ssrc = ssrc;
+    h->pt = pt;
+    h->call_in = call_in ? 1 : 0;                          // :111
+    h->keepalive_ms = keepalive_ms;                        // :115
+    h->calltype = (uint8_t)igdsp_tx_calltype_bits(calltype);   // :118
+    h->r2s_send_ms = now_ms;                               // :123
+    h->first_r2s = 1;                                      // :124 (packetCnt 0, callRecorder / slave enables false: :125-128)
+    return IGDSP_OK;
+}
+
+int igdsp_tx_packetize(igdsp_ctx *ctx, const int16_t *d_pcm, const uint8_t *d_g711, const uint8_t *d_ctl, uint32_t C, uint32_t F,
+                       uint32_t n, uint64_t t0_ms, uint32_t frame_ms, igdsp_tx_chan *d_state, uint8_t *d_last_payload, uint8_t *d_packets,
+                       uint32_t pkt_stride, uint16_t *d_sizes, igdsp_tx_info *d_info, int variant, void *stream)
+{
+    if (!ctx) return IGDSP_EINVAL;
+    if ((uint64_t)C * F == 0) return IGDSP_OK;
+    if ((d_pcm == nullptr) == (d_g711 == nullptr)) return IGDSP_EINVAL;                   // exactly one input form
+    if (!d_state || !d_last_payload || !d_packets || !d_sizes || !d_info) return IGDSP_EINVAL;
+    if (d_pcm && variant != IGDSP_ENC_SUN16 && variant != IGDSP_ENC_G191) return IGDSP_EINVAL;
+    if (int rc = check_shape(C, F, n)) return rc;
+    if (pkt_stride < 20u + n || (pkt_stride & 3u) || pkt_stride > 2048u || (reinterpret_cast<uintptr_t>(d_packets) & 3u)) return IGDSP_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(d_state) & 7u) || (reinterpret_cast<uintptr_t>(d_info) & 3u) || (reinterpret_cast<uintptr_t>(d_sizes) & 1u) ||
+        (reinterpret_cast<uintptr_t>(d_pcm) & 1u))
+        return IGDSP_EINVAL;
+    if ((uint64_t)F * n >= 0x80000000ull) return IGDSP_ERANGE;                              // ts + f * n and frame indices stay 32-bit
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    igdsp::LaunchCfg cfg = cfg_of(ctx, pick(ctx, stream));
+    if (d_pcm && (uint64_t)C * F * n >= (1ull << 22)) cfg.enc_tab = enc_table(ctx, variant);
+    HIP_TRY(ctx, launch_tx_packetize(cfg, d_pcm, d_g711, d_ctl, C, F, n, t0_ms, frame_ms, d_state, d_last_payload, d_packets, pkt_stride,
+                                     d_sizes, d_info, variant, pick(ctx, stream)));
+    return IGDSP_OK;
+}
+
 int igdsp_g726_reorder(igdsp_ctx *ctx, const uint8_t *d_in, uint8_t *d_out, uint64_t n_bytes, int mode, void *stream)
 {
     if (!ctx || mode < 1 || mode > 4) return IGDSP_EINVAL;
@@ -926,6 +982,22 @@ int igdsp_internal_stream_pieces(igdsp_ctx *ctx, const void *d_src, uint32_t n_i
     if (!ctx || !d_src || !d_dst || (stride & 3u) || stride < 16u * (uint32_t)(rows - (mode == 0 ? 2 : 1))) return IGDSP_EINVAL;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, launch_stream_pieces(cfg_of(ctx, pick(ctx, stream)), d_src, n_items, stride, hdr, mode, rows, d_dst, d_dst2, pick(ctx, stream)));
+    return IGDSP_OK;
+}
+
+// Calibration-only (not in include/igdsp.h): the compute-free packet writer that moves the bytes of an all-audio igdsp_tx_packetize launch
+// in the same traversal (tools/tx_bench.py --ab).  Exactly one of d_pcm / d_g711; n % 4 == 0.
+int igdsp_internal_tx_copy(igdsp_ctx *ctx, const int16_t *d_pcm, const uint8_t *d_g711, uint32_t C, uint32_t F, uint32_t n, uint8_t *d_packets,
+                           uint32_t pkt_stride, void *stream)
+{
+    if (!ctx || (d_pcm == nullptr) == (d_g711 == nullptr) || !d_packets || (n & 3u) || n == 0 || n > IGDSP_MAX_PAYLOAD || pkt_stride < 20u + n ||
+        (pkt_stride & 3u) || (reinterpret_cast<uintptr_t>(d_packets) & 3u) || (reinterpret_cast<uintptr_t>(d_pcm) & 7u) ||
+        (reinterpret_cast<uintptr_t>(d_g711) & 3u))
+        return IGDSP_EINVAL;
+    if ((uint64_t)C * F == 0) return IGDSP_OK;
+    if (int rc = check_shape(C, F, n)) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, launch_tx_copy_ab(cfg_of(ctx, pick(ctx, stream)), d_pcm, d_g711, C, F, n, d_packets, pkt_stride, pick(ctx, stream)));
     return IGDSP_OK;
 }
 

@@ -492,4 +492,54 @@ __device__ __forceinline__ void bq_finish(uint32_t *gq, uint32_t G)             
 }
 
 
+// ============================================================================
+// a2 — G.711 compression.  ONE branch-free formulation serves both laws and both encoder lineages
+// (include/igdsp.h): per-law constants select bias / rounding, the segment comes from count-leading-
+// zeros.  With msb = 31 - clz(mag):
+//   SUN16  mu : mag = min(|v| + 0x84, 0x7FFF)                 A : mag = v >= 0 ? v : max(-v - 8, 0)
+//          seg = max(msb,7) - 7        step = (mag >> (max(msb, mu?7:8) - 4)) & 15
+//   G191   mu : mag = min(|v>>2| + 0x21, 0x1FFF)              A : mag = (v>>3) ^ sign   (= -x-1 for x < 0)
+//          seg = max(msb, mu?5:4) - (mu?5:4)   step = (mag >> (max(msb,5) - 4)) & 15
+//   code = (seg<<4 | step) ^ (mu ? 0xFF : 0xD5) ^ (v < 0 ? 0x80 : 0)
+// (clamping mag is identical to the classic "segment 8 -> 0x7F ^ mask" overflow rule).
+// ============================================================================
+struct EncK { int k_and, k_add, sh; uint32_t c_shift, c_seg, base; };
+
+template <int VARIANT>
+__device__ __forceinline__ EncK enc_consts(bool alaw)
+{
+    EncK k;
+    if (VARIANT == IGDSP_ENC_SUN16) {
+        k.k_and = alaw ? -8 : 0; k.k_add = alaw ? 0 : 0x84; k.sh = 0;
+        k.c_shift = alaw ? 23u : 24u;      // 31 - floor(msb) for the step shift
+        k.c_seg = 24u;                     // 31 - 7
+    } else {
+        k.k_and = alaw ? 0 : 1; k.k_add = alaw ? 0 : 0x21; k.sh = alaw ? 3 : 2;
+        k.c_shift = 26u;                   // 31 - 5
+        k.c_seg = alaw ? 27u : 26u;        // 31 - {4,5}
+    }
+    k.base = alaw ? 0xD5u : 0xFFu;
+    return k;
+}
+
+template <int VARIANT>
+__device__ __forceinline__ uint32_t enc_uni(int v, const EncK k)
+{
+    int mag;
+    const int sign = v >> 31;                                   // -1 for negative samples
+    if (VARIANT == IGDSP_ENC_SUN16) {
+        const int av = (v ^ sign) - sign;                       // |v|, 32768 for -32768
+        mag = min(max(av + ((sign & k.k_and) + k.k_add), 0), 0x7FFF);
+    } else {
+        const int vd = v >> k.sh;                               // arithmetic: floors negatives
+        const int t = vd ^ sign;                                // x >= 0 ? x : -x - 1
+        mag = min(t + (sign & k.k_and) + k.k_add, 0x1FFF);      // mu: |x| + 0x21 ; A: -x - 1
+    }
+    const uint32_t c = (uint32_t)__clz(mag);                    // 32 for mag == 0
+    const uint32_t shift = 27u - min(c, k.c_shift);             // max(msb, floor) - 4
+    const uint32_t sg = k.c_seg - min(c, k.c_seg);              // max(msb, f) - f
+    const uint32_t step = ((uint32_t)mag >> shift) & 15u;
+    return ((sg << 4) | step) ^ k.base ^ ((uint32_t)sign & 0x80u);
+}
+
 }  // namespace igdsp

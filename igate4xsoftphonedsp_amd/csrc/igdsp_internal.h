@@ -77,6 +77,11 @@ hipError_t launch_hold_reset(igdsp_chan_hold *hold, uint32_t C, const uint8_t *m
 hipError_t launch_depayload(const LaunchCfg &cfg, const uint8_t *packets, const uint16_t *sizes, const uint8_t *radio,
                             uint32_t C, uint32_t F, uint32_t stride, uint32_t n, uint8_t *payload, uint16_t *len,
                             igdsp_rtp_info *info, hipStream_t s);
+hipError_t launch_tx_copy_ab(const LaunchCfg &cfg, const int16_t *pcm, const uint8_t *g711, uint32_t C, uint32_t F, uint32_t n,
+                             uint8_t *packets, uint32_t stride, hipStream_t s);   // compute-free yardstick of launch_tx_packetize
+hipError_t launch_tx_packetize(const LaunchCfg &cfg, const int16_t *pcm, const uint8_t *g711, const uint8_t *ctl, uint32_t C, uint32_t F,
+                               uint32_t n, uint64_t t0, uint32_t frame_ms, igdsp_tx_chan *state, uint8_t *last, uint8_t *packets,
+                               uint32_t stride, uint16_t *sizes, igdsp_tx_info *info, int variant, hipStream_t s);
 hipError_t launch_wav_expand(const LaunchCfg &cfg, const uint8_t *payload, uint32_t C, uint32_t F, uint32_t n, uint32_t rate,
                              uint8_t *files, uint64_t file_stride, hipStream_t s);
 hipError_t launch_g726(const LaunchCfg &cfg, const uint8_t *in, uint8_t *out, uint64_t n_bytes, int mode, hipStream_t s);

@@ -31,7 +31,9 @@ extern "C" {
 /* 2: igdsp_io_alloc / igdsp_io_free, igdsp_wav_expand, staging ring (igdsp_level.dropped, IGDSP_STAGE_DEPTH); every round-1 entry is
  * unchanged in signature and meaning.
  * 3: additive again — the ED-137 gated window (igdsp_window, igdsp_decode_meter_window, igdsp_window_update, igdsp_chan_probe),
- * igdsp_set_ed137 / igdsp_set_gate_mode / igdsp_get_probe on the single-frame path, igdsp_flush_begin / igdsp_flush_end. */
+ * igdsp_set_ed137 / igdsp_set_gate_mode / igdsp_get_probe on the single-frame path, igdsp_flush_begin / igdsp_flush_end.
+ *    Later, still additive under 3: the ED-137 TX packetizer (igdsp_tx_chan, igdsp_tx_info, igdsp_tx_chan_init, igdsp_tx_calltype_bits,
+ *    igdsp_tx_packetize). */
 #define IGDSP_ABI_VERSION 3
 
 /* ---- error codes (0 == PJ_SUCCESS-style success) ------------------------- */
@@ -425,6 +427,86 @@ int igdsp_wav_expand(igdsp_ctx *ctx, const uint8_t *d_payload, uint32_t n_channe
  *          `(b0 >> 5) & 0x04`, which never fits, so those two output bits are always 0  (:6450-6498)
  * n_bytes must be a multiple of the group size (1, 3, 1, 5): the reference over-reads otherwise. */
 int igdsp_g726_reorder(igdsp_ctx *ctx, const uint8_t *d_in, uint8_t *d_out, uint64_t n_bytes, int g726UplinkBitrate, void *stream);
+
+/* ---- ED-137 TX packetizer: transport_send_rtp on the device (TransportAdapter.cpp:635-874) --------------------------------
+ * The send half of the adapter, batched: a launch's worth of outgoing frames in, the packets transport_send_rtp hands to
+ * pjmedia_transport_send_rtp out, bit for bit, plus what the reference derives on the way (ED-137 word, keep-alive choice,
+ * marker, audioLevel).  Radio legs only (adapter->radiostatus, :641).  Frame f of channel c is one call of transport_send_rtp at
+ * now = t0_ms + f * frame_ms, frames of a channel in order:
+ *   1 stream packet (what pjmedia encodes before the adapter sees it): 0x80, M << 7 | pt, seq, ts, ssrc (network order), then
+ *     the frame's n G.711 bytes.  Frame f carries seq + f (mod 2^16) and ts + f * n; every frame advances them, sent or not.
+ *   2 TX silence run (:657-673): only if 12 + n > 60; stream bytes 40, 50, 60 all 0xD5 -> run++ (qint16), else run = 0.
+ *   3 Idle-in zeroing (:675-679): calltype contains "Idle" and callIn -> sql = ptt = 0 (persists).
+ *   4 gate (:680-706): (ptt && !callIn) || (sql && callIn) copies the payload into the send buffer (d_last_payload, persists);
+ *     otherwise (uint64)(now - r2sSendtime) < (uint64)keepAlivePeroid && !firstR2SPacket -> NOT SENT (size 0, nothing else
+ *     changes), and a difference >= the period sets r2sSendtime = now (the quint64 wrap of now < r2sSendtime included).
+ *   5 header (:712-796, custom_rtp_hdr ed137_rtp.h:22-48): 0x90 (x = 1), m = firstR2SPacket && packetCnt == 0, profile 0x0167,
+ *     length 1; word = slave-enable debounce base (steady: 00 -> 0, 11 -> 0x131c0, rx -> 0x13140, tx -> 0x13180; changing: copy,
+ *     count = min(count + 1, 5), 00 -> 0x13100) | sql ? 1 << 28 | bssi << 3 & 0xf8 : !ptt ? 1 << 22 : 0 | ptt ? pttid << 22 &
+ *     0x0fc00000 | pttpriority << 29 & 0xe0000000 : 0; pt = 123 on an Rx leg with !callIn.
+ *   6 size / PT ladder (:804-839) as written: 20 bytes with pt 123, or 20 + n.  A 20 + n packet whose frame the gate did not
+ *     copy carries the send buffer's STALE payload (the last gated frame, zeros before any).
+ *   7 counters (:849-856): packetCnt / firstR2SPacket after every sent frame.
+ *   8 audioLevel (roip_ed137.cpp:6510-6517): sent with pt != 123 -> (uint8_t)(sum of the first n STREAM-packet bytes as signed
+ *     char / (int)n), header bytes included.
+ * The calltype predicates (case-sensitive QString::contains) are evaluated once on the host into IGDSP_TX_CT_* bits. */
+#define IGDSP_TX_CT_IDLE   0x01   /* contains "Idle"                     */
+#define IGDSP_TX_CT_RX     0x02   /* contains "Rxonly" or equals "Rx"    */
+#define IGDSP_TX_CT_TX     0x04   /* contains "Tx" or contains "TRx"     */
+/* Per-channel persistent state (device-resident, 64 bytes): tp_adapter's send-side fields (TransportAdapter.h:40-93).  Host code
+ * may change fields between launches: those are the setters setAdapterPtt / setTxRxSlaveEnable / setAdapterQslOn / setAdapterPttId /
+ * setcallRecorder (TransportAdapter.cpp:136-210); setTxRxSlaveEnable writes *_changed and zeroes slave_count. */
+typedef struct igdsp_tx_chan {
+    uint64_t r2s_send_ms;       /* adapter->r2sSendtime (ms)                                        */
+    uint32_t ts;                /* stream RTP timestamp of the next frame                           */
+    uint32_t ssrc;
+    int32_t  keepalive_ms;      /* adapter->keepAlivePeroid                                         */
+    int32_t  packet_cnt;        /* adapter->packetCnt                                               */
+    uint16_t seq;               /* stream RTP sequence number of the next frame                     */
+    uint8_t  pt;                /* stream RTP payload type (0 mu-law, 8 A-law)                      */
+    uint8_t  first_r2s;         /* adapter->firstR2SPacket                                          */
+    uint8_t  tx_slave, rx_slave, tx_slave_changed, rx_slave_changed;
+    int32_t  slave_count;       /* adapter->trxSlaveEnableChangedCount                              */
+    uint8_t  ptt, sql, call_in, call_recorder;
+    uint8_t  pttid, pttpriority, bssi, calltype;   /* calltype = IGDSP_TX_CT_* bits                 */
+    int16_t  tx_run;            /* adapter->rtpFalse (qint16)                                       */
+    uint8_t  level;             /* last outgoing audioLevel (OutgoingRTP)                           */
+    uint8_t  reserved0;
+    uint32_t reserved[4];
+} igdsp_tx_chan;
+/* Per-frame output, 8 bytes. */
+typedef struct igdsp_tx_info {
+    uint32_t ed137;             /* the ED-137 word, host order (0 when not sent)                    */
+    uint16_t size;              /* bytes handed to pjmedia_transport_send_rtp: 0 (not sent), 20, 20 + n */
+    uint8_t  flags;             /* IGDSP_TX_*                                                       */
+    uint8_t  level;             /* audioLevel when IGDSP_TX_LEVEL_VALID, else 0                     */
+} igdsp_tx_info;
+#define IGDSP_TX_SENT          0x01
+#define IGDSP_TX_KEEPALIVE_PT  0x02   /* pt 123 on the wire                                         */
+#define IGDSP_TX_MARKER        0x04
+#define IGDSP_TX_STALE_PAYLOAD 0x08   /* 20 + n bytes carrying the send buffer, not this frame      */
+#define IGDSP_TX_LEVEL_VALID   0x10   /* setOutgoingRTP ran: level is the new OutgoingRTP           */
+/* d_ctl[f][c] bits (optional array). */
+#define IGDSP_TX_CTL_PTT   0x01
+#define IGDSP_TX_CTL_SQL   0x02
+#define IGDSP_TX_CTL_MARK  0x04   /* the stream header's M bit                                     */
+#define IGDSP_TX_CTL_SET   0x80   /* setAdapterPtt / setAdapterQslOn before this frame: ptt = bit 0, sql = bit 1 */
+
+/* transport_adapter_create's defaults (TransportAdapter.cpp:108-127, zalloc for the rest): first_r2s = 1, r2s_send_ms = now_ms,
+ * keepalive_ms, call_in, calltype bits; seq / ts / ssrc / pt are the stream's.  Host-only, no GPU needed.  pt > 127 -> EINVAL. */
+int igdsp_tx_chan_init(igdsp_tx_chan *h, const char *calltype, int call_in, uint8_t pt, uint32_t ssrc, uint16_t seq0,
+                       uint32_t ts0, int32_t keepalive_ms, uint64_t now_ms);
+/* IGDSP_TX_CT_* bits of a calltype string (NULL -> 0).  Host-only. */
+int igdsp_tx_calltype_bits(const char *calltype);
+/* Exactly one of d_pcm[f][c][n] (int16, encoded on the fly, law from the channel's pt: 8 A-law, else mu-law; variant =
+ * IGDSP_ENC_*) or d_g711[f][c][n] (already encoded).  d_ctl[f][c] optional.  d_state[c], d_last_payload[c][n] persist across
+ * launches (zero the payloads once).  d_packets[f][c][pkt_stride]: pkt_stride % 4 == 0, >= 20 + n, <= 2048, the layout
+ * igdsp_depayload reads; bytes past sizes[f][c] are never written, and an unsent frame leaves its slot untouched.
+ * d_sizes[f][c], d_info[f][c] required. */
+int igdsp_tx_packetize(igdsp_ctx *ctx, const int16_t *d_pcm, const uint8_t *d_g711, const uint8_t *d_ctl,
+                       uint32_t n_channels, uint32_t n_frames, uint32_t samples_per_frame, uint64_t t0_ms, uint32_t frame_ms,
+                       igdsp_tx_chan *d_state, uint8_t *d_last_payload, uint8_t *d_packets, uint32_t pkt_stride,
+                       uint16_t *d_sizes, igdsp_tx_info *d_info, int variant, void *stream);
 
 /* ---- synthetic input generators (device side; SURVEY 8(d) definitions) ---------
  * D-uniform: byte k of global byte index g is
