@@ -569,7 +569,8 @@ int igdsp_encode(igdsp_ctx *ctx, const int16_t *d_pcm, const uint8_t *d_codec, u
     if (int rc = check_shape(C, F, n)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     igdsp::LaunchCfg cfg = cfg_of(ctx, pick(ctx, stream));
-    if ((uint64_t)C * F * n >= (1ull << 25)) cfg.enc_tab = enc_table(ctx, variant);   // the batches k_encode_lut16 serves
+    if (encode_wants_table(encode_route(C, F, n, reinterpret_cast<uintptr_t>(d_pcm), reinterpret_cast<uintptr_t>(d_out), (uint32_t)cfg.compute_units)))
+        cfg.enc_tab = enc_table(ctx, variant);
     HIP_TRY(ctx, launch_encode(cfg, d_pcm, d_codec, C, F, n, d_out, variant, pick(ctx, stream)));
     return IGDSP_OK;
 }
@@ -751,55 +752,11 @@ int igdsp_decode_meter_window(igdsp_ctx *ctx, uint32_t layout, const uint8_t *d_
     const uint32_t alarm = win->probe_alarm ? win->probe_alarm : IGDSP_PROBE_ALARM;
     hipStream_t s = pick(ctx, stream);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (fused) {
-        // channel-group-major fused kernel: the windows live in registers; at least one unit per resident wave, a segment is
-        // never shorter than 8 frames nor longer than 65 535 (silent / clipped counts of a unit are 16 bits)
-        igdsp::WinArgs w;
-        w.work = static_cast<uint4 *>(win->d_work);
-        w.gate_mask = ((win->gate_mode & IGDSP_GATE_SQU) ? 0x10000000u : 0u) | ((win->gate_mode & IGDSP_GATE_PTT) ? 0xe0000000u : 0u);   // Functions.cpp:1160, 1136
-        w.alarm = alarm; w.n_groups = C / 64u; w.F = F;
-        // (16 units per CU for its 12 waves: at 65 536 channels 4 segments — a third of the waves take a second unit — measured
-        // 0.2873-0.2929 ms against 0.2973-0.3023 with 3 segments = one unit per wave, 0.2906-0.2954 with 5, 0.2903-0.2957 with 8)
-        const uint32_t want = (uint32_t)ctx->cus * 16u;
-        uint32_t n_seg = w.n_groups >= want ? 1u : (want + w.n_groups - 1u) / w.n_groups;
-        if (const char *e = std::getenv("IGDSP_WIN_NSEG")) n_seg = (uint32_t)std::max(1, std::atoi(e));   // experiments
-        n_seg = std::max(1u, std::min(std::min(n_seg, kWinMaxSeg), std::max(1u, F / 8u)));
-        if (F / n_seg > 65535u) return fail(ctx, IGDSP_ERANGE, "decode_meter_window: more than 8 x 65535 frames per launch");
-        w.n_seg = n_seg;
-        // Block-owned form (the default where it fits): a block owns gpb = 4, 2 or 1 consecutive channel groups for the launch,
-        // hands their items to its waves in (frame, group) order and keeps their windows and runs in its LDS — the item-level
-        // balance of the time-major kernels inside a block, no summaries, no finish kernel.  gpb: as many groups per block as
-        // still give every CU a block; taken up to one round of blocks and when the blocks fill whole rounds of the CUs to 85 % (a launch
-        // of 1.25 rounds would idle 3/8 of the chip in its second round: the register form above has no such steps).  The packed LDS counters hold
-        // 255 frames: longer launches go out as equal parts on the stream (hold / probe / the aggregate carry across them).
-        {
-            const uint32_t cus = (uint32_t)std::max(1, ctx->cus);
-            uint32_t gpb = 1u;
-            for (uint32_t g = 4u; g > 1u; g >>= 1) if (w.n_groups % g == 0u && w.n_groups / g >= cus) { gpb = g; break; }
-            if (const char *e = std::getenv("IGDSP_WIN_GPB")) { const uint32_t g = (uint32_t)std::atoi(e); if ((g == 1u || g == 2u || g == 4u) && w.n_groups % g == 0u) gpb = g; }   // tests
-            const uint32_t blocks = w.n_groups / gpb, rounds = (blocks + cus - 1u) / cus;
-            // (measured around the tuned 65 536 channels, register form / block form ms: 2 048 ch 0.0992 / 0.0658, 8 192 ch 0.1014 / 0.0685, 12 288 ch
-            // 0.1021 / 0.0705 — up to one round of blocks the block form always wins, the register form walks its segments serially — 24 576 ch
-            // 0.1218 / 0.1397, 49 152 ch 0.2332 / 0.2559: 1.5 rounds idle half the chip in the second)
-            bool blk = rounds == 1u || (uint64_t)blocks * 100u >= (uint64_t)rounds * cus * 85u;
-            if (const char *e = std::getenv("IGDSP_WIN_BLK")) blk = std::atoi(e) != 0;       // experiments and tests: 0 = never, 1 = always
-            if (blk) {
-                w.gpb = gpb; w.gsh = gpb == 4u ? 2u : (gpb == 2u ? 1u : 0u);
-                w.hold = win->d_hold; w.gate = win->d_gate; w.probe = win->d_probe;
-                const uint32_t parts = (F + 254u) / 255u;
-                const uint64_t pkt_frame = (uint64_t)C * (stride ? stride : (uint32_t)IGDSP_SLOT_BYTES);
-                for (uint32_t k = 0; k < parts; ++k) {
-                    const uint32_t f0 = (uint32_t)(((uint64_t)F * k) / parts), f1 = (uint32_t)(((uint64_t)F * (k + 1u)) / parts);
-                    const uint64_t r0 = (uint64_t)f0 * C;
-                    w.F = f1 - f0;
-                    HIP_TRY(ctx, launch_decode_meter_rtp(cfg_of(ctx, s), d_packets + (uint64_t)f0 * pkt_frame, sizes ? sizes + r0 : nullptr, d_codec, C, f1 - f0, stride, hdr,
-                                                         d_stats ? d_stats + r0 : nullptr, d_info ? d_info + r0 : nullptr, d_agg, rank, s, radio, &w));
-                }
-                return IGDSP_OK;
-            }
-        }
-        HIP_TRY(ctx, launch_decode_meter_rtp(cfg_of(ctx, s), d_packets, sizes, d_codec, C, F, stride, hdr, d_stats, d_info, d_agg, rank, s, radio, &w));
-        HIP_TRY(ctx, launch_window_finish(w.work, C, n_seg, alarm, win->d_hold, win->d_gate, win->d_probe, s));
+    if (fused) {   // channel-group-major fused kernel with the window folded in (launch_decode_meter_window)
+        bool too_long = false;
+        HIP_TRY(ctx, launch_decode_meter_window(cfg_of(ctx, s), d_packets, sizes, d_codec, C, F, stride, hdr, radio, d_stats, d_info, d_agg, rank, *win,
+                                                &too_long, s));
+        if (too_long) return fail(ctx, IGDSP_ERANGE, "decode_meter_window: more than 8 x 65535 frames per launch");
         return IGDSP_OK;
     }
     // other channel counts: the plain fused kernel, then the record-wise window fold on the same stream
@@ -868,7 +825,7 @@ int igdsp_tx_packetize(igdsp_ctx *ctx, const int16_t *d_pcm, const uint8_t *d_g7
     if ((uint64_t)F * n >= 0x80000000ull) return IGDSP_ERANGE;                              // ts + f * n and frame indices stay 32-bit
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     igdsp::LaunchCfg cfg = cfg_of(ctx, pick(ctx, stream));
-    if (d_pcm && (uint64_t)C * F * n >= (1ull << 22)) cfg.enc_tab = enc_table(ctx, variant);
+    if (tx_wants_table(d_pcm != nullptr, C, F, n)) cfg.enc_tab = enc_table(ctx, variant);
     HIP_TRY(ctx, launch_tx_packetize(cfg, d_pcm, d_g711, d_ctl, C, F, n, t0_ms, frame_ms, d_state, d_last_payload, d_packets, pkt_stride,
                                      d_sizes, d_info, variant, pick(ctx, stream)));
     return IGDSP_OK;

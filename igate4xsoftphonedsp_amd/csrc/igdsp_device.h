@@ -16,13 +16,6 @@
 
 namespace igdsp {
 
-static inline uint32_t blocks_for(uint64_t items, uint32_t per_block, uint32_t cap)
-{
-    uint64_t b = (items + per_block - 1) / per_block;
-    if (b < 1) b = 1;
-    return (uint32_t)(b > cap ? cap : b);
-}
-
 // ----------------------------------------------------------------------------
 // G.711 expansion magnitude by the ITU segment formula (used to build the LDS
 // tables in-kernel; no table ever comes from host memory).
@@ -320,7 +313,6 @@ __device__ __forceinline__ void hold_add(igdsp_chan_hold *gp, const igdsp_chan_h
 // by ONE v_perm_b32: byte0 = replica offset, byte1 = law|code7.
 // (|x|/4)^2 <= 8064^2 < 2^26 so 16 samples fit a u32 partial; x^2 = 16 * that.
 // ============================================================================
-constexpr int kLutEntries = 256 * 32;   // uint2 each
 
 __device__ __forceinline__ void fill_lut(uint2 *lut)
 {
@@ -430,7 +422,6 @@ __device__ __forceinline__ uint4 pack_stats160(uint64_t s, uint32_t peak, uint32
     return make_uint4((uint32_t)sumsq, (uint32_t)(sumsq >> 32), __float_as_uint(rms), peak | (byte_mean << 16) | (flags << 24));
 }
 
-constexpr int kSuperFrames = 2 * kChunkFrames;                 // 64
 constexpr int kStripEntries = kSuperFrames * kPiecesPerFrame;  // 640 x 8 B = 5 KiB per wave
 // Order in which batches of work items are visited: the two halves of the item range alternately, so that at any
 // moment the launch reads and WRITES in two distant places of every buffer.  Write streams spread over two classes of

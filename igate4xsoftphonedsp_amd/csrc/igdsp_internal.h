@@ -4,19 +4,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "igdsp.h"
+#include "igdsp_route.h"
 
 namespace igdsp {
-
-// Geometry of the tuned n == 160 path: a wavefront owns a super-chunk of 64 consecutive channel-frames
-// (10 240 contiguous bytes), processed as two halves of 32 frames = 5120 bytes = 5 wave-wide 16 B/lane loads each.
-constexpr int kFrame = IGDSP_SAMPLES_PER_FRAME;        // 160 B
-constexpr int kChunkFrames = 32;
-constexpr int kChunkBytes = kChunkFrames * kFrame;     // 5120
-constexpr int kPiecesPerFrame = kFrame / 16;           // 10 x 16 B
-constexpr int kPiecesPerChunk = kChunkFrames * kPiecesPerFrame;  // 320
-constexpr int kLoadsPerChunk = kPiecesPerChunk / 64;   // 5
-constexpr int kWavesPerBlock = 16;                     // 1024 threads, one block per CU
-constexpr int kBlockThreads = kWavesPerBlock * 64;
 
 struct LaunchCfg {
     int compute_units;   // persistent grid = compute_units blocks
@@ -26,7 +16,7 @@ struct LaunchCfg {
     const uint8_t *enc_tab = nullptr;   // igdsp_encode: the context's ready-made compressor table of this lineage (2 x 65 536 bytes), or nullptr
 };
 
-// The ED-137 gated window of a fused packet launch (igdsp_decode_meter_window): work = uint4[n_seg][3][C] unit summaries (window
+// The ED-137 gated window of a fused packet launch (launch_decode_meter_window): work = uint4[n_seg][3][C] unit summaries (window
 // words 0, 1 and the silence-run word, k_window_finish); a unit = (one of n_groups = C / 64 channel groups, one of n_seg segments
 // of the F frames).
 struct WinArgs {
@@ -41,7 +31,6 @@ struct WinArgs {
 };
 constexpr int kWinRing = 16;                             // frames of a group that may be folded before an earlier one is (power of two)
 constexpr int kWinBlkCh = 256;                           // channels a block can own (7 dwords of LDS each)
-constexpr uint32_t kWinMaxSeg = 8;                       // igdsp_window_work_bytes = kWinMaxSeg x C x 48
 
 hipError_t init_device_attributes();       // per-device kernel attributes; igdsp_create calls it with its device current
 hipError_t launch_decode_meter(const LaunchCfg &cfg, int variant,
@@ -51,7 +40,13 @@ hipError_t launch_decode_meter(const LaunchCfg &cfg, int variant,
                                igdsp_aggregate *agg, uint32_t rank, hipStream_t s);
 hipError_t launch_decode_meter_rtp(const LaunchCfg &cfg, const uint8_t *slots, const uint16_t *sizes, const uint8_t *codec, uint32_t C,
                                    uint32_t F, uint32_t stride, uint32_t hdr, igdsp_frame_stats *stats, igdsp_rtp_info *info,
-                                   igdsp_aggregate *agg, uint32_t rank, hipStream_t s, const uint8_t *radio = nullptr, const WinArgs *win = nullptr);
+                                   igdsp_aggregate *agg, uint32_t rank, hipStream_t s, const uint8_t *radio = nullptr);
+// igdsp_decode_meter_window's fused path (C % 64 == 0, win.d_work given): the window folded into the decode + meter pass, in the form
+// window_route picks, k_window_finish included.  *too_long: F needs more than kWinMaxSeg segments of 65 535 frames; nothing launched.
+hipError_t launch_decode_meter_window(const LaunchCfg &cfg, const uint8_t *packets, const uint16_t *sizes, const uint8_t *codec, uint32_t C,
+                                      uint32_t F, uint32_t stride, uint32_t hdr, const uint8_t *radio, igdsp_frame_stats *stats,
+                                      igdsp_rtp_info *info, igdsp_aggregate *agg, uint32_t rank, const igdsp_window &win, bool *too_long,
+                                      hipStream_t s);
 // window fold of records (per-frame ED-137 gates, silence run): igdsp_window_update; and the chaining of a fused launch's per-segment
 // run summaries into probe[c]
 hipError_t launch_window_update(const igdsp_frame_stats *stats, const igdsp_rtp_info *info, const uint16_t *len, uint32_t C, uint32_t F, uint32_t n,

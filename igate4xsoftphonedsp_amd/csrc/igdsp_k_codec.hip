@@ -136,14 +136,7 @@ __global__ __launch_bounds__(1024) void k_encode_v8_table(const int16_t *__restr
 // enc_uni (one block per CU, kEncWaves waves).  The whole LDS address {law, v.hi, v.lo} is one v_perm_b32 of the loaded
 // PCM word, so a sample costs ~2 VALU + one ds_read_u8 and the kernel sits on the copy-like HBM bound.  Frame /
 // channel bookkeeping is incremental (adds and compares): the grid-stride step is decomposed once per thread into
-// whole frames + groups, so no division runs inside the loop.
-// Waves per block (late round 3, same-box A/B builds): 16 / 14 / 12 / 10 / 8 / 6 / 4 → 0.651–0.662 / 0.650–0.658 / 0.641–0.642 / 0.636–0.637 / 0.646–0.648 /
-// 0.770 / 1.05 ms.  The 2 : 1 read : write mix sits between the read-heavy kernels (the more waves the better) and the store / round-trip
-// kernels (4–6): ten waves of 8 KiB chunks keep enough loads in flight, more only add write fronts.
-#ifndef IGDSP_ENC_WAVES
-#define IGDSP_ENC_WAVES 10
-#endif
-constexpr int kEncWaves = IGDSP_ENC_WAVES;
+// whole frames + groups, so no division runs inside the loop.  Waves per block: kEncWaves (igdsp_route.h).
 template <int VARIANT>
 __global__ __launch_bounds__(kEncWaves * 64) void k_encode_lut16(const int16_t *__restrict__ pcm, const uint8_t *__restrict__ codec,
                                                        uint32_t C, uint32_t n, uint32_t n_groups, uint8_t *__restrict__ out,
@@ -250,10 +243,6 @@ __global__ __launch_bounds__(256) void k_encode_scalar(const int16_t *__restrict
 // Same LUT, strip and load pipeline as k_meter_chunk64; the re-encode is the full compression
 // arithmetic (enc_uni) applied to the decoded PCM value, not a shortcut.  Needs C % 64 == 0, n == 160.
 // ============================================================================
-#ifndef IGDSP_RT_WAVES
-#define IGDSP_RT_WAVES 12
-#endif
-constexpr int kRtWaves = IGDSP_RT_WAVES;
 // LDS map of k_roundtrip_chunk64 (158 KiB of the CU's 160 KiB), chosen so that both table addresses come out
 // of the instruction stream without adds:
 //   [  0,  32 KiB)  compressor grid table  tab[law][neg][k] = enc(neg ? -4k : 4k), one byte per cell
@@ -465,10 +454,6 @@ __global__ __launch_bounds__(kRtWaves * 64) void k_roundtrip_chunk64(
 // frame peak comes from max(entry.y) >> 16 (the low bytes only break ties).  mu-law 0x7F ("-0") decodes to PCM 0 and
 // re-encodes as enc(0) = 0xFF, exactly as two's-complement PCM between a real decoder and encoder would.
 // ============================================================================
-#ifndef IGDSP_RTL_WAVES
-#define IGDSP_RTL_WAVES 12
-#endif
-constexpr int kRtlWaves = IGDSP_RTL_WAVES;
 
 // Every one of the 256 entries is evaluated ONCE per block (two compressor evaluations each) into its replica 0 and copied to the
 // other 31 replicas from there: with the few waves the block-owned round trip runs (6 x 64 threads) evaluating all 8 192 slots took
@@ -673,8 +658,6 @@ __global__ __launch_bounds__(kRtlWaves * 64) void k_roundtrip_lut64(
 // needs, as the item orders of k_roundtrip_lut64 do.
 // ============================================================================
 constexpr int kRtBlkCh = 256;                             // channels a block can own (7 dwords of LDS each)
-constexpr int kRtbWaves = 12;                             // strips for up to 12 waves; the launcher starts fewer (rtb_waves)
-constexpr int kRtsbWaves = 10;                            // the same for k_roundtrip_strided<BLK> (its strips and rings are larger)
 
 template <int VARIANT>
 __global__ __launch_bounds__(kRtbWaves * 64) void k_roundtrip_blk64(
@@ -1357,39 +1340,24 @@ __global__ __launch_bounds__(1024) void k_build_enc_table(uint8_t *__restrict__ 
 
 hipError_t launch_build_enc_table(int variant, uint8_t *tab, hipStream_t s)
 {
-    if (variant == IGDSP_ENC_G191) hipLaunchKernelGGL((k_build_enc_table<IGDSP_ENC_G191>), dim3(128), dim3(1024), 0, s, tab);
-    else                           hipLaunchKernelGGL((k_build_enc_table<IGDSP_ENC_SUN16>), dim3(128), dim3(1024), 0, s, tab);
+    with_enc(variant, [&](auto V) { hipLaunchKernelGGL((k_build_enc_table<V>), dim3(128), dim3(1024), 0, s, tab); });
     return hipGetLastError();
 }
 
 hipError_t launch_encode(const LaunchCfg &cfg, const int16_t *pcm, const uint8_t *codec, uint32_t C, uint32_t F,
                          uint32_t n, uint8_t *out, int variant, hipStream_t s)
 {
-    const uint64_t n_samples = (uint64_t)C * F * n;
-    if (n_samples == 0) return hipSuccess;
-    const bool v8 = ((n & 7u) == 0u) && ((reinterpret_cast<uintptr_t>(pcm) & 15u) == 0u) &&
-                    ((reinterpret_cast<uintptr_t>(out) & 7u) == 0u);
-    const uint32_t cap = (uint32_t)cfg.compute_units * 8u;
-    if (v8 && n_samples >= (1u << 25) && (n_samples >> 3) < 0xFFFF0000ull) {   // large batches: full 16-bit table, one block per CU (32-bit group ids)
-        const uint32_t groups = (uint32_t)(n_samples >> 3);    // 32-bit group ids (checked above)
-        const uint32_t grid = blocks_for(groups, 1024, (uint32_t)cfg.compute_units);
-        if (variant == IGDSP_ENC_G191) hipLaunchKernelGGL((k_encode_lut16<IGDSP_ENC_G191>), dim3(grid), dim3(kEncWaves * 64), 0, s, pcm, codec, C, n, groups, out, cfg.gqueue, cfg.enc_tab);
-        else                           hipLaunchKernelGGL((k_encode_lut16<IGDSP_ENC_SUN16>), dim3(grid), dim3(kEncWaves * 64), 0, s, pcm, codec, C, n, groups, out, cfg.gqueue, cfg.enc_tab);
-    } else if (v8 && n_samples >= (1u << 22)) {                 // big batches: table-driven compressor, persistent blocks
-        const uint64_t groups = n_samples >> 3;
-        const uint32_t grid = blocks_for(groups, 1024, (uint32_t)cfg.compute_units * 2u);
-        if (variant == IGDSP_ENC_G191) hipLaunchKernelGGL((k_encode_v8_table<IGDSP_ENC_G191>), dim3(grid), dim3(1024), 0, s, pcm, codec, C, n, groups, out);
-        else                           hipLaunchKernelGGL((k_encode_v8_table<IGDSP_ENC_SUN16>), dim3(grid), dim3(1024), 0, s, pcm, codec, C, n, groups, out);
-    } else if (v8) {
-        const uint64_t groups = n_samples >> 3;
-        const uint32_t grid = blocks_for(groups, 256, cap);
-        if (variant == IGDSP_ENC_G191) hipLaunchKernelGGL((k_encode_v8<IGDSP_ENC_G191>), dim3(grid), dim3(256), 0, s, pcm, codec, C, n, groups, out);
-        else                           hipLaunchKernelGGL((k_encode_v8<IGDSP_ENC_SUN16>), dim3(grid), dim3(256), 0, s, pcm, codec, C, n, groups, out);
-    } else {
-        const uint32_t grid = blocks_for(n_samples, 256, cap);
-        if (variant == IGDSP_ENC_G191) hipLaunchKernelGGL((k_encode_scalar<IGDSP_ENC_G191>), dim3(grid), dim3(256), 0, s, pcm, codec, C, n, n_samples, out);
-        else                           hipLaunchKernelGGL((k_encode_scalar<IGDSP_ENC_SUN16>), dim3(grid), dim3(256), 0, s, pcm, codec, C, n, n_samples, out);
-    }
+    const EncRoute r = encode_route(C, F, n, reinterpret_cast<uintptr_t>(pcm), reinterpret_cast<uintptr_t>(out), (uint32_t)cfg.compute_units);
+    const dim3 g(r.grid), b(r.threads);
+    with_enc(variant, [&](auto V) {
+        switch (r.form) {
+        case EncForm::none: break;
+        case EncForm::lut16: hipLaunchKernelGGL((k_encode_lut16<V>), g, b, 0, s, pcm, codec, C, n, (uint32_t)r.groups, out, cfg.gqueue, cfg.enc_tab); break;
+        case EncForm::v8_table: hipLaunchKernelGGL((k_encode_v8_table<V>), g, b, 0, s, pcm, codec, C, n, r.groups, out); break;
+        case EncForm::v8: hipLaunchKernelGGL((k_encode_v8<V>), g, b, 0, s, pcm, codec, C, n, r.groups, out); break;
+        case EncForm::scalar: hipLaunchKernelGGL((k_encode_scalar<V>), g, b, 0, s, pcm, codec, C, n, r.groups, out); break;
+        }
+    });
     return hipGetLastError();
 }
 
@@ -1399,138 +1367,49 @@ hipError_t launch_encode_table(const LaunchCfg &cfg, const int16_t *pcm, const u
     const uint64_t n_samples = (uint64_t)C * F * n;
     if (n_samples == 0) return hipSuccess;
     const uint32_t grid = blocks_for(n_samples, 1024 * 16, (uint32_t)cfg.compute_units);
-    if (variant == IGDSP_ENC_G191) hipLaunchKernelGGL((k_encode_table<IGDSP_ENC_G191>), dim3(grid), dim3(1024), 0, s, pcm, codec, C, n, n_samples, out);
-    else                           hipLaunchKernelGGL((k_encode_table<IGDSP_ENC_SUN16>), dim3(grid), dim3(1024), 0, s, pcm, codec, C, n, n_samples, out);
+    with_enc(variant, [&](auto V) { hipLaunchKernelGGL((k_encode_table<V>), dim3(grid), dim3(1024), 0, s, pcm, codec, C, n, n_samples, out); });
     return hipGetLastError();
-}
-
-// Waves per block of the block-owned round-trip kernels.  Unlike the read-heavy kernels (the more waves the better: each has one
-// item of loads in flight) the 1 : 1 read / write mix is fastest with FEW resident waves per CU: at 160-byte frames 16 / 14 / 12 / 10
-// / 8 / 6 / 4 / 3 waves ran 0.4613 / 0.4607 / 0.4580 / 0.4552 / 0.4522 / 0.4498 / 0.4519 / 0.4785 ms in same-box A/B builds.
-static uint32_t rtb_waves(uint32_t n, int max_waves, uint32_t gpb)
-{
-    // about 60 KB of loads in flight per CU: 6 waves at 160 bytes per frame, 4 at 240, 10 (the strips' limit) at 80 and below; the tailed
-    // sizes want two more (164 bytes: 4 / 6 / 8 / 10 waves 0.6413 / 0.5146 / 0.4854 / 0.4915 ms; 240: 0.6636 / 0.6740 / 0.6746 / 0.6804)
-    uint32_t w = n >= 200u ? 4u : (n > 160u ? 8u : (n >= 120u ? 6u : (n >= 48u ? 10u : 16u)));
-    if (const char *e = std::getenv("IGDSP_RTB_WAVES")) w = (uint32_t)std::max(1, std::atoi(e));   // experiments
-    return std::max(std::max(gpb, 1u), std::min(w, (uint32_t)max_waves));                         // (a wave per owned group folds it at the block's end)
-}
-
-// Where the block-owned form pays (65 536 channels = 256 blocks of four groups is the tuned case; measured around it, 128 frames,
-// placed buffers, static / block-owned ms): 0.6 to 1 round of blocks — 10 240 ch 0.0863 / 0.0841, 12 288 ch 0.1108 / 0.0856.  Below 0.6 of a
-// round the static form spreads its units over more CUs (8 192 ch 0.0754 / 0.0804, 4 096 ch 0.0649 / 0.0769); 1.5 rounds idle half the chip
-// in the second (24 576 ch 0.2003 / 0.2099, 49 152 ch 0.3572 / 0.3769), and even two whole rounds lose to the static form, whose blocks
-// stay (131 072 ch 0.9216 / 0.9311).
-static bool rtb_fills(uint32_t blocks, uint32_t rounds, uint32_t cus)
-{
-    return rounds == 1u && blocks * 10u >= cus * 6u;
 }
 
 hipError_t launch_roundtrip(const LaunchCfg &cfg, int kernel_variant, const uint8_t *payload, const uint8_t *codec, uint32_t C, uint32_t F,
                             uint32_t n, uint8_t *out, igdsp_frame_stats *stats, igdsp_chan_hold *hold,
                             const uint8_t *gate, int variant, hipStream_t s)
 {
-    if ((uint64_t)C * F == 0) return hipSuccess;
-    // Item order of the fused kernels.  Consecutive groups per block pay when the output's halves lie in two memory classes
-    // (0.4695 vs 0.4756 ms); with the whole output in one class it is the other way round (0.5116 vs 0.4920 ms): tools/rt_knobs.py,
-    // alternating in one process.  IGDSP_RT_ORDER overrides (experiments, and the test of the order the placement would pick).
-    uint32_t order = cfg.out_spread ? 1u : 0u;
-    if (const char *e = std::getenv("IGDSP_RT_ORDER")) order = (uint32_t)std::atoi(e);
-    uint32_t mid_start = cfg.out_spread ? 1u : 0u;               // block-owned form: odd blocks walk the frames from the middle (both halves of a spread output written at any moment)
-    if (const char *e = std::getenv("IGDSP_RT_MID")) mid_start = std::atoi(e) != 0 ? 1u : 0u;   // experiments
-    // The fused channel-group-major kernels take whole groups of 64 channels of 160-byte frames in 16-byte aligned
-    // buffers; the C % 64 channels left over, and every other shape (n != 160, unaligned buffers), go through
-    // k_roundtrip_general on the same stream.  kernel_variant 4 selects the compressor-cell-table form of the fused
-    // kernel (k_roundtrip_chunk64, kept for A/B runs); the default folds the compressor into the expansion LUT.
-    const bool aligned = ((reinterpret_cast<uintptr_t>(payload) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(stats)) & 15u) == 0u;
-    // the reference's other frame sizes (24, 80, 164 / 168, 240; dword-aligned buffers suffice) keep the fused walk: k_roundtrip_strided
-    const uint32_t Qn = n >> 4, Tn = (n >> 2) & 3u;
-    const bool strided = kernel_variant != 1 && n != (uint32_t)kFrame && (n & 3u) == 0u && Tn != 3u && n >= 16u &&
-                         (((reinterpret_cast<uintptr_t>(payload) | reinterpret_cast<uintptr_t>(out)) & 3u) == 0u) && ((reinterpret_cast<uintptr_t>(stats) & 15u) == 0u) &&
-                         ((Qn == 1u && Tn != 0u) || (Qn == 5u && Tn == 0u) || (Qn == 10u && Tn != 0u) || (Qn == 15u && Tn == 0u));
-    if (strided && C >= (uint32_t)kSuperFrames) {
-        const uint32_t n_groups_s = C / kSuperFrames;
-        const uint32_t want = (uint32_t)cfg.compute_units * (uint32_t)kRtlWaves;
-        uint32_t n_seg = n_groups_s >= want ? 1u : (want + n_groups_s - 1u) / n_groups_s;
-        n_seg = std::max(1u, std::min(n_seg, std::max(1u, F / 8u)));
-        n_seg = std::max(n_seg, F / 65535u + 1u);
-        const uint32_t grid = blocks_for((uint64_t)n_groups_s * n_seg, kRtlWaves, (uint32_t)cfg.compute_units);
-        // block-owned form (same rule as for 160-byte frames below)
-        uint32_t gpb = 1u;
-        const uint32_t cus = (uint32_t)std::max(1, cfg.compute_units);
-        for (uint32_t g = 4u; g > 1u; g >>= 1) if (n_groups_s % g == 0u && n_groups_s / g >= cus) { gpb = g; break; }
-        if (const char *e = std::getenv("IGDSP_RT_GPB")) { const uint32_t g = (uint32_t)std::atoi(e); if ((g == 1u || g == 2u || g == 4u) && n_groups_s % g == 0u) gpb = g; }   // tests
-        const uint32_t blocks = n_groups_s / gpb, rounds = (blocks + cus - 1u) / cus;
-        bool blk = F <= 65535u && rtb_fills(blocks, rounds, cus);
-        if (const char *e = std::getenv("IGDSP_RT_BLK")) blk = F <= 65535u && std::atoi(e) != 0;       // experiments and tests
-        if (blk) {
-            const uint32_t gsh = gpb == 4u ? 2u : (gpb == 2u ? 1u : 0u);
-            const dim3 gb(blocks), bb(rtb_waves(n, Qn <= 1u ? 16 : kRtsbWaves, gpb) * 64u);
-#define IGDSP_RTSB(QV, TV)                                                                                                                                     \
-            if (Qn == QV && (Tn != 0u) == TV) {                                                                                                                 \
-                if (variant == IGDSP_ENC_G191) hipLaunchKernelGGL((k_roundtrip_strided<QV, TV, IGDSP_ENC_G191, true>), gb, bb, 0, s, payload, codec, C, F, n, out, stats, hold, gate, gpb, n_groups_s, gsh | (mid_start << 2));  \
-                else                           hipLaunchKernelGGL((k_roundtrip_strided<QV, TV, IGDSP_ENC_SUN16, true>), gb, bb, 0, s, payload, codec, C, F, n, out, stats, hold, gate, gpb, n_groups_s, gsh | (mid_start << 2)); \
-            }
-            IGDSP_RTSB(1, true) IGDSP_RTSB(5, false) IGDSP_RTSB(10, true) IGDSP_RTSB(15, false)
-#undef IGDSP_RTSB
-        } else {
-        const dim3 g3(grid), b3(kRtlWaves * 64);
-#define IGDSP_RTS(QV, TV)                                                                                                                                      \
-        if (Qn == QV && (Tn != 0u) == TV) {                                                                                                                     \
-            if (variant == IGDSP_ENC_G191) hipLaunchKernelGGL((k_roundtrip_strided<QV, TV, IGDSP_ENC_G191>), g3, b3, 0, s, payload, codec, C, F, n, out, stats, hold, gate, n_seg, n_groups_s, order);  \
-            else                           hipLaunchKernelGGL((k_roundtrip_strided<QV, TV, IGDSP_ENC_SUN16>), g3, b3, 0, s, payload, codec, C, F, n, out, stats, hold, gate, n_seg, n_groups_s, order); \
+    const RtRoute r = roundtrip_route(C, F, n, kernel_variant, reinterpret_cast<uintptr_t>(payload), reinterpret_cast<uintptr_t>(out),
+                                      reinterpret_cast<uintptr_t>(stats), cfg.out_spread, (uint32_t)cfg.compute_units, knobs_from_env());
+    const dim3 g(r.grid), b(r.threads);
+    with_enc(variant, [&](auto V) {
+        switch (r.form) {
+        case RtForm::none: break;
+        case RtForm::lut64:
+            hipLaunchKernelGGL((k_roundtrip_lut64<V>), g, b, 0, s, payload, codec, C, F, out, stats, hold, gate, r.n_seg, r.n_groups, r.order);
+            break;
+        case RtForm::chunk64:
+            hipLaunchKernelGGL((k_roundtrip_chunk64<V>), g, b, 0, s, payload, codec, C, F, out, stats, hold, gate, r.n_seg, r.n_groups);
+            break;
+        case RtForm::blk64:
+            hipLaunchKernelGGL((k_roundtrip_blk64<V>), g, b, 0, s, payload, codec, C, F, out, stats, hold, gate, r.gpb, r.gsh, r.mid_start);
+            break;
+        case RtForm::strided:
+            with_key(RoundtripStridedKeys{}, r.key, [&](auto K) {
+                hipLaunchKernelGGL((k_roundtrip_strided<key_q(K), key_tail(K), V>), g, b, 0, s, payload, codec, C, F, n, out, stats, hold, gate, r.n_seg,
+                                   r.n_groups, r.order);
+            });
+            break;
+        case RtForm::strided_blk:
+            with_key(RoundtripStridedKeys{}, r.key, [&](auto K) {
+                hipLaunchKernelGGL((k_roundtrip_strided<key_q(K), key_tail(K), V, true>), g, b, 0, s, payload, codec, C, F, n, out, stats, hold, gate,
+                                   r.gpb, r.n_groups, r.gsh | (r.mid_start << 2));
+            });
+            break;
         }
-        IGDSP_RTS(1, true) IGDSP_RTS(5, false) IGDSP_RTS(10, true) IGDSP_RTS(15, false)
-#undef IGDSP_RTS
-        }
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        const uint32_t c_first = n_groups_s * (uint32_t)kSuperFrames, c_count = C - c_first;
-        if (c_count != 0u) {
-            const uint32_t gridg = blocks_for(c_count, 4, (uint32_t)cfg.compute_units * 8u);
-            if (variant == IGDSP_ENC_G191) hipLaunchKernelGGL((k_roundtrip_general<IGDSP_ENC_G191>), dim3(gridg), dim3(256), 0, s, payload, codec, C, F, n, c_first, c_count, out, stats, hold, gate);
-            else                           hipLaunchKernelGGL((k_roundtrip_general<IGDSP_ENC_SUN16>), dim3(gridg), dim3(256), 0, s, payload, codec, C, F, n, c_first, c_count, out, stats, hold, gate);
-        }
-        return hipGetLastError();
-    }
-    const uint32_t n_groups = (n == (uint32_t)kFrame && aligned && kernel_variant != 1) ? C / kSuperFrames : 0u;
-    if (n_groups != 0u) {
-        // fill the chip: at least one work item per resident wave; a segment is never shorter than 8 frames
-        const int waves = kernel_variant == 4 ? kRtWaves : kRtlWaves;
-        const uint32_t want = (uint32_t)cfg.compute_units * (uint32_t)waves;
-        uint32_t n_seg = n_groups >= want ? 1u : (want + n_groups - 1u) / n_groups;
-        if (const char *e = std::getenv("IGDSP_RT_NSEG")) n_seg = (uint32_t)std::max(1, std::atoi(e));   // experiments
-        n_seg = std::max(1u, std::min(n_seg, std::max(1u, F / 8u)));
-        n_seg = std::max(n_seg, F / 65535u + 1u);               // the fused kernels count silent / clipped frames of a segment in 16 bits
-        const uint32_t grid = blocks_for((uint64_t)n_groups * n_seg, waves, (uint32_t)cfg.compute_units);
-        // block-owned form: gpb = as many groups per block (<= 4: the LDS) as still give every CU a block; taken where rtb_fills says
-        // it pays and F fits the 16-bit silent / clipped counts
-        uint32_t gpb = 1u;
-        const uint32_t cus = (uint32_t)std::max(1, cfg.compute_units);
-        for (uint32_t g = 4u; g > 1u; g >>= 1) if (n_groups % g == 0u && n_groups / g >= cus) { gpb = g; break; }
-        if (const char *e = std::getenv("IGDSP_RT_GPB")) { const uint32_t g = (uint32_t)std::atoi(e); if ((g == 1u || g == 2u || g == 4u) && n_groups % g == 0u) gpb = g; }   // tests
-        const uint32_t blocks = n_groups / gpb, rounds = (blocks + cus - 1u) / cus;
-        bool blk = kernel_variant != 4 && F <= 65535u && rtb_fills(blocks, rounds, cus);
-        if (const char *e = std::getenv("IGDSP_RT_BLK")) blk = kernel_variant != 4 && F <= 65535u && std::atoi(e) != 0;   // experiments and tests
-        if (blk) {
-            const uint32_t gsh = gpb == 4u ? 2u : (gpb == 2u ? 1u : 0u);
-            if (variant == IGDSP_ENC_G191) hipLaunchKernelGGL((k_roundtrip_blk64<IGDSP_ENC_G191>), dim3(blocks), dim3(rtb_waves(n, kRtbWaves, gpb) * 64u), 0, s, payload, codec, C, F, out, stats, hold, gate, gpb, gsh, mid_start);
-            else                           hipLaunchKernelGGL((k_roundtrip_blk64<IGDSP_ENC_SUN16>), dim3(blocks), dim3(rtb_waves(n, kRtbWaves, gpb) * 64u), 0, s, payload, codec, C, F, out, stats, hold, gate, gpb, gsh, mid_start);
-        } else if (kernel_variant == 4) {
-            if (variant == IGDSP_ENC_G191) hipLaunchKernelGGL((k_roundtrip_chunk64<IGDSP_ENC_G191>), dim3(grid), dim3(kRtWaves * 64), 0, s, payload, codec, C, F, out, stats, hold, gate, n_seg, n_groups);
-            else                           hipLaunchKernelGGL((k_roundtrip_chunk64<IGDSP_ENC_SUN16>), dim3(grid), dim3(kRtWaves * 64), 0, s, payload, codec, C, F, out, stats, hold, gate, n_seg, n_groups);
-        } else {
-            if (variant == IGDSP_ENC_G191) hipLaunchKernelGGL((k_roundtrip_lut64<IGDSP_ENC_G191>), dim3(grid), dim3(kRtlWaves * 64), 0, s, payload, codec, C, F, out, stats, hold, gate, n_seg, n_groups, order);
-            else                           hipLaunchKernelGGL((k_roundtrip_lut64<IGDSP_ENC_SUN16>), dim3(grid), dim3(kRtlWaves * 64), 0, s, payload, codec, C, F, out, stats, hold, gate, n_seg, n_groups, order);
-        }
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    const uint32_t c_first = n_groups * (uint32_t)kSuperFrames, c_count = C - c_first;
-    if (c_count != 0u) {
-        const uint32_t grid = blocks_for(c_count, 4, (uint32_t)cfg.compute_units * 8u);
-        if (variant == IGDSP_ENC_G191) hipLaunchKernelGGL((k_roundtrip_general<IGDSP_ENC_G191>), dim3(grid), dim3(256), 0, s, payload, codec, C, F, n, c_first, c_count, out, stats, hold, gate);
-        else                           hipLaunchKernelGGL((k_roundtrip_general<IGDSP_ENC_SUN16>), dim3(grid), dim3(256), 0, s, payload, codec, C, F, n, c_first, c_count, out, stats, hold, gate);
+    });
+    if (r.form != RtForm::none) { hipError_t e = hipGetLastError(); if (e != hipSuccess) return e; }
+    if (r.gen_grid != 0u) {
+        const uint32_t c_count = C - r.c_first;
+        with_enc(variant, [&](auto V) {
+            hipLaunchKernelGGL((k_roundtrip_general<V>), dim3(r.gen_grid), dim3(256), 0, s, payload, codec, C, F, n, r.c_first, c_count, out, stats, hold, gate);
+        });
     }
     return hipGetLastError();
 }

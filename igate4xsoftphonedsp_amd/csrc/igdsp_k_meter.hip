@@ -207,15 +207,7 @@ __device__ __forceinline__ void process_half(const uint2 *lut, uint2 *strip_half
 // Balance: block b owns super-chunks b, b+G, b+2G, ...; its 16 waves pull the next one from an LDS
 // counter, so the waves of a CU finish within one iteration of each other.
 // ============================================================================
-// waves per block: 16 (1024 threads, 128 VGPRs) for the meter-only kernel: a read-heavy kernel wants every wave it can get, each
-// has one super-chunk of loads in flight.  The PCM-store variant writes two bytes for every byte it reads, and a 1 : 2 mix is
-// fastest with FEW resident waves per CU — 12 / 10 / 8 / 6 / 5 / 4 / 3 / 2 waves: 0.6706 / 0.6680 / 0.6636 / 0.6573 / 0.6520 / 0.6388 / 0.6995 /
-// 1.013 ms in same-box A/B builds (late round 3; 12 had been chosen for its registers) — every wave is one more front of 20 KiB
-// write bursts, and four already keep enough loads in flight.
-#ifndef IGDSP_STORE_WAVES
-#define IGDSP_STORE_WAVES 4
-#endif
-template <bool STORE_PCM> struct ChunkGeom { static constexpr int kWaves = STORE_PCM ? IGDSP_STORE_WAVES : kWavesPerBlock; };
+// waves per block: ChunkGeom (igdsp_route.h).
 
 // DIAG: a separate diagnostic instantiation (never the shipped path) that stamps where a
 // wave's cycles go; the stamps leave only through `diag`, no output is computed from them.
@@ -380,7 +372,6 @@ __global__ __launch_bounds__(ChunkGeom<STORE_PCM>::kWaves * 64) void k_meter_chu
 // load registers too slowly" bound of variant 2.  Static interleaved distribution; item k of a wave
 // lives in register set k % 4 and each piece is re-loaded from item k + 4 the moment it is folded.
 // ============================================================================
-constexpr int kFatWaves = 8;
 constexpr int kFatDepth = 4;
 
 template <bool AGG>
@@ -492,8 +483,6 @@ __global__ __launch_bounds__(kFatWaves * 64) void k_meter_fat(
 // Algorithmic bytes per sample: (n + 1 + 16) / n.
 // ============================================================================
 constexpr int kImgMaxPieces = IGDSP_MAX_PAYLOAD * kSuperFrames / 16 / 64;      // 16 wave-wide loads cover 64 frames of 256 bytes
-
-constexpr uint32_t kImgMaxWaves = 12;          // 768 threads: up to 170 VGPRs, room for the sixteen piece registers of the next item
 
 template <bool AGG, bool RAGGED>
 __global__ __launch_bounds__(kImgMaxWaves * 64) void k_meter_image(
@@ -676,12 +665,7 @@ __global__ __launch_bounds__(kImgMaxWaves * 64) void k_meter_image(
 // ============================================================================
 // STORE: the decoded int16 PCM goes out as well (pcm[F][C][n], dword aligned): every payload piece stores its 32 bytes as two
 // dword-aligned 16-byte stores, the tail piece the 8 T bytes of the frame's tail samples; 12 waves (eight more live registers).
-#ifndef IGDSP_SSTORE_WAVES
-#define IGDSP_SSTORE_WAVES 0
-#endif
-// (the PCM-store variant, a 1 : 2 read : write mix, is fastest with few waves, as k_meter_chunk64<STORE>: 164-byte frames 12 / 8 / 6 / 5 / 4
-// waves 0.7264 / 0.7133 / 0.7036 / 0.741 / 0.861 ms; 240: 10 / 8 / 6 / 5 / 4 0.9926 / 0.9865 / 0.980 / 0.9766 / 0.9975; 80: 12 / 10 / 8 / 6 0.3472 / 0.3462 / 0.3424 / 0.3402)
-template <int QP, bool STORE = false> struct StridedGeom { static constexpr int kWaves = STORE ? (IGDSP_SSTORE_WAVES ? IGDSP_SSTORE_WAVES : (QP <= 2 ? 16 : 6)) : (QP <= 11 ? 16 : 12); };
+// (waves per block: StridedGeom, igdsp_route.h)
 
 template <int Q, bool TAIL, bool AGG, bool STORE = false>
 __global__ __launch_bounds__((StridedGeom<Q + (TAIL ? 1 : 0), STORE>::kWaves * 64)) void k_meter_strided(
@@ -979,13 +963,7 @@ __global__ __launch_bounds__((StridedGeom<Q + (TAIL ? 1 : 0), STORE>::kWaves * 6
 // is long enough for the silence probe (bytes 28 / 38 / 48 need n > 48).  Items of 64 frames; a queue slot stands for kTinySlot
 // consecutive items (four: the slots are what the block / device queue balances); kTinyDepth items of loads stay in flight per wave across slot boundaries.
 // ============================================================================
-constexpr int kTinyWaves = 16, kTinyDepth = 4;
-// items per queue slot (>= kTinyDepth: the prologue).  16 made a wave's share two slots, i.e. static in effect; 32 / 16 / 8 / 4 items: 0.0683 /
-// 0.0693 / 0.0682 / 0.0676 ms at 24-byte frames, 65 536 x 128 (same-box A/B builds, late round 3)
-#ifndef IGDSP_TINY_SLOT
-#define IGDSP_TINY_SLOT 4
-#endif
-constexpr uint32_t kTinySlot = IGDSP_TINY_SLOT;
+// (kTinyWaves, kTinyDepth and kTinySlot: igdsp_route.h)
 
 template <int N4, bool AGG>
 __global__ __launch_bounds__(kTinyWaves * 64) void k_meter_tiny(
@@ -1107,117 +1085,40 @@ hipError_t launch_decode_meter(const LaunchCfg &cfg, int variant, const uint8_t 
                                const uint16_t *len, uint32_t C, uint32_t F, uint32_t n, igdsp_frame_stats *stats,
                                int16_t *pcm, igdsp_aggregate *agg, uint32_t rank, hipStream_t s)
 {
+    const MeterRoute r = decode_meter_route(C, F, n, variant, len != nullptr, reinterpret_cast<uintptr_t>(payload), reinterpret_cast<uintptr_t>(pcm),
+                                            reinterpret_cast<uintptr_t>(stats), (uint32_t)cfg.compute_units, knobs_from_env());
     uint32_t *gq = cfg.gqueue;
-    const uint64_t n_frames64 = (uint64_t)C * F;
-    if (n_frames64 == 0) return hipSuccess;
-    const uint32_t n_frames = (uint32_t)n_frames64;
-    const bool chunk_ok = (n == (uint32_t)kFrame) && (len == nullptr) &&
-                          ((reinterpret_cast<uintptr_t>(payload) & 15u) == 0u) &&
-                          (pcm == nullptr || (reinterpret_cast<uintptr_t>(pcm) & 15u) == 0u) &&
-                          ((reinterpret_cast<uintptr_t>(stats) & 15u) == 0u);
-    // tuned path takes the whole super-chunks (64 frames); the < 64 remaining frames, and every shape it
-    // does not cover, go through the general wave-per-frame kernel on the same stream.
-    uint32_t done = 0;
-    if (variant == 3 && chunk_ok && pcm == nullptr && n_frames >= (uint32_t)kSuperFrames) {
-        const uint32_t n_super = n_frames / kSuperFrames;
-        done = n_super * kSuperFrames;
-        const uint32_t grid = blocks_for(n_super, kFatWaves, (uint32_t)cfg.compute_units);
-        if (agg) hipLaunchKernelGGL((k_meter_fat<true>), dim3(grid), dim3(kFatWaves * 64), 0, s, payload, codec, C, done, stats, agg, rank);
-        else     hipLaunchKernelGGL((k_meter_fat<false>), dim3(grid), dim3(kFatWaves * 64), 0, s, payload, codec, C, done, stats, agg, rank);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    } else if (variant != 1 && chunk_ok && n_frames >= (uint32_t)kSuperFrames) {
-        const uint32_t n_super = n_frames / kSuperFrames;
-        done = n_super * kSuperFrames;
-        uint64_t *nodiag = nullptr;
-        if (pcm) {
-            constexpr int w = ChunkGeom<true>::kWaves;
-            const uint32_t grid = blocks_for(n_super, w, (uint32_t)cfg.compute_units);
-            if (agg) hipLaunchKernelGGL((k_meter_chunk64<true, true>), dim3(grid), dim3(w * 64), 0, s, payload, codec, C, done, stats, pcm, agg, rank, nodiag, gq);
-            else     hipLaunchKernelGGL((k_meter_chunk64<true, false>), dim3(grid), dim3(w * 64), 0, s, payload, codec, C, done, stats, pcm, agg, rank, nodiag, gq);
-        } else {
-            const uint32_t grid = blocks_for(n_super, kWavesPerBlock, (uint32_t)cfg.compute_units);
-            if (agg) hipLaunchKernelGGL((k_meter_chunk64<false, true>), dim3(grid), dim3(kBlockThreads), 0, s, payload, codec, C, done, stats, pcm, agg, rank, nodiag, gq);
-            else     hipLaunchKernelGGL((k_meter_chunk64<false, false>), dim3(grid), dim3(kBlockThreads), 0, s, payload, codec, C, done, stats, pcm, agg, rank, nodiag, gq);
+    uint64_t *nodiag = nullptr;
+    const dim3 g(r.grid), b(r.threads);
+    const uint32_t done = r.done, n_frames = C * F;
+    with_bool(agg != nullptr, [&](auto A) {
+        switch (r.fast) {
+        case MeterFast::none: break;
+        case MeterFast::fat: hipLaunchKernelGGL((k_meter_fat<A>), g, b, 0, s, payload, codec, C, done, stats, agg, rank); break;
+        case MeterFast::chunk:
+            with_bool(r.store, [&](auto P) { hipLaunchKernelGGL((k_meter_chunk64<P, A>), g, b, 0, s, payload, codec, C, done, stats, pcm, agg, rank, nodiag, gq); });
+            break;
+        case MeterFast::tiny:
+            with_key(Keys<4, 5, 6, 7, 8>{}, r.key, [&](auto N4) { hipLaunchKernelGGL((k_meter_tiny<N4, A>), g, b, 0, s, payload, codec, C, done, stats, agg, rank, gq); });
+            break;
+        case MeterFast::strided: {
+            auto launch = [&](auto K, auto P) {
+                hipLaunchKernelGGL((k_meter_strided<key_q(K), key_tail(K), A, P>), g, b, 0, s, payload, codec, C, done, n, stats, agg, rank, gq, pcm);
+            };
+            if (r.store) with_key(ReferenceSizeKeys{}, r.key, [&](auto K) { launch(K, std::true_type{}); });
+            else         with_key(MeterStridedKeys{}, r.key, [&](auto K) { launch(K, std::false_type{}); });
+            break;
         }
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    // 16 .. 32-byte frames, records only: a lane per frame (k_meter_tiny)
-    if (done == 0 && variant != 1 && len == nullptr && pcm == nullptr && (n & 3u) == 0u && n >= 16u && n <= 32u && n_frames >= (uint32_t)kSuperFrames &&
-        ((reinterpret_cast<uintptr_t>(payload) & 3u) == 0u) && ((reinterpret_cast<uintptr_t>(stats) & 15u) == 0u) && std::getenv("IGDSP_NO_TINY") == nullptr) {
-        const uint32_t n_items = n_frames / kSuperFrames;
-        const uint32_t whole = n_items * kSuperFrames;
-        const uint32_t grid = blocks_for((n_items + kTinySlot - 1u) / kTinySlot, kTinyWaves, (uint32_t)cfg.compute_units);
-#define IGDSP_TINY(NV)                                                                                                                              \
-        if ((n >> 2) == NV) {                                                                                                                        \
-            if (agg) hipLaunchKernelGGL((k_meter_tiny<NV, true>), dim3(grid), dim3(kTinyWaves * 64), 0, s, payload, codec, C, whole, stats, agg, rank, gq);   \
-            else     hipLaunchKernelGGL((k_meter_tiny<NV, false>), dim3(grid), dim3(kTinyWaves * 64), 0, s, payload, codec, C, whole, stats, agg, rank, gq);  \
-            done = whole;                                                                                                                            \
         }
-        IGDSP_TINY(4) IGDSP_TINY(5) IGDSP_TINY(6) IGDSP_TINY(7) IGDSP_TINY(8)
-#undef IGDSP_TINY
-        if (done) { hipError_t e = hipGetLastError(); if (e != hipSuccess) return e; }
-    }
-    // dense frames of 16 Q + 4 T bytes, Q in {1, 4, 5, 6, 8, 10, 12, 15}, T <= 2 (the reference's 164 / 24 and the 5 ms multiples
-    // up to 240) keep the chunk pipeline: k_meter_strided.  With PCM output: the reference's own sizes (24, 80, 164 / 168, 240).
-    if (done == 0 && variant != 1 && len == nullptr && (n & 3u) == 0u && n_frames >= (uint32_t)kSuperFrames &&   // (160-byte frames land here only when their buffer is not 16-byte aligned)
-        ((n >> 2) & 3u) != 3u && n >= 16u && ((reinterpret_cast<uintptr_t>(pcm) & 3u) == 0u) &&
-        ((reinterpret_cast<uintptr_t>(payload) & 3u) == 0u) && ((reinterpret_cast<uintptr_t>(stats) & 15u) == 0u) && std::getenv("IGDSP_NO_STRIDED") == nullptr) {
-        const uint32_t Qn = n >> 4;
-        const bool tail = (n & 15u) != 0u;
-        const uint32_t n_super = n_frames / kSuperFrames;
-        const uint32_t whole = n_super * kSuperFrames;
-#define IGDSP_STRIDED(QV, TV)                                                                                                                         \
-        if (Qn == QV && tail == TV && pcm == nullptr) {                                                                                               \
-            constexpr int w = StridedGeom<QV + (TV ? 1 : 0)>::kWaves;                                                                                 \
-            const uint32_t grid = blocks_for(n_super, w, (uint32_t)cfg.compute_units);                                                                \
-            if (agg) hipLaunchKernelGGL((k_meter_strided<QV, TV, true>), dim3(grid), dim3(w * 64), 0, s, payload, codec, C, whole, n, stats, agg, rank, gq, pcm);   \
-            else     hipLaunchKernelGGL((k_meter_strided<QV, TV, false>), dim3(grid), dim3(w * 64), 0, s, payload, codec, C, whole, n, stats, agg, rank, gq, pcm);  \
-            done = whole;                                                                                                                             \
-        }
-#define IGDSP_STRIDED_PCM(QV, TV)                                                                                                                     \
-        if (Qn == QV && tail == TV && pcm != nullptr) {                                                                                               \
-            constexpr int w = StridedGeom<QV + (TV ? 1 : 0), true>::kWaves;                                                                           \
-            const uint32_t grid = blocks_for(n_super, w, (uint32_t)cfg.compute_units);                                                                \
-            if (agg) hipLaunchKernelGGL((k_meter_strided<QV, TV, true, true>), dim3(grid), dim3(w * 64), 0, s, payload, codec, C, whole, n, stats, agg, rank, gq, pcm);   \
-            else     hipLaunchKernelGGL((k_meter_strided<QV, TV, false, true>), dim3(grid), dim3(w * 64), 0, s, payload, codec, C, whole, n, stats, agg, rank, gq, pcm);  \
-            done = whole;                                                                                                                             \
-        }
-        IGDSP_STRIDED(1, false) IGDSP_STRIDED(1, true) IGDSP_STRIDED(4, false) IGDSP_STRIDED(4, true) IGDSP_STRIDED(5, false) IGDSP_STRIDED(5, true)
-        IGDSP_STRIDED(6, false) IGDSP_STRIDED(6, true) IGDSP_STRIDED(8, false) IGDSP_STRIDED(8, true) IGDSP_STRIDED(10, false) IGDSP_STRIDED(10, true)
-        IGDSP_STRIDED(12, false) IGDSP_STRIDED(12, true) IGDSP_STRIDED(15, false)   // (15, true) = 244 / 248 bytes: 16 pieces x 12 waves of strip do not fit
-        IGDSP_STRIDED_PCM(1, true) IGDSP_STRIDED_PCM(5, false) IGDSP_STRIDED_PCM(10, true) IGDSP_STRIDED_PCM(10, false) IGDSP_STRIDED_PCM(15, false)
-#undef IGDSP_STRIDED
-#undef IGDSP_STRIDED_PCM
-        if (done) { hipError_t e = hipGetLastError(); if (e != hipSuccess) return e; }
-    }
-    if (done < n_frames) {
-        // what the tuned n == 160 kernel does not take: other frame sizes, ragged lengths, the < 64-frame tail.  Meter-only
-        // work with n % 4 == 0 goes through the LDS-image kernel (every lane meters one frame); PCM output, n % 4 != 0 and
-        // unaligned buffers through the literal wave-per-frame kernel.
-        const bool image_ok = variant != 1 && pcm == nullptr && (n & 3u) == 0u && ((reinterpret_cast<uintptr_t>(stats) & 15u) == 0u) &&
-                              ((reinterpret_cast<uintptr_t>(payload) & 3u) == 0u) && n_frames - done >= 16u;
-        if (image_ok) {
-            const uint32_t img = (uint32_t)kSuperFrames * n;
-            const uint32_t lut_bytes = (uint32_t)kLutEntries * 8u;
-            uint32_t waves = std::max(1u, std::min(kImgMaxWaves, (160u * 1024u - lut_bytes - 2048u) / img));
-            if (const char *e = std::getenv("IGDSP_IMG_WAVES")) waves = std::max(1u, std::min(waves, (uint32_t)std::atoi(e)));   // experiments
-            const uint32_t items = (n_frames - done + (uint32_t)kSuperFrames - 1u) / (uint32_t)kSuperFrames;
-            const uint32_t grid = blocks_for(items, waves, (uint32_t)cfg.compute_units);
-            const size_t smem = (size_t)waves * img;              // dynamic part: the images (the LUT is static)
-            const dim3 g3(grid), b3(waves * 64u);
-            if (len) {
-                if (agg) hipLaunchKernelGGL((k_meter_image<true, true>), g3, b3, smem, s, payload, codec, len, C, done, n_frames, n, stats, agg, rank);
-                else     hipLaunchKernelGGL((k_meter_image<false, true>), g3, b3, smem, s, payload, codec, len, C, done, n_frames, n, stats, agg, rank);
-            } else {
-                if (agg) hipLaunchKernelGGL((k_meter_image<true, false>), g3, b3, smem, s, payload, codec, len, C, done, n_frames, n, stats, agg, rank);
-                else     hipLaunchKernelGGL((k_meter_image<false, false>), g3, b3, smem, s, payload, codec, len, C, done, n_frames, n, stats, agg, rank);
-            }
-        } else {
-            const uint32_t grid = blocks_for((n_frames - done + 7) / 8, 4, (uint32_t)cfg.compute_units * 8u);
-            hipLaunchKernelGGL(k_meter_wave_per_frame, dim3(grid), dim3(256), 0, s, payload, codec, len, C, done, n_frames, n, stats, pcm, agg, rank);
-        }
+    });
+    if (r.fast != MeterFast::none) { hipError_t e = hipGetLastError(); if (e != hipSuccess) return e; }
+    const dim3 rg(r.rest_grid), rb(r.rest_threads);
+    if (r.rest == MeterRest::image) {
+        with_bool(agg != nullptr, [&](auto A) { with_bool(len != nullptr, [&](auto L) {
+            hipLaunchKernelGGL((k_meter_image<A, L>), rg, rb, r.rest_lds, s, payload, codec, len, C, done, n_frames, n, stats, agg, rank);
+        }); });
+    } else if (r.rest == MeterRest::wave_per_frame) {
+        hipLaunchKernelGGL(k_meter_wave_per_frame, rg, rb, 0, s, payload, codec, len, C, done, n_frames, n, stats, pcm, agg, rank);
     }
     return hipGetLastError();
 }

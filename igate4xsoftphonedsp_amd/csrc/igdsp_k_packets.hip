@@ -21,7 +21,6 @@ constexpr int kRtpHalfLoads = kSlotPieces * kChunkFrames / 64;     // 6 loads pe
 // counters showed SQ_LDS_BANK_CONFLICT = 4.2e7 cycles per launch (a quarter of the LDS pipe's time) in the packed kernel.
 constexpr int kRtpRow = kSlotPieces + 2;
 constexpr int kRtpStrip = kSuperFrames * kRtpRow;                  // 896 entries = 7 KiB per wave
-constexpr int kRtpWaves = 12;                                      // 64 KiB LUT + 84 KiB strips
 
 // SLOT = true : 192-byte slots (size word + pad + packet at +12), every piece 16-byte aligned.
 // SLOT = false: packets packed at `stride` bytes exactly as received; piece addresses are only dword aligned.
@@ -756,48 +755,69 @@ __global__ __launch_bounds__(256) void k_depayload_bytes(const uint8_t *__restri
     }
 }
 
+// k_meter_rtp64<AGG, SLOT, MIXED, WIN> of a packet layout: stride == 0 the 192-byte slot format (SLOT); otherwise packets packed at
+// `stride` with a `hdr`-byte RTP header, or, with `radio`, a per-channel 20 / 12-byte header (MIXED).  fn(SLOT, MIXED, stride, hdr).
+template <class Fn> static void with_layout(uint32_t stride, uint32_t hdr, const uint8_t *radio, Fn &&fn)
+{
+    if (stride == 0)           fn(std::true_type{}, std::false_type{}, 192u, 20u);
+    else if (radio != nullptr) fn(std::false_type{}, std::true_type{}, stride, 12u);
+    else                       fn(std::false_type{}, std::false_type{}, stride, hdr);
+}
+
 hipError_t launch_decode_meter_rtp(const LaunchCfg &cfg, const uint8_t *slots, const uint16_t *sizes, const uint8_t *codec, uint32_t C,
                                    uint32_t F, uint32_t stride, uint32_t hdr, igdsp_frame_stats *stats, igdsp_rtp_info *info,
-                                   igdsp_aggregate *agg, uint32_t rank, hipStream_t s, const uint8_t *radio, const WinArgs *win)
+                                   igdsp_aggregate *agg, uint32_t rank, hipStream_t s, const uint8_t *radio)
 {
-    // stride == 0: the 192-byte slot format; otherwise packets packed at `stride` with a `hdr`-byte RTP header, or, with
-    // `radio`, a per-channel 20 / 12-byte header.  win: the gated window in the same pass (C % 64 == 0; launch_window_fused)
     const uint32_t n_frames = C * F;                       // caller guarantees a multiple of 64
     if (n_frames == 0) return hipSuccess;
-    dim3 blk(kRtpWaves * 64);
-    if (win != nullptr) {
-        uint32_t waves = kRtpWaves;
-        if (const char *e = std::getenv("IGDSP_WIN_WAVES")) waves = (uint32_t)std::max(1, std::min((int)kRtpWaves, std::atoi(e)));   // experiments
-        blk = dim3(waves * 64);
-        const uint32_t grid = blocks_for((uint64_t)win->n_groups * win->n_seg, waves, (uint32_t)cfg.compute_units);
-        uint32_t *noq = nullptr;                           // units are assigned statically (a grid apart), no device queue
-        if (win->gpb != 0u) {                              // block-owned channel groups: one block per gpb groups
-            if (waves < win->gpb) blk = dim3(win->gpb * 64);      // (a wave per group folds it at the block's end)
-            const uint32_t gridb = win->n_groups / win->gpb;
-            if (stride == 0)          hipLaunchKernelGGL((k_meter_rtp64<true, true, false, 2>), dim3(gridb), blk, 0, s, slots, sizes, codec, C, n_frames, 192u, 20u, stats, info, agg, rank, noq, radio, *win);
-            else if (radio != nullptr) hipLaunchKernelGGL((k_meter_rtp64<true, false, true, 2>), dim3(gridb), blk, 0, s, slots, sizes, codec, C, n_frames, stride, 12u, stats, info, agg, rank, noq, radio, *win);
-            else                       hipLaunchKernelGGL((k_meter_rtp64<true, false, false, 2>), dim3(gridb), blk, 0, s, slots, sizes, codec, C, n_frames, stride, hdr, stats, info, agg, rank, noq, radio, *win);
-            return hipGetLastError();
-        }
-        // (one instantiation per layout: without an aggregate the AGG code still runs and wave_exit drops the totals — the
-        // aggregate-free packed instantiation needed 170 VGPRs and spilled)
-        if (stride == 0)          hipLaunchKernelGGL((k_meter_rtp64<true, true, false, 1>), dim3(grid), blk, 0, s, slots, sizes, codec, C, n_frames, 192u, 20u, stats, info, agg, rank, noq, radio, *win);
-        else if (radio != nullptr) hipLaunchKernelGGL((k_meter_rtp64<true, false, true, 1>), dim3(grid), blk, 0, s, slots, sizes, codec, C, n_frames, stride, 12u, stats, info, agg, rank, noq, radio, *win);
-        else                       hipLaunchKernelGGL((k_meter_rtp64<true, false, false, 1>), dim3(grid), blk, 0, s, slots, sizes, codec, C, n_frames, stride, hdr, stats, info, agg, rank, noq, radio, *win);
-        return hipGetLastError();
-    }
     const uint32_t grid = blocks_for(n_frames / kSuperFrames, kRtpWaves, (uint32_t)cfg.compute_units);
-    if (stride == 0) {
-        if (agg) hipLaunchKernelGGL((k_meter_rtp64<true, true>), dim3(grid), blk, 0, s, slots, sizes, codec, C, n_frames, 192u, 20u, stats, info, agg, rank, cfg.gqueue, radio, WinArgs{});
-        else     hipLaunchKernelGGL((k_meter_rtp64<false, true>), dim3(grid), blk, 0, s, slots, sizes, codec, C, n_frames, 192u, 20u, stats, info, agg, rank, cfg.gqueue, radio, WinArgs{});
-    } else if (radio != nullptr) {
-        if (agg) hipLaunchKernelGGL((k_meter_rtp64<true, false, true>), dim3(grid), blk, 0, s, slots, sizes, codec, C, n_frames, stride, 12u, stats, info, agg, rank, cfg.gqueue, radio, WinArgs{});
-        else     hipLaunchKernelGGL((k_meter_rtp64<false, false, true>), dim3(grid), blk, 0, s, slots, sizes, codec, C, n_frames, stride, 12u, stats, info, agg, rank, cfg.gqueue, radio, WinArgs{});
-    } else {
-        if (agg) hipLaunchKernelGGL((k_meter_rtp64<true, false>), dim3(grid), blk, 0, s, slots, sizes, codec, C, n_frames, stride, hdr, stats, info, agg, rank, cfg.gqueue, radio, WinArgs{});
-        else     hipLaunchKernelGGL((k_meter_rtp64<false, false>), dim3(grid), blk, 0, s, slots, sizes, codec, C, n_frames, stride, hdr, stats, info, agg, rank, cfg.gqueue, radio, WinArgs{});
-    }
+    with_layout(stride, hdr, radio, [&](auto SLOT, auto MIXED, uint32_t st, uint32_t hd) { with_bool(agg != nullptr, [&](auto A) {
+        hipLaunchKernelGGL((k_meter_rtp64<A, SLOT, MIXED>), dim3(grid), dim3(kRtpWaves * 64), 0, s, slots, sizes, codec, C, n_frames, st, hd, stats, info,
+                           agg, rank, cfg.gqueue, radio, WinArgs{});
+    }); });
     return hipGetLastError();
+}
+
+hipError_t launch_decode_meter_window(const LaunchCfg &cfg, const uint8_t *packets, const uint16_t *sizes, const uint8_t *codec, uint32_t C,
+                                      uint32_t F, uint32_t stride, uint32_t hdr, const uint8_t *radio, igdsp_frame_stats *stats,
+                                      igdsp_rtp_info *info, igdsp_aggregate *agg, uint32_t rank, const igdsp_window &win, bool *too_long,
+                                      hipStream_t s)
+{
+    const WinRoute r = window_route(C, F, (uint32_t)cfg.compute_units, knobs_from_env());
+    *too_long = !r.fits;
+    if (!r.fits || (uint64_t)C * F == 0) return hipSuccess;
+    WinArgs w;
+    w.work = static_cast<uint4 *>(win.d_work);
+    w.gate_mask = ((win.gate_mode & IGDSP_GATE_SQU) ? 0x10000000u : 0u) | ((win.gate_mode & IGDSP_GATE_PTT) ? 0xe0000000u : 0u);   // Functions.cpp:1160, 1136
+    w.alarm = win.probe_alarm ? win.probe_alarm : IGDSP_PROBE_ALARM;
+    w.n_seg = r.n_seg; w.n_groups = r.n_groups; w.F = F;
+    // (one instantiation per layout: without an aggregate the AGG code still runs and wave_exit drops the totals — the
+    // aggregate-free packed instantiation needed 170 VGPRs and spilled)
+    auto launch = [&](auto FORM, const uint8_t *pk, const uint16_t *sz, uint32_t f_count, igdsp_frame_stats *st_out, igdsp_rtp_info *in_out) {
+        const uint32_t n_frames = C * f_count;
+        with_layout(stride, hdr, radio, [&](auto SLOT, auto MIXED, uint32_t st, uint32_t hd) {
+            hipLaunchKernelGGL((k_meter_rtp64<true, SLOT, MIXED, FORM>), dim3(r.grid), dim3(r.threads), 0, s, pk, sz, codec, C, n_frames, st, hd, st_out,
+                               in_out, agg, rank, (uint32_t *)nullptr, radio, w);   // units are assigned statically (a grid apart), no device queue
+        });
+        return hipGetLastError();
+    };
+    if (!r.blk) {   // register form: per-segment run summaries in work, chained into hold / probe by k_window_finish
+        const hipError_t e = launch(std::integral_constant<int, 1>{}, packets, sizes, F, stats, info);
+        return e != hipSuccess ? e : launch_window_finish(w.work, C, r.n_seg, w.alarm, win.d_hold, win.d_gate, win.d_probe, s);
+    }
+    // block-owned form, in r.parts equal launches of at most 255 frames
+    w.gpb = r.gpb; w.gsh = r.gsh;
+    w.hold = win.d_hold; w.gate = win.d_gate; w.probe = win.d_probe;
+    const uint64_t pkt_frame = (uint64_t)C * (stride ? stride : (uint32_t)IGDSP_SLOT_BYTES);
+    for (uint32_t k = 0; k < r.parts; ++k) {
+        const uint32_t f0 = (uint32_t)(((uint64_t)F * k) / r.parts), f1 = (uint32_t)(((uint64_t)F * (k + 1u)) / r.parts);
+        const uint64_t r0 = (uint64_t)f0 * C;
+        w.F = f1 - f0;
+        const hipError_t e = launch(std::integral_constant<int, 2>{}, packets + (uint64_t)f0 * pkt_frame, sizes ? sizes + r0 : nullptr, f1 - f0,
+                                    stats ? stats + r0 : nullptr, info ? info + r0 : nullptr);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 hipError_t launch_depayload(const LaunchCfg &cfg, const uint8_t *packets, const uint16_t *sizes, const uint8_t *radio,

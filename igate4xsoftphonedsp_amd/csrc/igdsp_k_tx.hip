@@ -22,16 +22,12 @@ namespace igdsp {
 static_assert(sizeof(igdsp_tx_chan) == 64 && alignof(igdsp_tx_chan) == 8, "igdsp_tx_chan is 64 bytes (capi.TX_CHAN)");
 static_assert(sizeof(igdsp_tx_info) == 8, "igdsp_tx_info is 8 bytes (capi.TX_INFO)");
 
-constexpr int kTxWaves = 8;
-constexpr int kTxCh = 16;                       // channels per wave
 constexpr int kTxFc = 8;                        // frames per chunk
 constexpr int kTxPk = kTxCh * kTxFc;            // packets per chunk (128)
 #ifndef IGDSP_TX_UNROLL
 #define IGDSP_TX_UNROLL 4
 #endif
 constexpr int kTxU = IGDSP_TX_UNROLL;           // bulk iterations whose loads are issued together
-
-enum : int { kTxG711 = 0, kTxPcm = 1, kTxPcmTab = 2 };
 
 // record meta word
 constexpr uint32_t kMSize20 = 1u, kMSizeFull = 2u;            // bits 0-1: size class
@@ -464,23 +460,16 @@ hipError_t launch_tx_packetize(const LaunchCfg &cfg, const int16_t *pcm, const u
                                uint32_t n, uint64_t t0, uint32_t frame_ms, igdsp_tx_chan *state, uint8_t *last, uint8_t *packets,
                                uint32_t stride, uint16_t *sizes, igdsp_tx_info *info, int variant, hipStream_t s)
 {
-    TxArgs a{pcm, g711, ctl, C, F, n, t0, frame_ms, state, last, packets, stride, sizes, info, cfg.enc_tab, (C + kTxCh - 1) / kTxCh, 0u};
-    const uintptr_t al = pcm ? 7u : 3u;
-    a.vec = ((n & 3u) == 0u && ((reinterpret_cast<uintptr_t>(pcm ? (const void *)pcm : (const void *)g711) & al) == 0u) &&
-             ((reinterpret_cast<uintptr_t>(last) & 3u) == 0u)) ? 1u : 0u;
-    const bool tab = pcm != nullptr && (uint64_t)C * F * n >= (1ull << 22) && tab_lds_ready();
-    const uint32_t cap = (uint32_t)cfg.compute_units * (tab ? 1u : 2u);
-    const uint32_t grid = blocks_for(a.n_groups, kTxWaves, cap);
-    const size_t lds = tab ? 2u * 65536u : 0u;
-#define IGDSP_TX_LAUNCH(FORM)                                                                                                      \
-    do {                                                                                                                           \
-        if (variant == IGDSP_ENC_G191) hipLaunchKernelGGL((k_tx_packetize<FORM, IGDSP_ENC_G191>), dim3(grid), dim3(kTxWaves * 64), lds, s, a); \
-        else                           hipLaunchKernelGGL((k_tx_packetize<FORM, IGDSP_ENC_SUN16>), dim3(grid), dim3(kTxWaves * 64), lds, s, a); \
-    } while (0)
-    if (!pcm) hipLaunchKernelGGL((k_tx_packetize<kTxG711, IGDSP_ENC_G191>), dim3(grid), dim3(kTxWaves * 64), 0, s, a);
-    else if (tab) IGDSP_TX_LAUNCH(kTxPcmTab);
-    else IGDSP_TX_LAUNCH(kTxPcm);
-#undef IGDSP_TX_LAUNCH
+    const bool tab_lds = tx_wants_table(pcm != nullptr, C, F, n) && tab_lds_ready();
+    const TxRoute r = tx_route(C, F, n, reinterpret_cast<uintptr_t>(pcm), reinterpret_cast<uintptr_t>(g711), reinterpret_cast<uintptr_t>(last),
+                               (uint32_t)cfg.compute_units, tab_lds);
+    const TxArgs a{pcm, g711, ctl, C, F, n, t0, frame_ms, state, last, packets, stride, sizes, info, cfg.enc_tab, r.n_groups, r.vec};
+    const dim3 g(r.grid), b(r.threads);
+    switch (r.form) {
+    case kTxG711: hipLaunchKernelGGL((k_tx_packetize<kTxG711, IGDSP_ENC_G191>), g, b, r.lds, s, a); break;   // (no encoder: one lineage)
+    case kTxPcm: with_enc(variant, [&](auto V) { hipLaunchKernelGGL((k_tx_packetize<kTxPcm, V>), g, b, r.lds, s, a); }); break;
+    case kTxPcmTab: with_enc(variant, [&](auto V) { hipLaunchKernelGGL((k_tx_packetize<kTxPcmTab, V>), g, b, r.lds, s, a); }); break;
+    }
     return hipGetLastError();
 }
 

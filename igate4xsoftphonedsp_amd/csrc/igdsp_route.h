@@ -1,0 +1,415 @@
+// igdsp_route.h — which kernel serves a shape, and with what geometry.  Host-only, plain C++17 (no HIP): the launchers in
+// igdsp_k_*.hip call these functions and only launch what they return; tests/route/route_driver.cpp compiles them with g++
+// and tests/test_route_cpu.py pins the routes.  Every route function is pure: the shape, the buffers' addresses (alignment
+// only), the CU count and the env knobs (Knobs, read once per launcher call by knobs_from_env) go in, a route comes out.
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <cstdlib>
+#include <optional>
+#include <type_traits>
+#include <utility>
+
+#include "igdsp.h"
+
+namespace igdsp {
+
+// ---- Geometry shared by the kernels and their routes
+
+// Geometry of the tuned n == 160 path: a wavefront owns a super-chunk of 64 consecutive channel-frames
+// (10 240 contiguous bytes), processed as two halves of 32 frames = 5120 bytes = 5 wave-wide 16 B/lane loads each.
+constexpr int kFrame = IGDSP_SAMPLES_PER_FRAME;        // 160 B
+constexpr int kChunkFrames = 32;
+constexpr int kChunkBytes = kChunkFrames * kFrame;     // 5120
+constexpr int kPiecesPerFrame = kFrame / 16;           // 10 x 16 B
+constexpr int kPiecesPerChunk = kChunkFrames * kPiecesPerFrame;  // 320
+constexpr int kLoadsPerChunk = kPiecesPerChunk / 64;   // 5
+constexpr int kWavesPerBlock = 16;                     // 1024 threads, one block per CU
+constexpr int kBlockThreads = kWavesPerBlock * 64;
+constexpr int kSuperFrames = 2 * kChunkFrames;         // 64
+constexpr int kLutEntries = 256 * 32;                  // the 32-replica expansion LUT, uint2 each
+constexpr uint32_t kWinMaxSeg = 8;                     // igdsp_window_work_bytes = kWinMaxSeg x C x 48
+
+// k_meter_chunk64 waves per block: 16 (1024 threads, 128 VGPRs) for the meter-only kernel: a read-heavy kernel wants every wave it can
+// get, each has one super-chunk of loads in flight.  The PCM-store variant writes two bytes for every byte it reads, and a 1 : 2 mix is
+// fastest with FEW resident waves per CU — 12 / 10 / 8 / 6 / 5 / 4 / 3 / 2 waves: 0.6706 / 0.6680 / 0.6636 / 0.6573 / 0.6520 / 0.6388 / 0.6995 /
+// 1.013 ms in same-box A/B builds (late round 3; 12 had been chosen for its registers) — every wave is one more front of 20 KiB
+// write bursts, and four already keep enough loads in flight.
+#ifndef IGDSP_STORE_WAVES
+#define IGDSP_STORE_WAVES 4
+#endif
+template <bool STORE_PCM> struct ChunkGeom { static constexpr int kWaves = STORE_PCM ? IGDSP_STORE_WAVES : kWavesPerBlock; };
+constexpr int kFatWaves = 8;
+constexpr uint32_t kImgMaxWaves = 12;          // 768 threads: up to 170 VGPRs, room for the sixteen piece registers of the next item
+// k_meter_strided<Q, TAIL, AGG, STORE>, QP = Q + TAIL pieces per frame.
+#ifndef IGDSP_SSTORE_WAVES
+#define IGDSP_SSTORE_WAVES 0
+#endif
+// (the PCM-store variant, a 1 : 2 read : write mix, is fastest with few waves, as k_meter_chunk64<STORE>: 164-byte frames 12 / 8 / 6 / 5 / 4
+// waves 0.7264 / 0.7133 / 0.7036 / 0.741 / 0.861 ms; 240: 10 / 8 / 6 / 5 / 4 0.9926 / 0.9865 / 0.980 / 0.9766 / 0.9975; 80: 12 / 10 / 8 / 6 0.3472 / 0.3462 / 0.3424 / 0.3402)
+constexpr int strided_meter_waves(int qp, bool store) { return store ? (IGDSP_SSTORE_WAVES ? IGDSP_SSTORE_WAVES : (qp <= 2 ? 16 : 6)) : (qp <= 11 ? 16 : 12); }
+template <int QP, bool STORE = false> struct StridedGeom { static constexpr int kWaves = strided_meter_waves(QP, STORE); };
+constexpr int kTinyWaves = 16, kTinyDepth = 4;           // k_meter_tiny
+// items per queue slot (>= kTinyDepth: the prologue).  16 made a wave's share two slots, i.e. static in effect; 32 / 16 / 8 / 4 items: 0.0683 /
+// 0.0693 / 0.0682 / 0.0676 ms at 24-byte frames, 65 536 x 128 (same-box A/B builds, late round 3)
+#ifndef IGDSP_TINY_SLOT
+#define IGDSP_TINY_SLOT 4
+#endif
+constexpr uint32_t kTinySlot = IGDSP_TINY_SLOT;
+
+// Waves per block of k_encode_lut16 (late round 3, same-box A/B builds): 16 / 14 / 12 / 10 / 8 / 6 / 4 → 0.651–0.662 / 0.650–0.658 / 0.641–0.642 /
+// 0.636–0.637 / 0.646–0.648 / 0.770 / 1.05 ms.  The 2 : 1 read : write mix sits between the read-heavy kernels (the more waves the better) and the
+// store / round-trip kernels (4–6): ten waves of 8 KiB chunks keep enough loads in flight, more only add write fronts.
+#ifndef IGDSP_ENC_WAVES
+#define IGDSP_ENC_WAVES 10
+#endif
+constexpr int kEncWaves = IGDSP_ENC_WAVES;
+#ifndef IGDSP_RT_WAVES
+#define IGDSP_RT_WAVES 12
+#endif
+constexpr int kRtWaves = IGDSP_RT_WAVES;                  // k_roundtrip_chunk64
+#ifndef IGDSP_RTL_WAVES
+#define IGDSP_RTL_WAVES 12
+#endif
+constexpr int kRtlWaves = IGDSP_RTL_WAVES;                // k_roundtrip_lut64, k_roundtrip_strided
+constexpr int kRtbWaves = 12;                             // strips for up to 12 waves; the launcher starts fewer (rtb_waves)
+constexpr int kRtsbWaves = 10;                            // the same for k_roundtrip_strided<BLK> (its strips and rings are larger)
+constexpr int kRtpWaves = 12;                             // k_meter_rtp64: 64 KiB LUT + 84 KiB strips
+constexpr int kTxWaves = 8;
+constexpr int kTxCh = 16;                                 // k_tx_packetize: channels per wave
+enum : int { kTxG711 = 0, kTxPcm = 1, kTxPcmTab = 2 };    // k_tx_packetize<FORM>
+
+static inline uint32_t blocks_for(uint64_t items, uint32_t per_block, uint32_t cap)
+{
+    const uint64_t b = std::max<uint64_t>(1u, (items + per_block - 1) / per_block);
+    return (uint32_t)(b > cap ? cap : b);
+}
+
+// ---- Env knobs (experiments and tests).  Read on every launcher call: the GPU tests set them between calls on one context.
+struct Knobs {
+    bool no_tiny = false, no_strided = false;      // IGDSP_NO_TINY / IGDSP_NO_STRIDED: set at all
+    std::optional<int> img_waves;                  // IGDSP_IMG_WAVES
+    std::optional<int> rt_order, rt_mid, rt_nseg, rt_gpb, rt_blk, rtb_waves;   // IGDSP_RT_ORDER / _MID / _NSEG / _GPB / _BLK, IGDSP_RTB_WAVES
+    std::optional<int> win_nseg, win_gpb, win_blk, win_waves;                  // IGDSP_WIN_NSEG / _GPB / _BLK / _WAVES
+};
+
+inline Knobs knobs_from_env()
+{
+    auto num = [](const char *name) -> std::optional<int> {
+        if (const char *e = std::getenv(name)) return std::atoi(e);
+        return std::nullopt;
+    };
+    Knobs k;
+    k.no_tiny = std::getenv("IGDSP_NO_TINY") != nullptr;
+    k.no_strided = std::getenv("IGDSP_NO_STRIDED") != nullptr;
+    k.img_waves = num("IGDSP_IMG_WAVES");
+    k.rt_order = num("IGDSP_RT_ORDER"); k.rt_mid = num("IGDSP_RT_MID"); k.rt_nseg = num("IGDSP_RT_NSEG");
+    k.rt_gpb = num("IGDSP_RT_GPB"); k.rt_blk = num("IGDSP_RT_BLK"); k.rtb_waves = num("IGDSP_RTB_WAVES");
+    k.win_nseg = num("IGDSP_WIN_NSEG"); k.win_gpb = num("IGDSP_WIN_GPB"); k.win_blk = num("IGDSP_WIN_BLK"); k.win_waves = num("IGDSP_WIN_WAVES");
+    return k;
+}
+
+// ---- Compile-time dispatch: a runtime choice among a fixed set of template arguments.  Only the listed values are instantiated.
+template <class Fn> void with_bool(bool b, Fn &&fn) { b ? fn(std::true_type{}) : fn(std::false_type{}); }
+// the compressor lineage: IGDSP_ENC_G191, or (anything else) IGDSP_ENC_SUN16
+template <class Fn> void with_enc(int variant, Fn &&fn)
+{
+    variant == IGDSP_ENC_G191 ? fn(std::integral_constant<int, IGDSP_ENC_G191>{}) : fn(std::integral_constant<int, IGDSP_ENC_SUN16>{});
+}
+template <int... Ks> using Keys = std::integer_sequence<int, Ks...>;
+template <int... Ks> constexpr bool has_key(Keys<Ks...>, int k) { return ((k == Ks) || ...); }
+template <int... Ks, class Fn> void with_key(Keys<Ks...>, int k, Fn &&fn) { ((k == Ks ? (fn(std::integral_constant<int, Ks>{}), 0) : 0), ...); }
+
+// The strided kernels are instantiated per (Q, TAIL): frames of Q 16-byte pieces plus, with TAIL, 4 or 8 bytes more.
+constexpr int qt_key(uint32_t q, bool tail) { return (int)q * 2 + (tail ? 1 : 0); }
+constexpr int key_q(int key) { return key / 2; }
+constexpr bool key_tail(int key) { return (key & 1) != 0; }
+// (15, true) = 244 / 248 bytes: 16 pieces x 12 waves of strip do not fit
+using MeterStridedKeys = Keys<qt_key(1, false), qt_key(1, true), qt_key(4, false), qt_key(4, true), qt_key(5, false), qt_key(5, true),
+                              qt_key(6, false), qt_key(6, true), qt_key(8, false), qt_key(8, true), qt_key(10, false), qt_key(10, true),
+                              qt_key(12, false), qt_key(12, true), qt_key(15, false)>;
+// with PCM output, and the round trip: the reference's own sizes (24, 80, 164 / 168, 240)
+using ReferenceSizeKeys = Keys<qt_key(1, true), qt_key(5, false), qt_key(10, true), qt_key(10, false), qt_key(15, false)>;
+using RoundtripStridedKeys = Keys<qt_key(1, true), qt_key(5, false), qt_key(10, true), qt_key(15, false)>;
+
+constexpr bool aligned(uintptr_t p, uintptr_t a) { return (p & (a - 1u)) == 0u; }
+
+// ---- Block-owned form (round trip and fused window): a block owns gpb = 1 << gsh consecutive channel groups of 64 for the launch.
+// gpb: as many groups per block (<= 4: the LDS) as still give every CU a block; `force` (IGDSP_RT_GPB / IGDSP_WIN_GPB, tests) picks
+// 1, 2 or 4 where it divides n_groups.
+inline uint32_t groups_per_block(uint32_t n_groups, uint32_t cus, std::optional<int> force)
+{
+    uint32_t gpb = 1u;
+    for (uint32_t g = 4u; g > 1u; g >>= 1) if (n_groups % g == 0u && n_groups / g >= cus) { gpb = g; break; }
+    if (force) { const uint32_t g = (uint32_t)*force; if ((g == 1u || g == 2u || g == 4u) && n_groups % g == 0u) gpb = g; }
+    return gpb;
+}
+inline uint32_t gpb_shift(uint32_t gpb) { return gpb == 4u ? 2u : (gpb == 2u ? 1u : 0u); }
+inline uint32_t rounds_of(uint32_t blocks, uint32_t cus) { return (blocks + cus - 1u) / cus; }
+
+// Where the block-owned round trip pays (65 536 channels = 256 blocks of four groups is the tuned case; measured around it, 128 frames,
+// placed buffers, static / block-owned ms): 0.6 to 1 round of blocks — 10 240 ch 0.0863 / 0.0841, 12 288 ch 0.1108 / 0.0856.  Below 0.6 of a
+// round the static form spreads its units over more CUs (8 192 ch 0.0754 / 0.0804, 4 096 ch 0.0649 / 0.0769); 1.5 rounds idle half the chip
+// in the second (24 576 ch 0.2003 / 0.2099, 49 152 ch 0.3572 / 0.3769), and even two whole rounds lose to the static form, whose blocks
+// stay (131 072 ch 0.9216 / 0.9311).
+inline bool roundtrip_block_fills(uint32_t blocks, uint32_t cus) { return rounds_of(blocks, cus) == 1u && blocks * 10u >= cus * 6u; }
+
+// Where the block-owned window pays: up to one round of blocks, and where the blocks fill whole rounds of the CUs to 85 % (a launch
+// of 1.25 rounds would idle 3/8 of the chip in its second round: the register form has no such steps).  (Measured around the tuned
+// 65 536 channels, register form / block form ms: 2 048 ch 0.0992 / 0.0658, 8 192 ch 0.1014 / 0.0685, 12 288 ch 0.1021 / 0.0705 — up
+// to one round of blocks the block form always wins, the register form walks its segments serially — 24 576 ch 0.1218 / 0.1397,
+// 49 152 ch 0.2332 / 0.2559: 1.5 rounds idle half the chip in the second.)
+inline bool window_block_fills(uint32_t blocks, uint32_t cus)
+{
+    const uint32_t rounds = rounds_of(blocks, cus);
+    return rounds == 1u || (uint64_t)blocks * 100u >= (uint64_t)rounds * cus * 85u;
+}
+
+// ---- igdsp_decode_meter (launch_decode_meter)
+enum class MeterFast { none, fat, chunk, tiny, strided };
+enum class MeterRest { none, image, wave_per_frame };
+struct MeterRoute {
+    MeterFast fast = MeterFast::none;
+    bool store = false;              // chunk / strided: the PCM-storing instantiation
+    int key = 0;                     // tiny: n / 4; strided: qt_key(Q, TAIL)
+    uint32_t grid = 0, threads = 0;
+    uint32_t done = 0;               // frames [0, done) go to the fast kernel, [done, C * F) to the rest kernel
+    MeterRest rest = MeterRest::none;
+    uint32_t rest_grid = 0, rest_threads = 0, rest_lds = 0;
+};
+
+// variant: the context's experiment variant (igdsp_set_variant: 1 = the general kernels only, 3 = k_meter_fat).
+inline MeterRoute decode_meter_route(uint32_t C, uint32_t F, uint32_t n, int variant, bool has_len, uintptr_t payload, uintptr_t pcm,
+                                     uintptr_t stats, uint32_t cus, const Knobs &k)
+{
+    MeterRoute r;
+    if ((uint64_t)C * F == 0) return r;
+    const uint32_t n_frames = C * F;
+    const bool chunk_ok = n == (uint32_t)kFrame && !has_len && aligned(payload, 16) && aligned(pcm, 16) && aligned(stats, 16);
+    // tuned path takes the whole super-chunks (64 frames); the < 64 remaining frames, and every shape it
+    // does not cover, go through the rest kernel on the same stream.
+    const uint32_t n_super = n_frames / kSuperFrames, whole = n_super * kSuperFrames;
+    if (variant == 3 && chunk_ok && pcm == 0 && n_frames >= (uint32_t)kSuperFrames) {
+        r.fast = MeterFast::fat;
+        r.grid = blocks_for(n_super, kFatWaves, cus); r.threads = kFatWaves * 64; r.done = whole;
+    } else if (variant != 1 && chunk_ok && n_frames >= (uint32_t)kSuperFrames) {
+        const int w = pcm ? ChunkGeom<true>::kWaves : ChunkGeom<false>::kWaves;
+        r.fast = MeterFast::chunk; r.store = pcm != 0;
+        r.grid = blocks_for(n_super, w, cus); r.threads = w * 64; r.done = whole;
+    }
+    // 16 .. 32-byte frames, records only: a lane per frame (k_meter_tiny)
+    if (r.done == 0 && variant != 1 && !has_len && pcm == 0 && (n & 3u) == 0u && n >= 16u && n <= 32u && n_frames >= (uint32_t)kSuperFrames &&
+        aligned(payload, 4) && aligned(stats, 16) && !k.no_tiny) {
+        r.fast = MeterFast::tiny; r.key = (int)(n >> 2);
+        r.grid = blocks_for((n_super + kTinySlot - 1u) / kTinySlot, kTinyWaves, cus); r.threads = kTinyWaves * 64; r.done = whole;
+    }
+    // dense frames of 16 Q + 4 T bytes, Q in {1, 4, 5, 6, 8, 10, 12, 15}, T <= 2 (the reference's 164 / 24 and the 5 ms multiples
+    // up to 240) keep the chunk pipeline: k_meter_strided.  With PCM output: the reference's own sizes (24, 80, 164 / 168, 240).
+    // (160-byte frames land here only when their buffer is not 16-byte aligned.)
+    if (r.done == 0 && variant != 1 && !has_len && (n & 3u) == 0u && n_frames >= (uint32_t)kSuperFrames && ((n >> 2) & 3u) != 3u && n >= 16u &&
+        aligned(pcm, 4) && aligned(payload, 4) && aligned(stats, 16) && !k.no_strided) {
+        const int key = qt_key(n >> 4, (n & 15u) != 0u);
+        if (pcm ? has_key(ReferenceSizeKeys{}, key) : has_key(MeterStridedKeys{}, key)) {
+            const int w = strided_meter_waves(key_q(key) + (key_tail(key) ? 1 : 0), pcm != 0);
+            r.fast = MeterFast::strided; r.store = pcm != 0; r.key = key;
+            r.grid = blocks_for(n_super, w, cus); r.threads = w * 64; r.done = whole;
+        }
+    }
+    if (r.done < n_frames) {
+        // what the fast kernels do not take: other frame sizes, ragged lengths, the < 64-frame tail.  Meter-only work with
+        // n % 4 == 0 goes through the LDS-image kernel (every lane meters one frame); PCM output, n % 4 != 0 and unaligned
+        // buffers through the literal wave-per-frame kernel.
+        const bool image_ok = variant != 1 && pcm == 0 && (n & 3u) == 0u && aligned(stats, 16) && aligned(payload, 4) && n_frames - r.done >= 16u;
+        if (image_ok) {
+            const uint32_t img = (uint32_t)kSuperFrames * n;
+            const uint32_t lut_bytes = (uint32_t)kLutEntries * 8u;
+            uint32_t waves = std::max(1u, std::min(kImgMaxWaves, (160u * 1024u - lut_bytes - 2048u) / img));
+            if (k.img_waves) waves = std::max(1u, std::min(waves, (uint32_t)*k.img_waves));   // experiments
+            const uint32_t items = (n_frames - r.done + (uint32_t)kSuperFrames - 1u) / (uint32_t)kSuperFrames;
+            r.rest = MeterRest::image;
+            r.rest_grid = blocks_for(items, waves, cus); r.rest_threads = waves * 64u;
+            r.rest_lds = waves * img;              // dynamic part: the images (the LUT is static)
+        } else {
+            r.rest = MeterRest::wave_per_frame;
+            r.rest_grid = blocks_for((n_frames - r.done + 7) / 8, 4, cus * 8u); r.rest_threads = 256;
+        }
+    }
+    return r;
+}
+
+// ---- igdsp_roundtrip_peakhold (launch_roundtrip)
+enum class RtForm { none, lut64, chunk64, blk64, strided, strided_blk };
+struct RtRoute {
+    RtForm form = RtForm::none;
+    int key = 0;                           // strided forms: qt_key(Q, TAIL)
+    uint32_t grid = 0, threads = 0;
+    uint32_t n_groups = 0;                 // whole groups of 64 channels the fused form takes
+    uint32_t n_seg = 0, order = 0;         // register forms
+    uint32_t gpb = 0, gsh = 0, mid_start = 0;      // block-owned forms
+    uint32_t c_first = 0, gen_grid = 0;    // channels [c_first, C) go to k_roundtrip_general (256 threads), if any
+};
+
+// Waves per block of the block-owned round-trip kernels.  Unlike the read-heavy kernels (the more waves the better: each has one
+// item of loads in flight) the 1 : 1 read / write mix is fastest with FEW resident waves per CU: at 160-byte frames 16 / 14 / 12 / 10
+// / 8 / 6 / 4 / 3 waves ran 0.4613 / 0.4607 / 0.4580 / 0.4552 / 0.4522 / 0.4498 / 0.4519 / 0.4785 ms in same-box A/B builds.
+inline uint32_t rtb_waves(uint32_t n, int max_waves, uint32_t gpb, const Knobs &k)
+{
+    // about 60 KB of loads in flight per CU: 6 waves at 160 bytes per frame, 4 at 240, 10 (the strips' limit) at 80 and below; the tailed
+    // sizes want two more (164 bytes: 4 / 6 / 8 / 10 waves 0.6413 / 0.5146 / 0.4854 / 0.4915 ms; 240: 0.6636 / 0.6740 / 0.6746 / 0.6804)
+    uint32_t w = n >= 200u ? 4u : (n > 160u ? 8u : (n >= 120u ? 6u : (n >= 48u ? 10u : 16u)));
+    if (k.rtb_waves) w = (uint32_t)std::max(1, *k.rtb_waves);   // experiments
+    return std::max(std::max(gpb, 1u), std::min(w, (uint32_t)max_waves));   // (a wave per owned group folds it at the block's end)
+}
+
+// Segments of the register forms: at least one work item per resident wave; a segment is never shorter than 8 frames, and
+// the fused kernels count silent / clipped frames of a segment in 16 bits.
+inline uint32_t roundtrip_segments(uint32_t n_groups, uint32_t F, uint32_t cus, int waves, std::optional<int> force)
+{
+    const uint32_t want = cus * (uint32_t)waves;
+    uint32_t n_seg = n_groups >= want ? 1u : (want + n_groups - 1u) / n_groups;
+    if (force) n_seg = (uint32_t)std::max(1, *force);   // experiments
+    n_seg = std::max(1u, std::min(n_seg, std::max(1u, F / 8u)));
+    return std::max(n_seg, F / 65535u + 1u);
+}
+
+// kernel_variant: the context's experiment variant (1 = the general kernel only, 4 = k_roundtrip_chunk64, kept for A/B runs).
+inline RtRoute roundtrip_route(uint32_t C, uint32_t F, uint32_t n, int kernel_variant, uintptr_t payload, uintptr_t out, uintptr_t stats,
+                               bool out_spread, uint32_t cus, const Knobs &k)
+{
+    RtRoute r;
+    if ((uint64_t)C * F == 0) return r;
+    // Item order of the register forms.  Consecutive groups per block pay when the output's halves lie in two memory classes
+    // (0.4695 vs 0.4756 ms); with the whole output in one class it is the other way round (0.5116 vs 0.4920 ms): tools/rt_knobs.py,
+    // alternating in one process.  IGDSP_RT_ORDER overrides (experiments, and the test of the order the placement would pick).
+    const uint32_t order = k.rt_order ? (uint32_t)*k.rt_order : (out_spread ? 1u : 0u);
+    // block-owned forms: odd blocks walk the frames from the middle (both halves of a spread output written at any moment)
+    const uint32_t mid_start = k.rt_mid ? (*k.rt_mid != 0 ? 1u : 0u) : (out_spread ? 1u : 0u);   // (IGDSP_RT_MID: experiments)
+    const uint32_t cus1 = std::max(1u, cus);
+    // The fused channel-group-major kernels take whole groups of 64 channels of 160-byte frames in 16-byte aligned buffers
+    // (k_roundtrip_lut64; kernel_variant 4: the compressor-cell-table form k_roundtrip_chunk64), and of the reference's other
+    // frame sizes (24, 80, 164 / 168, 240) in dword-aligned buffers (k_roundtrip_strided).  The C % 64 channels left over, and
+    // every other shape, go through k_roundtrip_general on the same stream.
+    const uint32_t Tn = (n >> 2) & 3u;
+    const int key = qt_key(n >> 4, Tn != 0u);
+    const bool strided = kernel_variant != 1 && n != (uint32_t)kFrame && (n & 3u) == 0u && Tn != 3u && n >= 16u && aligned(payload | out, 4) &&
+                         aligned(stats, 16) && has_key(RoundtripStridedKeys{}, key) && C >= (uint32_t)kSuperFrames;
+    const bool fused160 = n == (uint32_t)kFrame && aligned(payload | out | stats, 16) && kernel_variant != 1 && C >= (uint32_t)kSuperFrames;
+    if (strided || fused160) {
+        const uint32_t n_groups = C / kSuperFrames;
+        const int waves = kernel_variant == 4 && !strided ? kRtWaves : kRtlWaves;
+        const uint32_t n_seg = roundtrip_segments(n_groups, F, cus, waves, strided ? std::nullopt : k.rt_nseg);
+        // block-owned form: taken where roundtrip_block_fills says it pays and F fits the 16-bit silent / clipped counts
+        const uint32_t gpb = groups_per_block(n_groups, cus1, k.rt_gpb);
+        const uint32_t blocks = n_groups / gpb;
+        const bool blk_ok = F <= 65535u && (strided || kernel_variant != 4);
+        const bool blk = blk_ok && (k.rt_blk ? *k.rt_blk != 0 : roundtrip_block_fills(blocks, cus1));   // (IGDSP_RT_BLK: experiments and tests)
+        r.n_groups = n_groups; r.c_first = n_groups * (uint32_t)kSuperFrames;
+        if (strided) r.key = key;
+        if (blk) {
+            r.form = strided ? RtForm::strided_blk : RtForm::blk64;
+            r.grid = blocks; r.gpb = gpb; r.gsh = gpb_shift(gpb); r.mid_start = mid_start;
+            r.threads = rtb_waves(n, strided ? (key_q(key) <= 1 ? 16 : kRtsbWaves) : kRtbWaves, gpb, k) * 64u;
+        } else {
+            r.form = strided ? RtForm::strided : (kernel_variant == 4 ? RtForm::chunk64 : RtForm::lut64);
+            r.grid = blocks_for((uint64_t)n_groups * n_seg, waves, cus); r.threads = waves * 64;
+            r.n_seg = n_seg; r.order = order;
+        }
+    }
+    if (C > r.c_first) r.gen_grid = blocks_for(C - r.c_first, 4, cus * 8u);
+    return r;
+}
+
+// ---- igdsp_encode (launch_encode)
+enum class EncForm { none, lut16, v8_table, v8, scalar };
+struct EncRoute {
+    EncForm form = EncForm::none;
+    uint32_t grid = 0, threads = 0;
+    uint64_t groups = 0;                   // 8-sample groups (v8 forms) or samples (scalar)
+};
+
+inline EncRoute encode_route(uint32_t C, uint32_t F, uint32_t n, uintptr_t pcm, uintptr_t out, uint32_t cus)
+{
+    EncRoute r;
+    const uint64_t n_samples = (uint64_t)C * F * n;
+    if (n_samples == 0) return r;
+    const bool v8 = (n & 7u) == 0u && aligned(pcm, 16) && aligned(out, 8);
+    if (v8 && n_samples >= (1u << 25) && (n_samples >> 3) < 0xFFFF0000ull) {   // large batches: full 16-bit table, one block per CU (32-bit group ids)
+        r = {EncForm::lut16, blocks_for(n_samples >> 3, 1024, cus), (uint32_t)kEncWaves * 64u, n_samples >> 3};
+    } else if (v8 && n_samples >= (1u << 22)) {                                 // big batches: table-driven compressor, persistent blocks
+        r = {EncForm::v8_table, blocks_for(n_samples >> 3, 1024, cus * 2u), 1024u, n_samples >> 3};
+    } else if (v8) {
+        r = {EncForm::v8, blocks_for(n_samples >> 3, 256, cus * 8u), 256u, n_samples >> 3};
+    } else {
+        r = {EncForm::scalar, blocks_for(n_samples, 256, cus * 8u), 256u, n_samples};
+    }
+    return r;
+}
+// k_encode_lut16 reads the context's ready-made 16-bit compressor table (igdsp_encode builds it only for these launches)
+inline bool encode_wants_table(const EncRoute &r) { return r.form == EncForm::lut16; }
+
+// ---- igdsp_decode_meter_window, fused path: C % 64 == 0 and a work buffer (launch_decode_meter_window)
+struct WinRoute {
+    bool fits = false;                     // F / n_seg <= 65 535: silent / clipped counts of a unit are 16 bits (else IGDSP_ERANGE)
+    bool blk = false;                      // block-owned form (no summaries, no finish kernel) or register form + k_window_finish
+    uint32_t n_groups = 0, n_seg = 0;
+    uint32_t gpb = 0, gsh = 0, parts = 1;  // block-owned form: launched as `parts` equal launches of <= 255 frames
+    uint32_t grid = 0, threads = 0;
+};
+
+inline WinRoute window_route(uint32_t C, uint32_t F, uint32_t cus, const Knobs &k)
+{
+    WinRoute r;
+    r.n_groups = C / 64u;
+    // Register form: the windows live in registers; at least one unit per resident wave, a segment is never shorter than 8 frames
+    // nor longer than 65 535.  (16 units per CU for its 12 waves: at 65 536 channels 4 segments — a third of the waves take a second
+    // unit — measured 0.2873-0.2929 ms against 0.2973-0.3023 with 3 segments = one unit per wave, 0.2906-0.2954 with 5, 0.2903-0.2957 with 8)
+    const uint32_t want = cus * 16u;
+    uint32_t n_seg = r.n_groups >= want ? 1u : (want + r.n_groups - 1u) / r.n_groups;
+    if (k.win_nseg) n_seg = (uint32_t)std::max(1, *k.win_nseg);   // experiments
+    r.n_seg = std::max(1u, std::min(std::min(n_seg, kWinMaxSeg), std::max(1u, F / 8u)));
+    r.fits = F / r.n_seg <= 65535u;
+    // Block-owned form (the default where it fits): a block owns gpb = 4, 2 or 1 consecutive channel groups for the launch,
+    // hands their items to its waves in (frame, group) order and keeps their windows and runs in its LDS — the item-level
+    // balance of the time-major kernels inside a block, no summaries, no finish kernel.  The packed LDS counters hold 255
+    // frames: longer launches go out as equal parts on the stream (hold / probe / the aggregate carry across them).
+    const uint32_t cus1 = std::max(1u, cus);
+    const uint32_t gpb = groups_per_block(r.n_groups, cus1, k.win_gpb);
+    r.blk = k.win_blk ? *k.win_blk != 0 : window_block_fills(r.n_groups / gpb, cus1);   // (IGDSP_WIN_BLK: 0 = never, 1 = always)
+    uint32_t waves = kRtpWaves;
+    if (k.win_waves) waves = (uint32_t)std::max(1, std::min((int)kRtpWaves, *k.win_waves));   // experiments
+    r.threads = waves * 64u;
+    if (r.blk) {
+        r.gpb = gpb; r.gsh = gpb_shift(gpb); r.parts = (F + 254u) / 255u;
+        r.grid = r.n_groups / gpb;
+        if (waves < gpb) r.threads = gpb * 64u;   // (a wave per group folds it at the block's end)
+    } else {
+        r.grid = blocks_for((uint64_t)r.n_groups * r.n_seg, waves, cus);
+    }
+    return r;
+}
+
+// ---- igdsp_tx_packetize (launch_tx_packetize)
+struct TxRoute {
+    int form = kTxG711;
+    uint32_t vec = 0;                      // dword / 8-byte aligned inputs: vector loads
+    uint32_t n_groups = 0, grid = 0, threads = 0, lds = 0;
+};
+
+// Large PCM launches encode through the context's LDS table (kTxPcmTab), as k_encode_lut16 does
+inline bool tx_wants_table(bool pcm, uint32_t C, uint32_t F, uint32_t n) { return pcm && (uint64_t)C * F * n >= (1ull << 22); }
+
+// tab_lds: the table form's 128 KiB LDS limit is raised on this device (checked only where tx_wants_table)
+inline TxRoute tx_route(uint32_t C, uint32_t F, uint32_t n, uintptr_t pcm, uintptr_t g711, uintptr_t last, uint32_t cus, bool tab_lds)
+{
+    TxRoute r;
+    r.n_groups = (C + kTxCh - 1) / kTxCh;
+    r.vec = ((n & 3u) == 0u && aligned(pcm ? pcm : g711, pcm ? 8 : 4) && aligned(last, 4)) ? 1u : 0u;
+    const bool tab = tx_wants_table(pcm != 0, C, F, n) && tab_lds;
+    r.form = pcm == 0 ? kTxG711 : (tab ? kTxPcmTab : kTxPcm);
+    r.grid = blocks_for(r.n_groups, kTxWaves, cus * (tab ? 1u : 2u));
+    r.threads = kTxWaves * 64;
+    r.lds = tab ? 2u * 65536u : 0u;
+    return r;
+}
+
+}  // namespace igdsp
