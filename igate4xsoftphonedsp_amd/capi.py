@@ -60,6 +60,10 @@ TX_INFO = np.dtype([("ed137", "<u4"), ("size", "<u2"), ("flags", "u1"), ("level"
 TX_CT_IDLE, TX_CT_RX, TX_CT_TX = 1, 2, 4
 TX_SENT, TX_KEEPALIVE_PT, TX_MARKER, TX_STALE_PAYLOAD, TX_LEVEL_VALID = 1, 2, 4, 8, 16
 TX_CTL_PTT, TX_CTL_SQL, TX_CTL_MARK, TX_CTL_SET = 1, 2, 4, 0x80
+# the staged send path (igdsp_on_tx_frame / igdsp_tx_flush): one igdsp_tx_packet per processed frame, packets in 256-byte slots
+TX_PACKET = np.dtype([("pkt", "<u8"), ("call_id", "<i4"), ("ed137", "<u4"), ("size", "<u2"), ("flags", "u1"), ("level", "u1")], align=True)
+TX_MAX_N = 236
+TX_SLOT = 256
 AGGREGATE = np.dtype({      # one 128-byte line per counter (include/igdsp.h); the padding is not exposed as fields
     "names": ["sumsq", "samples", "frames", "n_silent", "n_clipped", "byte_mean_sum", "peak_slot"],
     "formats": ["<u8", "<u8", "<u8", "<u8", "<u8", "<u8", ("<u8", (AGG_MAX_RANKS,))],
@@ -144,6 +148,19 @@ PROTOTYPES = [
     ("igdsp_tx_chan_init", _int, [_vp, C.c_char_p, _int, C.c_uint8, _u32, C.c_uint16, _u32, _i32, _u64]),
     ("igdsp_tx_calltype_bits", _int, [C.c_char_p]),
     ("igdsp_tx_packetize", _int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _u64, _u32, _vp, _vp, _vp, _u32, _vp, _vp, _int, _vp]),
+    ("igdsp_tx_open", _int, [_vp, _i32, C.c_char_p, _int, _i32, _u64]),
+    ("igdsp_tx_close", _int, [_vp, _i32]),
+    ("igdsp_tx_set_ptt", _int, [_vp, _i32, _int, _int, _int]),
+    ("igdsp_tx_set_sql", _int, [_vp, _i32, _int, _int, _i32]),
+    ("igdsp_tx_set_ptt_id", _int, [_vp, _i32, _int]),
+    ("igdsp_tx_set_slave", _int, [_vp, _i32, _int, _int]),
+    ("igdsp_tx_set_recorder", _int, [_vp, _i32, _int]),
+    ("igdsp_tx_set_calltype", _int, [_vp, _i32, C.c_char_p]),
+    ("igdsp_on_tx_frame", _int, [_vp, _i32, _vp, _u32, _u64]),
+    ("igdsp_tx_flush", _int, [_vp, C.POINTER(_u32)]),
+    ("igdsp_tx_results", _int, [_vp, C.POINTER(_vp), C.POINTER(_u32)]),
+    ("igdsp_tx_get_chan", _int, [_vp, _i32, _vp]),
+    ("igdsp_tx_counts", _int, [_vp, _i32, C.POINTER(_u32), C.POINTER(_u32)]),
     ("igdsp_g726_reorder", _int, [_vp, _vp, _vp, _u64, _int, _vp]),
     ("igdsp_gen_uniform", _int, [_vp, _vp, _u64, _u64, _u64, _vp]),
     ("igdsp_dev_alloc", _int, [_vp, C.POINTER(_vp), C.c_size_t]),
@@ -362,6 +379,63 @@ class Context:
         self._ck(self.L.igdsp_tx_packetize(self.h, _ptr(pcm), _ptr(g711), _ptr(ctl), C_, F_, n, t0_ms, frame_ms, _ptr(state),
                                            _ptr(last_payload), _ptr(packets), stride, _ptr(sizes), _ptr(info), variant, stream),
                  "igdsp_tx_packetize")
+
+    # -- staged ED-137 send path (transport_send_rtp as pjmedia calls it)
+    def tx_open(self, call_id: int, calltype: str, call_in: bool, keepalive_ms: int = 200, now_ms: int = 0):
+        self._ck(self.L.igdsp_tx_open(self.h, call_id, calltype.encode(), 1 if call_in else 0, keepalive_ms, now_ms), "igdsp_tx_open")
+
+    def tx_close(self, call_id: int):
+        self._ck(self.L.igdsp_tx_close(self.h, call_id), "igdsp_tx_close")
+
+    def tx_set_ptt(self, call_id: int, ptt: bool, priority: int = 0, user_rec: int = 0):
+        self._ck(self.L.igdsp_tx_set_ptt(self.h, call_id, 1 if ptt else 0, priority, user_rec), "igdsp_tx_set_ptt")
+
+    def tx_set_sql(self, call_id: int, sql: bool, priority: int = 0, bssi: int = -1):
+        """bssi < 0: the 3-argument setAdapterQslOn (bssi unchanged)"""
+        self._ck(self.L.igdsp_tx_set_sql(self.h, call_id, 1 if sql else 0, priority, bssi), "igdsp_tx_set_sql")
+
+    def tx_set_ptt_id(self, call_id: int, pttid: int):
+        self._ck(self.L.igdsp_tx_set_ptt_id(self.h, call_id, pttid), "igdsp_tx_set_ptt_id")
+
+    def tx_set_slave(self, call_id: int, rx: bool, tx: bool):
+        self._ck(self.L.igdsp_tx_set_slave(self.h, call_id, 1 if rx else 0, 1 if tx else 0), "igdsp_tx_set_slave")
+
+    def tx_set_recorder(self, call_id: int, on: bool):
+        self._ck(self.L.igdsp_tx_set_recorder(self.h, call_id, 1 if on else 0), "igdsp_tx_set_recorder")
+
+    def tx_set_calltype(self, call_id: int, calltype: str):
+        self._ck(self.L.igdsp_tx_set_calltype(self.h, call_id, calltype.encode()), "igdsp_tx_set_calltype")
+
+    def on_tx_frame(self, call_id: int, pkt: bytes, now_ms: int) -> int:
+        """0, or the negative code (IGDSP_EBUSY: the leg's ring was full and this frame was refused)"""
+        return self.L.igdsp_on_tx_frame(self.h, call_id, pkt, len(pkt), now_ms)
+
+    def tx_flush(self) -> int:
+        n = _u32()
+        self._ck(self.L.igdsp_tx_flush(self.h, C.byref(n)), "igdsp_tx_flush")
+        return n.value
+
+    def tx_results(self):
+        """(entries: TX_PACKET [N], packets: uint8 [N][TX_SLOT]) — copies of the last flush's results"""
+        p, n = _vp(), _u32()
+        self._ck(self.L.igdsp_tx_results(self.h, C.byref(p), C.byref(n)), "igdsp_tx_results")
+        if n.value == 0:
+            return np.zeros(0, TX_PACKET), np.zeros((0, TX_SLOT), np.uint8)
+        ent = np.frombuffer((C.c_uint8 * (n.value * TX_PACKET.itemsize)).from_address(p.value), TX_PACKET).copy()
+        # the flush writes the slots contiguously, frame i at entries[0].pkt + i * TX_SLOT
+        pk = np.frombuffer((C.c_uint8 * (n.value * TX_SLOT)).from_address(int(ent["pkt"][0])), np.uint8).reshape(n.value, TX_SLOT).copy()
+        return ent, pk
+
+    def tx_get_chan(self, call_id: int) -> np.ndarray:
+        out = np.zeros((), TX_CHAN)
+        self._ck(self.L.igdsp_tx_get_chan(self.h, call_id, out.ctypes.data_as(_vp)), "igdsp_tx_get_chan")
+        return out
+
+    def tx_counts(self, call_id: int):
+        """(refused, dropped) of the call's leg since its igdsp_tx_open"""
+        r, d = _u32(), _u32()
+        self._ck(self.L.igdsp_tx_counts(self.h, call_id, C.byref(r), C.byref(d)), "igdsp_tx_counts")
+        return r.value, d.value
 
     # -- ED-137 gated window
     @staticmethod

@@ -92,6 +92,12 @@ struct igdsp_ctx {
     struct SnapshotPool;
     SnapshotPool *pool = nullptr;
 
+    // the staged ED-137 send path (igdsp_tx_open .. igdsp_tx_flush, igdsp_capi.hip): its own staging rings, stream, pinned
+    // blocks and device state, created by the first igdsp_tx_open so that RX-only users pay nothing for it
+    struct TxSide;
+    std::atomic<TxSide *> tx{nullptr};
+    std::mutex tx_init_mu;
+
     // device-wide work counters, ONE PAIR PER LAUNCH STREAM.  A persistent kernel draws its batches from the counter pair {next
     // batch, blocks done} it is handed and its last block re-arms the pair, so two kernels may share a pair only if they can never
     // be in flight together: launches on one stream serialise, launches on different streams do not.  (Round 2 handed launch k pair

@@ -77,6 +77,11 @@ hipError_t launch_tx_copy_ab(const LaunchCfg &cfg, const int16_t *pcm, const uin
 hipError_t launch_tx_packetize(const LaunchCfg &cfg, const int16_t *pcm, const uint8_t *g711, const uint8_t *ctl, uint32_t C, uint32_t F,
                                uint32_t n, uint64_t t0, uint32_t frame_ms, igdsp_tx_chan *state, uint8_t *last, uint8_t *packets,
                                uint32_t stride, uint16_t *sizes, igdsp_tx_info *info, int variant, hipStream_t s);
+// igdsp_tx_flush's device step over one compacted upload block (csrc/igdsp_txstage.h's layout): per-frame packets in 256-byte slots,
+// igdsp_tx_info per frame, the legs' state (in place and a copy per run for the download) and their send buffers [legs][236].
+hipError_t launch_tx_staged(const LaunchCfg &cfg, const void *runs, const void *recs, const uint32_t *stream, uint32_t n_runs,
+                            igdsp_tx_chan *state, uint8_t *send_buf, igdsp_tx_info *info, igdsp_tx_chan *chan_out, uint32_t *packets,
+                            hipStream_t s);
 hipError_t launch_wav_expand(const LaunchCfg &cfg, const uint8_t *payload, uint32_t C, uint32_t F, uint32_t n, uint32_t rate,
                              uint8_t *files, uint64_t file_stride, hipStream_t s);
 hipError_t launch_g726(const LaunchCfg &cfg, const uint8_t *in, uint8_t *out, uint64_t n_bytes, int mode, hipStream_t s);

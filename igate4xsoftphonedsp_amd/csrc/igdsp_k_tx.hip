@@ -51,16 +51,6 @@ struct TxArgs {
     uint32_t vec;      // n % 4 == 0 and every payload row dword (g711) / 8-byte (pcm) aligned
 };
 
-// Pass boundary inside one wavefront: LDS written by some lanes is read by others after it.
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ uint32_t bswap32(uint32_t x) { return __builtin_bswap32(x); }
-
 template <int FORM, int VARIANT>
 __device__ __forceinline__ uint32_t enc_sample(int v, uint32_t law, const uint8_t *tab)
 {
@@ -121,45 +111,6 @@ __device__ __forceinline__ void put_dword(uint8_t *p, uint32_t d, uint32_t k)
     if (k >= 4u) { *reinterpret_cast<uint32_t *>(p) = d; return; }
     for (uint32_t i = 0; i < k; ++i) p[i] = (uint8_t)(d >> (8u * i));
 }
-
-__device__ __forceinline__ int sbyte_sum(uint32_t d, uint32_t k)   // sum of the first k bytes of d as signed char
-{
-    int s = 0;
-    for (uint32_t i = 0; i < 4u; ++i) s += i < k ? (int)(int8_t)(d >> (8u * i)) : 0;
-    return s;
-}
-
-// igdsp_tx_chan unpacked into registers (the packed struct kept whole ends up in scratch / LDS): read once, written once per launch
-struct TxState {
-    uint64_t r2s_send_ms = 0;
-    uint32_t ts = 0, ssrc = 0, seq = 0, pt = 0, first_r2s = 0, tx_slave = 0, rx_slave = 0, tx_slave_changed = 0, rx_slave_changed = 0;
-    int32_t keepalive_ms = 0, packet_cnt = 0, slave_count = 0, tx_run = 0;
-    uint32_t ptt = 0, sql = 0, call_in = 0, call_recorder = 0, pttid = 0, pttpriority = 0, bssi = 0, calltype = 0, level = 0, w11 = 0;
-    __device__ __forceinline__ void load(const igdsp_tx_chan *p)
-    {
-        const uint32_t *u = reinterpret_cast<const uint32_t *>(p);
-        r2s_send_ms = *reinterpret_cast<const uint64_t *>(p);
-        ts = u[2]; ssrc = u[3]; keepalive_ms = (int32_t)u[4]; packet_cnt = (int32_t)u[5];
-        seq = u[6] & 0xFFFFu; pt = (u[6] >> 16) & 0xFFu; first_r2s = u[6] >> 24;
-        tx_slave = u[7] & 0xFFu; rx_slave = (u[7] >> 8) & 0xFFu; tx_slave_changed = (u[7] >> 16) & 0xFFu; rx_slave_changed = u[7] >> 24;
-        slave_count = (int32_t)u[8];
-        ptt = u[9] & 0xFFu; sql = (u[9] >> 8) & 0xFFu; call_in = (u[9] >> 16) & 0xFFu; call_recorder = u[9] >> 24;
-        pttid = u[10] & 0xFFu; pttpriority = (u[10] >> 8) & 0xFFu; bssi = (u[10] >> 16) & 0xFFu; calltype = u[10] >> 24;
-        tx_run = (int32_t)(int16_t)(u[11] & 0xFFFFu); level = (u[11] >> 16) & 0xFFu; w11 = u[11] & 0xFF000000u;
-    }
-    __device__ __forceinline__ void store(igdsp_tx_chan *p) const     // reserved bytes 48 .. 63 are left as they are
-    {
-        uint32_t *u = reinterpret_cast<uint32_t *>(p);
-        *reinterpret_cast<uint64_t *>(p) = r2s_send_ms;
-        u[2] = ts; u[3] = ssrc; u[4] = (uint32_t)keepalive_ms; u[5] = (uint32_t)packet_cnt;
-        u[6] = (seq & 0xFFFFu) | pt << 16 | first_r2s << 24;
-        u[7] = tx_slave | rx_slave << 8 | tx_slave_changed << 16 | rx_slave_changed << 24;
-        u[8] = (uint32_t)slave_count;
-        u[9] = ptt | sql << 8 | call_in << 16 | call_recorder << 24;
-        u[10] = pttid | pttpriority << 8 | bssi << 16 | calltype << 24;
-        u[11] = ((uint32_t)tx_run & 0xFFFFu) | level << 16 | w11;
-    }
-};
 
 template <int FORM, int VARIANT>
 __global__ __launch_bounds__(kTxWaves * 64) void k_tx_packetize(const TxArgs a)

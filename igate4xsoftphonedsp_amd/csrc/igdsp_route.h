@@ -412,4 +412,20 @@ inline TxRoute tx_route(uint32_t C, uint32_t F, uint32_t n, uintptr_t pcm, uintp
     return r;
 }
 
+// ---- igdsp_tx_flush (launch_tx_staged): a wave owns kTsLegs staged legs (runs) of the flush; lanes 0 .. kTsLegs-1 decide, the
+// whole wave writes the packets.  No dynamic LDS: each wave's records (kTsLegs x IGDSP_STAGE_DEPTH) are static.
+constexpr int kTsWaves = 4;
+constexpr int kTsLegs = 16;
+struct TxStagedRoute {
+    uint32_t n_groups = 0, grid = 0, threads = 0, lds = 0;
+};
+inline TxStagedRoute tx_staged_route(uint32_t n_runs, uint32_t cus)
+{
+    TxStagedRoute r;
+    r.n_groups = (n_runs + kTsLegs - 1) / kTsLegs;
+    r.grid = blocks_for(r.n_groups, kTsWaves, cus * 8u);
+    r.threads = kTsWaves * 64;
+    return r;
+}
+
 }  // namespace igdsp

@@ -33,7 +33,7 @@ extern "C" {
  * 3: additive again — the ED-137 gated window (igdsp_window, igdsp_decode_meter_window, igdsp_window_update, igdsp_chan_probe),
  * igdsp_set_ed137 / igdsp_set_gate_mode / igdsp_get_probe on the single-frame path, igdsp_flush_begin / igdsp_flush_end.
  *    Later, still additive under 3: the ED-137 TX packetizer (igdsp_tx_chan, igdsp_tx_info, igdsp_tx_chan_init, igdsp_tx_calltype_bits,
- *    igdsp_tx_packetize). */
+ *    igdsp_tx_packetize); the staged send path behind transport_send_rtp (igdsp_tx_open .. igdsp_tx_flush, igdsp_tx_packet). */
 #define IGDSP_ABI_VERSION 3
 
 /* ---- error codes (0 == PJ_SUCCESS-style success) ------------------------- */
@@ -507,6 +507,64 @@ int igdsp_tx_packetize(igdsp_ctx *ctx, const int16_t *d_pcm, const uint8_t *d_g7
                        uint32_t n_channels, uint32_t n_frames, uint32_t samples_per_frame, uint64_t t0_ms, uint32_t frame_ms,
                        igdsp_tx_chan *d_state, uint8_t *d_last_payload, uint8_t *d_packets, uint32_t pkt_stride,
                        uint16_t *d_sizes, igdsp_tx_info *d_info, int variant, void *stream);
+
+/* ---- Staged ED-137 send path: transport_send_rtp as pjmedia calls it (TransportAdapter.cpp:635-874) ------------------------
+ * The drop-in form of the packetizer above.  pjmedia calls transport_send_rtp(tp, pkt, size) once per leg per frame, on the
+ * conference bridge's clock, with the stream packet it has already encoded; the adapter setters change the leg between calls from
+ * other threads.  Here the call stages the packet (igdsp_on_tx_frame), the setters stage their values, and the owner thread
+ * packetises everything staged once per bridge tick on the device (igdsp_tx_flush), then hands each packet to
+ * pjmedia_transport_send_rtp itself.  Radio legs only (adapter->radiostatus, :641).
+ *
+ * Each staged frame is exactly one call of the reference's transport_send_rtp at currenttime = now_ms, for its leg, in staging
+ * order, with the eight steps of igdsp_tx_packetize, except that bytes 2..11 of the output header, and the stream bytes the
+ * audioLevel sum and the silence probe read (byte 1 with the stream's M bit included), are the staged packet's own, and
+ * n = size - 12 is per frame (1 <= n <= 236: send_pkt_buff[256] holds 20 + n, TransportAdapter.h:69).  The send buffer is one
+ * persistent 236-byte region per leg: a gated frame overwrites [0, n) of it, so a stale packet carries older bytes past a shorter
+ * copy, as the reference does.
+ *
+ * Legs: igdsp_tx_open opens one on the channel igdsp_map_call gave call_id, with transport_adapter_create's defaults
+ * (:108-127); the first igdsp_tx_open of a context allocates the TX staging and device state (RX-only users pay nothing).  A
+ * second igdsp_tx_open of the same channel starts over from the defaults; igdsp_tx_close drops the leg's staged frames (counted in
+ * igdsp_tx_counts' dropped).  A producer must not stage on a leg while it is opened or closed.
+ * Staging (igdsp_on_tx_frame): wait-free for the caller — a single-producer ring per leg, IGDSP_STAGE_DEPTH frames deep (one
+ * producer per leg: pjmedia serialises send_rtp per stream).  A full ring refuses the NEW frame with IGDSP_EBUSY (counted in
+ * refused).  Rejected with IGDSP_EINVAL: NULL, a packet that is not RTP V = 2 with P = X = 0 and CC = 0, n outside [1, 236]
+ * (pjmedia's own stream never produces them; the reference would read them undefined).  No open leg: IGDSP_ENOENT.
+ * Setters: igdsp_tx_set_* are the adapter setters (:135-223).  Wait-free too; each changes only the fields it names.  They apply in
+ * happens-before order with the same leg's igdsp_on_tx_frame: one that returned before frame k was staged takes effect before
+ * frame k's step; one racing with the staging of frame k lands on k or on k + 1, never lost or torn; one after the last staged
+ * frame carries over to the next.  The device's own changes (Idle-in zeroing of ptt / sql) survive setters of other fields.
+ * igdsp_tx_set_sql: bssi < 0 is the 3-argument overload (bssi unchanged); priority is accepted and unused, as sqlpriority is
+ * zeroed before every use (:739).  igdsp_tx_set_slave zeroes the debounce count, as setTxRxSlaveEnable does.
+ * Flush (igdsp_tx_flush, ONE owner thread; may run concurrently with igdsp_flush / igdsp_flush_begin on another thread, it has its
+ * own stream and buffers): takes every staged frame, packetises them in one upload / kernel / download, and returns when the
+ * results are readable.  igdsp_tx_results: one entry per processed frame, legs in channel order and frames in staging order,
+ * unsent frames (size 0) included; valid until the next igdsp_tx_flush.  igdsp_tx_get_chan: the leg's state as of the last
+ * finished flush (staged setters not yet applied). */
+typedef struct igdsp_tx_packet {
+    const uint8_t *pkt;         /* `size` bytes for pjmedia_transport_send_rtp; valid until the next igdsp_tx_flush          */
+    int32_t  call_id;
+    uint32_t ed137;             /* host order, 0 when not sent                                                              */
+    uint16_t size;              /* 0 (keep-alive rate limit: not sent), 20, or 20 + n                                       */
+    uint8_t  flags;             /* IGDSP_TX_* as in igdsp_tx_info                                                           */
+    uint8_t  level;             /* OutgoingRTP when IGDSP_TX_LEVEL_VALID                                                    */
+} igdsp_tx_packet;
+#define IGDSP_TX_MAX_N     236   /* largest payload of a staged frame                                               */
+int igdsp_tx_open(igdsp_ctx *ctx, int32_t call_id, const char *calltype, int call_in, int32_t keepalive_ms, uint64_t now_ms);
+int igdsp_tx_close(igdsp_ctx *ctx, int32_t call_id);
+int igdsp_tx_set_ptt(igdsp_ctx *ctx, int32_t call_id, int ptt, int priority, int user_rec);   /* setAdapterPtt       */
+int igdsp_tx_set_sql(igdsp_ctx *ctx, int32_t call_id, int sql, int priority, int32_t bssi);  /* setAdapterQslOn     */
+int igdsp_tx_set_ptt_id(igdsp_ctx *ctx, int32_t call_id, int pttid);                         /* setAdapterPttId     */
+int igdsp_tx_set_slave(igdsp_ctx *ctx, int32_t call_id, int rx, int tx);                     /* setTxRxSlaveEnable  */
+int igdsp_tx_set_recorder(igdsp_ctx *ctx, int32_t call_id, int on);                          /* setcallRecorder     */
+int igdsp_tx_set_calltype(igdsp_ctx *ctx, int32_t call_id, const char *calltype);            /* setCallType         */
+/* the body of transport_send_rtp: stage pjmedia's stream packet (12-byte RTP header + n G.711 bytes); now_ms = currenttime */
+int igdsp_on_tx_frame(igdsp_ctx *ctx, int32_t call_id, const void *pkt, uint32_t size, uint64_t now_ms);
+int igdsp_tx_flush(igdsp_ctx *ctx, uint32_t *n_frames_out);
+int igdsp_tx_results(igdsp_ctx *ctx, const igdsp_tx_packet **out, uint32_t *n_out);
+int igdsp_tx_get_chan(igdsp_ctx *ctx, int32_t call_id, igdsp_tx_chan *out);
+/* frames of the call's leg refused by a full ring / dropped by igdsp_tx_close, since its igdsp_tx_open (either pointer may be NULL) */
+int igdsp_tx_counts(igdsp_ctx *ctx, int32_t call_id, uint32_t *refused, uint32_t *dropped);
 
 /* ---- synthetic input generators (device side; SURVEY 8(d) definitions) ---------
  * D-uniform: byte k of global byte index g is
