@@ -14,113 +14,15 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <condition_variable>
-#include <functional>
 #include <mutex>
 #include <new>
-#include <thread>
 #include <string>
 #include <unordered_map>
 #include <vector>
 
 using namespace igdsp;
-
-namespace {
-// Layout of the flush upload block (same offsets in the pinned host copy and in its device mirror; every section starts on
-// a 256-byte boundary).  Group A = whole 160-byte frames, dense at stride 160 (the tuned chunk kernel's layout); group B =
-// every other length, slots of 256 bytes with a length per frame (the general kernel).  seq = every staged frame in the
-// order its channel received it: {record id (group B: | 0x80000000), ED-137 word}; runs[c] = {first seq entry, count} of
-// channel c (count 0: nothing staged).
-struct UploadLayout { size_t payA, payB, lenB, ptA, ptB, seq, runs, total; };
-inline UploadLayout upload_layout(size_t max_frames, size_t max_channels)
-{
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    UploadLayout L;
-    size_t o = 0;
-    L.payA = o; o = up(o + max_frames * IGDSP_SAMPLES_PER_FRAME);
-    L.payB = o; o = up(o + max_frames * kSlot);
-    L.lenB = o; o = up(o + max_frames * sizeof(uint16_t));
-    L.ptA = o;  o = up(o + max_frames);
-    L.ptB = o;  o = up(o + max_frames);
-    L.seq = o;  o = up(o + max_frames * 2 * sizeof(uint32_t));
-    L.runs = o; o = up(o + max_channels * 2 * sizeof(uint32_t));
-    L.total = o;
-    return L;
-}
-inline void cpu_relax()
-{
-#if defined(__x86_64__) || defined(__i386__)
-    __builtin_ia32_pause();
-#elif defined(__aarch64__)
-    asm volatile("yield");
-#endif
-}
-constexpr uint32_t kRecB = 0x80000000u;
-constexpr uint32_t kPoolMinChannels = 16384;            // below this one thread snapshots faster than a pool wakes up
-constexpr uint32_t kPoolMaxThreads = 16;               // (8 threads: 0.44-0.53 ms of owner time at 65 536 calls depending on the box; 16: below)
-
-// What one snapshot worker found in its channel range [c0, c1): its frames sit in ITS region of every section (frame index
-// c0 * kStageDepth onwards), so workers never touch each other's bytes.
-struct SnapPart { uint32_t c0 = 0, c1 = 0, nA = 0, nB = 0, nSeq = 0; };
-}  // namespace
-
-// A few persistent helper threads for the flush's snapshot at many channels.  run() hands part i to thread i (the caller takes
-// part 0) and returns when all are done.
-struct igdsp_ctx::SnapshotPool {
-    std::vector<std::thread> threads;
-    std::mutex m;
-    std::condition_variable cv_go, cv_done;
-    uint64_t epoch = 0;
-    uint32_t pending = 0;
-    bool quit = false;
-    std::function<void(uint32_t)> job;
-
-    explicit SnapshotPool(uint32_t helpers)
-    {
-        for (uint32_t i = 0; i < helpers; ++i)
-            threads.emplace_back([this, i] {
-                uint64_t seen = 0;
-                for (;;) {
-                    std::unique_lock<std::mutex> lk(m);
-                    cv_go.wait(lk, [&] { return quit || epoch != seen; });
-                    if (quit) return;
-                    seen = epoch;
-                    lk.unlock();
-                    job(i + 1);
-                    lk.lock();
-                    if (--pending == 0) cv_done.notify_one();
-                }
-            });
-    }
-    ~SnapshotPool()
-    {
-        { std::lock_guard<std::mutex> lk(m); quit = true; }
-        cv_go.notify_all();
-        for (auto &t : threads) t.join();
-    }
-    void run(const std::function<void(uint32_t)> &fn)
-    {
-        { std::lock_guard<std::mutex> lk(m); job = fn; pending = (uint32_t)threads.size(); ++epoch; }
-        cv_go.notify_all();
-        fn(0);
-        std::unique_lock<std::mutex> lk(m);
-        cv_done.wait(lk, [&] { return pending == 0; });
-    }
-};
-
-// Read one channel's published state: copy out of the front set, retry if a flush_end moved it meanwhile (two flushes would
-// have to complete within the copy of ~60 bytes for a second retry).
-template <typename Fn>
-static inline void read_published(igdsp_ctx *ctx, Fn &&fn)
-{
-    for (;;) {
-        const uint64_t s1 = ctx->pub_seq.load(std::memory_order_acquire);
-        if (s1 & 1u) { cpu_relax(); continue; }                       // igdsp_reset_hold is rewriting the front set
-        fn(ctx->pub[ctx->front.load(std::memory_order_acquire)]);
-        std::atomic_thread_fence(std::memory_order_acquire);
-        if (ctx->pub_seq.load(std::memory_order_relaxed) == s1) return;
-    }
-}
+using igdsp_rx::kSlot;
+using igdsp_rx::kStageDepth;
 
 // ---- the staged ED-137 send path: everything igdsp_tx_open creates on first use ----
 struct igdsp_ctx::TxSide {
@@ -134,14 +36,14 @@ struct igdsp_ctx::TxSide {
     std::vector<igdsp_tx_chan> chan;                    // per leg, as of the last finished flush
     std::vector<int32_t> call_of;                       // per leg: the call that opened it
     std::vector<igdsp_tx_packet> results;               // the last flush's packets
-    SnapshotPool *pool = nullptr;
+    std::unique_ptr<SnapshotPool> pool;                 // the snapshot's helpers, sized as the RX flush's (igdsp_snappool.h)
     bool timing = false;
     float t_ms[5] = {};                                 // last flush: snapshot, upload, kernel, download, whole call
     std::mutex mu;                                      // owner entries: open / close / flush / results / get_chan
 
     ~TxSide()
     {
-        delete pool;
+        pool.reset();
         if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
         for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
         for (void *p : {(void *)h_up, (void *)h_out}) if (p) (void)hipHostFree(p);
@@ -188,12 +90,7 @@ igdsp_ctx::TxSide *tx_side(igdsp_ctx *ctx, int *rc)
         *rc = IGDSP_ENOMEM;
         return nullptr;
     }
-    if (legs >= kPoolMinChannels) {                      // the snapshot's helpers, sized as the RX flush's (igdsp_create)
-        const uint32_t hw = std::max(1u, std::thread::hardware_concurrency());
-        uint32_t threads = std::min(std::min(kPoolMaxThreads, std::max(1u, hw / 2u)), legs / (kPoolMinChannels / 4u));
-        if (const char *e = std::getenv("IGDSP_FLUSH_THREADS")) threads = (uint32_t)std::max(1, std::min(64, std::atoi(e)));
-        if (threads > 1u) tx->pool = new (std::nothrow) igdsp_ctx::SnapshotPool(threads - 1u);
-    }
+    tx->pool = make_pool(legs);
     ctx->tx.store(tx, std::memory_order_release);
     return tx;
 }
@@ -222,25 +119,16 @@ int igdsp_create(igdsp_ctx **out, int device, uint32_t max_channels)
     ctx->max_channels = max_channels;
     ctx->direct = std::vector<std::atomic<uint32_t>>(kDirectCalls);
     for (auto &d : ctx->direct) d.store(kNoChan, std::memory_order_relaxed);
-    ctx->slot_lock = std::vector<std::atomic_flag>(max_channels);
-    for (auto &f : ctx->slot_lock) f.clear();
-    ctx->cur_ed137 = std::vector<std::atomic<uint32_t>>(max_channels);
-    ctx->frames_seen = std::vector<std::atomic<uint32_t>>(max_channels);
-    ctx->frames_dropped = std::vector<std::atomic<uint32_t>>(max_channels);
-    for (uint32_t c = 0; c < max_channels; ++c) { ctx->cur_ed137[c].store(0); ctx->frames_seen[c].store(0); ctx->frames_dropped[c].store(0); }
-    ctx->head.assign(max_channels, 0);
-    ctx->tail.assign(max_channels, 0);
     const size_t max_frames = (size_t)max_channels * kStageDepth;       // most frames one flush can take
-    const size_t ring = max_frames * kSlot;
-    ctx->up_bytes = upload_layout(max_frames, max_channels).total;
+    ctx->up_bytes = igdsp_rx::upload_layout(max_frames, max_channels).total;
     bool ok = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&ctx->flush_done, hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipHostMalloc((void **)&ctx->h_ring, ring, hipHostMallocDefault) == hipSuccess;
-    ok = ok && hipHostMalloc((void **)&ctx->h_rlen, max_frames * sizeof(uint16_t), hipHostMallocDefault) == hipSuccess;
-    ok = ok && hipHostMalloc((void **)&ctx->h_rpt, max_frames, hipHostMallocDefault) == hipSuccess;
-    ok = ok && hipHostMalloc((void **)&ctx->h_red, max_frames * sizeof(uint32_t), hipHostMallocDefault) == hipSuccess;
+    for (int i = 0; i < igdsp_rx::RingMem::kArrays; ++i)
+        ok = ok && hipHostMalloc(ctx->ring.array(i), igdsp_rx::RingMem::bytes(max_channels, i), hipHostMallocDefault) == hipSuccess;
+    if (ok) ctx->rx.init(max_channels, ctx->ring);
     ok = ok && hipHostMalloc((void **)&ctx->h_up, ctx->up_bytes, hipHostMallocDefault) == hipSuccess;
-    for (auto &pb : ctx->pub) {
+    for (uint32_t i = 0; i < 2; ++i) {
+        igdsp_rx::Published &pb = ctx->pub.set(i);
         ok = ok && hipHostMalloc((void **)&pb.last, max_channels * sizeof(igdsp_frame_stats), hipHostMallocDefault) == hipSuccess;
         ok = ok && hipHostMalloc((void **)&pb.hold, max_channels * sizeof(igdsp_chan_hold), hipHostMallocDefault) == hipSuccess;
         ok = ok && hipHostMalloc((void **)&pb.probe, max_channels * sizeof(igdsp_chan_probe), hipHostMallocDefault) == hipSuccess;
@@ -264,7 +152,8 @@ int igdsp_create(igdsp_ctx **out, int device, uint32_t max_channels)
         return IGDSP_EDEVICE;
     }
     bool up = launch_hold_reset(ctx->d_hold, max_channels, nullptr, ctx->stream) == hipSuccess;
-    for (auto &pb : ctx->pub) {
+    for (uint32_t i = 0; i < 2; ++i) {
+        igdsp_rx::Published &pb = ctx->pub.set(i);
         std::memset(pb.last, 0, max_channels * sizeof(igdsp_frame_stats));
         std::memset(pb.probe, 0, max_channels * sizeof(igdsp_chan_probe));
         up = up && hipMemcpyAsync(pb.hold, ctx->d_hold, max_channels * sizeof(igdsp_chan_hold), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
@@ -273,12 +162,7 @@ int igdsp_create(igdsp_ctx **out, int device, uint32_t max_channels)
         igdsp_destroy(ctx);
         return IGDSP_EDEVICE;
     }
-    if (max_channels >= kPoolMinChannels) {
-        const uint32_t hw = std::max(1u, std::thread::hardware_concurrency());
-        uint32_t threads = std::min(std::min(kPoolMaxThreads, std::max(1u, hw / 2u)), max_channels / (kPoolMinChannels / 4u));   // >= 4 096 channels per thread
-        if (const char *e = std::getenv("IGDSP_FLUSH_THREADS")) threads = (uint32_t)std::max(1, std::min(64, std::atoi(e)));
-        if (threads > 1u) ctx->pool = new (std::nothrow) igdsp_ctx::SnapshotPool(threads - 1u);
-    }
+    ctx->pool = make_pool(max_channels);
     *out = ctx;
     return IGDSP_OK;
 }
@@ -286,14 +170,15 @@ int igdsp_create(igdsp_ctx **out, int device, uint32_t max_channels)
 int igdsp_destroy(igdsp_ctx *ctx)
 {
     if (!ctx) return IGDSP_OK;                       // tolerate NULL like the reference's setters (TransportAdapter.cpp:135-223)
-    delete ctx->pool;
+    ctx->pool.reset();
     if (ctx->device >= 0) (void)hipSetDevice(ctx->device);
     delete ctx->tx.load();
     igdsp_io_drop_spares(ctx);
     if (ctx->stream) { (void)hipStreamSynchronize(ctx->stream); (void)hipStreamDestroy(ctx->stream); }
     if (ctx->flush_done) (void)hipEventDestroy(ctx->flush_done);
-    void *hosts[] = {ctx->h_ring, ctx->h_rlen, ctx->h_rpt, ctx->h_red, ctx->h_up, ctx->pub[0].last, ctx->pub[0].hold, ctx->pub[0].probe,
-                     ctx->pub[1].last, ctx->pub[1].hold, ctx->pub[1].probe};
+    for (int i = 0; i < igdsp_rx::RingMem::kArrays; ++i) if (*ctx->ring.array(i)) (void)hipHostFree(*ctx->ring.array(i));
+    const igdsp_rx::Published &p0 = ctx->pub.set(0), &p1 = ctx->pub.set(1);
+    void *hosts[] = {ctx->h_up, p0.last, p0.hold, p0.probe, p1.last, p1.hold, p1.probe};
     for (void *p : hosts) if (p) (void)hipHostFree(p);
     void *devs[] = {ctx->d_up, ctx->d_stats, ctx->d_last, ctx->d_hold, ctx->d_probe, ctx->d_queues, ctx->d_enc_tab[0], ctx->d_enc_tab[1]};
     for (void *p : devs) if (p) (void)hipFree(p);
@@ -353,25 +238,7 @@ int igdsp_on_rtp_frame(igdsp_ctx *ctx, int32_t call_id, uint8_t pt, const uint8_
     if (payloadlen > kSlot || (payloadlen && !payload)) return IGDSP_EINVAL;
     const uint32_t ch = lookup(ctx, call_id);
     if (ch == kNoChan) return IGDSP_ENOENT;          // the reference's if-chain falls through silently; we report it
-    if (payloadlen == 0) return IGDSP_OK;
-    std::atomic_flag &lk = ctx->slot_lock[ch];
-    while (lk.test_and_set(std::memory_order_acquire)) cpu_relax();     // held by another producer / the flush for one <= 256-byte copy
-    int rc = IGDSP_OK;
-    if (ctx->head[ch] - ctx->tail[ch] == kStageDepth) {                 // the owner thread is > 160 ms late: the oldest frame goes
-        ctx->tail[ch] += 1;
-        ctx->frames_dropped[ch].fetch_add(1, std::memory_order_relaxed);
-        rc = IGDSP_EBUSY;
-    }
-    const size_t slot = (size_t)(ctx->head[ch] % kStageDepth) * ctx->max_channels + ch;   // slot-major: the flush walks each slot plane sequentially
-    std::memcpy(ctx->h_ring + slot * kSlot, payload, payloadlen);
-    ctx->h_rlen[slot] = (uint16_t)payloadlen;
-    ctx->h_rpt[slot] = pt;
-    ctx->h_red[slot] = ctx->cur_ed137[ch].load(std::memory_order_relaxed);
-    ctx->head[ch] += 1;
-    lk.clear(std::memory_order_release);
-    uint32_t hw = ctx->hi_water.load(std::memory_order_relaxed);
-    while (hw < ch + 1 && !ctx->hi_water.compare_exchange_weak(hw, ch + 1, std::memory_order_relaxed)) {}
-    return rc;
+    return ctx->rx.stage(ch, pt, payload, payloadlen);
 }
 
 // setIncomingED137Value (roip_ed137.h:273): the word the call's frames carry from now on
@@ -380,7 +247,7 @@ int igdsp_set_ed137(igdsp_ctx *ctx, int32_t call_id, uint32_t ed137_value)
     if (!ctx) return IGDSP_EINVAL;
     const uint32_t ch = lookup(ctx, call_id);
     if (ch == kNoChan) return IGDSP_ENOENT;
-    ctx->cur_ed137[ch].store(ed137_value, std::memory_order_relaxed);
+    ctx->rx.set_word(ch, ed137_value);
     return IGDSP_OK;
 }
 
@@ -389,48 +256,6 @@ int igdsp_set_gate_mode(igdsp_ctx *ctx, uint32_t gate_mode)
     if (!ctx || gate_mode > IGDSP_GATE_SQU_OR_PTT) return IGDSP_EINVAL;
     ctx->gate_mode.store(gate_mode, std::memory_order_relaxed);
     return IGDSP_OK;
-}
-
-// One worker's share of the snapshot: every channel of [part.c0, part.c1), staged frames oldest first, compacted into the
-// worker's own region of the upload block, under the channel's flag.
-static void snapshot_part(igdsp_ctx *ctx, const UploadLayout &L, SnapPart &part)
-{
-    uint8_t *up = ctx->h_up;
-    uint16_t *lenB = reinterpret_cast<uint16_t *>(up + L.lenB);
-    uint32_t *seq = reinterpret_cast<uint32_t *>(up + L.seq), *runs = reinterpret_cast<uint32_t *>(up + L.runs);
-    const uint32_t base = part.c0 * kStageDepth;                       // first frame index of this worker's regions
-    uint32_t nA = 0, nB = 0, nS = 0;
-    for (uint32_t c = part.c0; c < part.c1; ++c) {
-        std::atomic_flag &lk = ctx->slot_lock[c];
-        while (lk.test_and_set(std::memory_order_acquire)) cpu_relax();
-        const uint32_t t0 = ctx->tail[c], h0 = ctx->head[c];
-        const uint32_t s0 = nS;
-        for (uint32_t k = t0; k != h0; ++k) {
-            const size_t slot = (size_t)(k % kStageDepth) * ctx->max_channels + c;
-            const uint16_t l = ctx->h_rlen[slot];
-            uint32_t id;
-            if (l == IGDSP_SAMPLES_PER_FRAME) {
-                id = base + nA++;
-                std::memcpy(up + L.payA + (size_t)id * IGDSP_SAMPLES_PER_FRAME, ctx->h_ring + slot * kSlot, l);
-                up[L.ptA + id] = ctx->h_rpt[slot];
-            } else {
-                const uint32_t ib = base + nB++;
-                std::memcpy(up + L.payB + (size_t)ib * kSlot, ctx->h_ring + slot * kSlot, l);
-                lenB[ib] = l;
-                up[L.ptB + ib] = ctx->h_rpt[slot];
-                id = ib | kRecB;
-            }
-            seq[2 * (size_t)(base + nS)] = id;
-            seq[2 * (size_t)(base + nS) + 1] = ctx->h_red[slot];
-            ++nS;
-        }
-        ctx->tail[c] = h0;
-        lk.clear(std::memory_order_release);
-        runs[2 * (size_t)c] = base + s0;
-        runs[2 * (size_t)c + 1] = nS - s0;
-        if (h0 != t0) ctx->frames_seen[c].fetch_add(h0 - t0, std::memory_order_relaxed);
-    }
-    part.nA = nA; part.nB = nB; part.nSeq = nS;
 }
 
 static int flush_end_locked(igdsp_ctx *ctx, int wait)
@@ -443,9 +268,7 @@ static int flush_end_locked(igdsp_ctx *ctx, int wait)
     } else {
         HIP_TRY(ctx, hipEventSynchronize(ctx->flush_done));
     }
-    // the back set is complete: make it the front set.  Readers that were half way through the old one notice pub_seq moving.
-    ctx->front.store(ctx->front.load(std::memory_order_relaxed) ^ 1u, std::memory_order_release);
-    ctx->pub_seq.fetch_add(2, std::memory_order_release);
+    ctx->pub.flip();                                                    // the back set is complete: make it the front set
     ctx->flush_open = false;
     return IGDSP_OK;
 }
@@ -454,18 +277,18 @@ static int flush_begin_locked(igdsp_ctx *ctx, uint32_t *n_frames_out)
 {
     if (int rc = flush_end_locked(ctx, 1)) return rc;               // one flush at a time: the upload block is single
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const uint32_t nch = ctx->hi_water.load(std::memory_order_relaxed);
+    const uint32_t nch = ctx->rx.channels_seen();
     if (n_frames_out) *n_frames_out = 0;
     if (nch == 0) return IGDSP_OK;
     const size_t max_frames = (size_t)ctx->max_channels * kStageDepth;
-    const UploadLayout L = upload_layout(max_frames, ctx->max_channels);
+    const igdsp_rx::UploadLayout L = igdsp_rx::upload_layout(max_frames, ctx->max_channels);
     // 1. snapshot every channel's staged frames (oldest first) into the upload block, compacted per worker region
-    SnapPart parts[64];
-    uint32_t n_parts = 1;
-    if (ctx->pool && nch >= kPoolMinChannels) n_parts = std::min<uint32_t>((uint32_t)ctx->pool->threads.size() + 1u, 64u);
-    for (uint32_t i = 0; i < n_parts; ++i) { parts[i].c0 = (uint32_t)((uint64_t)nch * i / n_parts); parts[i].c1 = (uint32_t)((uint64_t)nch * (i + 1) / n_parts); }
-    if (n_parts == 1) snapshot_part(ctx, L, parts[0]);
-    else ctx->pool->run([&](uint32_t i) { if (i < n_parts) snapshot_part(ctx, L, parts[i]); });
+    igdsp_rx::SnapPart parts[kMaxParts];
+    const uint32_t n_parts = for_each_part(nch >= kPoolMinChannels ? ctx->pool.get() : nullptr, nch, [&](uint32_t i, uint32_t c0, uint32_t c1) {
+        parts[i].c0 = c0;
+        parts[i].c1 = c1;
+        ctx->rx.snapshot(parts[i], ctx->h_up, L);
+    });
     uint32_t staged = 0, endA = 0, endB = 0, endS = 0;
     for (uint32_t i = 0; i < n_parts; ++i) {
         staged += parts[i].nSeq;
@@ -506,7 +329,7 @@ static int flush_begin_locked(igdsp_ctx *ctx, uint32_t *n_frames_out)
     HIP_TRY(ctx, launch_flush_fold(stA, stB, reinterpret_cast<const uint16_t *>(d + L.lenB), reinterpret_cast<const uint2 *>(d + L.seq),
                                    reinterpret_cast<const uint2 *>(d + L.runs), nch, ctx->gate_mode.load(std::memory_order_relaxed), IGDSP_PROBE_ALARM,
                                    ctx->d_hold, ctx->d_probe, ctx->d_last, s));
-    const igdsp_ctx::Published &back = ctx->pub[ctx->front.load(std::memory_order_relaxed) ^ 1u];
+    const igdsp_rx::Published &back = ctx->pub.back();
     HIP_TRY(ctx, hipMemcpyAsync(back.last, ctx->d_last, (size_t)nch * sizeof(igdsp_frame_stats), hipMemcpyDeviceToHost, s));
     HIP_TRY(ctx, hipMemcpyAsync(back.hold, ctx->d_hold, (size_t)nch * sizeof(igdsp_chan_hold), hipMemcpyDeviceToHost, s));
     HIP_TRY(ctx, hipMemcpyAsync(back.probe, ctx->d_probe, (size_t)nch * sizeof(igdsp_chan_probe), hipMemcpyDeviceToHost, s));
@@ -544,15 +367,15 @@ int igdsp_poll(igdsp_ctx *ctx, uint32_t channel, igdsp_level *out)
     if (channel >= ctx->max_channels) return IGDSP_ERANGE;
     igdsp_frame_stats s;
     uint16_t peak_hold = 0;
-    read_published(ctx, [&](const igdsp_ctx::Published &p) { s = p.last[channel]; peak_hold = p.hold[channel].peak_hold; });
+    ctx->pub.read([&](const igdsp_rx::Published &p) { s = p.last[channel]; peak_hold = p.hold[channel].peak_hold; });
     out->byte_mean = s.byte_mean;
     out->flags = s.flags;
     out->peak = s.peak;
     out->rms = s.rms;
     out->percent = (int32_t)(float)(((double)s.rms * 100.0) / (double)IGDSP_METER_FULL_SCALE);   // audiometer.cpp:30-31
     out->peak_hold = peak_hold;
-    out->dropped = (uint16_t)std::min<uint32_t>(ctx->frames_dropped[channel].load(std::memory_order_relaxed), 65535u);
-    out->frames = ctx->frames_seen[channel].load(std::memory_order_relaxed);
+    out->dropped = (uint16_t)std::min<uint32_t>(ctx->rx.frames_dropped(channel), 65535u);
+    out->frames = ctx->rx.frames_seen(channel);
     return IGDSP_OK;
 }
 
@@ -575,12 +398,11 @@ int igdsp_reset_hold(igdsp_ctx *ctx, uint32_t channel)
     const uint32_t cn = (channel == 0xFFFFFFFFu) ? ctx->max_channels : 1;
     HIP_TRY(ctx, launch_hold_reset(ctx->d_hold + c0, cn, nullptr, ctx->stream));
     // both published sets show the reset window at once (no flush is open, so nothing else writes them)
-    const uint32_t f = ctx->front.load(std::memory_order_relaxed);
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->pub[f ^ 1u].hold + c0, ctx->d_hold + c0, cn * sizeof(igdsp_chan_hold), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->pub.back().hold + c0, ctx->d_hold + c0, cn * sizeof(igdsp_chan_hold), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->pub_seq.fetch_add(1, std::memory_order_acq_rel);             // odd: readers wait
-    std::memcpy(ctx->pub[f].hold + c0, ctx->pub[f ^ 1u].hold + c0, cn * sizeof(igdsp_chan_hold));
-    ctx->pub_seq.fetch_add(1, std::memory_order_release);
+    ctx->pub.rewrite_front([&](igdsp_rx::Published &front, const igdsp_rx::Published &back) {
+        std::memcpy(front.hold + c0, back.hold + c0, cn * sizeof(igdsp_chan_hold));
+    });
     return IGDSP_OK;
 }
 
@@ -588,7 +410,7 @@ int igdsp_get_hold(igdsp_ctx *ctx, uint32_t channel, igdsp_chan_hold *out)
 {
     if (!ctx || !out) return IGDSP_EINVAL;
     if (channel >= ctx->max_channels) return IGDSP_ERANGE;
-    read_published(ctx, [&](const igdsp_ctx::Published &p) { *out = p.hold[channel]; });
+    ctx->pub.read([&](const igdsp_rx::Published &p) { *out = p.hold[channel]; });
     return IGDSP_OK;
 }
 
@@ -596,7 +418,7 @@ int igdsp_get_probe(igdsp_ctx *ctx, uint32_t channel, igdsp_chan_probe *out)
 {
     if (!ctx || !out) return IGDSP_EINVAL;
     if (channel >= ctx->max_channels) return IGDSP_ERANGE;
-    read_published(ctx, [&](const igdsp_ctx::Published &p) { *out = p.probe[channel]; });
+    ctx->pub.read([&](const igdsp_rx::Published &p) { *out = p.probe[channel]; });
     return IGDSP_OK;
 }
 
@@ -1026,15 +848,8 @@ int igdsp_tx_flush(igdsp_ctx *ctx, uint32_t *n_frames_out)
     // 1. snapshot: count, then emit each part's legs at its offsets (a pool of helpers at many legs, as the RX flush)
     using igdsp_tx::Stager;
     const uint32_t legs = tx->st.legs();
-    uint32_t n_parts = tx->pool ? std::min<uint32_t>((uint32_t)tx->pool->threads.size() + 1u, 64u) : 1u;
-    uint32_t lo[65];
-    Stager::Counts cnt[64], base[64];
-    for (uint32_t i = 0; i <= n_parts; ++i) lo[i] = (uint32_t)((uint64_t)legs * i / n_parts);
-    auto each = [&](const std::function<void(uint32_t)> &fn) {
-        if (n_parts == 1) fn(0);
-        else tx->pool->run([&](uint32_t i) { if (i < n_parts) fn(i); });
-    };
-    each([&](uint32_t i) { cnt[i] = tx->st.count(lo[i], lo[i + 1]); });
+    Stager::Counts cnt[kMaxParts], base[kMaxParts];
+    const uint32_t n_parts = for_each_part(tx->pool.get(), legs, [&](uint32_t i, uint32_t l0, uint32_t l1) { cnt[i] = tx->st.count(l0, l1); });
     Stager::Counts tot;
     for (uint32_t i = 0; i < n_parts; ++i) {
         base[i] = tot;
@@ -1049,7 +864,7 @@ int igdsp_tx_flush(igdsp_ctx *ctx, uint32_t *n_frames_out)
     }
     if (hipError_t e = tx_reserve(tx, &tx->h_out, &tx->d_out, &tx->out_cap, O.total))
         return fail(ctx, e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation ? IGDSP_ENOMEM : IGDSP_EDEVICE, "igdsp_tx_flush: result block", e);
-    each([&](uint32_t i) { tx->st.emit(lo[i], lo[i + 1], tx->h_up, L, base[i]); });
+    for_each_part(tx->pool.get(), legs, [&](uint32_t i, uint32_t l0, uint32_t l1) { tx->st.emit(l0, l1, tx->h_up, L, base[i]); });
     const auto t1 = std::chrono::steady_clock::now();
     // 2. upload, packetise, download, on the TX stream
     hipStream_t s = tx->stream;

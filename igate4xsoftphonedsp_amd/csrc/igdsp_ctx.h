@@ -2,6 +2,8 @@
 // entry uses.  Not part of the ABI (include/igdsp.h is).
 #pragma once
 #include "igdsp_internal.h"
+#include "igdsp_rxstage.h"
+#include "igdsp_snappool.h"
 
 #include <atomic>
 #include <cstdio>
@@ -11,8 +13,6 @@
 #include <vector>
 
 namespace {
-constexpr uint32_t kSlot = IGDSP_MAX_PAYLOAD;          // staging slot bytes (tp_adapter::payload_buff[256])
-constexpr uint32_t kStageDepth = IGDSP_STAGE_DEPTH;    // frames per channel between two flushes (8 x 20 ms)
 constexpr uint32_t kNoChan = 0xFFFFFFFFu;
 constexpr int32_t kDirectCalls = 1 << 16;              // pjsua_call_id values are small non-negative ints
 }  // namespace
@@ -52,45 +52,31 @@ struct igdsp_ctx {
     std::unordered_map<int32_t, uint32_t> far;
     std::mutex far_mu;
 
-    // staging (host pinned): a ring of kStageDepth frames per channel, ring[slot][c][256] + rlen / rpt / red per slot (slot-major: the
-    // frames all calls staged at the same tick position sit next to each other, so the flush reads sequentially); head counts frames
-    // written, tail frames taken by a flush (head - tail <= kStageDepth).  tp_adapter::payload_buff[256] semantics per slot
-    // (TransportAdapter.h:66): the reference's hook runs on EVERY frame (TransportAdapter.cpp:303), so every frame is kept.
-    // red = the call's ED-137 word when the frame was staged (igdsp_set_ed137 = setIncomingED137Value, roip_ed137.h:273).
-    uint8_t *h_ring = nullptr;
-    uint16_t *h_rlen = nullptr;
-    uint8_t *h_rpt = nullptr;
-    uint32_t *h_red = nullptr;
-    std::vector<uint32_t> head, tail;
-    std::vector<std::atomic<uint32_t>> cur_ed137;       // per channel: the word frames staged from now on carry
-    std::vector<std::atomic_flag> slot_lock;
-    std::atomic<uint32_t> hi_water{0};                 // 1 + highest channel ever staged
+    // staging: a ring of kStageDepth frames per channel in pinned memory (allocated by igdsp_create) and the stager that works in
+    // it (csrc/igdsp_rxstage.h)
+    igdsp_rx::RingMem ring;
+    igdsp_rx::Stager rx;
     std::atomic<uint32_t> gate_mode{IGDSP_GATE_ALWAYS}; // igdsp_set_gate_mode: how a flush gates each frame's fold into the window
 
     // flush: one pinned upload block + its device mirror (sections at 256-byte aligned offsets), per-channel device state and
     // its published host snapshots.  igdsp_flush_begin snapshots + enqueues, igdsp_flush_end waits and publishes; the device
     // writes each flush's {newest record, hold, probe} of every channel into the BACK set of pinned arrays, flush_end makes it
-    // the front set (pub_seq moves): igdsp_poll / get_hold / get_probe read the front set and never take flush_mu.
+    // the front set (igdsp_rxstage.h: PublishedSet): igdsp_poll / get_hold / get_probe read the front set and never take flush_mu.
     uint8_t *h_up = nullptr, *d_up = nullptr;
     size_t up_bytes = 0;
     igdsp_frame_stats *d_stats = nullptr;               // one record per staged frame of this flush (regions may have gaps, see flush_begin)
     igdsp_frame_stats *d_last = nullptr;                // per channel: record of its newest metered frame
     igdsp_chan_hold *d_hold = nullptr;
     igdsp_chan_probe *d_probe = nullptr;
-    struct Published { igdsp_frame_stats *last; igdsp_chan_hold *hold; igdsp_chan_probe *probe; };
-    Published pub[2] = {};                              // pinned; pub[front] is what the poll entries read
-    std::atomic<uint32_t> front{0};
-    std::atomic<uint64_t> pub_seq{0};                   // moves whenever `front` does (readers retry when it moved under them)
-    std::vector<std::atomic<uint32_t>> frames_seen, frames_dropped;   // per channel: frames taken by a flush / overwritten before one took them
+    igdsp_rx::PublishedSet pub;                         // pinned; its front set is what the poll entries read
     hipEvent_t flush_done = nullptr;
     bool flush_open = false;                            // a flush_begin without its flush_end
     uint32_t flush_nch = 0;                             // channels the open flush downloads
     std::mutex flush_mu;                                // owner-thread entries (flush*, reset_hold)
 
     // snapshot helpers: at many channels the flush's host-side snapshot (one pass over every channel's ring) is shared out to a
-    // few threads (igdsp_capi.hip: SnapshotPool)
-    struct SnapshotPool;
-    SnapshotPool *pool = nullptr;
+    // few threads (csrc/igdsp_snappool.h); nullptr: the owner thread snapshots alone
+    std::unique_ptr<igdsp::SnapshotPool> pool;
 
     // the staged ED-137 send path (igdsp_tx_open .. igdsp_tx_flush, igdsp_capi.hip): its own staging rings, stream, pinned
     // blocks and device state, created by the first igdsp_tx_open so that RX-only users pay nothing for it
