@@ -143,6 +143,7 @@ int igdsp_create(igdsp_ctx **out, int device, uint32_t max_channels)
     ok = ok && hipMemset(ctx->d_last, 0, max_channels * sizeof(igdsp_frame_stats)) == hipSuccess;
     ok = ok && hipMemset(ctx->d_probe, 0, max_channels * sizeof(igdsp_chan_probe)) == hipSuccess;
     if (const char *e = std::getenv("IGDSP_GLOBAL_QUEUE")) ctx->global_queue = std::atoi(e) != 0;
+    if (const char *e = std::getenv("IGDSP_IO_SPARE_CHUNKS")) ctx->io_spare_cap = (size_t)std::max(0, std::atoi(e));
     if (!ok) {
         igdsp_destroy(ctx);
         return IGDSP_ENOMEM;

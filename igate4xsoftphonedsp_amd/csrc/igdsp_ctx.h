@@ -37,7 +37,7 @@ struct igdsp_ctx {
     // search's inputs landed in, 1 = "not 0" (not split further), 2 / 3 = the two other classes once a bulk search split them.
     std::vector<hipMemGenericAllocationHandle_t> io_spare[4];
     size_t io_spare_chunk = 0;                          // chunk size the spares were created with
-    size_t io_spare_cap = 16;                           // chunks kept per class (IGDSP_IO_SPARE_CHUNKS; 0 = keep none)
+    size_t io_spare_cap = 16;                           // chunks kept per class (IGDSP_IO_SPARE_CHUNKS, read by igdsp_create; 0 = keep none)
     uint32_t io_epoch = 0;                              // moves with every full search: class labels of older buffer sets no longer apply
     std::mutex io_mu;
     bool is_spread(const void *p)

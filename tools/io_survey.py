@@ -1,11 +1,10 @@
 #!/usr/bin/env python3
-"""Class map of consecutive 128 MiB chunks as igdsp_io_alloc sees it (IGDSP_IO_DEBUG / IGDSP_IO_SURVEY print every probe):
+"""Class map of consecutive 128 MiB chunks as igdsp_io_alloc sees it (IGDSP_IO_DEBUG prints every probe):
 asks for a RECORD + a BULK buffer of <GiB> each so that the walk covers many chunks.  usage: io_survey.py [GiB] [stride]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 os.environ["IGDSP_IO_DEBUG"] = "1"
-os.environ["IGDSP_IO_SURVEY"] = "1"
 if len(sys.argv) > 2:
     os.environ["IGDSP_IO_STRIDE"] = sys.argv[2]
 import torch
