@@ -23,6 +23,7 @@ MAX_PAYLOAD = 256
 STAGE_DEPTH = 8
 ENC_SUN16, ENC_G191 = 0, 1
 FLAG_SILENT, FLAG_PROBE_D5, FLAG_CLIPPED, FLAG_EMPTY = 1, 2, 4, 8
+FLAG_SATURATED = 0x10        # igdsp_conf_mix
 AGG_MAX_RANKS = 8
 AGG_LINE_WORDS = 16
 AGG_WORDS = 7 * AGG_LINE_WORDS
@@ -161,6 +162,9 @@ PROTOTYPES = [
     ("igdsp_tx_results", _int, [_vp, C.POINTER(_vp), C.POINTER(_u32)]),
     ("igdsp_tx_get_chan", _int, [_vp, _i32, _vp]),
     ("igdsp_tx_counts", _int, [_vp, _i32, C.POINTER(_u32), C.POINTER(_u32)]),
+    ("igdsp_conf_level_q7", _int, [C.c_float]),
+    ("igdsp_conf_build", _int, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, C.POINTER(_u32)]),
+    ("igdsp_conf_mix", _int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp]),
     ("igdsp_g726_reorder", _int, [_vp, _vp, _vp, _u64, _int, _vp]),
     ("igdsp_gen_uniform", _int, [_vp, _vp, _u64, _u64, _u64, _vp]),
     ("igdsp_dev_alloc", _int, [_vp, C.POINTER(_vp), C.c_size_t]),
@@ -225,6 +229,30 @@ def tx_chan_init(calltype: str, call_in: bool, pt: int, ssrc: int, seq0: int, ts
     if rc != 0:
         raise IgdspError(rc, "igdsp_tx_chan_init")
     return out
+
+
+def conf_level_q7(level: float) -> int:
+    """igdsp_conf_level_q7: the Q7 receive level of a float slot volume (host only, no GPU); raises on IGDSP_EINVAL."""
+    q = load().igdsp_conf_level_q7(level)
+    if q < 0:
+        raise IgdspError(q, "igdsp_conf_level_q7")
+    return q
+
+
+def conf_build(channel, port, n_channels: int, n_ports: int):
+    """igdsp_conf_build: (channel, port) connection lists -> (port_ptr uint32 [n_ports + 1], members uint32 [n_members]) (host only)."""
+    ch = np.ascontiguousarray(channel, dtype=np.uint32).reshape(-1)
+    pt = np.ascontiguousarray(port, dtype=np.uint32).reshape(-1)
+    if ch.shape != pt.shape:
+        raise ValueError("channel and port lists differ in length")
+    ptr = np.zeros(n_ports + 1, np.uint32)
+    mem = np.zeros(max(1, ch.size), np.uint32)
+    nm = _u32()
+    rc = load().igdsp_conf_build(ch.ctypes.data_as(_vp), pt.ctypes.data_as(_vp), ch.size, n_channels, n_ports, ptr.ctypes.data_as(_vp),
+                                 mem.ctypes.data_as(_vp), C.byref(nm))
+    if rc != 0:
+        raise IgdspError(rc, "igdsp_conf_build")
+    return ptr, mem[: nm.value].copy()
 
 
 def _ptr(x) -> int | None:
@@ -379,6 +407,13 @@ class Context:
         self._ck(self.L.igdsp_tx_packetize(self.h, _ptr(pcm), _ptr(g711), _ptr(ctl), C_, F_, n, t0_ms, frame_ms, _ptr(state),
                                            _ptr(last_payload), _ptr(packets), stride, _ptr(sizes), _ptr(info), variant, stream),
                  "igdsp_tx_packetize")
+
+    def conf_mix(self, gain, port_ptr, members, n_members, C_, P_, F_, n, out=None, stats=None, payload=None, codec=None, pcm=None,
+                 length=None, stream=None):
+        """igdsp_conf_mix: exactly one of payload [F][C][n] u8 (+ codec [C]) / pcm [F][C][n] int16; out [F][P][n] int16 and / or
+        stats [F][P] (device buffers)."""
+        self._ck(self.L.igdsp_conf_mix(self.h, _ptr(payload), _ptr(codec), _ptr(pcm), _ptr(length), _ptr(gain), _ptr(port_ptr), _ptr(members),
+                                       n_members, C_, P_, F_, n, _ptr(out), _ptr(stats), stream), "igdsp_conf_mix")
 
     # -- staged ED-137 send path (transport_send_rtp as pjmedia calls it)
     def tx_open(self, call_id: int, calltype: str, call_in: bool, keepalive_ms: int = 200, now_ms: int = 0):

@@ -734,6 +734,70 @@ int igdsp_tx_packetize(igdsp_ctx *ctx, const int16_t *d_pcm, const uint8_t *d_g7
     return IGDSP_OK;
 }
 
+// ---- conference mix: pjmedia's bridge step as the reference drives it (pjsua_conf_connect roip_ed137.cpp:4907-4917, Functions.cpp:718-740;
+// pjsua_conf_adjust_rx_level in setSlotVolume roip_ed137.cpp:5190-5233, setvolumeSiteTone roip_ed137.cpp:6869-6878) ----
+int igdsp_conf_level_q7(float level)
+{
+    if (!(level == level)) return IGDSP_EINVAL;                                               // NaN
+    const float adj = (level - 1.0f) * 128.0f;                                                // float, as pjsua does it
+    if (!(adj > -1.0e6f && adj < 1.0e6f)) return IGDSP_EINVAL;                                // (int) of it must be defined
+    const int q = 128 + (int)adj;                                                             // (int): toward zero
+    return (q < 0 || q > 65535) ? IGDSP_EINVAL : q;
+}
+
+int igdsp_conf_build(const uint32_t *channel, const uint32_t *port, uint32_t n_conn, uint32_t n_channels, uint32_t n_ports,
+                     uint32_t *port_ptr, uint32_t *members, uint32_t *n_members)
+{
+    if (!port_ptr || !n_members || (n_conn && (!channel || !port || !members))) return IGDSP_EINVAL;
+    std::vector<uint64_t> key;
+    try { key.resize(n_conn); } catch (...) { return IGDSP_ENOMEM; }
+    for (uint32_t i = 0; i < n_conn; ++i) {
+        if (channel[i] >= n_channels || port[i] >= n_ports) return IGDSP_EINVAL;
+        key[i] = (uint64_t)port[i] << 32 | channel[i];
+    }
+    std::sort(key.begin(), key.end());
+    key.erase(std::unique(key.begin(), key.end()), key.end());
+    uint32_t j = 0;
+    for (uint32_t p = 0; p <= n_ports; ++p) {
+        while (j < key.size() && (key[j] >> 32) < p) ++j;
+        port_ptr[p] = j;
+    }
+    for (size_t i = 0; i < key.size(); ++i) members[i] = (uint32_t)key[i];
+    *n_members = (uint32_t)key.size();
+    return IGDSP_OK;
+}
+
+// the argument rules of igdsp_conf_mix (shared with the yardstick entry)
+static int conf_check(igdsp_ctx *ctx, const uint8_t *d_payload, const uint8_t *d_codec, const int16_t *d_pcm, const uint16_t *d_len,
+                      const uint16_t *d_gain, const uint32_t *d_port_ptr, const uint32_t *d_members, uint32_t n_members, uint32_t C, uint32_t P,
+                      uint32_t F, uint32_t n, const int16_t *d_out, const igdsp_frame_stats *d_stats)
+{
+    if (!ctx) return IGDSP_EINVAL;
+    if ((d_payload == nullptr) == (d_pcm == nullptr) || (d_payload && !d_codec)) return IGDSP_EINVAL;   // exactly one input form
+    if (!d_out && !d_stats) return IGDSP_EINVAL;
+    if (!d_gain || !d_port_ptr || (n_members && !d_members)) return IGDSP_EINVAL;
+    if (int rc = check_shape(C, F, n)) return rc;
+    if (int rc = check_shape(P, F, n)) return rc;
+    const uintptr_t a2 = reinterpret_cast<uintptr_t>(d_pcm) | reinterpret_cast<uintptr_t>(d_len) | reinterpret_cast<uintptr_t>(d_gain) |
+                         reinterpret_cast<uintptr_t>(d_out);
+    const uintptr_t a4 = reinterpret_cast<uintptr_t>(d_port_ptr) | reinterpret_cast<uintptr_t>(d_members);
+    if ((a2 & 1u) || (a4 & 3u) || (reinterpret_cast<uintptr_t>(d_stats) & 7u)) return IGDSP_EINVAL;
+    return IGDSP_OK;
+}
+
+int igdsp_conf_mix(igdsp_ctx *ctx, const uint8_t *d_payload, const uint8_t *d_codec, const int16_t *d_pcm, const uint16_t *d_len,
+                   const uint16_t *d_gain, const uint32_t *d_port_ptr, const uint32_t *d_members, uint32_t n_members, uint32_t C, uint32_t P,
+                   uint32_t F, uint32_t n, int16_t *d_out, igdsp_frame_stats *d_stats, void *stream)
+{
+    if (!ctx) return IGDSP_EINVAL;
+    if ((uint64_t)P * F == 0) return IGDSP_OK;                                               // nothing to write
+    if (int rc = conf_check(ctx, d_payload, d_codec, d_pcm, d_len, d_gain, d_port_ptr, d_members, n_members, C, P, F, n, d_out, d_stats)) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, launch_conf_mix(cfg_of(ctx, pick(ctx, stream)), d_payload, d_codec, d_pcm, d_len, d_gain, d_port_ptr, d_members, n_members, C, P,
+                                 F, n, d_out, d_stats, pick(ctx, stream)));
+    return IGDSP_OK;
+}
+
 // ---- staged ED-137 send path (transport_send_rtp as pjmedia calls it, TransportAdapter.cpp:635-874) ----
 // the TX side and channel of call_id (whether or not a leg is open there), or nullptr with *rc set
 static igdsp_ctx::TxSide *tx_chan_of(igdsp_ctx *ctx, int32_t call_id, uint32_t *leg, int *rc)
@@ -1094,6 +1158,21 @@ int igdsp_internal_tx_copy(igdsp_ctx *ctx, const int16_t *d_pcm, const uint8_t *
     if (int rc = check_shape(C, F, n)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, launch_tx_copy_ab(cfg_of(ctx, pick(ctx, stream)), d_pcm, d_g711, C, F, n, d_packets, pkt_stride, pick(ctx, stream)));
+    return IGDSP_OK;
+}
+
+// Calibration-only (not in include/igdsp.h): the compute-free yardstick of igdsp_conf_mix (tools/conf_bench.py) — the same traversal,
+// the same bytes read and written, no decode / scale / clamp / stats.  Arguments as igdsp_conf_mix.
+int igdsp_internal_conf_copy(igdsp_ctx *ctx, const uint8_t *d_payload, const uint8_t *d_codec, const int16_t *d_pcm, const uint16_t *d_len,
+                             const uint16_t *d_gain, const uint32_t *d_port_ptr, const uint32_t *d_members, uint32_t n_members, uint32_t C,
+                             uint32_t P, uint32_t F, uint32_t n, int16_t *d_out, igdsp_frame_stats *d_stats, void *stream)
+{
+    if (!ctx) return IGDSP_EINVAL;
+    if ((uint64_t)P * F == 0) return IGDSP_OK;
+    if (int rc = conf_check(ctx, d_payload, d_codec, d_pcm, d_len, d_gain, d_port_ptr, d_members, n_members, C, P, F, n, d_out, d_stats)) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, launch_conf_copy_ab(cfg_of(ctx, pick(ctx, stream)), d_payload, d_codec, d_pcm, d_len, d_gain, d_port_ptr, d_members, n_members, C,
+                                     P, F, n, d_out, d_stats, pick(ctx, stream)));
     return IGDSP_OK;
 }
 

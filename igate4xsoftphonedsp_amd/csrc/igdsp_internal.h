@@ -82,6 +82,14 @@ hipError_t launch_tx_packetize(const LaunchCfg &cfg, const int16_t *pcm, const u
 hipError_t launch_tx_staged(const LaunchCfg &cfg, const void *runs, const void *recs, const uint32_t *stream, uint32_t n_runs,
                             igdsp_tx_chan *state, uint8_t *send_buf, igdsp_tx_info *info, igdsp_tx_chan *chan_out, uint32_t *packets,
                             hipStream_t s);
+// igdsp_conf_mix: exactly one of g711 (+ codec) / pcm; out and stats may be nullptr (not both: the C ABI checks)
+hipError_t launch_conf_mix(const LaunchCfg &cfg, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm, const uint16_t *len,
+                           const uint16_t *gain, const uint32_t *port_ptr, const uint32_t *members, uint32_t n_members, uint32_t C, uint32_t P,
+                           uint32_t F, uint32_t n, int16_t *out, igdsp_frame_stats *stats, hipStream_t s);
+// compute-free yardstick of launch_conf_mix: the same traversal, the same bytes read and written, no decode / scale / clamp / stats
+hipError_t launch_conf_copy_ab(const LaunchCfg &cfg, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm, const uint16_t *len,
+                               const uint16_t *gain, const uint32_t *port_ptr, const uint32_t *members, uint32_t n_members, uint32_t C, uint32_t P,
+                               uint32_t F, uint32_t n, int16_t *out, igdsp_frame_stats *stats, hipStream_t s);
 hipError_t launch_wav_expand(const LaunchCfg &cfg, const uint8_t *payload, uint32_t C, uint32_t F, uint32_t n, uint32_t rate,
                              uint8_t *files, uint64_t file_stride, hipStream_t s);
 hipError_t launch_g726(const LaunchCfg &cfg, const uint8_t *in, uint8_t *out, uint64_t n_bytes, int mode, hipStream_t s);

@@ -412,6 +412,32 @@ inline TxRoute tx_route(uint32_t C, uint32_t F, uint32_t n, uintptr_t pcm, uintp
     return r;
 }
 
+// ---- igdsp_conf_mix (launch_conf_mix, launch_conf_copy_ab): k_conf_mix<IN, COPY>.  An item is one (frame, port); a block of kConfWaves
+// waves takes groups of kConfWaves consecutive items.  Which ports are narrow (a wave mixes the port-frame alone) and which are wide
+// (the block splits the member list among its waves) is decided per item on the device from the CSR, so a launch with a skewed
+// table needs no copy of it to the host; the route only picks the input form, the vector paths and the grid.
+constexpr int kConfWaves = 16;                            // 1024 threads, one block per CU (64 KiB LUT + 32 KiB wide-form partials)
+constexpr int kConfU = 8;                                 // frame loads of a wave in flight together (divides 64)
+constexpr uint32_t kConfWideMin = 128;                    // members above which a port is mixed by the whole block
+enum : int { kConfG711 = 0, kConfPcm = 1 };               // k_conf_mix<IN>
+struct ConfRoute {
+    int form = kConfG711;
+    uint32_t vec_in = 0, vec_out = 0;      // n % 4 == 0 and rows aligned: dword (G.711) / 8-byte (PCM) loads, 8-byte stores
+    uint32_t grid = 0, threads = 0;
+};
+inline ConfRoute conf_route(uint32_t P, uint32_t F, uint32_t n, bool pcm, uintptr_t in, uintptr_t out, uint32_t cus)
+{
+    ConfRoute r;
+    const uint64_t items = (uint64_t)P * F;
+    if (items == 0) return r;
+    r.form = pcm ? kConfPcm : kConfG711;
+    r.vec_in = ((n & 3u) == 0u && aligned(in, pcm ? 8 : 4)) ? 1u : 0u;
+    r.vec_out = ((n & 3u) == 0u && aligned(out, 8)) ? 1u : 0u;
+    r.grid = blocks_for((items + kConfWaves - 1) / kConfWaves, 1, std::max(1u, cus));
+    r.threads = kConfWaves * 64;
+    return r;
+}
+
 // ---- igdsp_tx_flush (launch_tx_staged): a wave owns kTsLegs staged legs (runs) of the flush; lanes 0 .. kTsLegs-1 decide, the
 // whole wave writes the packets.  No dynamic LDS: each wave's records (kTsLegs x IGDSP_STAGE_DEPTH) are static.
 constexpr int kTsWaves = 4;

@@ -21,7 +21,67 @@ static long long now_ms()
 }
 
 // ---------------------------------------------------------------------------------------------
-RoIP_ED137::RoIP_ED137() : inviteMode(SERVER), referenceTxQuirk(false), ed137Events(0), onValueChanged(nullptr), m_softPhoneID(1), ctx_(nullptr)
+ConfLevels::ConfLevels(uint32_t n_channels) : SLOT_VOLUME(2.0f), sidetone(0.1f), n_(n_channels), gain_(nullptr), call_of_(nullptr)
+{
+    for (int i = 0; i < 4; ++i) radio_call[i] = -1;
+    gain_ = new (std::nothrow) uint16_t[n_ ? n_ : 1];
+    call_of_ = new (std::nothrow) int[n_ ? n_ : 1];
+    if (!gain_ || !call_of_) n_ = 0;
+    for (uint32_t c = 0; c < n_; ++c) { gain_[c] = (uint16_t)igdsp_conf_level_q7(2.0f); call_of_[c] = -1; }
+}
+
+ConfLevels::~ConfLevels()
+{
+    delete[] gain_;
+    delete[] call_of_;
+}
+
+int ConfLevels::mapCall(int callId, uint32_t channel)
+{
+    for (uint32_t c = 0; c < n_; ++c) if (call_of_[c] == callId) call_of_[c] = -1;
+    if (channel >= n_) return IGDSP_OK;
+    call_of_[channel] = callId;
+    return IGDSP_OK;
+}
+
+int ConfLevels::channelOf(int callId) const
+{
+    if (callId < 0) return -1;
+    for (uint32_t c = 0; c < n_; ++c) if (call_of_[c] == callId) return (int)c;
+    return -1;
+}
+
+// roip_ed137.cpp:5190-5233: the float steps and clamps as written, then the level to the call's slot
+bool ConfLevels::setSlotVolume(int callId, bool increase, bool current)
+{
+    const int c = channelOf(callId);
+    if (c < 0) return false;                                      // pjsua_call_get_info failed
+    if (!current) {
+        if (increase) {
+            SLOT_VOLUME += 0.1f;
+            if (SLOT_VOLUME >= MAX_SLOT_VOLUME) SLOT_VOLUME = MAX_SLOT_VOLUME;
+        } else {
+            SLOT_VOLUME -= 0.1f;
+            if (SLOT_VOLUME <= MIN_SLOT_VOLUME) SLOT_VOLUME = MIN_SLOT_VOLUME;
+        }
+    }
+    const int q = igdsp_conf_level_q7(SLOT_VOLUME);               // pjsua_conf_adjust_rx_level
+    if (q < 0) return false;
+    gain_[c] = (uint16_t)q;
+    return true;
+}
+
+// roip_ed137.cpp:6869-6878
+void ConfLevels::setvolumeSiteTone(int callId)
+{
+    bool bound = false;
+    for (int i = 0; i < 4; ++i) bound = bound || (callId == radio_call[i]);
+    SLOT_VOLUME = bound ? sidetone : 0.5f;
+    setSlotVolume(callId, false, true);
+}
+
+// ---------------------------------------------------------------------------------------------
+RoIP_ED137::RoIP_ED137() : inviteMode(SERVER), referenceTxQuirk(false), ed137Events(0), onValueChanged(nullptr), conf(8u), m_softPhoneID(1), ctx_(nullptr)
 {
     std::memset(window, 0, sizeof window);
     for (int i = 0; i < 4; ++i) window[i].OutgoingRTPmin = 255;          // roip_ed137.h:745
@@ -67,6 +127,8 @@ int RoIP_ED137::bindRadio(int slot, int call_id)
         igdsp_unmap_call(ctx_, tx_key(radio[slot]->call_id));
     }
     radio[slot]->call_id = call_id;
+    conf.radio_call[slot] = call_id;
+    conf.mapCall(call_id, (uint32_t)(2 * slot));                  // its conference slot: the RX channel (call_id < 0: nothing)
     if (call_id < 0) return IGDSP_OK;
     int rc = igdsp_map_call(ctx_, rx_key(call_id), (uint32_t)(2 * slot));
     if (rc == IGDSP_OK) rc = igdsp_map_call(ctx_, tx_key(call_id), (uint32_t)(2 * slot + 1));
@@ -391,3 +453,38 @@ int igdsp_wav_stop(void *wv)
 }
 
 }  // extern "C"
+
+// ---- conference receive levels, no context needed
+void *igdsp_host_levels_new(uint32_t n_channels)
+{
+    ConfLevels *l = new (std::nothrow) ConfLevels(n_channels);
+    if (l && l->channels() != n_channels) { delete l; return nullptr; }
+    return l;
+}
+void igdsp_host_levels_free(void *l) { delete static_cast<ConfLevels *>(l); }
+int igdsp_host_levels_map_call(void *l, int call_id, uint32_t channel) { return l ? static_cast<ConfLevels *>(l)->mapCall(call_id, channel) : IGDSP_EINVAL; }
+int igdsp_host_levels_bind_radio(void *l, int slot, int call_id)
+{
+    if (!l || slot < 0 || slot > 3) return IGDSP_EINVAL;
+    static_cast<ConfLevels *>(l)->radio_call[slot] = call_id;
+    return IGDSP_OK;
+}
+int igdsp_host_levels_set(void *l, float slot_volume, float sidetone)
+{
+    if (!l) return IGDSP_EINVAL;
+    static_cast<ConfLevels *>(l)->SLOT_VOLUME = slot_volume;
+    static_cast<ConfLevels *>(l)->sidetone = sidetone;
+    return IGDSP_OK;
+}
+float igdsp_host_levels_slot_volume(void *l) { return l ? static_cast<ConfLevels *>(l)->SLOT_VOLUME : -1.0f; }
+int igdsp_host_set_slot_volume(void *l, int call_id, int increase, int current)
+{
+    return l && static_cast<ConfLevels *>(l)->setSlotVolume(call_id, increase != 0, current != 0) ? 1 : 0;
+}
+int igdsp_host_set_volume_sidetone(void *l, int call_id)
+{
+    if (!l) return IGDSP_EINVAL;
+    static_cast<ConfLevels *>(l)->setvolumeSiteTone(call_id);
+    return IGDSP_OK;
+}
+const uint16_t *igdsp_host_levels_gains(void *l) { return l ? static_cast<ConfLevels *>(l)->gains() : nullptr; }

@@ -80,6 +80,31 @@ struct ptt_window {
     uint8_t  OutgoingRTPav, OutgoingRTPmax, OutgoingRTPmin;
 };
 
+// Receive levels of the calls on the conference bridge (setSlotVolume roip_ed137.cpp:5190-5233, setvolumeSiteTone :6869-6878): the
+// reference's one float SLOT_VOLUME, stepped by 0.1f in [MIN_SLOT_VOLUME, MAX_SLOT_VOLUME] (roip_ed137.h:246-247), applied to a call's
+// conference slot as pjsua_conf_adjust_rx_level does — here a per-channel Q7 gain (igdsp_conf_level_q7) for igdsp_conf_mix.  Needs no
+// device: a call's channel is its conference slot (mapCall), an unmapped call fails as pjsua_call_get_info does.
+class ConfLevels {
+public:
+    static constexpr float MIN_SLOT_VOLUME = 0.0f, MAX_SLOT_VOLUME = 2.0f;
+    explicit ConfLevels(uint32_t n_channels);
+    ~ConfLevels();
+    float SLOT_VOLUME;                       // 2.0f at start (roip_ed137.cpp:210)
+    float sidetone;                          // 0.1f (roip_ed137.h:779), set by initSoftPhone
+    int radio_call[4];                       // trx1->radio1, trx1->radio2, trx2->radio1, trx2->radio2 (-1 = none)
+    int mapCall(int callId, uint32_t channel);   // the call's conference slot; channel >= n_channels unmaps
+    // false where the reference's returns false: no such call, or a level pjsua_conf_adjust_rx_level rejects (nothing applied)
+    bool setSlotVolume(int callId, bool increase, bool current);
+    void setvolumeSiteTone(int callId);
+    const uint16_t *gains() const { return gain_; }   // [n_channels] Q7, 256 (the start level 2.0) until set
+    uint32_t channels() const { return n_; }
+private:
+    int channelOf(int callId) const;
+    uint32_t n_;
+    uint16_t *gain_;
+    int *call_of_;                           // [n_channels] call id of each channel, -1 = none
+};
+
 class RoIP_ED137 {
 public:
     // Unlike the reference singleton (roip_ed137.cpp:192) the instance owns an igdsp context; device < 0
@@ -104,6 +129,11 @@ public:
     void (*onValueChanged)(int call_id, int is_tx, int percent);   // AudioMeter::onValueChanged stand-in
     igdsp_ctx *ctx() { return ctx_; }
     int bindRadio(int slot, int call_id);    // slot 0..3; maps RX to channel 2*slot, TX to 2*slot+1
+    // conference receive levels of the four radios' RX channels 0, 2, 4, 6 (conf.radio_call and the call -> channel map follow
+    // bindRadio); the bridge's gain array is conf.gains()
+    ConfLevels conf;
+    bool setSlotVolume(int callId, bool increase, bool current) { return conf.setSlotVolume(callId, increase, current); }
+    void setvolumeSiteTone(int callId) { conf.setvolumeSiteTone(callId); }
 
     // SURVEY 8(f) rank 3 — PTT-window level logger (Functions.cpp:2126-2230), sampled per tick like the reference.
     // audioInLevel is the linear input level (the reference receives it over the WebSocket VU broadcast,
@@ -139,6 +169,16 @@ igdsp_ctx  *igdsp_host_ctx(void *h);
 int         igdsp_host_keeplog(void *h, int slot, double audioInLevel);
 int         igdsp_host_ptt_event(void *h, int slot, const char *strEvent, const char *url, double audioInLevel, char *json, size_t cap);
 int         igdsp_host_get_window(void *h, int slot, ptt_window *out);
+// conference receive levels without a context (ConfLevels): the bool results as 1 / 0
+void           *igdsp_host_levels_new(uint32_t n_channels);
+void            igdsp_host_levels_free(void *l);
+int             igdsp_host_levels_map_call(void *l, int call_id, uint32_t channel);
+int             igdsp_host_levels_bind_radio(void *l, int slot, int call_id);
+int             igdsp_host_levels_set(void *l, float slot_volume, float sidetone);   /* SLOT_VOLUME / sidetone as the reference assigns them */
+float           igdsp_host_levels_slot_volume(void *l);
+int             igdsp_host_set_slot_volume(void *l, int call_id, int increase, int current);
+int             igdsp_host_set_volume_sidetone(void *l, int call_id);
+const uint16_t *igdsp_host_levels_gains(void *l);   /* [n_channels] Q7 */
 // Meter output on the reference's other channel: AudioMeter (audiometer.cpp:11-34) reads ASCII decimal levels from the
 // FIFO /tmp/capturefifo<card>, 32 bytes per read, and emits onValueChanged(int(float(v*100.0/30000.0))).  These write
 // such records, so the reference's own meter consumer can be fed from igdsp_poll().rms.  open() waits up to

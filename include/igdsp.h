@@ -33,7 +33,8 @@ extern "C" {
  * 3: additive again — the ED-137 gated window (igdsp_window, igdsp_decode_meter_window, igdsp_window_update, igdsp_chan_probe),
  * igdsp_set_ed137 / igdsp_set_gate_mode / igdsp_get_probe on the single-frame path, igdsp_flush_begin / igdsp_flush_end.
  *    Later, still additive under 3: the ED-137 TX packetizer (igdsp_tx_chan, igdsp_tx_info, igdsp_tx_chan_init, igdsp_tx_calltype_bits,
- *    igdsp_tx_packetize); the staged send path behind transport_send_rtp (igdsp_tx_open .. igdsp_tx_flush, igdsp_tx_packet). */
+ *    igdsp_tx_packetize); the staged send path behind transport_send_rtp (igdsp_tx_open .. igdsp_tx_flush, igdsp_tx_packet); the
+ *    conference mix (igdsp_conf_level_q7, igdsp_conf_build, igdsp_conf_mix, IGDSP_FLAG_SATURATED). */
 #define IGDSP_ABI_VERSION 3
 
 /* ---- error codes (0 == PJ_SUCCESS-style success) ------------------------- */
@@ -565,6 +566,52 @@ int igdsp_tx_results(igdsp_ctx *ctx, const igdsp_tx_packet **out, uint32_t *n_ou
 int igdsp_tx_get_chan(igdsp_ctx *ctx, int32_t call_id, igdsp_tx_chan *out);
 /* frames of the call's leg refused by a full ring / dropped by igdsp_tx_close, since its igdsp_tx_open (either pointer may be NULL) */
 int igdsp_tx_counts(igdsp_ctx *ctx, int32_t call_id, uint32_t *refused, uint32_t *dropped);
+
+/* ---- Conference mix: the bridge step after RX decode (pjmedia's conference bridge as the reference drives it) -------------------
+ * Every call's conference slot is connected to the sound-card channel slots (on_call_media_state, roip_ed137.cpp:4907-4917, through
+ * connectPort / disconnectPort, Functions.cpp:718-740), and each call's receive level is set with pjsua_conf_adjust_rx_level(conf_slot,
+ * SLOT_VOLUME) (setSlotVolume, roip_ed137.cpp:5190-5233): steps of 0.1f within [0, 2] (roip_ed137.h:246-247), 2.0 at start
+ * (roip_ed137.cpp:210), 2.0 / 0.0 for the PTT-priority unmute / mute (roip_ed137.cpp:6140-6320), the sidetone level or 0.5 while the
+ * local operator transmits (setvolumeSiteTone, roip_ed137.cpp:6869-6878; Functions.cpp:1660-1700).  The bridge scales each source by
+ * its level, sums the sources connected to an output port and plays the result.
+ *
+ * igdsp_conf_mix does that step for a batch of frames: a PORT is an output (a sound-card channel, a console, a recorder), its members
+ * are channels, given as CSR: members[port_ptr[p] .. port_ptr[p + 1]).  For frame f, port p, sample s:
+ *   x   = the decoded sample of member m (the G.711 tables of igdsp_decode_meter; with d_pcm the PCM value); 0 when s >= len[f][m]
+ *   a   = clamp16(trunc(x * gain[m] / 128))          C integer division, toward zero (an arithmetic >> 7 differs for negative x)
+ *   S   = the exact sum of a over the port's members (64-bit; member order does not matter)
+ *   out[f][p][s] = clamp16(S)
+ * Records [f][p] over out, as igdsp_frame_stats: sumsq exact, rms = sqrtf((float)sumsq / n), peak = max |out| (up to 32768),
+ * byte_mean 0, flags IGDSP_FLAG_SILENT (peak <= 8) | IGDSP_FLAG_SATURATED (a clamp of either stage fired in this port-frame).
+ * EMPTY: the port has no member < n_channels with len > 0 in this frame (no members, members >= n_channels only, or every member's
+ * len 0): out is zeros and the record is igdsp_decode_meter's len-0 record (all 0, IGDSP_FLAG_EMPTY).  EMPTY depends on membership
+ * and len only, never on the gain: a muted member keeps the frame live.
+ * A bad table is safe: members >= n_channels contribute nothing and are never dereferenced, port_ptr values are clamped to n_members,
+ * a port with port_ptr[p + 1] < port_ptr[p] is empty, and a member listed twice is mixed twice (igdsp_conf_build removes duplicates).
+ *
+ * Fidelity.  The Q7 rule is pjmedia's receive-level adjustment as it is commonly published (itemp = itemp * adj / 128, clamped to
+ * int16), and pjsua's float level -> adj mapping is (int)((level - 1) * 128) with adj = 128 + that (igdsp_conf_level_q7).  Both are
+ * UNVERIFIED here: pjmedia is a third-party dependency of the reference and is not in this tree.  pjmedia's adaptive normalisation
+ * of a sum of several transmitters is deliberately NOT restated: the mix saturates instead; the two agree whenever at most one
+ * member of a port contributes (the PTT arbitration's usual state: one call unmuted, the others at level 0). */
+#define IGDSP_FLAG_SATURATED 0x10  /* igdsp_conf_mix: a per-member or the final int16 clamp fired in this port-frame */
+/* Q7 receive level of a float slot volume: 128 + (int)((level - 1.0f) * 128.0f) in float arithmetic, as pjsua converts it
+ * (0.0 -> 0, 0.1f -> 13, 0.5 -> 64, 1.0 -> 128, 2.0 -> 256).  IGDSP_EINVAL for NaN, a negative result (an adjustment below -128)
+ * or a result above 65535.  Host-only, no GPU needed. */
+int igdsp_conf_level_q7(float level);
+/* The CSR of a connection list: n_conn (channel[i], port[i]) pairs -> port_ptr[n_ports + 1] and members[] (room for n_conn entries),
+ * *n_members written.  Members sorted by port, then channel; duplicate connections removed (pjsua_conf_connect of an existing
+ * connection is a no-op).  A channel >= n_channels or port >= n_ports -> IGDSP_EINVAL, nothing written.  Host-only. */
+int igdsp_conf_build(const uint32_t *channel, const uint32_t *port, uint32_t n_conn, uint32_t n_channels, uint32_t n_ports,
+                     uint32_t *port_ptr, uint32_t *members, uint32_t *n_members);
+/* Exactly one input: d_payload[f][c][n] G.711 with d_codec[c] (RTP PT: 8 A-law, else mu-law), or d_pcm[f][c][n] int16.  d_len[f][c]
+ * optional (as igdsp_decode_meter).  d_gain[c] Q7 (128 = unity), d_port_ptr[n_ports + 1], d_members[n_members] (may be NULL when
+ * n_members is 0).  At least one of d_out[f][p][n] int16 and d_stats[f][p].  n = 1..256.  n_ports == 0 or n_frames == 0: nothing to
+ * do.  Enqueued on `stream`, not synchronised. */
+int igdsp_conf_mix(igdsp_ctx *ctx, const uint8_t *d_payload, const uint8_t *d_codec, const int16_t *d_pcm, const uint16_t *d_len,
+                   const uint16_t *d_gain, const uint32_t *d_port_ptr, const uint32_t *d_members, uint32_t n_members,
+                   uint32_t n_channels, uint32_t n_ports, uint32_t n_frames, uint32_t samples_per_frame,
+                   int16_t *d_out, igdsp_frame_stats *d_stats, void *stream);
 
 /* ---- synthetic input generators (device side; SURVEY 8(d) definitions) ---------
  * D-uniform: byte k of global byte index g is
