@@ -24,6 +24,7 @@ STAGE_DEPTH = 8
 ENC_SUN16, ENC_G191 = 0, 1
 FLAG_SILENT, FLAG_PROBE_D5, FLAG_CLIPPED, FLAG_EMPTY = 1, 2, 4, 8
 FLAG_SATURATED = 0x10        # igdsp_conf_mix
+BSS_VOTE_FRAMES = 10         # IGDSP_BSS_VOTE_FRAMES
 AGG_MAX_RANKS = 8
 AGG_LINE_WORDS = 16
 AGG_WORDS = 7 * AGG_LINE_WORDS
@@ -43,6 +44,7 @@ CHAN_HOLD = np.dtype(
     align=True,
 )
 RTP_INFO = np.dtype([("ed137", "<u4"), ("payload_len", "<u2"), ("pt", "u1"), ("flags", "u1")], align=True)
+BSS_STATE = np.dtype([("count", "<u4"), ("voted", "<u4"), ("on", "<u4"), ("votes", "<u4")], align=True)   # igdsp_bss_state
 CHAN_PROBE = np.dtype([("run", "<u4"), ("alarms", "<u4")], align=True)
 GATE_ALWAYS, GATE_SQU, GATE_PTT, GATE_SQU_OR_PTT = 0, 1, 2, 3
 PKT_SLOTS, PKT_PACKED, PKT_MIXED = 0, 1, 2
@@ -165,6 +167,8 @@ PROTOTYPES = [
     ("igdsp_conf_level_q7", _int, [C.c_float]),
     ("igdsp_conf_build", _int, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, C.POINTER(_u32)]),
     ("igdsp_conf_mix", _int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp]),
+    ("igdsp_bss_select", _int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp,
+                                _vp]),
     ("igdsp_g726_reorder", _int, [_vp, _vp, _vp, _u64, _int, _vp]),
     ("igdsp_gen_uniform", _int, [_vp, _vp, _u64, _u64, _u64, _vp]),
     ("igdsp_dev_alloc", _int, [_vp, C.POINTER(_vp), C.c_size_t]),
@@ -414,6 +418,14 @@ class Context:
         stats [F][P] (device buffers)."""
         self._ck(self.L.igdsp_conf_mix(self.h, _ptr(payload), _ptr(codec), _ptr(pcm), _ptr(length), _ptr(gain), _ptr(port_ptr), _ptr(members),
                                        n_members, C_, P_, F_, n, _ptr(out), _ptr(stats), stream), "igdsp_conf_mix")
+
+    def bss_select(self, info, group_ptr, members, n_members, state, words, C_, G_, F_, n=160, payload=None, codec=None, pcm=None,
+                   length=None, gain=None, mute=None, vote_frames=0, sel=None, out=None, stats=None, stream=None):
+        """igdsp_bss_select: info [F][C] RTP_INFO; at most one of payload [F][C][n] u8 (+ codec [C]) / pcm [F][C][n] int16; state [G]
+        BSS_STATE and words [n_members] u32 carried across calls; sel [F][G] int32, out [F][G][n] int16, stats [F][G] (device buffers)."""
+        self._ck(self.L.igdsp_bss_select(self.h, _ptr(info), _ptr(payload), _ptr(codec), _ptr(pcm), _ptr(length), _ptr(gain), _ptr(group_ptr),
+                                         _ptr(members), n_members, _ptr(mute), C_, G_, F_, n, vote_frames, _ptr(state), _ptr(words), _ptr(sel),
+                                         _ptr(out), _ptr(stats), stream), "igdsp_bss_select")
 
     # -- staged ED-137 send path (transport_send_rtp as pjmedia calls it)
     def tx_open(self, call_id: int, calltype: str, call_in: bool, keepalive_ms: int = 200, now_ms: int = 0):

@@ -798,6 +798,45 @@ int igdsp_conf_mix(igdsp_ctx *ctx, const uint8_t *d_payload, const uint8_t *d_co
     return IGDSP_OK;
 }
 
+// ---- best signal selection: the receiver vote of checkEvents (roip_ed137.cpp:5985-6119; get_IPRadioSquelch / get_IPRadioBss,
+// Functions.cpp:1001-1022; setvolume, Functions.cpp:1664-1705) ----
+// the argument rules of igdsp_bss_select (shared with the yardstick entry)
+static int bss_check(igdsp_ctx *ctx, const igdsp_rtp_info *d_info, const uint8_t *d_payload, const uint8_t *d_codec, const int16_t *d_pcm,
+                     const uint16_t *d_len, const uint16_t *d_gain, const uint32_t *d_group_ptr, const uint32_t *d_members, uint32_t n_members,
+                     uint32_t C, uint32_t G, uint32_t F, uint32_t n, const igdsp_bss_state *d_state, const uint32_t *d_words,
+                     const int32_t *d_sel, const int16_t *d_out, const igdsp_frame_stats *d_stats)
+{
+    if (!ctx || !d_info || !d_group_ptr || !d_state) return IGDSP_EINVAL;
+    if (n_members && (!d_members || !d_words)) return IGDSP_EINVAL;
+    if (n_members > (1u << 24)) return IGDSP_EINVAL;                                          // positions are 24-bit in the vote key
+    if (d_payload && d_pcm) return IGDSP_EINVAL;                                              // at most one input form
+    if (d_payload && !d_codec) return IGDSP_EINVAL;
+    if ((d_out || d_stats) && !d_payload && !d_pcm) return IGDSP_EINVAL;                      // audio outputs need audio
+    if (int rc = check_shape(C, F, n)) return rc;
+    if (int rc = check_shape(G, F, n)) return rc;
+    const uintptr_t a2 = reinterpret_cast<uintptr_t>(d_pcm) | reinterpret_cast<uintptr_t>(d_len) | reinterpret_cast<uintptr_t>(d_gain) |
+                         reinterpret_cast<uintptr_t>(d_out);
+    const uintptr_t a4 = reinterpret_cast<uintptr_t>(d_info) | reinterpret_cast<uintptr_t>(d_group_ptr) | reinterpret_cast<uintptr_t>(d_members) |
+                         reinterpret_cast<uintptr_t>(d_state) | reinterpret_cast<uintptr_t>(d_words) | reinterpret_cast<uintptr_t>(d_sel);
+    if ((a2 & 1u) || (a4 & 3u) || (reinterpret_cast<uintptr_t>(d_stats) & 7u)) return IGDSP_EINVAL;
+    return IGDSP_OK;
+}
+
+int igdsp_bss_select(igdsp_ctx *ctx, const igdsp_rtp_info *d_info, const uint8_t *d_payload, const uint8_t *d_codec, const int16_t *d_pcm,
+                     const uint16_t *d_len, const uint16_t *d_gain, const uint32_t *d_group_ptr, const uint32_t *d_members, uint32_t n_members,
+                     const uint8_t *d_mute, uint32_t C, uint32_t G, uint32_t F, uint32_t n, uint32_t vote_frames, igdsp_bss_state *d_state,
+                     uint32_t *d_words, int32_t *d_sel, int16_t *d_out, igdsp_frame_stats *d_stats, void *stream)
+{
+    if (!ctx) return IGDSP_EINVAL;
+    if ((uint64_t)G * F == 0) return IGDSP_OK;                                               // nothing to do
+    if (int rc = bss_check(ctx, d_info, d_payload, d_codec, d_pcm, d_len, d_gain, d_group_ptr, d_members, n_members, C, G, F, n, d_state, d_words,
+                           d_sel, d_out, d_stats)) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, launch_bss_select(cfg_of(ctx, pick(ctx, stream)), d_info, d_payload, d_codec, d_pcm, d_len, d_gain, d_group_ptr, d_members,
+                                   n_members, d_mute, C, G, F, n, vote_frames, d_state, d_words, d_sel, d_out, d_stats, pick(ctx, stream)));
+    return IGDSP_OK;
+}
+
 // ---- staged ED-137 send path (transport_send_rtp as pjmedia calls it, TransportAdapter.cpp:635-874) ----
 // the TX side and channel of call_id (whether or not a leg is open there), or nullptr with *rc set
 static igdsp_ctx::TxSide *tx_chan_of(igdsp_ctx *ctx, int32_t call_id, uint32_t *leg, int *rc)
@@ -1173,6 +1212,24 @@ int igdsp_internal_conf_copy(igdsp_ctx *ctx, const uint8_t *d_payload, const uin
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, launch_conf_copy_ab(cfg_of(ctx, pick(ctx, stream)), d_payload, d_codec, d_pcm, d_len, d_gain, d_port_ptr, d_members, n_members, C,
                                      P, F, n, d_out, d_stats, pick(ctx, stream)));
+    return IGDSP_OK;
+}
+
+// Calibration-only (not in include/igdsp.h): the compute-free yardstick of igdsp_bss_select (tools/bss_bench.py) — the same traversal,
+// the same bytes read and written, no decode / scale / clamp / stats / state machine (every non-empty group "selects" its first
+// member).  Arguments as igdsp_bss_select; the state is not touched, and sel / out / stats hold raw bytes.
+int igdsp_internal_bss_copy(igdsp_ctx *ctx, const igdsp_rtp_info *d_info, const uint8_t *d_payload, const uint8_t *d_codec, const int16_t *d_pcm,
+                            const uint16_t *d_len, const uint16_t *d_gain, const uint32_t *d_group_ptr, const uint32_t *d_members,
+                            uint32_t n_members, const uint8_t *d_mute, uint32_t C, uint32_t G, uint32_t F, uint32_t n, uint32_t vote_frames,
+                            igdsp_bss_state *d_state, uint32_t *d_words, int32_t *d_sel, int16_t *d_out, igdsp_frame_stats *d_stats, void *stream)
+{
+    if (!ctx) return IGDSP_EINVAL;
+    if ((uint64_t)G * F == 0) return IGDSP_OK;
+    if (int rc = bss_check(ctx, d_info, d_payload, d_codec, d_pcm, d_len, d_gain, d_group_ptr, d_members, n_members, C, G, F, n, d_state, d_words,
+                           d_sel, d_out, d_stats)) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, launch_bss_copy_ab(cfg_of(ctx, pick(ctx, stream)), d_info, d_payload, d_codec, d_pcm, d_len, d_gain, d_group_ptr, d_members,
+                                    n_members, d_mute, C, G, F, n, vote_frames, d_state, d_words, d_sel, d_out, d_stats, pick(ctx, stream)));
     return IGDSP_OK;
 }
 

@@ -90,6 +90,17 @@ hipError_t launch_conf_mix(const LaunchCfg &cfg, const uint8_t *g711, const uint
 hipError_t launch_conf_copy_ab(const LaunchCfg &cfg, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm, const uint16_t *len,
                                const uint16_t *gain, const uint32_t *port_ptr, const uint32_t *members, uint32_t n_members, uint32_t C, uint32_t P,
                                uint32_t F, uint32_t n, int16_t *out, igdsp_frame_stats *stats, hipStream_t s);
+// igdsp_bss_select: at most one of g711 (+ codec) / pcm; sel, out, stats may each be nullptr (out and stats need an input: the C ABI
+// checks); gain nullptr = 256
+hipError_t launch_bss_select(const LaunchCfg &cfg, const igdsp_rtp_info *info, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm,
+                             const uint16_t *len, const uint16_t *gain, const uint32_t *group_ptr, const uint32_t *members, uint32_t n_members,
+                             const uint8_t *mute, uint32_t C, uint32_t G, uint32_t F, uint32_t n, uint32_t vote_frames, igdsp_bss_state *state,
+                             uint32_t *words, int32_t *sel, int16_t *out, igdsp_frame_stats *stats, hipStream_t s);
+// compute-free yardstick of launch_bss_select: the same traversal and bytes, no decode / scale / clamp / stats / state machine
+hipError_t launch_bss_copy_ab(const LaunchCfg &cfg, const igdsp_rtp_info *info, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm,
+                              const uint16_t *len, const uint16_t *gain, const uint32_t *group_ptr, const uint32_t *members, uint32_t n_members,
+                              const uint8_t *mute, uint32_t C, uint32_t G, uint32_t F, uint32_t n, uint32_t vote_frames, igdsp_bss_state *state,
+                              uint32_t *words, int32_t *sel, int16_t *out, igdsp_frame_stats *stats, hipStream_t s);
 hipError_t launch_wav_expand(const LaunchCfg &cfg, const uint8_t *payload, uint32_t C, uint32_t F, uint32_t n, uint32_t rate,
                              uint8_t *files, uint64_t file_stride, hipStream_t s);
 hipError_t launch_g726(const LaunchCfg &cfg, const uint8_t *in, uint8_t *out, uint64_t n_bytes, int mode, hipStream_t s);

@@ -14,7 +14,7 @@
 // Member metadata (channel, gain, length, law) are read 64 members at a time, one per lane, and handed to the member loop with
 // v_readlane, so the frame loads of a batch do not wait behind a chain of dependent scalar loads.  Members at or past C and members
 // whose gain or length is 0 are never read.
-#include "igdsp_device.h"
+#include "igdsp_q7.h"
 
 namespace igdsp {
 
@@ -65,21 +65,6 @@ __device__ __forceinline__ uint2 conf_load(const ConfArgs &a, uint64_t row, uint
     }
 }
 
-// sample k of a loaded value: magnitude and sign
-template <int IN>
-__device__ __forceinline__ void conf_sample(const uint2 *lut, uint2 v, uint32_t law80, uint32_t off, uint32_t k, uint32_t &ax, uint32_t &neg)
-{
-    if (IN == kConfG711) {
-        const uint32_t t = (v.x & 0x7F7F7F7Fu) | law80;
-        ax = lut_at(lut, t, off, 0x0C0C0400u + (k << 8)).y;
-        neg = ((v.x >> (8u * k + 7u)) & 1u) ^ 1u;                  // a G.711 code is negative iff its bit 7 is clear
-    } else {
-        const int32_t x = (int32_t)(int16_t)(((k < 2u ? v.x : v.y) >> (16u * (k & 1u))) & 0xFFFFu);
-        ax = (uint32_t)(x < 0 ? -x : x);
-        neg = x < 0 ? 1u : 0u;
-    }
-}
-
 // Mix members [b, e) of frame f into acc.  COPY: the yardstick — the same loads, folded by xor instead of decoded and scaled.
 template <int IN, bool COPY>
 __device__ __forceinline__ void conf_range(const ConfArgs &a, const uint2 *lut, uint32_t f, uint32_t b, uint32_t e, uint32_t lane, ConfAcc &acc)
@@ -123,14 +108,8 @@ __device__ __forceinline__ void conf_range(const ConfArgs &a, const uint2 *lut, 
 #pragma unroll
                 for (uint32_t k = 0; k < 4u; ++k) {
                     uint32_t ax, neg;
-                    conf_sample<IN>(lut, v[u], law80, off, k, ax, neg);
-                    uint32_t q = g == 128u ? ax : (ax * g) >> 7;           // |x| * g / 128 truncated = |trunc(x * g / 128)|
-                    if (4u * lane + k >= l) q = 0u;                        // past this member's len (and past n)
-                    if (g > 128u) {                                        // only a gain above unity can leave int16
-                        const uint32_t lim = 32767u + neg;
-                        acc.sat |= q > lim ? 1u : 0u;
-                        q = min(q, lim);
-                    }
+                    q7_sample<IN>(lut, v[u], law80, off, k, ax, neg);
+                    IGDSP_Q7_LEVEL(q, ax, neg, g, 4u * lane + k, l, acc.sat);   // 0 past this member's len (and past n)
                     s32[k] += neg ? -(int32_t)q : (int32_t)q;
                 }
             }

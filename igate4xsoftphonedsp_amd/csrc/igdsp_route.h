@@ -438,6 +438,46 @@ inline ConfRoute conf_route(uint32_t P, uint32_t F, uint32_t n, bool pcm, uintpt
     return r;
 }
 
+// ---- igdsp_bss_select (launch_bss_select, launch_bss_copy_ab): k_bss_select<IN, COPY> + k_bss_words.  A wave owns gpw consecutive
+// groups for the frames of a part: its lanes gather the members' info records (one member slot per lane, a 64-slot chunk at a time)
+// and fold each frame's open members into a vote key per group in LDS; lanes 0 .. gpw-1 then step the groups' state machines over
+// the part's frames, and the whole wave emits the voted frames.  gpw is chosen so that a wave's groups fill about one chunk of 64
+// member slots.  The vote keys of a part live in LDS ([kBssPart][kBssGroups] per wave), so a launch of more frames goes out in
+// parts of kBssPart frames; after each part k_bss_words (a thread per member slot) stores the slots' last words, which the next
+// part reads.  The state is carried through d_state, as between launches.
+constexpr int kBssWaves = 4;                              // waves per block: they share the 64 KiB LUT (+ 32 KiB of vote keys)
+constexpr uint32_t kBssGroups = 16;                       // groups per wave at most (decision lanes)
+constexpr uint32_t kBssPart = 128;                        // frames per part
+constexpr uint32_t kBssU = 8;                             // loads of a lane in flight together
+constexpr uint32_t kBssWordsThreads = 256;                // k_bss_words
+enum : int { kBssNone = 2 };                              // k_bss_select<IN>: kConfG711, kConfPcm, or no audio
+struct BssRoute {
+    int form = kBssNone;
+    uint32_t gpw = 0;                      // groups per wave
+    uint32_t vec_in = 0, vec_out = 0;      // as ConfRoute
+    uint32_t grid = 0, threads = 0;        // k_bss_select, every part
+    uint32_t part_frames = 0, parts = 0;   // the last part takes the rest
+    uint32_t words_grid = 0;               // k_bss_words, every part (0: no member slots)
+};
+inline BssRoute bss_route(uint32_t G, uint32_t F, uint32_t n, uint32_t n_members, int form, uintptr_t in, uintptr_t out)
+{
+    BssRoute r;
+    if ((uint64_t)G * F == 0) return r;
+    r.form = form;
+    const uint64_t avg = std::max<uint64_t>(1u, ((uint64_t)n_members + G - 1) / G);
+    r.gpw = kBssGroups;
+    while (r.gpw > 1u && r.gpw * avg > 64u) r.gpw >>= 1;
+    r.vec_in = form != kBssNone && (n & 3u) == 0u && aligned(in, form == kConfPcm ? 8 : 4) ? 1u : 0u;
+    r.vec_out = form != kBssNone && (n & 3u) == 0u && aligned(out, 8) ? 1u : 0u;
+    const uint64_t waves = ((uint64_t)G + r.gpw - 1) / r.gpw;
+    r.grid = (uint32_t)((waves + kBssWaves - 1) / kBssWaves);
+    r.threads = kBssWaves * 64;
+    r.part_frames = std::min(F, kBssPart);
+    r.parts = (F + kBssPart - 1) / kBssPart;
+    r.words_grid = (uint32_t)(((uint64_t)n_members + kBssWordsThreads - 1) / kBssWordsThreads);
+    return r;
+}
+
 // ---- igdsp_tx_flush (launch_tx_staged): a wave owns kTsLegs staged legs (runs) of the flush; lanes 0 .. kTsLegs-1 decide, the
 // whole wave writes the packets.  No dynamic LDS: each wave's records (kTsLegs x IGDSP_STAGE_DEPTH) are static.
 constexpr int kTsWaves = 4;

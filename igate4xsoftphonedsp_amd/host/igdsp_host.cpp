@@ -454,6 +454,93 @@ int igdsp_wav_stop(void *wv)
 
 }  // extern "C"
 
+// ---- best signal selection (roip_ed137.cpp:5609-5669, 5985-6119), no context needed
+BssVoter::BssVoter() : sqlStatusCount(0), sqlStatusOn(false), voteTicks(5), votes(0), staleLastRx(false)
+{
+    for (int i = 0; i < 4; ++i) { radio[i].callState = false; radio[i].lastRx = 0; radio[i].rssi = -1; radio[i].audioSQLOn = false; }
+}
+
+int BssVoter::voted() const
+{
+    for (int i = 0; i < 4; ++i)
+        if (radio[i].audioSQLOn) return i;
+    return -1;
+}
+
+int BssVoter::tick(const uint32_t words[4], const bool call_up[4], bool force_mute)
+{
+    // the per-radio block (:5614-5669): runs only for a call that is up
+    for (int i = 0; i < 4; ++i) {
+        Radio &r = radio[i];
+        r.callState = call_up[i];
+        if (!r.callState) {
+            if (!staleLastRx) r.lastRx = 0;
+            continue;
+        }
+        int sqlon = (int)IGDSP_ED137_SQU(words[i]);          // get_IPRadioSquelch
+        if (force_mute) sqlon = false;
+        r.rssi = (int)IGDSP_ED137_BSS(words[i]);             // get_IPRadioBss
+        r.lastRx = sqlon;                                    // (the lastRxmsec hold at :5658-5669 never fires)
+    }
+    Radio *r1 = &radio[0], *r2 = &radio[1], *r3 = &radio[2], *r4 = &radio[3];
+    // :5987-6026 — a closed radio loses its vote, and the count with it
+    for (int i = 0; i < 4; ++i) {
+        Radio &r = radio[i];
+        if ((r.callState == false) || (r.lastRx == 0)) {
+            if (r.audioSQLOn == true) {
+                sqlStatusCount = 0;
+                sqlStatusOn = false;
+            }
+            r.audioSQLOn = false;
+            r.rssi = -1;
+        }
+    }
+    // :6027-6117
+    if ((r1->lastRx > 0) || (r2->lastRx > 0) || (r3->lastRx > 0) || (r4->lastRx > 0)) {
+        sqlStatusCount++;
+        if ((sqlStatusCount >= voteTicks) & (sqlStatusOn == false)) {
+            sqlStatusOn = true;                              // (every open radio is set to MUTE here)
+            int pick = -1;
+            if ((r1->rssi >= r2->rssi) & (r1->rssi >= r3->rssi) & (r1->rssi >= r4->rssi) & (r1->lastRx != 0)) pick = 0;
+            else if ((r2->rssi >= r1->rssi) & (r2->rssi >= r3->rssi) & (r2->rssi >= r4->rssi) & (r2->lastRx != 0)) pick = 1;
+            else if ((r3->rssi >= r1->rssi) & (r3->rssi >= r2->rssi) & (r3->rssi >= r4->rssi) & (r3->lastRx != 0)) pick = 2;
+            else if ((r4->rssi >= r1->rssi) & (r4->rssi >= r2->rssi) & (r4->rssi >= r3->rssi) & (r4->lastRx != 0)) pick = 3;
+            if (pick >= 0) {
+                for (int i = 0; i < 4; ++i) radio[i].audioSQLOn = i == pick;   // (the voted one UNMUTE)
+                ++votes;
+            }
+        }
+    } else {
+        sqlStatusCount = 0;
+        sqlStatusOn = false;
+        for (int i = 0; i < 4; ++i) radio[i].audioSQLOn = false;
+    }
+    return voted();
+}
+
+void *igdsp_host_bss_new(int vote_ticks, int stale_last_rx)
+{
+    BssVoter *v = new (std::nothrow) BssVoter();
+    if (v) { v->voteTicks = vote_ticks; v->staleLastRx = stale_last_rx != 0; }
+    return v;
+}
+void igdsp_host_bss_free(void *v) { delete static_cast<BssVoter *>(v); }
+int igdsp_host_bss_tick(void *v, const uint32_t *words4, const int *call_up4, int force_mute)
+{
+    if (!v || !words4 || !call_up4) return IGDSP_EINVAL;
+    const bool up[4] = {call_up4[0] != 0, call_up4[1] != 0, call_up4[2] != 0, call_up4[3] != 0};
+    return static_cast<BssVoter *>(v)->tick(words4, up, force_mute != 0);
+}
+int igdsp_host_bss_state(void *v, int *count, int *on, unsigned *votes)
+{
+    if (!v) return IGDSP_EINVAL;
+    const BssVoter *b = static_cast<const BssVoter *>(v);
+    if (count) *count = b->sqlStatusCount;
+    if (on) *on = b->sqlStatusOn ? 1 : 0;
+    if (votes) *votes = b->votes;
+    return IGDSP_OK;
+}
+
 // ---- conference receive levels, no context needed
 void *igdsp_host_levels_new(uint32_t n_channels)
 {

@@ -105,6 +105,33 @@ private:
     int *call_of_;                           // [n_channels] call id of each channel, -1 = none
 };
 
+// Best signal selection, the SERVER-mode block of RoIP_ED137::checkEvents (roip_ed137.cpp:5609-5669, 5985-6119) over the reference's
+// four radios, restated literally and without a context: the per-radio squelch / BSS read and the vote on lastRx, rssi, audioSQLOn,
+// sqlStatusCount and sqlStatusOn, in the fixed order trx1.radio1, trx1.radio2, trx2.radio1, trx2.radio2.  A host that keeps the vote
+// on the CPU calls tick() where checkEvents runs it; igdsp_bss_select is the same vote on the device, one tick per frame.
+class BssVoter {
+public:
+    struct Radio {
+        bool callState;                      // the call is up (the per-radio block runs)
+        int lastRx;                          // the squelch as checkEvents last read it
+        int rssi;                            // BSS index, -1 while closed
+        bool audioSQLOn;                     // the voted radio
+    };
+    BssVoter();
+    Radio radio[4];                          // trx1->radio1, trx1->radio2, trx2->radio1, trx2->radio2
+    int sqlStatusCount;
+    bool sqlStatusOn;
+    int voteTicks;                           // 5 in the reference (sqlStatusCount >= 5)
+    unsigned votes;                          // votes taken (telemetry)
+    // The reference keeps a dropped call's last lastRx (its per-radio block does not run); igdsp_bss_select counts the call as
+    // closed.  false (default): as igdsp_bss_select; true: the reference's stale lastRx.
+    bool staleLastRx;
+    // One tick: words[i] = the radio's stored ED-137 word (get_ed137_value), call_up[i] = its callState, force_mute = forceMuteSqlOn /
+    // group PTT under MUTEALL.  Returns the voted radio (0..3), or -1.
+    int tick(const uint32_t words[4], const bool call_up[4], bool force_mute);
+    int voted() const;
+};
+
 class RoIP_ED137 {
 public:
     // Unlike the reference singleton (roip_ed137.cpp:192) the instance owns an igdsp context; device < 0
@@ -179,6 +206,11 @@ float           igdsp_host_levels_slot_volume(void *l);
 int             igdsp_host_set_slot_volume(void *l, int call_id, int increase, int current);
 int             igdsp_host_set_volume_sidetone(void *l, int call_id);
 const uint16_t *igdsp_host_levels_gains(void *l);   /* [n_channels] Q7 */
+// best signal selection without a context (BssVoter): tick returns the voted radio, -1 for none (IGDSP_EINVAL for a NULL handle)
+void *igdsp_host_bss_new(int vote_ticks, int stale_last_rx);
+void  igdsp_host_bss_free(void *v);
+int   igdsp_host_bss_tick(void *v, const uint32_t *words4, const int *call_up4, int force_mute);
+int   igdsp_host_bss_state(void *v, int *count, int *on, unsigned *votes);
 // Meter output on the reference's other channel: AudioMeter (audiometer.cpp:11-34) reads ASCII decimal levels from the
 // FIFO /tmp/capturefifo<card>, 32 bytes per read, and emits onValueChanged(int(float(v*100.0/30000.0))).  These write
 // such records, so the reference's own meter consumer can be fed from igdsp_poll().rms.  open() waits up to

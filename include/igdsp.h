@@ -34,7 +34,8 @@ extern "C" {
  * igdsp_set_ed137 / igdsp_set_gate_mode / igdsp_get_probe on the single-frame path, igdsp_flush_begin / igdsp_flush_end.
  *    Later, still additive under 3: the ED-137 TX packetizer (igdsp_tx_chan, igdsp_tx_info, igdsp_tx_chan_init, igdsp_tx_calltype_bits,
  *    igdsp_tx_packetize); the staged send path behind transport_send_rtp (igdsp_tx_open .. igdsp_tx_flush, igdsp_tx_packet); the
- *    conference mix (igdsp_conf_level_q7, igdsp_conf_build, igdsp_conf_mix, IGDSP_FLAG_SATURATED). */
+ *    conference mix (igdsp_conf_level_q7, igdsp_conf_build, igdsp_conf_mix, IGDSP_FLAG_SATURATED); best signal selection
+ *    (igdsp_bss_state, IGDSP_BSS_VOTE_FRAMES, igdsp_bss_select). */
 #define IGDSP_ABI_VERSION 3
 
 /* ---- error codes (0 == PJ_SUCCESS-style success) ------------------------- */
@@ -612,6 +613,69 @@ int igdsp_conf_mix(igdsp_ctx *ctx, const uint8_t *d_payload, const uint8_t *d_co
                    const uint16_t *d_gain, const uint32_t *d_port_ptr, const uint32_t *d_members, uint32_t n_members,
                    uint32_t n_channels, uint32_t n_ports, uint32_t n_frames, uint32_t samples_per_frame,
                    int16_t *d_out, igdsp_frame_stats *d_stats, void *stream);
+
+/* ---- Best signal selection: the ED-137 receiver vote between depayload and the bridge -------------------------------------------
+ * A gateway hears one frequency through several receivers; each one's ED-137 word carries its squelch (SQU, bit 28) and a 5-bit BSS
+ * quality index (bits 7-3).  The reference (SERVER mode, rxBestSignalEnable, on by default) votes for one receiver in checkEvents
+ * (roip_ed137.cpp:5985-6119) over its four radios, from get_IPRadioSquelch / get_IPRadioBss (Functions.cpp:1001-1022), and plays it
+ * by slot volume (setvolume, Functions.cpp:1664-1705): every open radio MUTE, the voted one UNMUTE (SLOT_VOLUME 2.0 = Q7 256).
+ *
+ * igdsp_bss_select runs that vote for n_groups groups (one frequency each) over n_frames frames.  A group's members are channels, as
+ * CSR: member slots k in [group_ptr[g], group_ptr[g + 1]); their ORDER is the tie-break order (the reference's fixed trx1.radio1,
+ * trx1.radio2, trx2.radio1, trx2.radio2).  Per frame f, in order:
+ *   1. Words.  For EVERY slot k < n_members with c = members[k] < n_channels: words[k] = info[f][c].ed137 iff the frame carries a
+ *      stored word, i.e. !(info.flags & IGDSP_RTP_RUNT) and info.pt is 0, 8, 18 or 123 (transport_rtp_cb, TransportAdapter.cpp:
+ *      247-256, 408-415; 123 is the R2S keep-alive); otherwise words[k] keeps its value.  Words are kept per slot, not per channel:
+ *      a channel listed twice is two slots with the same word.
+ *   2. Squelch, per member: rx = SQU(words[k]) && c < n_channels && !(d_mute && d_mute[g]); rssi = BSS(words[k]).
+ *   3. Step the group's state (count, on, voted):
+ *      - if the voted member has rx == 0 (or voted names no slot of the group): count = 0, on = 0, voted = 0;
+ *      - if any member has rx: count = min(count + 1, UINT32_MAX); if count >= vote_frames and !on: on = 1, votes += 1 (mod 2^32),
+ *        voted = 1 + the position of the FIRST member (in member order) whose rx holds and whose rssi is >= every open member's;
+ *      - otherwise count = 0, on = 0, voted = 0.
+ *      A vote LATCHES: a stronger receiver that opens later does not take over.  When the voted receiver closes while others stay
+ *      open the count restarts in that same frame (it is 1 there) and a new vote follows vote_frames - 1 frames later.
+ *   4. Emit.  sel[f][g] = members[b + voted - 1] (a channel < n_channels), or -1 when nothing is voted.  With audio, for the voted
+ *      channel c: out[f][g][s] = clamp16(trunc(x * gain[c] / 128)) for s < len[f][c] (x: the decoded sample as igdsp_conf_mix reads
+ *      it), 0 past len; the record [f][g] over out as igdsp_conf_mix writes it (sumsq, rms, peak, byte_mean 0, IGDSP_FLAG_SILENT,
+ *      IGDSP_FLAG_SATURATED when the clamp fired).  Nothing voted, or the voted member's len 0: out is zeros and the record is
+ *      igdsp_decode_meter's len-0 record (all 0, IGDSP_FLAG_EMPTY).  A voted frame equals igdsp_conf_mix of a one-member port.
+ * The state (d_state[g]) and the words (d_words[k]) carry the vote across launches: F launches of one frame give the same bits as one
+ * launch of F frames.  An all-zero state is the reset state (a memset resets it); zero words are closed receivers.  The state
+ * belongs to one table: rebuilding group_ptr / members means resetting the state and the words.  igdsp_conf_build sorts members by
+ * channel, so a host that wants a priority order other than channel order builds the CSR itself.
+ * An all-zero igdsp_rtp_info is a PT-0 packet with word 0, not a missing frame: a missing frame carries IGDSP_RTP_RUNT, as
+ * igdsp_depayload writes it for size 0.
+ * A bad table is safe: group_ptr values are clamped to n_members, a group with group_ptr[g + 1] < group_ptr[g] is empty, members
+ * >= n_channels are calls that are not up (never read, never open, never voted).
+ *
+ * Fidelity.  PINNED to the reference: the vote, the latch, the count restart, the tie order and the word rule (step 1).
+ * UNVERIFIED: pjmedia's Q7 level arithmetic, as for igdsp_conf_mix.  DIFFERENT ON PURPOSE: (a) the tick is one frame (the reference
+ * runs checkEvents on its 40 ms timer and on audio edges), so the threshold is vote_frames (IGDSP_BSS_VOTE_FRAMES = 5 ticks of 40 ms
+ * at 20 ms frames); (b) what a receiver plays before the first vote depends on volume history outside the reference's BSS block:
+ * here it is silence; (c) a dropped call (member >= n_channels) is a closed receiver, where the reference keeps its stale lastRx.
+ * The force-mute / group-PTT rule (roip_ed137.cpp:5630-5655) is d_mute[g], set by the host per launch (its SqlGroupDelay release
+ * stays on the host).  The lastRxmsec hold (roip_ed137.cpp:5658-5669) is dead code in the reference and has no counterpart. */
+typedef struct igdsp_bss_state {  /* per group, 16 bytes; ALL-ZERO = reset */
+    uint32_t count;               /* sqlStatusCount, saturating                                                      */
+    uint32_t voted;               /* 1 + position of the voted member in the group's member list, 0 = none (audioSQLOn) */
+    uint32_t on;                  /* sqlStatusOn (any non-zero value is on; written back as 0 / 1)                  */
+    uint32_t votes;               /* votes taken so far (telemetry, wraps)                                           */
+} igdsp_bss_state;
+#define IGDSP_BSS_VOTE_FRAMES 10  /* default threshold: 5 ticks of the reference's 40 ms timer at 20 ms frames */
+/* d_info[f][c] (igdsp_depayload's records) required.  Audio, at most one: d_payload[f][c][n] G.711 with d_codec[c] (RTP PT: 8 A-law,
+ * else mu-law), or d_pcm[f][c][n] int16; d_len[f][c] optional (as igdsp_decode_meter).  d_gain[c] Q7, NULL = 256 (UNMUTE at
+ * SLOT_VOLUME 2.0).  d_group_ptr[n_groups + 1] required, d_members[n_members] (n_members <= 2^24; NULL when 0).  d_mute[g] optional.
+ * vote_frames 0 = IGDSP_BSS_VOTE_FRAMES.  d_state[n_groups] and d_words[n_members] required (read and written).  Outputs, each
+ * optional: d_sel[f][g], d_out[f][g][n] int16, d_stats[f][g]; d_out and d_stats need an audio input.  Without audio only sel, the
+ * state and the words are produced (n is then still checked: 1..256).  n_groups == 0 or n_frames == 0: nothing to do.  Enqueued
+ * on `stream`, not synchronised. */
+int igdsp_bss_select(igdsp_ctx *ctx, const igdsp_rtp_info *d_info,
+                     const uint8_t *d_payload, const uint8_t *d_codec, const int16_t *d_pcm, const uint16_t *d_len,
+                     const uint16_t *d_gain, const uint32_t *d_group_ptr, const uint32_t *d_members, uint32_t n_members,
+                     const uint8_t *d_mute, uint32_t n_channels, uint32_t n_groups, uint32_t n_frames, uint32_t samples_per_frame,
+                     uint32_t vote_frames, igdsp_bss_state *d_state, uint32_t *d_words,
+                     int32_t *d_sel, int16_t *d_out, igdsp_frame_stats *d_stats, void *stream);
 
 /* ---- synthetic input generators (device side; SURVEY 8(d) definitions) ---------
  * D-uniform: byte k of global byte index g is
