@@ -25,6 +25,10 @@ ENC_SUN16, ENC_G191 = 0, 1
 FLAG_SILENT, FLAG_PROBE_D5, FLAG_CLIPPED, FLAG_EMPTY = 1, 2, 4, 8
 FLAG_SATURATED = 0x10        # igdsp_conf_mix
 BSS_VOTE_FRAMES = 10         # IGDSP_BSS_VOTE_FRAMES
+JB_DEPTH, JB_DELAY = 16, 3   # IGDSP_JB_DEPTH, IGDSP_JB_DELAY
+JB_IDLE, JB_PLAYED, JB_LOST = 1, 2, 3
+JB_PKT_NONE, JB_PKT_INVALID, JB_PKT_KEEPALIVE, JB_PKT_PLACED, JB_PKT_LATE, JB_PKT_DUPLICATE, JB_PKT_RESTART = 0, 1, 2, 3, 4, 5, 6
+JB_HEARD, JB_PLAYING, JB_TRANSIT = 1, 2, 4
 AGG_MAX_RANKS = 8
 AGG_LINE_WORDS = 16
 AGG_WORDS = 7 * AGG_LINE_WORDS
@@ -46,6 +50,17 @@ CHAN_HOLD = np.dtype(
 RTP_INFO = np.dtype([("ed137", "<u4"), ("payload_len", "<u2"), ("pt", "u1"), ("flags", "u1")], align=True)
 BSS_STATE = np.dtype([("count", "<u4"), ("voted", "<u4"), ("on", "<u4"), ("votes", "<u4")], align=True)   # igdsp_bss_state
 CHAN_PROBE = np.dtype([("run", "<u4"), ("alarms", "<u4")], align=True)
+# the jitter buffer (igdsp_jb_receive / igdsp_jb_report)
+JB_STATE = np.dtype(
+    [("ssrc", "<u4"), ("cycles", "<u4"), ("base_seq", "<u4"), ("bad_seq", "<u4"), ("probation", "<u4"), ("received", "<u4"),
+     ("transit", "<u4"), ("jitter", "<u4"), ("epoch", "<u4"), ("max_seq", "<u2"), ("head", "<u2"), ("wait", "u1"), ("lost_run", "u1"),
+     ("flags", "u1"), ("reserved0", "u1"), ("played", "<u4"), ("lost", "<u4"), ("late", "<u4"), ("duplicate", "<u4"), ("invalid", "<u4"),
+     ("keepalives", "<u4"), ("discarded", "<u4"), ("restarts", "<u4"), ("reserved1", "<u4")],
+    align=True,
+)
+JB_PRIOR = np.dtype([("expected_prior", "<u4"), ("received_prior", "<u4"), ("epoch", "<u4"), ("reserved", "<u4")], align=True)
+JB_RR = np.dtype([("ssrc", "<u4"), ("ext_max_seq", "<u4"), ("cum_lost", "<i4"), ("jitter", "<u4"), ("fraction_lost", "u1"), ("valid", "u1"),
+                  ("reserved", "<u2")], align=True)
 GATE_ALWAYS, GATE_SQU, GATE_PTT, GATE_SQU_OR_PTT = 0, 1, 2, 3
 PKT_SLOTS, PKT_PACKED, PKT_MIXED = 0, 1, 2
 PROBE_ALARM = 500
@@ -169,6 +184,9 @@ PROTOTYPES = [
     ("igdsp_conf_mix", _int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp]),
     ("igdsp_bss_select", _int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp,
                                 _vp]),
+    ("igdsp_jb_ring_bytes", C.c_size_t, [_u32, _u32]),
+    ("igdsp_jb_report", _int, [_vp, _vp, _vp]),
+    ("igdsp_jb_receive", _int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("igdsp_g726_reorder", _int, [_vp, _vp, _vp, _u64, _int, _vp]),
     ("igdsp_gen_uniform", _int, [_vp, _vp, _u64, _u64, _u64, _vp]),
     ("igdsp_dev_alloc", _int, [_vp, C.POINTER(_vp), C.c_size_t]),
@@ -257,6 +275,22 @@ def conf_build(channel, port, n_channels: int, n_ports: int):
     if rc != 0:
         raise IgdspError(rc, "igdsp_conf_build")
     return ptr, mem[: nm.value].copy()
+
+def jb_ring_bytes(n_channels: int, n: int = SAMPLES_PER_FRAME) -> int:
+    """igdsp_jb_ring_bytes (host only, no GPU): bytes of the jitter-buffer ring of n_channels at n samples per frame."""
+    return int(load().igdsp_jb_ring_bytes(n_channels, n))
+
+
+def jb_report(state, prior) -> np.ndarray:
+    """igdsp_jb_report (host only, no GPU): the RFC 3550 receiver-report fields of one JB_STATE record; advances prior (a JB_PRIOR
+    record, updated in place) and returns a JB_RR record."""
+    st = np.ascontiguousarray(np.asarray(state, dtype=JB_STATE).reshape(()))
+    assert prior.dtype == JB_PRIOR and prior.flags["C_CONTIGUOUS"]
+    out = np.zeros((), dtype=JB_RR)
+    rc = load().igdsp_jb_report(st.ctypes.data_as(_vp), prior.ctypes.data_as(_vp), out.ctypes.data_as(_vp))
+    if rc != 0:
+        raise IgdspError(rc, "igdsp_jb_report")
+    return out
 
 
 def _ptr(x) -> int | None:
@@ -426,6 +460,15 @@ class Context:
         self._ck(self.L.igdsp_bss_select(self.h, _ptr(info), _ptr(payload), _ptr(codec), _ptr(pcm), _ptr(length), _ptr(gain), _ptr(group_ptr),
                                          _ptr(members), n_members, _ptr(mute), C_, G_, F_, n, vote_frames, _ptr(state), _ptr(words), _ptr(sel),
                                          _ptr(out), _ptr(stats), stream), "igdsp_bss_select")
+
+    def jb_receive(self, packets, radio, state, ring, payload, length, info, C_, T_, S_=1, stride=180, n=160, delay=JB_DELAY, sizes=None,
+                   arrival=None, tick_flags=None, pkt_status=None, stream=None):
+        """igdsp_jb_receive: packets [T*S][C][stride] in arrival order, sizes [T*S][C] u16, radio [C], arrival [T*S][C] u32 (optional);
+        state [C] JB_STATE and ring (jb_ring_bytes(C, n) bytes) carried across calls; payload [T][C][n], len [T][C], info [T][C],
+        tick_flags [T][C] u8, pkt_status [T*S][C] u8 out (device buffers)."""
+        self._ck(self.L.igdsp_jb_receive(self.h, _ptr(packets), _ptr(sizes), _ptr(radio), _ptr(arrival), C_, T_, S_, stride, n, delay,
+                                         _ptr(state), _ptr(ring), _ptr(payload), _ptr(length), _ptr(info), _ptr(tick_flags),
+                                         _ptr(pkt_status), stream), "igdsp_jb_receive")
 
     # -- staged ED-137 send path (transport_send_rtp as pjmedia calls it)
     def tx_open(self, call_id: int, calltype: str, call_in: bool, keepalive_ms: int = 200, now_ms: int = 0):

@@ -837,6 +837,68 @@ int igdsp_bss_select(igdsp_ctx *ctx, const igdsp_rtp_info *d_info, const uint8_t
     return IGDSP_OK;
 }
 
+// ---- jitter buffer: the pjmedia stream behind adapter->stream_rtp_cb (TransportAdapter.cpp:301): RFC 3550 A.1 / A.3 / A.8 and playout ----
+size_t igdsp_jb_ring_bytes(uint32_t n_channels, uint32_t samples_per_frame)
+{
+    if (samples_per_frame == 0 || samples_per_frame > IGDSP_MAX_PAYLOAD) return 0;
+    return (size_t)jb_ring_bytes(n_channels, samples_per_frame);
+}
+
+int igdsp_jb_report(const igdsp_jb_state *s, igdsp_jb_prior *prior, igdsp_jb_rr *out)
+{
+    if (!s || !prior || !out) return IGDSP_EINVAL;
+    *out = igdsp_jb_rr{};
+    if (!(s->flags & IGDSP_JB_HEARD)) return IGDSP_OK;
+    const uint32_t ext = s->cycles + s->max_seq;
+    const uint32_t expected = ext - s->base_seq + 1u;
+    const int64_t lost = (int64_t)expected - (int64_t)s->received;
+    const bool same = prior->epoch == s->epoch;                                 // init_seq zeroes the priors
+    const uint32_t exp_int = expected - (same ? prior->expected_prior : 0u), rec_int = s->received - (same ? prior->received_prior : 0u);
+    const int64_t lost_int = (int64_t)exp_int - (int64_t)rec_int;
+    out->ssrc = s->ssrc;
+    out->ext_max_seq = ext;
+    out->cum_lost = (int32_t)std::min<int64_t>(std::max<int64_t>(lost, -0x800000), 0x7FFFFF);
+    out->jitter = s->jitter >> 4;
+    out->fraction_lost = (exp_int == 0u || lost_int <= 0) ? 0u : (uint8_t)std::min<int64_t>((lost_int << 8) / exp_int, 255);
+    out->valid = 1;
+    prior->expected_prior = expected;
+    prior->received_prior = s->received;
+    prior->epoch = s->epoch;
+    return IGDSP_OK;
+}
+
+// the argument rules of igdsp_jb_receive (shared with the yardstick entry)
+static int jb_check(igdsp_ctx *ctx, const uint8_t *d_packets, const uint8_t *d_radio, const uint16_t *d_sizes, const uint32_t *d_arrival,
+                    uint32_t C, uint32_t T, uint32_t S, uint32_t stride, uint32_t n, uint32_t delay, const igdsp_jb_state *d_state,
+                    const void *d_ring, const uint8_t *d_payload, const uint16_t *d_len, const igdsp_rtp_info *d_info)
+{
+    if (!ctx || !d_packets || !d_radio || !d_state || !d_ring || !d_payload || !d_len || !d_info) return IGDSP_EINVAL;
+    if (S == 0 || S > IGDSP_STAGE_DEPTH || delay >= IGDSP_JB_DEPTH) return IGDSP_EINVAL;
+    if (stride < 20u || (stride & 3u) || stride > 2048u) return IGDSP_EINVAL;
+    if (int rc = check_shape(C, T, n)) return rc;
+    if ((uint64_t)C * T * S >= 0xFFFFFFE0ull) return IGDSP_ERANGE;
+    const uintptr_t a2 = reinterpret_cast<uintptr_t>(d_sizes) | reinterpret_cast<uintptr_t>(d_len);
+    const uintptr_t a4 = reinterpret_cast<uintptr_t>(d_packets) | reinterpret_cast<uintptr_t>(d_arrival) | reinterpret_cast<uintptr_t>(d_state) |
+                         reinterpret_cast<uintptr_t>(d_info);
+    if ((a2 & 1u) || (a4 & 3u) || (reinterpret_cast<uintptr_t>(d_info) & 7u) || (reinterpret_cast<uintptr_t>(d_ring) & 15u)) return IGDSP_EINVAL;
+    return IGDSP_OK;
+}
+
+int igdsp_jb_receive(igdsp_ctx *ctx, const uint8_t *d_packets, const uint16_t *d_sizes, const uint8_t *d_radio, const uint32_t *d_arrival,
+                     uint32_t C, uint32_t T, uint32_t S, uint32_t pkt_stride, uint32_t n, uint32_t delay_frames, igdsp_jb_state *d_state,
+                     void *d_ring, uint8_t *d_payload_out, uint16_t *d_len_out, igdsp_rtp_info *d_info_out, uint8_t *d_tick_flags,
+                     uint8_t *d_pkt_status, void *stream)
+{
+    if (!ctx) return IGDSP_EINVAL;
+    if ((uint64_t)C * T == 0) return IGDSP_OK;                                               // nothing to do
+    if (int rc = jb_check(ctx, d_packets, d_radio, d_sizes, d_arrival, C, T, S, pkt_stride, n, delay_frames, d_state, d_ring, d_payload_out,
+                          d_len_out, d_info_out)) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, launch_jb_receive(cfg_of(ctx, pick(ctx, stream)), d_packets, d_sizes, d_radio, d_arrival, C, T, S, pkt_stride, n, delay_frames,
+                                   d_state, d_ring, d_payload_out, d_len_out, d_info_out, d_tick_flags, d_pkt_status, pick(ctx, stream)));
+    return IGDSP_OK;
+}
+
 // ---- staged ED-137 send path (transport_send_rtp as pjmedia calls it, TransportAdapter.cpp:635-874) ----
 // the TX side and channel of call_id (whether or not a leg is open there), or nullptr with *rc set
 static igdsp_ctx::TxSide *tx_chan_of(igdsp_ctx *ctx, int32_t call_id, uint32_t *leg, int *rc)
@@ -1230,6 +1292,24 @@ int igdsp_internal_bss_copy(igdsp_ctx *ctx, const igdsp_rtp_info *d_info, const 
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, launch_bss_copy_ab(cfg_of(ctx, pick(ctx, stream)), d_info, d_payload, d_codec, d_pcm, d_len, d_gain, d_group_ptr, d_members,
                                     n_members, d_mute, C, G, F, n, vote_frames, d_state, d_words, d_sel, d_out, d_stats, pick(ctx, stream)));
+    return IGDSP_OK;
+}
+
+// Calibration-only (not in include/igdsp.h): the compute-free yardstick of igdsp_jb_receive (tools/jb_bench.py) — the rows of an
+// in-order lossless launch (arrival slot 0 of every tick copied as igdsp_depayload would), with no header walk, state machine or ring
+// store.  Arguments as igdsp_jb_receive; the state, the ring and d_pkt_status are not touched.
+int igdsp_internal_jb_copy(igdsp_ctx *ctx, const uint8_t *d_packets, const uint16_t *d_sizes, const uint8_t *d_radio, const uint32_t *d_arrival,
+                           uint32_t C, uint32_t T, uint32_t S, uint32_t pkt_stride, uint32_t n, uint32_t delay_frames, igdsp_jb_state *d_state,
+                           void *d_ring, uint8_t *d_payload_out, uint16_t *d_len_out, igdsp_rtp_info *d_info_out, uint8_t *d_tick_flags,
+                           uint8_t *d_pkt_status, void *stream)
+{
+    if (!ctx) return IGDSP_EINVAL;
+    if ((uint64_t)C * T == 0) return IGDSP_OK;
+    if (int rc = jb_check(ctx, d_packets, d_radio, d_sizes, d_arrival, C, T, S, pkt_stride, n, delay_frames, d_state, d_ring, d_payload_out,
+                          d_len_out, d_info_out)) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, launch_jb_copy(cfg_of(ctx, pick(ctx, stream)), d_packets, d_sizes, d_radio, d_arrival, C, T, S, pkt_stride, n, delay_frames,
+                                d_state, d_ring, d_payload_out, d_len_out, d_info_out, d_tick_flags, nullptr, pick(ctx, stream)));
     return IGDSP_OK;
 }
 

@@ -101,6 +101,15 @@ hipError_t launch_bss_copy_ab(const LaunchCfg &cfg, const igdsp_rtp_info *info, 
                               const uint16_t *len, const uint16_t *gain, const uint32_t *group_ptr, const uint32_t *members, uint32_t n_members,
                               const uint8_t *mute, uint32_t C, uint32_t G, uint32_t F, uint32_t n, uint32_t vote_frames, igdsp_bss_state *state,
                               uint32_t *words, int32_t *sel, int16_t *out, igdsp_frame_stats *stats, hipStream_t s);
+// igdsp_jb_receive: sizes, arrival, tick, pkt may each be nullptr; ring is igdsp_jb_ring_bytes(C, n) bytes, 16-byte aligned
+hipError_t launch_jb_receive(const LaunchCfg &cfg, const uint8_t *packets, const uint16_t *sizes, const uint8_t *radio, const uint32_t *arrival,
+                             uint32_t C, uint32_t T, uint32_t S, uint32_t stride, uint32_t n, uint32_t delay, igdsp_jb_state *state, void *ring,
+                             uint8_t *payload, uint16_t *len, igdsp_rtp_info *info, uint8_t *tick, uint8_t *pkt, hipStream_t s);
+// compute-free yardstick of launch_jb_receive: the same rows as an in-order lossless launch (arrival slot k = 0 of every tick played
+// straight from the packet), no header walk, state machine or ring store; the state is not touched
+hipError_t launch_jb_copy(const LaunchCfg &cfg, const uint8_t *packets, const uint16_t *sizes, const uint8_t *radio, const uint32_t *arrival,
+                          uint32_t C, uint32_t T, uint32_t S, uint32_t stride, uint32_t n, uint32_t delay, igdsp_jb_state *state, void *ring,
+                          uint8_t *payload, uint16_t *len, igdsp_rtp_info *info, uint8_t *tick, uint8_t *pkt, hipStream_t s);
 hipError_t launch_wav_expand(const LaunchCfg &cfg, const uint8_t *payload, uint32_t C, uint32_t F, uint32_t n, uint32_t rate,
                              uint8_t *files, uint64_t file_stride, hipStream_t s);
 hipError_t launch_g726(const LaunchCfg &cfg, const uint8_t *in, uint8_t *out, uint64_t n_bytes, int mode, hipStream_t s);

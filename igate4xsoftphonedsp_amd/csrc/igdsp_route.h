@@ -478,6 +478,41 @@ inline BssRoute bss_route(uint32_t G, uint32_t F, uint32_t n, uint32_t n_members
     return r;
 }
 
+// ---- igdsp_jb_receive (launch_jb_receive, launch_jb_copy): k_jb_receive<COPY>.  A wave owns kJbCh consecutive channels for the ticks
+// of one part (<= kJbPart ticks).  Lanes 0 .. kJbCh - 1 step their channel's state machine over the part's arrivals with the ring tags in
+// LDS and leave a source descriptor per (tick, channel) there: an arrival of the part, a ring slot, or none; then the whole wave writes
+// the records and copies the payload rows in 16-byte pieces, and stores the packets still unplayed at the part's end into the ring.  A
+// launch of more ticks goes out in parts; the state and the ring carry between them as between launches.
+constexpr int kJbWaves = 4;                               // waves per block, independent of each other
+constexpr uint32_t kJbCh = 16;                            // channels per wave (decision lanes)
+constexpr uint32_t kJbPart = 128;                         // ticks per part
+constexpr uint32_t kJbU = 4;                              // loads of a lane in flight together
+constexpr uint32_t kJbSlotHead = 16;                      // ring slot: {ed137, payload_len | pt << 16 | flags << 24, len, 0}, then payload
+inline uint64_t jb_slot_bytes(uint32_t n) { return kJbSlotHead + (((uint64_t)n + 15u) & ~15ull); }
+inline uint64_t jb_ring_bytes(uint32_t C, uint32_t n)         // tags [C][IGDSP_JB_DEPTH] u32, then slots [C][IGDSP_JB_DEPTH]
+{
+    return (uint64_t)C * IGDSP_JB_DEPTH * (4u + jb_slot_bytes(n));
+}
+struct JbRoute {
+    uint32_t vec = 0;                      // n % 16 == 0 and a 16-byte aligned payload output: 16-byte stores
+    uint32_t pieces = 0;                   // 16-byte pieces per frame
+    uint32_t grid = 0, threads = 0;        // every part
+    uint32_t part_ticks = 0, parts = 0;    // the last part takes the rest
+};
+inline JbRoute jb_route(uint32_t C, uint32_t T, uint32_t n, uintptr_t payload_out)
+{
+    JbRoute r;
+    if ((uint64_t)C * T == 0) return r;
+    r.vec = (n & 15u) == 0u && aligned(payload_out, 16) ? 1u : 0u;
+    r.pieces = (n + 15u) / 16u;
+    const uint64_t waves = ((uint64_t)C + kJbCh - 1) / kJbCh;
+    r.grid = (uint32_t)((waves + kJbWaves - 1) / kJbWaves);
+    r.threads = kJbWaves * 64;
+    r.part_ticks = std::min(T, kJbPart);
+    r.parts = (T + kJbPart - 1) / kJbPart;
+    return r;
+}
+
 // ---- igdsp_tx_flush (launch_tx_staged): a wave owns kTsLegs staged legs (runs) of the flush; lanes 0 .. kTsLegs-1 decide, the
 // whole wave writes the packets.  No dynamic LDS: each wave's records (kTsLegs x IGDSP_STAGE_DEPTH) are static.
 constexpr int kTsWaves = 4;

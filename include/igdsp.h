@@ -35,7 +35,8 @@ extern "C" {
  *    Later, still additive under 3: the ED-137 TX packetizer (igdsp_tx_chan, igdsp_tx_info, igdsp_tx_chan_init, igdsp_tx_calltype_bits,
  *    igdsp_tx_packetize); the staged send path behind transport_send_rtp (igdsp_tx_open .. igdsp_tx_flush, igdsp_tx_packet); the
  *    conference mix (igdsp_conf_level_q7, igdsp_conf_build, igdsp_conf_mix, IGDSP_FLAG_SATURATED); best signal selection
- *    (igdsp_bss_state, IGDSP_BSS_VOTE_FRAMES, igdsp_bss_select). */
+ *    (igdsp_bss_state, IGDSP_BSS_VOTE_FRAMES, igdsp_bss_select); the jitter buffer (igdsp_jb_state, igdsp_jb_prior, igdsp_jb_rr,
+ *    IGDSP_JB_*, igdsp_jb_ring_bytes, igdsp_jb_report, igdsp_jb_receive). */
 #define IGDSP_ABI_VERSION 3
 
 /* ---- error codes (0 == PJ_SUCCESS-style success) ------------------------- */
@@ -676,6 +677,122 @@ int igdsp_bss_select(igdsp_ctx *ctx, const igdsp_rtp_info *d_info,
                      const uint8_t *d_mute, uint32_t n_channels, uint32_t n_groups, uint32_t n_frames, uint32_t samples_per_frame,
                      uint32_t vote_frames, igdsp_bss_state *d_state, uint32_t *d_words,
                      int32_t *d_sel, int16_t *d_out, igdsp_frame_stats *d_stats, void *stream);
+
+/* ---- Jitter buffer: RTP sequence tracking and playout between depayload and the vote / the bridge ---------------------------------
+ * The reference hands every packet but the keep-alives to adapter->stream_rtp_cb (TransportAdapter.cpp:301): the pjmedia stream, which
+ * validates the RTP sequence, puts frames back in playout order in its jitter buffer and keeps the RTCP receive statistics.
+ * igdsp_jb_receive does that step for a batch: packets in ARRIVAL order in, one playout frame per channel per tick out, in the layout
+ * of igdsp_depayload, so that igdsp_decode_meter, igdsp_bss_select and igdsp_conf_mix take the outputs unchanged.
+ *
+ * Input.  packets[a][c][pkt_stride], sizes[a][c] (NULL: every packet fills its slot), radio[c]: igdsp_depayload's meaning.  Arrival
+ * slot a = t * slots_per_tick + k for tick t = 0 .. n_ticks - 1 and k = 0 .. slots_per_tick - 1, the arrival order within the tick
+ * (slots_per_tick = 1 .. IGDSP_STAGE_DEPTH).  sizes[a][c] == 0: no packet.  d_arrival[a][c] (optional): the arrival time in RTP clock
+ * units (8 kHz), used only for the jitter.
+ * Per packet, in arrival order (seq, ts and ssrc are RTP header bytes 2-3, 4-7 and 8-11, network order):
+ *   1. No packet: nothing happens (status NONE).
+ *   2. Invalid: a runt (size < header) or V != 2: invalid += 1, otherwise ignored (INVALID).
+ *   3. Keep-alive: PT 123: keepalives += 1; never enters the sequence logic, as the reference passes no PT 123 to the stream.  Its
+ *      record is kept for the tick (KEEPALIVE).
+ *   4. New source: if a source has been heard and ssrc differs from the state's, the source part of the state resets (the A.1 / A.8
+ *      fields), playout stops and the ring is discarded: discarded += frames in it, restarts += 1.
+ *   5. Validation: RFC 3550 Appendix A.1 as written: a new source starts with init_seq(seq), max_seq = seq - 1, probation =
+ *      MIN_SEQUENTIAL (2); then update_seq with MAX_DROPOUT 3000, MAX_MISORDER 100, RTP_SEQ_MOD 1 << 16: probation, cycle counting, and
+ *      the re-sync after two sequential packets following a large jump.  A packet for which update_seq returns 0 is counted invalid and
+ *      not placed (INVALID).  So the FIRST packet of a new source is never played; that is RFC behaviour.  As in A.1's C, "seq ==
+ *      max_seq + 1" is an int comparison: during probation 0 does not follow 65535.
+ *   6. Jitter (d_arrival given, packet accepted): RFC 3550 A.8 in integer form, all mod 2^32: transit = arrival - ts; unless this is
+ *      the source's first accepted packet, d = |transit - last transit| and jitter += d - ((jitter + 8) >> 4) (jitter is scaled by 16).
+ *   7. Start or placement.  Start (playout stopped, or update_seq has just run init_seq): discarded += frames in the ring, the ring is
+ *      emptied, restarts += 1 if playout was running; head = seq, wait = delay_frames, and the packet goes into the ring (RESTART).
+ *      Otherwise d = (int16_t)(seq - head): d < 0: late += 1, dropped (LATE); d >= IGDSP_JB_DEPTH: a Start at this packet, restarts
+ *      += 1 (RESTART); else ring slot (head + d) % IGDSP_JB_DEPTH: if it already holds this seq, duplicate += 1 and the first copy is
+ *      kept (DUPLICATE), otherwise the packet is placed there (PLACED).
+ * Per tick t, after that tick's arrivals:
+ *   - stopped, or wait > 0: IDLE (wait -= 1 if it was > 0);
+ *   - playing and the head's slot holds seq head: PLAYED: that packet's payload, len and info, bit-identical to what igdsp_depayload
+ *     writes for it (bytes past len zeroed, len 0 for PT 18 / other PTs / oversize, IGDSP_RTP_OVERSIZE); the slot is freed, head += 1,
+ *     lost_run = 0, played += 1;
+ *   - playing and the slot is empty: LOST: head += 1, lost_run += 1, lost += 1; when lost_run reaches IGDSP_JB_DEPTH playout stops and
+ *     what is still in the ring is discarded (discarded += frames).  An ED-137 radio stops sending audio when its squelch closes and
+ *     sends only keep-alives: its channel goes IDLE 16 ticks later;
+ *   - IDLE / LOST ticks: payload zeros, len 0, info = the record of the LAST keep-alive of this tick if there was one (so
+ *     igdsp_bss_select still stores its word), else {ed137 0, payload_len 0, pt 0, IGDSP_RTP_RUNT}, the missing-frame record.
+ * Outputs: payload[t][c][n], len[t][c], info[t][c] (required); d_tick_flags[t][c] (optional, IGDSP_JB_PLAYED / LOST / IDLE);
+ * d_pkt_status[a][c] (optional, IGDSP_JB_PKT_*).
+ * State: igdsp_jb_state[c] and the ring (igdsp_jb_ring_bytes(C, n) bytes of device memory, 16-byte aligned) belong to the caller and
+ * carry playout across launches: n_ticks launches of one tick give the same outputs and state, and a ring holding the same packets, as
+ * one launch of n_ticks ticks.
+ * All-zero is the reset state of both; resetting a channel means zeroing its state and its ring slice.  A ring belongs to one n.
+ *
+ * Fidelity.  PINNED to RFC 3550: A.1 (sequence validation), A.3 (igdsp_jb_report) and A.8 (jitter).  UNVERIFIED: that pjmedia's
+ * rtp.c / rtcp.c use the same constants (pjmedia is a third-party dependency of the reference and is not in this tree).  DIFFERENT ON
+ * PURPOSE: the buffer has a fixed delay (delay_frames at every playout start), where pjsua's default jbuf adapts; there is no
+ * concealment, LOST ticks are silence downstream (len 0); keep-alive words are not delayed by the buffer. */
+#define IGDSP_JB_DEPTH   16      /* ring slots per channel: 320 ms at 20 ms frames */
+#define IGDSP_JB_DELAY    3      /* default delay_frames: 60 ms */
+#define IGDSP_JB_IDLE     1      /* d_tick_flags */
+#define IGDSP_JB_PLAYED   2
+#define IGDSP_JB_LOST     3
+#define IGDSP_JB_PKT_NONE       0   /* d_pkt_status */
+#define IGDSP_JB_PKT_INVALID    1
+#define IGDSP_JB_PKT_KEEPALIVE  2
+#define IGDSP_JB_PKT_PLACED     3
+#define IGDSP_JB_PKT_LATE       4
+#define IGDSP_JB_PKT_DUPLICATE  5
+#define IGDSP_JB_PKT_RESTART    6   /* placed as the head of a (re)started playout */
+#define IGDSP_JB_HEARD      0x01    /* igdsp_jb_state.flags: a source has been heard */
+#define IGDSP_JB_PLAYING    0x02    /*   playout running (wait counts the pre-roll)  */
+#define IGDSP_JB_TRANSIT    0x04    /*   transit holds the source's last transit     */
+typedef struct igdsp_jb_state {     /* per channel, 80 bytes, ALL-ZERO = reset */
+    uint32_t ssrc;
+    uint32_t cycles;                /* A.1: shifted count of sequence number cycles */
+    uint32_t base_seq;
+    uint32_t bad_seq;               /* last 'bad' seq + 1 (RTP_SEQ_MOD + 1 = none) */
+    uint32_t probation;
+    uint32_t received;
+    uint32_t transit;               /* A.8: last transit, mod 2^32 */
+    uint32_t jitter;                /* scaled by 16 */
+    uint32_t epoch;                 /* init_seq calls so far: tells igdsp_jb_report that the A.1 priors were reset */
+    uint16_t max_seq;
+    uint16_t head;                  /* seq of the next playout tick */
+    uint8_t  wait;                  /* pre-roll ticks left */
+    uint8_t  lost_run;              /* consecutive LOST ticks */
+    uint8_t  flags;                 /* IGDSP_JB_HEARD | IGDSP_JB_PLAYING | IGDSP_JB_TRANSIT */
+    uint8_t  reserved0;
+    uint32_t played, lost, late, duplicate, invalid, keepalives, discarded, restarts;
+    uint32_t reserved1;
+} igdsp_jb_state;
+/* What igdsp_jb_report remembers between two reports of a channel (A.3's expected_prior / received_prior); all-zero to start. */
+typedef struct igdsp_jb_prior {
+    uint32_t expected_prior;
+    uint32_t received_prior;
+    uint32_t epoch;                 /* the state's epoch the priors belong to */
+    uint32_t reserved;
+} igdsp_jb_prior;
+/* The receiver-report fields of RFC 3550 6.4.1 for one channel. */
+typedef struct igdsp_jb_rr {
+    uint32_t ssrc;
+    uint32_t ext_max_seq;           /* cycles + max_seq                                         */
+    int32_t  cum_lost;              /* expected - received, clamped to [-0x800000, 0x7FFFFF]     */
+    uint32_t jitter;                /* interarrival jitter, RTP clock units (state jitter >> 4)  */
+    uint8_t  fraction_lost;         /* (lost_interval << 8) / expected_interval, 0 if none lost  */
+    uint8_t  valid;                 /* 1: a source has been heard (else every field is 0)       */
+    uint16_t reserved;
+} igdsp_jb_rr;
+/* Ring bytes for n_channels at n samples per frame: IGDSP_JB_DEPTH tags per channel, then IGDSP_JB_DEPTH slots per channel of a
+ * 16-byte record head and the payload rounded up to 16 bytes.  0 for n outside 1..256.  Host-only. */
+size_t igdsp_jb_ring_bytes(uint32_t n_channels, uint32_t samples_per_frame);
+/* RFC 3550 A.3 over one channel's state: extended highest seq, cumulative lost (24-bit clamp), fraction lost since the report that
+ * last advanced *prior (which this call advances; priors of an earlier init_seq epoch count as zero, as init_seq resets them), jitter.
+ * A state with no source heard gives an all-zero report.  Host-only, no GPU needed. */
+int igdsp_jb_report(const igdsp_jb_state *s, igdsp_jb_prior *prior, igdsp_jb_rr *out);
+/* d_packets, d_radio, d_state, d_ring, d_payload_out, d_len_out, d_info_out required; d_sizes, d_arrival, d_tick_flags, d_pkt_status
+ * optional.  pkt_stride % 4 == 0, 20 .. 2048; slots_per_tick 1 .. IGDSP_STAGE_DEPTH; delay_frames 0 .. IGDSP_JB_DEPTH - 1; n 1..256.
+ * n_channels == 0 or n_ticks == 0: nothing to do.  Enqueued on `stream`, not synchronised. */
+int igdsp_jb_receive(igdsp_ctx *ctx, const uint8_t *d_packets, const uint16_t *d_sizes, const uint8_t *d_radio, const uint32_t *d_arrival,
+                     uint32_t n_channels, uint32_t n_ticks, uint32_t slots_per_tick, uint32_t pkt_stride, uint32_t samples_per_frame,
+                     uint32_t delay_frames, igdsp_jb_state *d_state, void *d_ring, uint8_t *d_payload_out, uint16_t *d_len_out,
+                     igdsp_rtp_info *d_info_out, uint8_t *d_tick_flags, uint8_t *d_pkt_status, void *stream);
 
 /* ---- synthetic input generators (device side; SURVEY 8(d) definitions) ---------
  * D-uniform: byte k of global byte index g is
