@@ -1,6 +1,7 @@
 // Prints the routes of igdsp_route.h for tests/test_route_cpu.py.  One case per stdin line: an entry name, then key=value pairs
 // (numbers in any base strtoull reads; IGDSP_* keys are set in the environment and read back through knobs_from_env, the rest
-// are the route function's arguments).  One output line per case: the route's fields as key=value.
+// are the route function's arguments).  One output line per case: the route's fields as key=value.  "consts" prints the
+// compile-time geometry the tests derive work per wave from.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -76,6 +77,8 @@ int main()
             const TxRoute r = tx_route(C, F, n, pcm, g711, g("last", 0x1000), cus, g("tab_lds", 1) != 0);
             std::printf("form=%s vec=%u n_groups=%u grid=%u threads=%u lds=%u table=%d\n", tx_name(r.form), r.vec, r.n_groups, r.grid, r.threads, r.lds,
                         tx_wants_table(pcm != 0, C, F, n));
+        } else if (entry == "consts") {
+            std::printf("tiny_slot=%u super_frames=%d\n", kTinySlot, kSuperFrames);
         } else {
             std::printf("unknown entry %s\n", entry.c_str());
             return 1;

@@ -109,9 +109,10 @@ def test_ragged_lengths_and_odd_frame_sizes(ctx, orc, n):
 @pytest.mark.parametrize("ragged", [False, True])
 def test_other_frame_sizes_image_kernel(ctx, orc, n, ragged):
     """Frame sizes other than 160 (the reference's hook anticipates 164 and 24, roip_ed137.cpp:6561-6562) and ragged frames
-    no longer fall to the wave-per-frame kernel.  Dense frames of 16 Q + 4 T bytes with Q in {1, 5, 10, 15}, T <= 2 (16, 20,
-    24, 80, 88, 164, 168, 240) keep the chunk pipeline at a frame stride (k_meter_strided, with the tail piece handed to the
-    frame lane); every other n % 4 == 0 size, ragged lengths and the < 64-frame tail go through k_meter_image (one frame per
+    no longer fall to the wave-per-frame kernel.  Dense 16 .. 32-byte frames (16, 20, 24) go to k_meter_tiny (a lane per frame);
+    dense frames of 16 Q + 4 T bytes with Q in {4, 5, 6, 8, 10, 12, 15}, T <= 2 (64, 72, 80, 88, 96, 100, 128, 136, 164, 168, 192,
+    200, 240) keep the chunk pipeline at a frame stride (k_meter_strided, with the tail piece handed to the frame lane); every
+    other n % 4 == 0 size (4, 172, 244, 256), ragged lengths and the < 64-frame tail go through k_meter_image (one frame per
     lane from an LDS image of 64 frames).  Whole items, a tail item, channel wrap inside an item, mixed laws, edge frames,
     the aggregate; every record against the oracle."""
     if n == 160 and not ragged:
