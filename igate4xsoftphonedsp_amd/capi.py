@@ -29,6 +29,8 @@ JB_DEPTH, JB_DELAY = 16, 3   # IGDSP_JB_DEPTH, IGDSP_JB_DELAY
 JB_IDLE, JB_PLAYED, JB_LOST = 1, 2, 3
 JB_PKT_NONE, JB_PKT_INVALID, JB_PKT_KEEPALIVE, JB_PKT_PLACED, JB_PKT_LATE, JB_PKT_DUPLICATE, JB_PKT_RESTART = 0, 1, 2, 3, 4, 5, 6
 JB_HEARD, JB_PLAYING, JB_TRANSIT = 1, 2, 4
+PLC_PMIN, PLC_PMAX, PLC_SPAN, PLC_HIST, PLC_FLAT, PLC_STEP = 40, 120, 160, 280, 80, 82   # IGDSP_PLC_*
+FLAG_CONCEALED = 0x20        # igdsp_plc_conceal
 AGG_MAX_RANKS = 8
 AGG_LINE_WORDS = 16
 AGG_WORDS = 7 * AGG_LINE_WORDS
@@ -56,6 +58,12 @@ JB_STATE = np.dtype(
      ("transit", "<u4"), ("jitter", "<u4"), ("epoch", "<u4"), ("max_seq", "<u2"), ("head", "<u2"), ("wait", "u1"), ("lost_run", "u1"),
      ("flags", "u1"), ("reserved0", "u1"), ("played", "<u4"), ("lost", "<u4"), ("late", "<u4"), ("duplicate", "<u4"), ("invalid", "<u4"),
      ("keepalives", "<u4"), ("discarded", "<u4"), ("restarts", "<u4"), ("reserved1", "<u4")],
+    align=True,
+)
+# packet loss concealment (igdsp_plc_conceal)
+PLC_STATE = np.dtype(
+    [("hist", "<i2", (PLC_HIST,)), ("cycle", "<i2", (PLC_PMAX,)), ("head", "<u2"), ("pitch", "<u2"), ("pos", "<u2"), ("missing", "<u2"),
+     ("runs", "<u4"), ("concealed", "<u4"), ("reserved", "<u4", (4,))],
     align=True,
 )
 JB_PRIOR = np.dtype([("expected_prior", "<u4"), ("received_prior", "<u4"), ("epoch", "<u4"), ("reserved", "<u4")], align=True)
@@ -187,6 +195,7 @@ PROTOTYPES = [
     ("igdsp_jb_ring_bytes", C.c_size_t, [_u32, _u32]),
     ("igdsp_jb_report", _int, [_vp, _vp, _vp]),
     ("igdsp_jb_receive", _int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("igdsp_plc_conceal", _int, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
     ("igdsp_g726_reorder", _int, [_vp, _vp, _vp, _u64, _int, _vp]),
     ("igdsp_gen_uniform", _int, [_vp, _vp, _u64, _u64, _u64, _vp]),
     ("igdsp_dev_alloc", _int, [_vp, C.POINTER(_vp), C.c_size_t]),
@@ -469,6 +478,14 @@ class Context:
         self._ck(self.L.igdsp_jb_receive(self.h, _ptr(packets), _ptr(sizes), _ptr(radio), _ptr(arrival), C_, T_, S_, stride, n, delay,
                                          _ptr(state), _ptr(ring), _ptr(payload), _ptr(length), _ptr(info), _ptr(tick_flags),
                                          _ptr(pkt_status), stream), "igdsp_jb_receive")
+
+    def plc_conceal(self, tick_flags, state, out, C_, T_, n=160, payload=None, codec=None, pcm=None, length=None, len_out=None, stats=None,
+                    stream=None):
+        """igdsp_plc_conceal: tick_flags [T][C] u8 (IGDSP_JB_*); exactly one of payload [T][C][n] u8 (+ codec [C]) / pcm [T][C][n] int16;
+        length [T][C] u16 (optional); state [C] PLC_STATE carried across calls; out [T][C][n] int16, len_out [T][C] u16 and stats [T][C]
+        (the last two optional) (device buffers)."""
+        self._ck(self.L.igdsp_plc_conceal(self.h, _ptr(tick_flags), _ptr(payload), _ptr(codec), _ptr(pcm), _ptr(length), C_, T_, n, _ptr(state),
+                                          _ptr(out), _ptr(len_out), _ptr(stats), stream), "igdsp_plc_conceal")
 
     # -- staged ED-137 send path (transport_send_rtp as pjmedia calls it)
     def tx_open(self, call_id: int, calltype: str, call_in: bool, keepalive_ms: int = 200, now_ms: int = 0):

@@ -899,6 +899,34 @@ int igdsp_jb_receive(igdsp_ctx *ctx, const uint8_t *d_packets, const uint16_t *d
     return IGDSP_OK;
 }
 
+// ---- packet loss concealment between the jitter buffer and the bridge (the pjmedia stream's PLC; G.711 Appendix I's structure) ----
+// the argument rules of igdsp_plc_conceal (shared with the yardstick entry)
+static int plc_check(igdsp_ctx *ctx, const uint8_t *d_tick_flags, const uint8_t *d_payload, const uint8_t *d_codec, const int16_t *d_pcm,
+                     const uint16_t *d_len, uint32_t C, uint32_t T, uint32_t n, const igdsp_plc_state *d_state, const int16_t *d_out,
+                     const uint16_t *d_len_out, const igdsp_frame_stats *d_stats)
+{
+    if (!ctx || !d_tick_flags || !d_state || !d_out) return IGDSP_EINVAL;
+    if ((d_payload == nullptr) == (d_pcm == nullptr) || (d_payload && !d_codec)) return IGDSP_EINVAL;   // exactly one input form
+    if (int rc = check_shape(C, T, n)) return rc;
+    const uintptr_t a2 = reinterpret_cast<uintptr_t>(d_pcm) | reinterpret_cast<uintptr_t>(d_len) | reinterpret_cast<uintptr_t>(d_out) |
+                         reinterpret_cast<uintptr_t>(d_len_out);
+    if ((a2 & 1u) || (reinterpret_cast<uintptr_t>(d_state) & 3u) || (reinterpret_cast<uintptr_t>(d_stats) & 7u)) return IGDSP_EINVAL;
+    return IGDSP_OK;
+}
+
+int igdsp_plc_conceal(igdsp_ctx *ctx, const uint8_t *d_tick_flags, const uint8_t *d_payload, const uint8_t *d_codec, const int16_t *d_pcm,
+                      const uint16_t *d_len, uint32_t C, uint32_t T, uint32_t n, igdsp_plc_state *d_state, int16_t *d_out, uint16_t *d_len_out,
+                      igdsp_frame_stats *d_stats, void *stream)
+{
+    if (!ctx) return IGDSP_EINVAL;
+    if ((uint64_t)C * T == 0) return IGDSP_OK;                                               // nothing to do
+    if (int rc = plc_check(ctx, d_tick_flags, d_payload, d_codec, d_pcm, d_len, C, T, n, d_state, d_out, d_len_out, d_stats)) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, launch_plc_conceal(cfg_of(ctx, pick(ctx, stream)), d_tick_flags, d_payload, d_codec, d_pcm, d_len, C, T, n, d_state, d_out,
+                                    d_len_out, d_stats, pick(ctx, stream)));
+    return IGDSP_OK;
+}
+
 // ---- staged ED-137 send path (transport_send_rtp as pjmedia calls it, TransportAdapter.cpp:635-874) ----
 // the TX side and channel of call_id (whether or not a leg is open there), or nullptr with *rc set
 static igdsp_ctx::TxSide *tx_chan_of(igdsp_ctx *ctx, int32_t call_id, uint32_t *leg, int *rc)
@@ -1310,6 +1338,22 @@ int igdsp_internal_jb_copy(igdsp_ctx *ctx, const uint8_t *d_packets, const uint1
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, launch_jb_copy(cfg_of(ctx, pick(ctx, stream)), d_packets, d_sizes, d_radio, d_arrival, C, T, S, pkt_stride, n, delay_frames,
                                 d_state, d_ring, d_payload_out, d_len_out, d_info_out, d_tick_flags, nullptr, pick(ctx, stream)));
+    return IGDSP_OK;
+}
+
+// Calibration-only (not in include/igdsp.h): the compute-free yardstick of igdsp_plc_conceal (tools/plc_bench.py) — the same
+// traversal with every tick taken as PLAIN: the input bits widened to the output, no decode, pitch search, synthesis or stats (the
+// records carry only the length); the state's ring and scalars are written.  Arguments as igdsp_plc_conceal.
+int igdsp_internal_plc_copy(igdsp_ctx *ctx, const uint8_t *d_tick_flags, const uint8_t *d_payload, const uint8_t *d_codec, const int16_t *d_pcm,
+                            const uint16_t *d_len, uint32_t C, uint32_t T, uint32_t n, igdsp_plc_state *d_state, int16_t *d_out,
+                            uint16_t *d_len_out, igdsp_frame_stats *d_stats, void *stream)
+{
+    if (!ctx) return IGDSP_EINVAL;
+    if ((uint64_t)C * T == 0) return IGDSP_OK;
+    if (int rc = plc_check(ctx, d_tick_flags, d_payload, d_codec, d_pcm, d_len, C, T, n, d_state, d_out, d_len_out, d_stats)) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, launch_plc_copy(cfg_of(ctx, pick(ctx, stream)), d_tick_flags, d_payload, d_codec, d_pcm, d_len, C, T, n, d_state, d_out,
+                                 d_len_out, d_stats, pick(ctx, stream)));
     return IGDSP_OK;
 }
 

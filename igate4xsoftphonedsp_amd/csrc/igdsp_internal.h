@@ -110,6 +110,15 @@ hipError_t launch_jb_receive(const LaunchCfg &cfg, const uint8_t *packets, const
 hipError_t launch_jb_copy(const LaunchCfg &cfg, const uint8_t *packets, const uint16_t *sizes, const uint8_t *radio, const uint32_t *arrival,
                           uint32_t C, uint32_t T, uint32_t S, uint32_t stride, uint32_t n, uint32_t delay, igdsp_jb_state *state, void *ring,
                           uint8_t *payload, uint16_t *len, igdsp_rtp_info *info, uint8_t *tick, uint8_t *pkt, hipStream_t s);
+// igdsp_plc_conceal: exactly one of g711 (+ codec) / pcm; len, len_out, stats may each be nullptr
+hipError_t launch_plc_conceal(const LaunchCfg &cfg, const uint8_t *flags, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm,
+                              const uint16_t *len, uint32_t C, uint32_t T, uint32_t n, igdsp_plc_state *state, int16_t *out, uint16_t *len_out,
+                              igdsp_frame_stats *stats, hipStream_t s);
+// compute-free yardstick of launch_plc_conceal: the same traversal with every tick taken as PLAIN, the input bits widened to the output,
+// no decode, pitch search, synthesis or stats (records carry only the length); the ring and the scalars are written as by a launch
+hipError_t launch_plc_copy(const LaunchCfg &cfg, const uint8_t *flags, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm,
+                           const uint16_t *len, uint32_t C, uint32_t T, uint32_t n, igdsp_plc_state *state, int16_t *out, uint16_t *len_out,
+                           igdsp_frame_stats *stats, hipStream_t s);
 hipError_t launch_wav_expand(const LaunchCfg &cfg, const uint8_t *payload, uint32_t C, uint32_t F, uint32_t n, uint32_t rate,
                              uint8_t *files, uint64_t file_stride, hipStream_t s);
 hipError_t launch_g726(const LaunchCfg &cfg, const uint8_t *in, uint8_t *out, uint64_t n_bytes, int mode, hipStream_t s);

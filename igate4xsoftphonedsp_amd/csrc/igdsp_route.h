@@ -513,6 +513,40 @@ inline JbRoute jb_route(uint32_t C, uint32_t T, uint32_t n, uintptr_t payload_ou
     return r;
 }
 
+// ---- igdsp_plc_conceal (launch_plc_conceal, launch_plc_copy): k_plc<COPY>.  A wave owns kPlcCh consecutive channels for the ticks of
+// one part (<= kPlcPart ticks).  Lanes 0 .. kPlcCh - 1 walk their channel's tick flags (no samples: which ticks are plain, which start
+// or continue a run, which recover) and leave a kind and a length per (tick, channel) in LDS; the whole wave then decodes and stores
+// the plain and IDLE rows, kPlcPiece samples per lane and piece, kPlcU pieces of a lane in flight, in batches of whole rows (the
+// records are reduced from per-piece partials in LDS); then it walks the channels with loss one at a time, tick by tick, for the
+// synthetic rows; last it writes every channel's final history ring.  A launch of more ticks goes out in parts; the state carries
+// between them as between launches.
+constexpr int kPlcWaves = 4;                              // waves per block, independent of each other
+constexpr uint32_t kPlcCh = 16;                           // channels per wave
+constexpr uint32_t kPlcPart = 128;                        // ticks per part
+constexpr uint32_t kPlcU = 4;                             // pieces of a lane in flight together
+constexpr uint32_t kPlcPiece = 8;                         // samples per piece: 16 bytes out
+struct PlcRoute {
+    uint32_t vec = 0;                      // n % 8 == 0, the output 16-byte and the input 8-byte (G.711) / 16-byte (PCM) aligned
+    uint32_t pieces = 0;                   // pieces per row
+    uint32_t batch_rows = 0;               // rows per batch: kPlcU * 64 / pieces
+    uint32_t grid = 0, threads = 0;        // every part
+    uint32_t part_ticks = 0, parts = 0;    // the last part takes the rest
+};
+inline PlcRoute plc_route(uint32_t C, uint32_t T, uint32_t n, bool pcm, uintptr_t in, uintptr_t out)
+{
+    PlcRoute r;
+    if ((uint64_t)C * T == 0 || n == 0) return r;
+    r.vec = (n % kPlcPiece) == 0u && aligned(out, 16) && aligned(in, pcm ? 16 : 8) ? 1u : 0u;
+    r.pieces = (n + kPlcPiece - 1) / kPlcPiece;
+    r.batch_rows = kPlcU * 64u / r.pieces;
+    const uint64_t waves = ((uint64_t)C + kPlcCh - 1) / kPlcCh;
+    r.grid = (uint32_t)((waves + kPlcWaves - 1) / kPlcWaves);
+    r.threads = kPlcWaves * 64;
+    r.part_ticks = std::min(T, kPlcPart);
+    r.parts = (T + kPlcPart - 1) / kPlcPart;
+    return r;
+}
+
 // ---- igdsp_tx_flush (launch_tx_staged): a wave owns kTsLegs staged legs (runs) of the flush; lanes 0 .. kTsLegs-1 decide, the
 // whole wave writes the packets.  No dynamic LDS: each wave's records (kTsLegs x IGDSP_STAGE_DEPTH) are static.
 constexpr int kTsWaves = 4;

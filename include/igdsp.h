@@ -36,7 +36,8 @@ extern "C" {
  *    igdsp_tx_packetize); the staged send path behind transport_send_rtp (igdsp_tx_open .. igdsp_tx_flush, igdsp_tx_packet); the
  *    conference mix (igdsp_conf_level_q7, igdsp_conf_build, igdsp_conf_mix, IGDSP_FLAG_SATURATED); best signal selection
  *    (igdsp_bss_state, IGDSP_BSS_VOTE_FRAMES, igdsp_bss_select); the jitter buffer (igdsp_jb_state, igdsp_jb_prior, igdsp_jb_rr,
- *    IGDSP_JB_*, igdsp_jb_ring_bytes, igdsp_jb_report, igdsp_jb_receive). */
+ *    IGDSP_JB_*, igdsp_jb_ring_bytes, igdsp_jb_report, igdsp_jb_receive); packet loss concealment (igdsp_plc_state, IGDSP_PLC_*,
+ *    IGDSP_FLAG_CONCEALED, igdsp_plc_conceal). */
 #define IGDSP_ABI_VERSION 3
 
 /* ---- error codes (0 == PJ_SUCCESS-style success) ------------------------- */
@@ -726,8 +727,9 @@ int igdsp_bss_select(igdsp_ctx *ctx, const igdsp_rtp_info *d_info,
  *
  * Fidelity.  PINNED to RFC 3550: A.1 (sequence validation), A.3 (igdsp_jb_report) and A.8 (jitter).  UNVERIFIED: that pjmedia's
  * rtp.c / rtcp.c use the same constants (pjmedia is a third-party dependency of the reference and is not in this tree).  DIFFERENT ON
- * PURPOSE: the buffer has a fixed delay (delay_frames at every playout start), where pjsua's default jbuf adapts; there is no
- * concealment, LOST ticks are silence downstream (len 0); keep-alive words are not delayed by the buffer. */
+ * PURPOSE: the buffer has a fixed delay (delay_frames at every playout start), where pjsua's default jbuf adapts; the buffer itself
+ * does no concealment, LOST ticks come out as len 0 (igdsp_plc_conceal below fills them in); keep-alive words are not delayed by the
+ * buffer. */
 #define IGDSP_JB_DEPTH   16      /* ring slots per channel: 320 ms at 20 ms frames */
 #define IGDSP_JB_DELAY    3      /* default delay_frames: 60 ms */
 #define IGDSP_JB_IDLE     1      /* d_tick_flags */
@@ -793,6 +795,70 @@ int igdsp_jb_receive(igdsp_ctx *ctx, const uint8_t *d_packets, const uint16_t *d
                      uint32_t n_channels, uint32_t n_ticks, uint32_t slots_per_tick, uint32_t pkt_stride, uint32_t samples_per_frame,
                      uint32_t delay_frames, igdsp_jb_state *d_state, void *d_ring, uint8_t *d_payload_out, uint16_t *d_len_out,
                      igdsp_rtp_info *d_info_out, uint8_t *d_tick_flags, uint8_t *d_pkt_status, void *stream);
+
+/* ---- Packet loss concealment: between the jitter buffer and the bridge ------------------------------------------------------------
+ * igdsp_plc_conceal turns the jitter buffer's playout ticks into continuous PCM: a LOST tick (or a PLAYED one that carries no audio)
+ * repeats the last pitch period of what the channel played, fading out, and the first good tick after a loss fades back in; the
+ * structure of G.711 Appendix I.  Per channel it keeps the last IGDSP_PLC_HIST output samples and the pitch cycle of the current run.
+ *
+ * All arithmetic is integer (Q15 weights, ">> 15" an arithmetic floor shift), so every implementation agrees bit for bit.  Notation:
+ *   y[k]   the channel's history, oldest first (k = 0 .. 279): y[k] = hist[(head + k) % IGDSP_PLC_HIST];
+ *   x[s]   the tick's input sample: the decoded G.711 sample or d_pcm for s < min(len, n), 0 past that (d_len NULL: len = n);
+ *   w(i)   ((i + 1) << 15) / (q + 1), an integer division of positive numbers, for a blend of q samples;
+ *   gain(m) max(0, 32768 - max(0, m - IGDSP_PLC_FLAT) * IGDSP_PLC_STEP): full gain for 10 ms, -20 % per 10 ms, silence from 60 ms;
+ *   S(m)   the synthetic sample at run index m: (cycle[pos] * gain(m) + 16384) >> 15, then pos = (pos + 1) % pitch.
+ * Per tick t and channel c, in tick order (tick flags as igdsp_jb_receive writes them):
+ *   1. Good: PLAYED with len > 0.  missing == 0: out = x.  Otherwise the recovery: q = pitch >> 2; for i < min(q, n)
+ *      out[i] = (S(missing + i) * (32768 - w(i)) + x[i] * w(i) + 16384) >> 15, out[i] = x[i] past that; then missing = 0.
+ *   2. Concealed: LOST, or PLAYED with len == 0 (undecodable PTs, oversize frames).  If missing == 0 a run starts:
+ *      - pitch search: D(p) = sum_{i<160} |y[120 + i] - y[120 + i - p]| for p = IGDSP_PLC_PMIN .. IGDSP_PLC_PMAX; p = the smallest D,
+ *        the smallest p on ties (the key (D << 7) | p fits 32 bits: one min-reduction gives both rules);
+ *      - cycle: q = p >> 2; cycle[i] = y[280 - p + i] for i < p - q; for i = p - q .. p - 1, j = i - (p - q):
+ *        cycle[i] = (y[280 - p + i] * (32768 - w(j)) + y[280 - 2p + i] * w(j) + 16384) >> 15; entries >= p are left as they were;
+ *      - pitch = p, pos = 0, runs += 1;
+ *      - fade-in with no added delay: for i < min(q, n) out[i] = (y[279 - i] * (32768 - w(i)) + S(i) * w(i) + 16384) >> 15 (the
+ *        reversed tail blended into the cycle), out[i] = S(i) past that.
+ *      Otherwise (a run goes on) out[i] = S(missing + i).  Then missing = min(missing + n, 65535) and concealed += 1.
+ *   3. IDLE, or any other flag value: out = 0 and missing = 0.  No recovery fade ever follows an IDLE tick.
+ *   4. Every tick appends out[0 .. n) to the ring at head, then head = (head + n) % IGDSP_PLC_HIST (n <= 256 < 280: a tick never
+ *      overlaps itself).
+ * Every blend is convex, so no clamp is needed and every product fits int32.  The state is read as head % IGDSP_PLC_HIST, pitch
+ * clamped to [IGDSP_PLC_PMIN, IGDSP_PLC_PMAX] and pos % pitch, and written back so: a garbage state stays in bounds.
+ * Outputs: d_out[t][c][n] int16; d_len_out[t][c] = n, 0 for IDLE ticks; d_stats[t][c] the record igdsp_conf_mix writes, over out
+ * (sumsq, rms, peak, byte_mean 0, IGDSP_FLAG_SILENT) plus IGDSP_FLAG_CONCEALED on concealed ticks; IDLE ticks get the len-0 record
+ * (all 0, IGDSP_FLAG_EMPTY).  (d_out, d_len_out) feed igdsp_conf_mix / igdsp_bss_select through their d_pcm / d_len inputs unchanged.
+ * The state carries concealment across launches: n_ticks launches of one tick give the same outputs and state bytes as one launch of
+ * n_ticks ticks.  All-zero is the reset state (its history is silence).  A state belongs to one n.
+ *
+ * Fidelity.  The reference delegates concealment to pjmedia, which is not in this tree.  UNVERIFIED: which algorithm pjmedia applies.
+ * PINNED to G.711 Appendix I's structure: the constants (pitch range 40 .. 120, a 20 ms match window, 10 ms at full gain, -20 % per
+ * 10 ms, silence from 60 ms, a quarter-period overlap-add at both edges of a loss).  DIFFERENT ON PURPOSE: no 3.75 ms output delay
+ * (the reversed-tail fade-in replaces it); one pitch period throughout, where Appendix I widens to 2 and 3 periods after 10 and
+ * 20 ms; an integer AMDF pitch search (average magnitude difference), not a normalised float correlation; Q15 arithmetic. */
+#define IGDSP_PLC_PMIN   40    /* shortest pitch period, samples (200 Hz)            */
+#define IGDSP_PLC_PMAX  120    /* longest pitch period (66.7 Hz)                     */
+#define IGDSP_PLC_SPAN  160    /* samples compared per candidate period (20 ms)      */
+#define IGDSP_PLC_HIST  280    /* history kept per channel = SPAN + PMAX             */
+#define IGDSP_PLC_FLAT   80    /* concealed samples at full gain (10 ms)             */
+#define IGDSP_PLC_STEP   82    /* Q15 gain decrement per sample after that           */
+#define IGDSP_FLAG_CONCEALED 0x20  /* record flag: this tick's output is synthetic  */
+typedef struct igdsp_plc_state {   /* per channel, 832 bytes, ALL-ZERO = reset */
+    int16_t  hist[IGDSP_PLC_HIST]; /* ring: history sample k (0 = oldest) is hist[(head + k) % HIST] */
+    int16_t  cycle[IGDSP_PLC_PMAX];/* the pitch cycle of the current / last run   */
+    uint16_t head, pitch, pos;     /* ring head; period of the last run; next cycle index */
+    uint16_t missing;              /* samples concealed in the current run, saturating at 65535; 0 = no run */
+    uint32_t runs, concealed;      /* telemetry, wrapping: runs started, ticks concealed */
+    uint32_t reserved[4];
+} igdsp_plc_state;
+/* d_tick_flags[t][c] (IGDSP_JB_*), d_state[c] and d_out[t][c][n] required.  Exactly one input: d_payload[t][c][n] G.711 with
+ * d_codec[c] (RTP PT: 8 A-law, else mu-law; igdsp_decode_meter's tables), or d_pcm[t][c][n] int16.  d_len[t][c], d_len_out[t][c]
+ * and d_stats[t][c] optional.  n = 1..256.  n_channels == 0 or n_ticks == 0: nothing to do.  Outputs must not overlap the inputs.
+ * Enqueued on `stream`, not synchronised. */
+int igdsp_plc_conceal(igdsp_ctx *ctx, const uint8_t *d_tick_flags,
+                      const uint8_t *d_payload, const uint8_t *d_codec, const int16_t *d_pcm, const uint16_t *d_len,
+                      uint32_t n_channels, uint32_t n_ticks, uint32_t samples_per_frame,
+                      igdsp_plc_state *d_state, int16_t *d_out, uint16_t *d_len_out,
+                      igdsp_frame_stats *d_stats, void *stream);
 
 /* ---- synthetic input generators (device side; SURVEY 8(d) definitions) ---------
  * D-uniform: byte k of global byte index g is
