@@ -767,12 +767,13 @@ int igdsp_conf_build(const uint32_t *channel, const uint32_t *port, uint32_t n_c
     return IGDSP_OK;
 }
 
-// the argument rules of igdsp_conf_mix (shared with the yardstick entry)
-static int conf_check(igdsp_ctx *ctx, const uint8_t *d_payload, const uint8_t *d_codec, const int16_t *d_pcm, const uint16_t *d_len,
-                      const uint16_t *d_gain, const uint32_t *d_port_ptr, const uint32_t *d_members, uint32_t n_members, uint32_t C, uint32_t P,
-                      uint32_t F, uint32_t n, const int16_t *d_out, const igdsp_frame_stats *d_stats)
+// igdsp_conf_mix, or with yardstick its compute-free twin igdsp_internal_conf_copy
+static int conf_mix(igdsp_ctx *ctx, const uint8_t *d_payload, const uint8_t *d_codec, const int16_t *d_pcm, const uint16_t *d_len,
+                    const uint16_t *d_gain, const uint32_t *d_port_ptr, const uint32_t *d_members, uint32_t n_members, uint32_t C, uint32_t P,
+                    uint32_t F, uint32_t n, int16_t *d_out, igdsp_frame_stats *d_stats, void *stream, bool yardstick)
 {
     if (!ctx) return IGDSP_EINVAL;
+    if ((uint64_t)P * F == 0) return IGDSP_OK;                                               // nothing to write
     if ((d_payload == nullptr) == (d_pcm == nullptr) || (d_payload && !d_codec)) return IGDSP_EINVAL;   // exactly one input form
     if (!d_out && !d_stats) return IGDSP_EINVAL;
     if (!d_gain || !d_port_ptr || (n_members && !d_members)) return IGDSP_EINVAL;
@@ -782,6 +783,9 @@ static int conf_check(igdsp_ctx *ctx, const uint8_t *d_payload, const uint8_t *d
                          reinterpret_cast<uintptr_t>(d_out);
     const uintptr_t a4 = reinterpret_cast<uintptr_t>(d_port_ptr) | reinterpret_cast<uintptr_t>(d_members);
     if ((a2 & 1u) || (a4 & 3u) || (reinterpret_cast<uintptr_t>(d_stats) & 7u)) return IGDSP_EINVAL;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, launch_conf_mix(cfg_of(ctx, pick(ctx, stream)), d_payload, d_codec, d_pcm, d_len, d_gain, d_port_ptr, d_members, n_members, C, P,
+                                 F, n, d_out, d_stats, yardstick, pick(ctx, stream)));
     return IGDSP_OK;
 }
 
@@ -789,24 +793,20 @@ int igdsp_conf_mix(igdsp_ctx *ctx, const uint8_t *d_payload, const uint8_t *d_co
                    const uint16_t *d_gain, const uint32_t *d_port_ptr, const uint32_t *d_members, uint32_t n_members, uint32_t C, uint32_t P,
                    uint32_t F, uint32_t n, int16_t *d_out, igdsp_frame_stats *d_stats, void *stream)
 {
-    if (!ctx) return IGDSP_EINVAL;
-    if ((uint64_t)P * F == 0) return IGDSP_OK;                                               // nothing to write
-    if (int rc = conf_check(ctx, d_payload, d_codec, d_pcm, d_len, d_gain, d_port_ptr, d_members, n_members, C, P, F, n, d_out, d_stats)) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, launch_conf_mix(cfg_of(ctx, pick(ctx, stream)), d_payload, d_codec, d_pcm, d_len, d_gain, d_port_ptr, d_members, n_members, C, P,
-                                 F, n, d_out, d_stats, pick(ctx, stream)));
-    return IGDSP_OK;
+    return conf_mix(ctx, d_payload, d_codec, d_pcm, d_len, d_gain, d_port_ptr, d_members, n_members, C, P, F, n, d_out, d_stats, stream, false);
 }
 
 // ---- best signal selection: the receiver vote of checkEvents (roip_ed137.cpp:5985-6119; get_IPRadioSquelch / get_IPRadioBss,
 // Functions.cpp:1001-1022; setvolume, Functions.cpp:1664-1705) ----
-// the argument rules of igdsp_bss_select (shared with the yardstick entry)
-static int bss_check(igdsp_ctx *ctx, const igdsp_rtp_info *d_info, const uint8_t *d_payload, const uint8_t *d_codec, const int16_t *d_pcm,
-                     const uint16_t *d_len, const uint16_t *d_gain, const uint32_t *d_group_ptr, const uint32_t *d_members, uint32_t n_members,
-                     uint32_t C, uint32_t G, uint32_t F, uint32_t n, const igdsp_bss_state *d_state, const uint32_t *d_words,
-                     const int32_t *d_sel, const int16_t *d_out, const igdsp_frame_stats *d_stats)
+// igdsp_bss_select, or with yardstick its compute-free twin igdsp_internal_bss_copy
+static int bss_select(igdsp_ctx *ctx, const igdsp_rtp_info *d_info, const uint8_t *d_payload, const uint8_t *d_codec, const int16_t *d_pcm,
+                      const uint16_t *d_len, const uint16_t *d_gain, const uint32_t *d_group_ptr, const uint32_t *d_members, uint32_t n_members,
+                      const uint8_t *d_mute, uint32_t C, uint32_t G, uint32_t F, uint32_t n, uint32_t vote_frames, igdsp_bss_state *d_state,
+                      uint32_t *d_words, int32_t *d_sel, int16_t *d_out, igdsp_frame_stats *d_stats, void *stream, bool yardstick)
 {
-    if (!ctx || !d_info || !d_group_ptr || !d_state) return IGDSP_EINVAL;
+    if (!ctx) return IGDSP_EINVAL;
+    if ((uint64_t)G * F == 0) return IGDSP_OK;                                               // nothing to do
+    if (!d_info || !d_group_ptr || !d_state) return IGDSP_EINVAL;
     if (n_members && (!d_members || !d_words)) return IGDSP_EINVAL;
     if (n_members > (1u << 24)) return IGDSP_EINVAL;                                          // positions are 24-bit in the vote key
     if (d_payload && d_pcm) return IGDSP_EINVAL;                                              // at most one input form
@@ -819,6 +819,10 @@ static int bss_check(igdsp_ctx *ctx, const igdsp_rtp_info *d_info, const uint8_t
     const uintptr_t a4 = reinterpret_cast<uintptr_t>(d_info) | reinterpret_cast<uintptr_t>(d_group_ptr) | reinterpret_cast<uintptr_t>(d_members) |
                          reinterpret_cast<uintptr_t>(d_state) | reinterpret_cast<uintptr_t>(d_words) | reinterpret_cast<uintptr_t>(d_sel);
     if ((a2 & 1u) || (a4 & 3u) || (reinterpret_cast<uintptr_t>(d_stats) & 7u)) return IGDSP_EINVAL;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, launch_bss_select(cfg_of(ctx, pick(ctx, stream)), d_info, d_payload, d_codec, d_pcm, d_len, d_gain, d_group_ptr, d_members,
+                                   n_members, d_mute, C, G, F, n, vote_frames, d_state, d_words, d_sel, d_out, d_stats, yardstick,
+                                   pick(ctx, stream)));
     return IGDSP_OK;
 }
 
@@ -827,14 +831,8 @@ int igdsp_bss_select(igdsp_ctx *ctx, const igdsp_rtp_info *d_info, const uint8_t
                      const uint8_t *d_mute, uint32_t C, uint32_t G, uint32_t F, uint32_t n, uint32_t vote_frames, igdsp_bss_state *d_state,
                      uint32_t *d_words, int32_t *d_sel, int16_t *d_out, igdsp_frame_stats *d_stats, void *stream)
 {
-    if (!ctx) return IGDSP_EINVAL;
-    if ((uint64_t)G * F == 0) return IGDSP_OK;                                               // nothing to do
-    if (int rc = bss_check(ctx, d_info, d_payload, d_codec, d_pcm, d_len, d_gain, d_group_ptr, d_members, n_members, C, G, F, n, d_state, d_words,
-                           d_sel, d_out, d_stats)) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, launch_bss_select(cfg_of(ctx, pick(ctx, stream)), d_info, d_payload, d_codec, d_pcm, d_len, d_gain, d_group_ptr, d_members,
-                                   n_members, d_mute, C, G, F, n, vote_frames, d_state, d_words, d_sel, d_out, d_stats, pick(ctx, stream)));
-    return IGDSP_OK;
+    return bss_select(ctx, d_info, d_payload, d_codec, d_pcm, d_len, d_gain, d_group_ptr, d_members, n_members, d_mute, C, G, F, n, vote_frames,
+                      d_state, d_words, d_sel, d_out, d_stats, stream, false);
 }
 
 // ---- jitter buffer: the pjmedia stream behind adapter->stream_rtp_cb (TransportAdapter.cpp:301): RFC 3550 A.1 / A.3 / A.8 and playout ----
@@ -867,12 +865,15 @@ int igdsp_jb_report(const igdsp_jb_state *s, igdsp_jb_prior *prior, igdsp_jb_rr 
     return IGDSP_OK;
 }
 
-// the argument rules of igdsp_jb_receive (shared with the yardstick entry)
-static int jb_check(igdsp_ctx *ctx, const uint8_t *d_packets, const uint8_t *d_radio, const uint16_t *d_sizes, const uint32_t *d_arrival,
-                    uint32_t C, uint32_t T, uint32_t S, uint32_t stride, uint32_t n, uint32_t delay, const igdsp_jb_state *d_state,
-                    const void *d_ring, const uint8_t *d_payload, const uint16_t *d_len, const igdsp_rtp_info *d_info)
+// igdsp_jb_receive, or with yardstick its compute-free twin igdsp_internal_jb_copy (which leaves d_pkt_status alone)
+static int jb_receive(igdsp_ctx *ctx, const uint8_t *d_packets, const uint16_t *d_sizes, const uint8_t *d_radio, const uint32_t *d_arrival,
+                      uint32_t C, uint32_t T, uint32_t S, uint32_t stride, uint32_t n, uint32_t delay, igdsp_jb_state *d_state, void *d_ring,
+                      uint8_t *d_payload, uint16_t *d_len, igdsp_rtp_info *d_info, uint8_t *d_tick_flags, uint8_t *d_pkt_status, void *stream,
+                      bool yardstick)
 {
-    if (!ctx || !d_packets || !d_radio || !d_state || !d_ring || !d_payload || !d_len || !d_info) return IGDSP_EINVAL;
+    if (!ctx) return IGDSP_EINVAL;
+    if ((uint64_t)C * T == 0) return IGDSP_OK;                                               // nothing to do
+    if (!d_packets || !d_radio || !d_state || !d_ring || !d_payload || !d_len || !d_info) return IGDSP_EINVAL;
     if (S == 0 || S > IGDSP_STAGE_DEPTH || delay >= IGDSP_JB_DEPTH) return IGDSP_EINVAL;
     if (stride < 20u || (stride & 3u) || stride > 2048u) return IGDSP_EINVAL;
     if (int rc = check_shape(C, T, n)) return rc;
@@ -881,6 +882,9 @@ static int jb_check(igdsp_ctx *ctx, const uint8_t *d_packets, const uint8_t *d_r
     const uintptr_t a4 = reinterpret_cast<uintptr_t>(d_packets) | reinterpret_cast<uintptr_t>(d_arrival) | reinterpret_cast<uintptr_t>(d_state) |
                          reinterpret_cast<uintptr_t>(d_info);
     if ((a2 & 1u) || (a4 & 3u) || (reinterpret_cast<uintptr_t>(d_info) & 7u) || (reinterpret_cast<uintptr_t>(d_ring) & 15u)) return IGDSP_EINVAL;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, launch_jb_receive(cfg_of(ctx, pick(ctx, stream)), d_packets, d_sizes, d_radio, d_arrival, C, T, S, stride, n, delay, d_state, d_ring,
+                                   d_payload, d_len, d_info, d_tick_flags, yardstick ? nullptr : d_pkt_status, yardstick, pick(ctx, stream)));
     return IGDSP_OK;
 }
 
@@ -889,28 +893,27 @@ int igdsp_jb_receive(igdsp_ctx *ctx, const uint8_t *d_packets, const uint16_t *d
                      void *d_ring, uint8_t *d_payload_out, uint16_t *d_len_out, igdsp_rtp_info *d_info_out, uint8_t *d_tick_flags,
                      uint8_t *d_pkt_status, void *stream)
 {
-    if (!ctx) return IGDSP_EINVAL;
-    if ((uint64_t)C * T == 0) return IGDSP_OK;                                               // nothing to do
-    if (int rc = jb_check(ctx, d_packets, d_radio, d_sizes, d_arrival, C, T, S, pkt_stride, n, delay_frames, d_state, d_ring, d_payload_out,
-                          d_len_out, d_info_out)) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, launch_jb_receive(cfg_of(ctx, pick(ctx, stream)), d_packets, d_sizes, d_radio, d_arrival, C, T, S, pkt_stride, n, delay_frames,
-                                   d_state, d_ring, d_payload_out, d_len_out, d_info_out, d_tick_flags, d_pkt_status, pick(ctx, stream)));
-    return IGDSP_OK;
+    return jb_receive(ctx, d_packets, d_sizes, d_radio, d_arrival, C, T, S, pkt_stride, n, delay_frames, d_state, d_ring, d_payload_out, d_len_out,
+                      d_info_out, d_tick_flags, d_pkt_status, stream, false);
 }
 
 // ---- packet loss concealment between the jitter buffer and the bridge (the pjmedia stream's PLC; G.711 Appendix I's structure) ----
-// the argument rules of igdsp_plc_conceal (shared with the yardstick entry)
-static int plc_check(igdsp_ctx *ctx, const uint8_t *d_tick_flags, const uint8_t *d_payload, const uint8_t *d_codec, const int16_t *d_pcm,
-                     const uint16_t *d_len, uint32_t C, uint32_t T, uint32_t n, const igdsp_plc_state *d_state, const int16_t *d_out,
-                     const uint16_t *d_len_out, const igdsp_frame_stats *d_stats)
+// igdsp_plc_conceal, or with yardstick its compute-free twin igdsp_internal_plc_copy
+static int plc_conceal(igdsp_ctx *ctx, const uint8_t *d_tick_flags, const uint8_t *d_payload, const uint8_t *d_codec, const int16_t *d_pcm,
+                       const uint16_t *d_len, uint32_t C, uint32_t T, uint32_t n, igdsp_plc_state *d_state, int16_t *d_out, uint16_t *d_len_out,
+                       igdsp_frame_stats *d_stats, void *stream, bool yardstick)
 {
-    if (!ctx || !d_tick_flags || !d_state || !d_out) return IGDSP_EINVAL;
+    if (!ctx) return IGDSP_EINVAL;
+    if ((uint64_t)C * T == 0) return IGDSP_OK;                                               // nothing to do
+    if (!d_tick_flags || !d_state || !d_out) return IGDSP_EINVAL;
     if ((d_payload == nullptr) == (d_pcm == nullptr) || (d_payload && !d_codec)) return IGDSP_EINVAL;   // exactly one input form
     if (int rc = check_shape(C, T, n)) return rc;
     const uintptr_t a2 = reinterpret_cast<uintptr_t>(d_pcm) | reinterpret_cast<uintptr_t>(d_len) | reinterpret_cast<uintptr_t>(d_out) |
                          reinterpret_cast<uintptr_t>(d_len_out);
     if ((a2 & 1u) || (reinterpret_cast<uintptr_t>(d_state) & 3u) || (reinterpret_cast<uintptr_t>(d_stats) & 7u)) return IGDSP_EINVAL;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, launch_plc_conceal(cfg_of(ctx, pick(ctx, stream)), d_tick_flags, d_payload, d_codec, d_pcm, d_len, C, T, n, d_state, d_out,
+                                    d_len_out, d_stats, yardstick, pick(ctx, stream)));
     return IGDSP_OK;
 }
 
@@ -918,13 +921,7 @@ int igdsp_plc_conceal(igdsp_ctx *ctx, const uint8_t *d_tick_flags, const uint8_t
                       const uint16_t *d_len, uint32_t C, uint32_t T, uint32_t n, igdsp_plc_state *d_state, int16_t *d_out, uint16_t *d_len_out,
                       igdsp_frame_stats *d_stats, void *stream)
 {
-    if (!ctx) return IGDSP_EINVAL;
-    if ((uint64_t)C * T == 0) return IGDSP_OK;                                               // nothing to do
-    if (int rc = plc_check(ctx, d_tick_flags, d_payload, d_codec, d_pcm, d_len, C, T, n, d_state, d_out, d_len_out, d_stats)) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, launch_plc_conceal(cfg_of(ctx, pick(ctx, stream)), d_tick_flags, d_payload, d_codec, d_pcm, d_len, C, T, n, d_state, d_out,
-                                    d_len_out, d_stats, pick(ctx, stream)));
-    return IGDSP_OK;
+    return plc_conceal(ctx, d_tick_flags, d_payload, d_codec, d_pcm, d_len, C, T, n, d_state, d_out, d_len_out, d_stats, stream, false);
 }
 
 // ---- staged ED-137 send path (transport_send_rtp as pjmedia calls it, TransportAdapter.cpp:635-874) ----
@@ -1296,13 +1293,7 @@ int igdsp_internal_conf_copy(igdsp_ctx *ctx, const uint8_t *d_payload, const uin
                              const uint16_t *d_gain, const uint32_t *d_port_ptr, const uint32_t *d_members, uint32_t n_members, uint32_t C,
                              uint32_t P, uint32_t F, uint32_t n, int16_t *d_out, igdsp_frame_stats *d_stats, void *stream)
 {
-    if (!ctx) return IGDSP_EINVAL;
-    if ((uint64_t)P * F == 0) return IGDSP_OK;
-    if (int rc = conf_check(ctx, d_payload, d_codec, d_pcm, d_len, d_gain, d_port_ptr, d_members, n_members, C, P, F, n, d_out, d_stats)) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, launch_conf_copy_ab(cfg_of(ctx, pick(ctx, stream)), d_payload, d_codec, d_pcm, d_len, d_gain, d_port_ptr, d_members, n_members, C,
-                                     P, F, n, d_out, d_stats, pick(ctx, stream)));
-    return IGDSP_OK;
+    return conf_mix(ctx, d_payload, d_codec, d_pcm, d_len, d_gain, d_port_ptr, d_members, n_members, C, P, F, n, d_out, d_stats, stream, true);
 }
 
 // Calibration-only (not in include/igdsp.h): the compute-free yardstick of igdsp_bss_select (tools/bss_bench.py) — the same traversal,
@@ -1313,14 +1304,8 @@ int igdsp_internal_bss_copy(igdsp_ctx *ctx, const igdsp_rtp_info *d_info, const 
                             uint32_t n_members, const uint8_t *d_mute, uint32_t C, uint32_t G, uint32_t F, uint32_t n, uint32_t vote_frames,
                             igdsp_bss_state *d_state, uint32_t *d_words, int32_t *d_sel, int16_t *d_out, igdsp_frame_stats *d_stats, void *stream)
 {
-    if (!ctx) return IGDSP_EINVAL;
-    if ((uint64_t)G * F == 0) return IGDSP_OK;
-    if (int rc = bss_check(ctx, d_info, d_payload, d_codec, d_pcm, d_len, d_gain, d_group_ptr, d_members, n_members, C, G, F, n, d_state, d_words,
-                           d_sel, d_out, d_stats)) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, launch_bss_copy_ab(cfg_of(ctx, pick(ctx, stream)), d_info, d_payload, d_codec, d_pcm, d_len, d_gain, d_group_ptr, d_members,
-                                    n_members, d_mute, C, G, F, n, vote_frames, d_state, d_words, d_sel, d_out, d_stats, pick(ctx, stream)));
-    return IGDSP_OK;
+    return bss_select(ctx, d_info, d_payload, d_codec, d_pcm, d_len, d_gain, d_group_ptr, d_members, n_members, d_mute, C, G, F, n, vote_frames,
+                      d_state, d_words, d_sel, d_out, d_stats, stream, true);
 }
 
 // Calibration-only (not in include/igdsp.h): the compute-free yardstick of igdsp_jb_receive (tools/jb_bench.py) — the rows of an
@@ -1331,14 +1316,8 @@ int igdsp_internal_jb_copy(igdsp_ctx *ctx, const uint8_t *d_packets, const uint1
                            void *d_ring, uint8_t *d_payload_out, uint16_t *d_len_out, igdsp_rtp_info *d_info_out, uint8_t *d_tick_flags,
                            uint8_t *d_pkt_status, void *stream)
 {
-    if (!ctx) return IGDSP_EINVAL;
-    if ((uint64_t)C * T == 0) return IGDSP_OK;
-    if (int rc = jb_check(ctx, d_packets, d_radio, d_sizes, d_arrival, C, T, S, pkt_stride, n, delay_frames, d_state, d_ring, d_payload_out,
-                          d_len_out, d_info_out)) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, launch_jb_copy(cfg_of(ctx, pick(ctx, stream)), d_packets, d_sizes, d_radio, d_arrival, C, T, S, pkt_stride, n, delay_frames,
-                                d_state, d_ring, d_payload_out, d_len_out, d_info_out, d_tick_flags, nullptr, pick(ctx, stream)));
-    return IGDSP_OK;
+    return jb_receive(ctx, d_packets, d_sizes, d_radio, d_arrival, C, T, S, pkt_stride, n, delay_frames, d_state, d_ring, d_payload_out, d_len_out,
+                      d_info_out, d_tick_flags, d_pkt_status, stream, true);
 }
 
 // Calibration-only (not in include/igdsp.h): the compute-free yardstick of igdsp_plc_conceal (tools/plc_bench.py) — the same
@@ -1348,13 +1327,7 @@ int igdsp_internal_plc_copy(igdsp_ctx *ctx, const uint8_t *d_tick_flags, const u
                             const uint16_t *d_len, uint32_t C, uint32_t T, uint32_t n, igdsp_plc_state *d_state, int16_t *d_out,
                             uint16_t *d_len_out, igdsp_frame_stats *d_stats, void *stream)
 {
-    if (!ctx) return IGDSP_EINVAL;
-    if ((uint64_t)C * T == 0) return IGDSP_OK;
-    if (int rc = plc_check(ctx, d_tick_flags, d_payload, d_codec, d_pcm, d_len, C, T, n, d_state, d_out, d_len_out, d_stats)) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, launch_plc_copy(cfg_of(ctx, pick(ctx, stream)), d_tick_flags, d_payload, d_codec, d_pcm, d_len, C, T, n, d_state, d_out,
-                                 d_len_out, d_stats, pick(ctx, stream)));
-    return IGDSP_OK;
+    return plc_conceal(ctx, d_tick_flags, d_payload, d_codec, d_pcm, d_len, C, T, n, d_state, d_out, d_len_out, d_stats, stream, true);
 }
 
 // Calibration-only (not in include/igdsp.h): the packed-packet piece stream in the channel-group-major order of the fused window kernel

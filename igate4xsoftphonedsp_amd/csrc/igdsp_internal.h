@@ -82,43 +82,30 @@ hipError_t launch_tx_packetize(const LaunchCfg &cfg, const int16_t *pcm, const u
 hipError_t launch_tx_staged(const LaunchCfg &cfg, const void *runs, const void *recs, const uint32_t *stream, uint32_t n_runs,
                             igdsp_tx_chan *state, uint8_t *send_buf, igdsp_tx_info *info, igdsp_tx_chan *chan_out, uint32_t *packets,
                             hipStream_t s);
-// igdsp_conf_mix: exactly one of g711 (+ codec) / pcm; out and stats may be nullptr (not both: the C ABI checks)
+// igdsp_conf_mix: exactly one of g711 (+ codec) / pcm; out and stats may be nullptr (not both: the C ABI checks).  yardstick: the
+// compute-free form, the same traversal, the same bytes read and written, no decode / scale / clamp / stats
 hipError_t launch_conf_mix(const LaunchCfg &cfg, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm, const uint16_t *len,
                            const uint16_t *gain, const uint32_t *port_ptr, const uint32_t *members, uint32_t n_members, uint32_t C, uint32_t P,
-                           uint32_t F, uint32_t n, int16_t *out, igdsp_frame_stats *stats, hipStream_t s);
-// compute-free yardstick of launch_conf_mix: the same traversal, the same bytes read and written, no decode / scale / clamp / stats
-hipError_t launch_conf_copy_ab(const LaunchCfg &cfg, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm, const uint16_t *len,
-                               const uint16_t *gain, const uint32_t *port_ptr, const uint32_t *members, uint32_t n_members, uint32_t C, uint32_t P,
-                               uint32_t F, uint32_t n, int16_t *out, igdsp_frame_stats *stats, hipStream_t s);
+                           uint32_t F, uint32_t n, int16_t *out, igdsp_frame_stats *stats, bool yardstick, hipStream_t s);
 // igdsp_bss_select: at most one of g711 (+ codec) / pcm; sel, out, stats may each be nullptr (out and stats need an input: the C ABI
-// checks); gain nullptr = 256
+// checks); gain nullptr = 256.  yardstick: the compute-free form, the same traversal and bytes, no decode / scale / clamp / stats /
+// state machine
 hipError_t launch_bss_select(const LaunchCfg &cfg, const igdsp_rtp_info *info, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm,
                              const uint16_t *len, const uint16_t *gain, const uint32_t *group_ptr, const uint32_t *members, uint32_t n_members,
                              const uint8_t *mute, uint32_t C, uint32_t G, uint32_t F, uint32_t n, uint32_t vote_frames, igdsp_bss_state *state,
-                             uint32_t *words, int32_t *sel, int16_t *out, igdsp_frame_stats *stats, hipStream_t s);
-// compute-free yardstick of launch_bss_select: the same traversal and bytes, no decode / scale / clamp / stats / state machine
-hipError_t launch_bss_copy_ab(const LaunchCfg &cfg, const igdsp_rtp_info *info, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm,
-                              const uint16_t *len, const uint16_t *gain, const uint32_t *group_ptr, const uint32_t *members, uint32_t n_members,
-                              const uint8_t *mute, uint32_t C, uint32_t G, uint32_t F, uint32_t n, uint32_t vote_frames, igdsp_bss_state *state,
-                              uint32_t *words, int32_t *sel, int16_t *out, igdsp_frame_stats *stats, hipStream_t s);
-// igdsp_jb_receive: sizes, arrival, tick, pkt may each be nullptr; ring is igdsp_jb_ring_bytes(C, n) bytes, 16-byte aligned
+                             uint32_t *words, int32_t *sel, int16_t *out, igdsp_frame_stats *stats, bool yardstick, hipStream_t s);
+// igdsp_jb_receive: sizes, arrival, tick, pkt may each be nullptr; ring is igdsp_jb_ring_bytes(C, n) bytes, 16-byte aligned.
+// yardstick: the compute-free form, the same rows as an in-order lossless launch (arrival slot k = 0 of every tick played straight from
+// the packet), no header walk, state machine or ring store; the state is not touched
 hipError_t launch_jb_receive(const LaunchCfg &cfg, const uint8_t *packets, const uint16_t *sizes, const uint8_t *radio, const uint32_t *arrival,
                              uint32_t C, uint32_t T, uint32_t S, uint32_t stride, uint32_t n, uint32_t delay, igdsp_jb_state *state, void *ring,
-                             uint8_t *payload, uint16_t *len, igdsp_rtp_info *info, uint8_t *tick, uint8_t *pkt, hipStream_t s);
-// compute-free yardstick of launch_jb_receive: the same rows as an in-order lossless launch (arrival slot k = 0 of every tick played
-// straight from the packet), no header walk, state machine or ring store; the state is not touched
-hipError_t launch_jb_copy(const LaunchCfg &cfg, const uint8_t *packets, const uint16_t *sizes, const uint8_t *radio, const uint32_t *arrival,
-                          uint32_t C, uint32_t T, uint32_t S, uint32_t stride, uint32_t n, uint32_t delay, igdsp_jb_state *state, void *ring,
-                          uint8_t *payload, uint16_t *len, igdsp_rtp_info *info, uint8_t *tick, uint8_t *pkt, hipStream_t s);
-// igdsp_plc_conceal: exactly one of g711 (+ codec) / pcm; len, len_out, stats may each be nullptr
+                             uint8_t *payload, uint16_t *len, igdsp_rtp_info *info, uint8_t *tick, uint8_t *pkt, bool yardstick, hipStream_t s);
+// igdsp_plc_conceal: exactly one of g711 (+ codec) / pcm; len, len_out, stats may each be nullptr.  yardstick: the compute-free form,
+// the same traversal with every tick taken as PLAIN, the input bits widened to the output, no decode, pitch search, synthesis or stats
+// (records carry only the length); the ring and the scalars are written as by a launch
 hipError_t launch_plc_conceal(const LaunchCfg &cfg, const uint8_t *flags, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm,
                               const uint16_t *len, uint32_t C, uint32_t T, uint32_t n, igdsp_plc_state *state, int16_t *out, uint16_t *len_out,
-                              igdsp_frame_stats *stats, hipStream_t s);
-// compute-free yardstick of launch_plc_conceal: the same traversal with every tick taken as PLAIN, the input bits widened to the output,
-// no decode, pitch search, synthesis or stats (records carry only the length); the ring and the scalars are written as by a launch
-hipError_t launch_plc_copy(const LaunchCfg &cfg, const uint8_t *flags, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm,
-                           const uint16_t *len, uint32_t C, uint32_t T, uint32_t n, igdsp_plc_state *state, int16_t *out, uint16_t *len_out,
-                           igdsp_frame_stats *stats, hipStream_t s);
+                              igdsp_frame_stats *stats, bool yardstick, hipStream_t s);
 hipError_t launch_wav_expand(const LaunchCfg &cfg, const uint8_t *payload, uint32_t C, uint32_t F, uint32_t n, uint32_t rate,
                              uint8_t *files, uint64_t file_stride, hipStream_t s);
 hipError_t launch_g726(const LaunchCfg &cfg, const uint8_t *in, uint8_t *out, uint64_t n_bytes, int mode, hipStream_t s);

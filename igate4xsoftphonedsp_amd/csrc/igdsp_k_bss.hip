@@ -275,11 +275,10 @@ __global__ __launch_bounds__(kBssWordsThreads) void k_bss_words(const igdsp_rtp_
     }
 }
 
-template <bool COPY>
-static hipError_t launch_bss(const igdsp_rtp_info *info, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm, const uint16_t *len,
-                             const uint16_t *gain, const uint32_t *group_ptr, const uint32_t *members, uint32_t n_members, const uint8_t *mute,
-                             uint32_t C, uint32_t G, uint32_t F, uint32_t n, uint32_t vote_frames, igdsp_bss_state *state, uint32_t *words,
-                             int32_t *sel, int16_t *out, igdsp_frame_stats *stats, hipStream_t s)
+hipError_t launch_bss_select(const LaunchCfg &, const igdsp_rtp_info *info, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm,
+                             const uint16_t *len, const uint16_t *gain, const uint32_t *group_ptr, const uint32_t *members, uint32_t n_members,
+                             const uint8_t *mute, uint32_t C, uint32_t G, uint32_t F, uint32_t n, uint32_t vote_frames, igdsp_bss_state *state,
+                             uint32_t *words, int32_t *sel, int16_t *out, igdsp_frame_stats *stats, bool yardstick, hipStream_t s)
 {
     const int form = g711 ? kConfG711 : (pcm ? kConfPcm : kBssNone);
     const BssRoute r = bss_route(G, F, n, n_members, form, reinterpret_cast<uintptr_t>(pcm ? (const void *)pcm : (const void *)g711),
@@ -290,9 +289,8 @@ static hipError_t launch_bss(const igdsp_rtp_info *info, const uint8_t *g711, co
     for (uint32_t p = 0; p < r.parts; ++p) {
         a.f0 = p * kBssPart;
         a.pf = std::min(kBssPart, F - a.f0);
-        if (r.form == kConfG711)     hipLaunchKernelGGL((k_bss_select<kConfG711, COPY>), dim3(r.grid), dim3(r.threads), 0, s, a);
-        else if (r.form == kConfPcm) hipLaunchKernelGGL((k_bss_select<kConfPcm, COPY>), dim3(r.grid), dim3(r.threads), 0, s, a);
-        else                         hipLaunchKernelGGL((k_bss_select<kBssNone, COPY>), dim3(r.grid), dim3(r.threads), 0, s, a);
+        with_key(Keys<kConfG711, kConfPcm, kBssNone>{}, r.form, [&](auto IN) { with_bool(yardstick, [&](auto Y) {
+            hipLaunchKernelGGL((k_bss_select<IN, Y>), dim3(r.grid), dim3(r.threads), 0, s, a); }); });
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
         if (r.words_grid) {
             hipLaunchKernelGGL(k_bss_words, dim3(r.words_grid), dim3(kBssWordsThreads), 0, s, info, members, n_members, C, a.f0, a.pf, words);
@@ -300,24 +298,6 @@ static hipError_t launch_bss(const igdsp_rtp_info *info, const uint8_t *g711, co
         }
     }
     return hipSuccess;
-}
-
-hipError_t launch_bss_select(const LaunchCfg &, const igdsp_rtp_info *info, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm,
-                             const uint16_t *len, const uint16_t *gain, const uint32_t *group_ptr, const uint32_t *members, uint32_t n_members,
-                             const uint8_t *mute, uint32_t C, uint32_t G, uint32_t F, uint32_t n, uint32_t vote_frames, igdsp_bss_state *state,
-                             uint32_t *words, int32_t *sel, int16_t *out, igdsp_frame_stats *stats, hipStream_t s)
-{
-    return launch_bss<false>(info, g711, codec, pcm, len, gain, group_ptr, members, n_members, mute, C, G, F, n, vote_frames, state, words, sel,
-                             out, stats, s);
-}
-
-hipError_t launch_bss_copy_ab(const LaunchCfg &, const igdsp_rtp_info *info, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm,
-                              const uint16_t *len, const uint16_t *gain, const uint32_t *group_ptr, const uint32_t *members, uint32_t n_members,
-                              const uint8_t *mute, uint32_t C, uint32_t G, uint32_t F, uint32_t n, uint32_t vote_frames, igdsp_bss_state *state,
-                              uint32_t *words, int32_t *sel, int16_t *out, igdsp_frame_stats *stats, hipStream_t s)
-{
-    return launch_bss<true>(info, g711, codec, pcm, len, gain, group_ptr, members, n_members, mute, C, G, F, n, vote_frames, state, words, sel,
-                            out, stats, s);
 }
 
 }  // namespace igdsp

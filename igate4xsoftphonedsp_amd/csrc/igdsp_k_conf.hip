@@ -238,27 +238,14 @@ static ConfArgs conf_args(const uint8_t *g711, const uint8_t *codec, const int16
 
 hipError_t launch_conf_mix(const LaunchCfg &cfg, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm, const uint16_t *len,
                            const uint16_t *gain, const uint32_t *port_ptr, const uint32_t *members, uint32_t n_members, uint32_t C, uint32_t P,
-                           uint32_t F, uint32_t n, int16_t *out, igdsp_frame_stats *stats, hipStream_t s)
+                           uint32_t F, uint32_t n, int16_t *out, igdsp_frame_stats *stats, bool yardstick, hipStream_t s)
 {
     const ConfRoute r = conf_route(P, F, n, pcm != nullptr, reinterpret_cast<uintptr_t>(pcm ? (const void *)pcm : (const void *)g711),
                                    reinterpret_cast<uintptr_t>(out), (uint32_t)cfg.compute_units);
     if (r.grid == 0) return hipSuccess;
     const ConfArgs a = conf_args(g711, codec, pcm, len, gain, port_ptr, members, n_members, C, P, F, n, out, stats, r);
-    if (r.form == kConfPcm) hipLaunchKernelGGL((k_conf_mix<kConfPcm, false>), dim3(r.grid), dim3(r.threads), 0, s, a);
-    else                    hipLaunchKernelGGL((k_conf_mix<kConfG711, false>), dim3(r.grid), dim3(r.threads), 0, s, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_conf_copy_ab(const LaunchCfg &cfg, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm, const uint16_t *len,
-                               const uint16_t *gain, const uint32_t *port_ptr, const uint32_t *members, uint32_t n_members, uint32_t C, uint32_t P,
-                               uint32_t F, uint32_t n, int16_t *out, igdsp_frame_stats *stats, hipStream_t s)
-{
-    const ConfRoute r = conf_route(P, F, n, pcm != nullptr, reinterpret_cast<uintptr_t>(pcm ? (const void *)pcm : (const void *)g711),
-                                   reinterpret_cast<uintptr_t>(out), (uint32_t)cfg.compute_units);
-    if (r.grid == 0) return hipSuccess;
-    const ConfArgs a = conf_args(g711, codec, pcm, len, gain, port_ptr, members, n_members, C, P, F, n, out, stats, r);
-    if (r.form == kConfPcm) hipLaunchKernelGGL((k_conf_mix<kConfPcm, true>), dim3(r.grid), dim3(r.threads), 0, s, a);
-    else                    hipLaunchKernelGGL((k_conf_mix<kConfG711, true>), dim3(r.grid), dim3(r.threads), 0, s, a);
+    with_key(Keys<kConfG711, kConfPcm>{}, r.form, [&](auto IN) { with_bool(yardstick, [&](auto Y) {
+        hipLaunchKernelGGL((k_conf_mix<IN, Y>), dim3(r.grid), dim3(r.threads), 0, s, a); }); });
     return hipGetLastError();
 }
 

@@ -365,36 +365,22 @@ __global__ __launch_bounds__(kJbWaves * 64) void k_jb_receive(const JbArgs a)
     }
 }
 
-template <bool COPY>
-static hipError_t launch_jb(const uint8_t *packets, const uint16_t *sizes, const uint8_t *radio, const uint32_t *arrival, uint32_t C, uint32_t T,
-                            uint32_t S, uint32_t stride, uint32_t n, uint32_t delay, igdsp_jb_state *state, void *ring, uint8_t *payload,
-                            uint16_t *len, igdsp_rtp_info *info, uint8_t *tick, uint8_t *pkt, hipStream_t s)
+hipError_t launch_jb_receive(const LaunchCfg &, const uint8_t *packets, const uint16_t *sizes, const uint8_t *radio, const uint32_t *arrival,
+                             uint32_t C, uint32_t T, uint32_t S, uint32_t stride, uint32_t n, uint32_t delay, igdsp_jb_state *state, void *ring,
+                             uint8_t *payload, uint16_t *len, igdsp_rtp_info *info, uint8_t *tick, uint8_t *pkt, bool yardstick, hipStream_t s)
 {
     const JbRoute r = jb_route(C, T, n, reinterpret_cast<uintptr_t>(payload));
     if (r.grid == 0) return hipSuccess;
     JbArgs a{packets, sizes, radio, arrival, C, S, stride, n, delay, r.pieces, r.vec, 0u, 0u, state, static_cast<uint8_t *>(ring), payload,
              len, info, tick, pkt, jb_slot_bytes(n)};
+    const auto kernel = yardstick ? k_jb_receive<true> : k_jb_receive<false>;
     for (uint32_t p = 0; p < r.parts; ++p) {
         a.t0 = p * kJbPart;
         a.pt = std::min(kJbPart, T - a.t0);
-        hipLaunchKernelGGL((k_jb_receive<COPY>), dim3(r.grid), dim3(r.threads), 0, s, a);
+        hipLaunchKernelGGL(kernel, dim3(r.grid), dim3(r.threads), 0, s, a);
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     }
     return hipSuccess;
-}
-
-hipError_t launch_jb_receive(const LaunchCfg &, const uint8_t *packets, const uint16_t *sizes, const uint8_t *radio, const uint32_t *arrival,
-                             uint32_t C, uint32_t T, uint32_t S, uint32_t stride, uint32_t n, uint32_t delay, igdsp_jb_state *state, void *ring,
-                             uint8_t *payload, uint16_t *len, igdsp_rtp_info *info, uint8_t *tick, uint8_t *pkt, hipStream_t s)
-{
-    return launch_jb<false>(packets, sizes, radio, arrival, C, T, S, stride, n, delay, state, ring, payload, len, info, tick, pkt, s);
-}
-
-hipError_t launch_jb_copy(const LaunchCfg &, const uint8_t *packets, const uint16_t *sizes, const uint8_t *radio, const uint32_t *arrival,
-                          uint32_t C, uint32_t T, uint32_t S, uint32_t stride, uint32_t n, uint32_t delay, igdsp_jb_state *state, void *ring,
-                          uint8_t *payload, uint16_t *len, igdsp_rtp_info *info, uint8_t *tick, uint8_t *pkt, hipStream_t s)
-{
-    return launch_jb<true>(packets, sizes, radio, arrival, C, T, S, stride, n, delay, state, ring, payload, len, info, tick, pkt, s);
 }
 
 }  // namespace igdsp

@@ -379,35 +379,22 @@ __global__ __launch_bounds__(kPlcWaves * 64) void k_plc(const PlcArgs a)
     }
 }
 
-template <bool COPY>
-static hipError_t launch_plc(const uint8_t *flags, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm, const uint16_t *len, uint32_t C,
-                             uint32_t T, uint32_t n, igdsp_plc_state *state, int16_t *out, uint16_t *len_out, igdsp_frame_stats *stats, hipStream_t s)
+hipError_t launch_plc_conceal(const LaunchCfg &, const uint8_t *flags, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm,
+                              const uint16_t *len, uint32_t C, uint32_t T, uint32_t n, igdsp_plc_state *state, int16_t *out, uint16_t *len_out,
+                              igdsp_frame_stats *stats, bool yardstick, hipStream_t s)
 {
     const PlcRoute r = plc_route(C, T, n, pcm != nullptr, reinterpret_cast<uintptr_t>(pcm ? (const void *)pcm : (const void *)g711),
                                  reinterpret_cast<uintptr_t>(out));
     if (r.grid == 0) return hipSuccess;
     PlcArgs a{flags, g711, codec, pcm, len, C, n, r.pieces, r.batch_rows, r.vec, 0u, 0u, state, out, len_out, stats};
+    const auto kernel = yardstick ? k_plc<true> : k_plc<false>;
     for (uint32_t p = 0; p < r.parts; ++p) {
         a.t0 = p * kPlcPart;
         a.pt = std::min(kPlcPart, T - a.t0);
-        hipLaunchKernelGGL((k_plc<COPY>), dim3(r.grid), dim3(r.threads), 0, s, a);
+        hipLaunchKernelGGL(kernel, dim3(r.grid), dim3(r.threads), 0, s, a);
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     }
     return hipSuccess;
-}
-
-hipError_t launch_plc_conceal(const LaunchCfg &, const uint8_t *flags, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm,
-                              const uint16_t *len, uint32_t C, uint32_t T, uint32_t n, igdsp_plc_state *state, int16_t *out, uint16_t *len_out,
-                              igdsp_frame_stats *stats, hipStream_t s)
-{
-    return launch_plc<false>(flags, g711, codec, pcm, len, C, T, n, state, out, len_out, stats, s);
-}
-
-hipError_t launch_plc_copy(const LaunchCfg &, const uint8_t *flags, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm,
-                           const uint16_t *len, uint32_t C, uint32_t T, uint32_t n, igdsp_plc_state *state, int16_t *out, uint16_t *len_out,
-                           igdsp_frame_stats *stats, hipStream_t s)
-{
-    return launch_plc<true>(flags, g711, codec, pcm, len, C, T, n, state, out, len_out, stats, s);
 }
 
 }  // namespace igdsp

@@ -412,7 +412,7 @@ inline TxRoute tx_route(uint32_t C, uint32_t F, uint32_t n, uintptr_t pcm, uintp
     return r;
 }
 
-// ---- igdsp_conf_mix (launch_conf_mix, launch_conf_copy_ab): k_conf_mix<IN, COPY>.  An item is one (frame, port); a block of kConfWaves
+// ---- igdsp_conf_mix (launch_conf_mix): k_conf_mix<IN, COPY>.  An item is one (frame, port); a block of kConfWaves
 // waves takes groups of kConfWaves consecutive items.  Which ports are narrow (a wave mixes the port-frame alone) and which are wide
 // (the block splits the member list among its waves) is decided per item on the device from the CSR, so a launch with a skewed
 // table needs no copy of it to the host; the route only picks the input form, the vector paths and the grid.
@@ -438,7 +438,7 @@ inline ConfRoute conf_route(uint32_t P, uint32_t F, uint32_t n, bool pcm, uintpt
     return r;
 }
 
-// ---- igdsp_bss_select (launch_bss_select, launch_bss_copy_ab): k_bss_select<IN, COPY> + k_bss_words.  A wave owns gpw consecutive
+// ---- igdsp_bss_select (launch_bss_select): k_bss_select<IN, COPY> + k_bss_words.  A wave owns gpw consecutive
 // groups for the frames of a part: its lanes gather the members' info records (one member slot per lane, a 64-slot chunk at a time)
 // and fold each frame's open members into a vote key per group in LDS; lanes 0 .. gpw-1 then step the groups' state machines over
 // the part's frames, and the whole wave emits the voted frames.  gpw is chosen so that a wave's groups fill about one chunk of 64
@@ -478,7 +478,7 @@ inline BssRoute bss_route(uint32_t G, uint32_t F, uint32_t n, uint32_t n_members
     return r;
 }
 
-// ---- igdsp_jb_receive (launch_jb_receive, launch_jb_copy): k_jb_receive<COPY>.  A wave owns kJbCh consecutive channels for the ticks
+// ---- igdsp_jb_receive (launch_jb_receive): k_jb_receive<COPY>.  A wave owns kJbCh consecutive channels for the ticks
 // of one part (<= kJbPart ticks).  Lanes 0 .. kJbCh - 1 step their channel's state machine over the part's arrivals with the ring tags in
 // LDS and leave a source descriptor per (tick, channel) there: an arrival of the part, a ring slot, or none; then the whole wave writes
 // the records and copies the payload rows in 16-byte pieces, and stores the packets still unplayed at the part's end into the ring.  A
@@ -513,7 +513,7 @@ inline JbRoute jb_route(uint32_t C, uint32_t T, uint32_t n, uintptr_t payload_ou
     return r;
 }
 
-// ---- igdsp_plc_conceal (launch_plc_conceal, launch_plc_copy): k_plc<COPY>.  A wave owns kPlcCh consecutive channels for the ticks of
+// ---- igdsp_plc_conceal (launch_plc_conceal): k_plc<COPY>.  A wave owns kPlcCh consecutive channels for the ticks of
 // one part (<= kPlcPart ticks).  Lanes 0 .. kPlcCh - 1 walk their channel's tick flags (no samples: which ticks are plain, which start
 // or continue a run, which recover) and leave a kind and a length per (tick, channel) in LDS; the whole wave then decodes and stores
 // the plain and IDLE rows, kPlcPiece samples per lane and piece, kPlcU pieces of a lane in flight, in batches of whole rows (the

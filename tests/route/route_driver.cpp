@@ -1,4 +1,4 @@
-// Prints the routes of igdsp_route.h for tests/test_route_cpu.py.  One case per stdin line: an entry name, then key=value pairs
+// Prints the routes of igdsp_route.h for the route tests (through tests/route_util.py).  One case per stdin line: an entry name, then key=value pairs
 // (numbers in any base strtoull reads; IGDSP_* keys are set in the environment and read back through knobs_from_env, the rest
 // are the route function's arguments).  One output line per case: the route's fields as key=value.  "consts" prints the
 // compile-time geometry the tests derive work per wave from.
@@ -77,6 +77,18 @@ int main()
             const TxRoute r = tx_route(C, F, n, pcm, g711, g("last", 0x1000), cus, g("tab_lds", 1) != 0);
             std::printf("form=%s vec=%u n_groups=%u grid=%u threads=%u lds=%u table=%d\n", tx_name(r.form), r.vec, r.n_groups, r.grid, r.threads, r.lds,
                         tx_wants_table(pcm != 0, C, F, n));
+        } else if (entry == "bss") {   // form 0 G.711 / 1 PCM / 2 none; in, out: buffer addresses, alignment only
+            const BssRoute r = bss_route((uint32_t)g("G"), F, n, (uint32_t)g("members"), (int)g("form"), g("in", 0x1000), g("out", 0x1000));
+            std::printf("form=%d gpw=%u vec_in=%u vec_out=%u grid=%u threads=%u part_frames=%u parts=%u words_grid=%u\n", r.form, r.gpw, r.vec_in,
+                        r.vec_out, r.grid, r.threads, r.part_frames, r.parts, r.words_grid);
+        } else if (entry == "jb") {    // out: the payload output's address, alignment only
+            const JbRoute r = jb_route(C, (uint32_t)g("T"), n, g("out", 0x1000));
+            std::printf("vec=%u pieces=%u grid=%u threads=%u part_ticks=%u parts=%u ring=%llu\n", r.vec, r.pieces, r.grid, r.threads, r.part_ticks,
+                        r.parts, (unsigned long long)jb_ring_bytes(C, n));
+        } else if (entry == "plc") {   // pcm: 1 for the PCM input; in / out: the input's and the output's addresses, alignment only
+            const PlcRoute r = plc_route(C, (uint32_t)g("T"), n, g("pcm") != 0, g("in", 0x1000), g("out", 0x1000));
+            std::printf("vec=%u pieces=%u batch_rows=%u grid=%u threads=%u part_ticks=%u parts=%u\n", r.vec, r.pieces, r.batch_rows, r.grid,
+                        r.threads, r.part_ticks, r.parts);
         } else if (entry == "consts") {
             std::printf("tiny_slot=%u super_frames=%d\n", kTinySlot, kSuperFrames);
         } else {

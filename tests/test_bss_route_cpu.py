@@ -1,14 +1,11 @@
-"""-m "not gpu": the routes of igdsp_bss_select (bss_route in csrc/igdsp_route.h), compiled with g++ through
-tests/route/bss_route_driver.cpp: form, groups per wave, grid, block size and the split into parts of kBssPart = 128 frames, at the
-issue's shapes.  The GPU tests check outputs, not which geometry produced them; this table pins the geometry."""
-import os
+"""-m "not gpu": the routes of igdsp_bss_select (bss_route in csrc/igdsp_route.h), compiled with g++ through tests/route/route_driver.cpp
+(entry "bss"): form, groups per wave, grid, block size and the split into parts of kBssPart = 128 frames, at the issue's shapes.  The
+GPU tests check outputs, not which geometry produced them; this table pins the geometry."""
 import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "igate4xsoftphonedsp_amd", "csrc")
+from tests import route_util
 
 CASES = [
     # 65 536 channels in 16 384 groups of 4 x 128 frames: 16 groups (64 member slots) per wave, 4 waves per block, one part
@@ -37,15 +34,8 @@ CASES = [
 
 
 @pytest.fixture(scope="module")
-def routes(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("bss_route") / "bss_route_driver"
-    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
-                    os.path.join(ROOT, "tests", "route", "bss_route_driver.cpp"), "-o", str(exe)], check=True, capture_output=True, timeout=300)
-    r = subprocess.run([str(exe)], input="\n".join(case for case, _ in CASES) + "\n", capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0, r.stdout + r.stderr
-    lines = r.stdout.splitlines()
-    assert len(lines) == len(CASES)
-    return {case: dict(kv.split("=") for kv in line.split()) for (case, _), line in zip(CASES, lines)}
+def routes():
+    return dict(zip((case for case, _ in CASES), route_util.run(["bss " + case for case, _ in CASES])))
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")

@@ -1,14 +1,11 @@
-"""-m "not gpu": the routes of igdsp_jb_receive (jb_route in csrc/igdsp_route.h), compiled with g++ through tests/route/jb_route_driver.cpp:
-16 channels per wave and 4 waves per block, the split into parts of kJbPart = 128 ticks, the 16-byte store path and the ring size, at the
-issue's shapes.  The GPU tests check outputs, not which geometry produced them; this table pins the geometry."""
-import os
+"""-m "not gpu": the routes of igdsp_jb_receive (jb_route in csrc/igdsp_route.h), compiled with g++ through tests/route/route_driver.cpp
+(entry "jb"): 16 channels per wave and 4 waves per block, the split into parts of kJbPart = 128 ticks, the 16-byte store path and the
+ring size, at the issue's shapes.  The GPU tests check outputs, not which geometry produced them; this table pins the geometry."""
 import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "igate4xsoftphonedsp_amd", "csrc")
+from tests import route_util
 
 CASES = [
     # J1 / J2: 65 536 channels x 128 ticks: 4 096 waves in 1 024 blocks, one part; ring 16 x (4 + 16 + 160) bytes per channel
@@ -33,15 +30,8 @@ CASES = [
 
 
 @pytest.fixture(scope="module")
-def routes(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("jb_route") / "jb_route_driver"
-    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
-                    os.path.join(ROOT, "tests", "route", "jb_route_driver.cpp"), "-o", str(exe)], check=True, capture_output=True, timeout=300)
-    r = subprocess.run([str(exe)], input="\n".join(case for case, _ in CASES) + "\n", capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0, r.stdout + r.stderr
-    lines = r.stdout.splitlines()
-    assert len(lines) == len(CASES)
-    return {case: dict(kv.split("=") for kv in line.split()) for (case, _), line in zip(CASES, lines)}
+def routes():
+    return dict(zip((case for case, _ in CASES), route_util.run(["jb " + case for case, _ in CASES])))
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")

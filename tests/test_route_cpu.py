@@ -3,14 +3,11 @@ g++ through tests/route/route_driver.cpp.  The parity tests check outputs, not w
 routing itself (kernel form, instantiation key, grid, block size, dynamic LDS, the split between the fast and the general
 kernel), so a retune or a refactor shows here what it changed.  Unset fields of a case are not checked; "key" is the strided
 kernels' qt_key(Q, TAIL) = 2 Q + TAIL (tiny: n / 4).  IGDSP_* entries are set in the environment of the route driver."""
-import os
 import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "igate4xsoftphonedsp_amd", "csrc")
+from tests import route_util
 
 # (case, expected fields).  Addresses default to 0x1000 (every alignment); pcm / g711 absent unless given.
 CASES = [
@@ -80,16 +77,8 @@ CASES = [
 
 
 @pytest.fixture(scope="module")
-def routes(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("route") / "route_driver"
-    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
-                    os.path.join(ROOT, "tests", "route", "route_driver.cpp"), "-o", str(exe)], check=True, capture_output=True, timeout=300)
-    r = subprocess.run([str(exe)], input="\n".join(case for case, _ in CASES) + "\n", capture_output=True, text=True, timeout=60,
-                       env={k: v for k, v in os.environ.items() if not k.startswith("IGDSP_")})
-    assert r.returncode == 0, r.stdout + r.stderr
-    lines = r.stdout.splitlines()
-    assert len(lines) == len(CASES)
-    return {case: dict(kv.split("=") for kv in line.split()) for (case, _), line in zip(CASES, lines)}
+def routes():
+    return dict(zip((case for case, _ in CASES), route_util.run([case for case, _ in CASES])))
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")

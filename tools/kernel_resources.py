@@ -3,7 +3,6 @@
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ASM_DIR = os.path.join(ROOT, "igate4xsoftphonedsp_amd", "_asm")
-ASM = os.path.join(ASM_DIR, "igdsp_k_meter-hip-amdgcn-amd-amdhsa-gfx950.s")      # one of the translation units: staleness check
 
 
 def asm_files():
@@ -16,6 +15,20 @@ def resources(paths=None):
     for path in (paths or asm_files()):
         out += _resources_of(path)
     return out
+
+
+def fresh_resources():
+    """resources() of a current _asm/: build(save_asm=True) first when an igdsp_k_* translation unit has no .s there, or when a device
+    source, a header (include/igdsp.h among them) or build.py is newer than the oldest of those .s files."""
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    from igate4xsoftphonedsp_amd import build as b
+
+    asm = [os.path.join(ASM_DIR, os.path.splitext(s)[0] + "-hip-amdgcn-amd-amdhsa-gfx950.s") for s in b.DEVICE_SOURCES if s.startswith("igdsp_k_")]
+    deps = [os.path.join(b.CSRC, s) for s in b.DEVICE_SOURCES + b.HEADERS] + [os.path.abspath(b.__file__)]
+    if not all(map(os.path.exists, asm)) or max(map(os.path.getmtime, deps)) > min(map(os.path.getmtime, asm)):
+        b.build(save_asm=True)
+    return resources()
 
 
 def _resources_of(path):
