@@ -1,6 +1,7 @@
 // igdsp_device.h — device-side building blocks shared by the kernel translation units (igdsp_k_*.hip): G.711 expansion
 // formulas, streaming load / store helpers (global and buffer form), the launch-aggregate commit, record packing, the
-// 32-replica expansion LUT, probe helpers, the persistent-block work queue.  Header-only, namespace igdsp.
+// 32-replica expansion LUT, probe helpers, the persistent-block work queue, the block-owned form's LDS window and
+// item queue.  Header-only, namespace igdsp.
 //
 // Reference semantics the kernels reproduce (all citations /root/reference):
 //   G.711 expansion / compression : performed by pjmedia around adapter->stream_rtp_cb (TransportAdapter.cpp:301) / before
@@ -482,6 +483,118 @@ __device__ __forceinline__ void bq_finish(uint32_t *gq, uint32_t G)             
     if (threadIdx.x == 0 && atomicAdd(gq + 1, 1u) == G - 1u) { gq[0] = 0u; gq[1] = 0u; }
 }
 
+// The block-owned form (k_roundtrip_blk64, k_roundtrip_strided<BLK>; k_meter_rtp64<WIN == 2>): block b owns the gpb = 1 << gsh
+// consecutive channel groups of 64 from b * gpb (at most kBlkCh channels: groups_per_block, igdsp_route.h) for the whole launch and
+// hands their F * gpb items — one frame of one group — to its waves one at a time.
+template <typename T> __device__ __forceinline__ void lds_add(T *p, T v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+__device__ __forceinline__ void lds_max(uint32_t *p, uint32_t v) { __hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+__device__ __forceinline__ void lds_min(uint32_t *p, uint32_t v) { __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+__device__ __forceinline__ uint32_t wave_draw(uint32_t *counter, uint32_t lane)      // the next number of an LDS counter, wave-uniform
+{
+    uint32_t v = 0;
+    if (lane == 0) v = atomicAdd(counter, 1u);
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+}
+
+// The hold windows of the channels a block owns, in LDS: 7 dwords per channel, channel cl = (group within the block) * 64 + lane.
+// Every wave adds the frames it folds by workgroup-scope relaxed integer atomics (add / max / min: exact in any order); when all
+// items are through (a barrier), the wave that holds hold[c] of a group folds the group's windows into it — the block owns the
+// channel for the launch: plain read-modify-write.  The round trips fold every frame of the launch (add / fold).  The packet kernel
+// folds the frames its gate lets through and counts them and their samples in the two count planes (add_packet / fold_packets):
+// 8-bit frame, silent and clipped counts, 16-bit byte-mean sum and samples — at most 255 frames per launch (the launcher splits).
+template <bool ON = true>
+struct BlkHoldWindowT {
+    uint64_t sumsq[kBlkCh];                 // sum of squares << 4.  First member: the 64-bit LDS atomic needs the 8-byte alignment of its type
+    uint32_t level_sum[kBlkCh];             // byte-mean sum (packets: | samples << 16)
+    uint32_t peak[kBlkCh], level_max[kBlkCh], level_min[kBlkCh];
+    uint32_t counts[kBlkCh];                // silent | clipped << 16 (packets: frames | silent << 8 | clipped << 16)
+
+    __device__ __forceinline__ void init(uint32_t tid, uint32_t nthreads)       // all threads, before a barrier
+    {   // (two loops: as one, k_roundtrip_strided<5, false, *, BLK> takes two more SGPRs)
+        for (uint32_t i = tid; i < (uint32_t)kBlkCh; i += nthreads) { sumsq[i] = 0; level_sum[i] = 0u; counts[i] = 0u; }           // the sums
+        for (uint32_t i = tid; i < (uint32_t)kBlkCh; i += nthreads) { peak[i] = 0u; level_max[i] = 0u; level_min[i] = 255u; }       // the extremes
+    }
+    __device__ __forceinline__ void add(uint32_t cl, uint64_t sumsq16, uint32_t pk, uint32_t bm, uint32_t fl)
+    {
+        lds_add(&sumsq[cl], sumsq16); lds_add(&level_sum[cl], bm);
+        lds_max(&peak[cl], pk); lds_max(&level_max[cl], bm); lds_min(&level_min[cl], bm);
+        const uint32_t sc = ((fl & IGDSP_FLAG_SILENT) ? 1u : 0u) + ((fl & IGDSP_FLAG_CLIPPED) ? 0x10000u : 0u);
+        if (sc != 0u) lds_add(&counts[cl], sc);
+    }
+    __device__ __forceinline__ void add_packet(uint32_t cl, uint64_t sumsq16, uint32_t pk, uint32_t bm, uint32_t fl, uint32_t samples)
+    {
+        lds_add(&sumsq[cl], sumsq16);
+        lds_add(&counts[cl], 1u | ((fl & IGDSP_FLAG_SILENT) ? 0x100u : 0u) | ((fl & IGDSP_FLAG_CLIPPED) ? 0x10000u : 0u));
+        lds_add(&level_sum[cl], bm | (samples << 16));
+        lds_max(&peak[cl], pk); lds_max(&level_max[cl], bm); lds_min(&level_min[cl], bm);
+    }
+    __device__ __forceinline__ void fold(uint32_t t, uint32_t frames, uint32_t samples, igdsp_chan_hold &g) const
+    {
+        fold_levels(t, g);
+        g.count += frames; g.level_sum += level_sum[t]; g.samples += samples;
+        g.n_silent += counts[t] & 0xFFFFu; g.n_clipped += counts[t] >> 16;
+    }
+    __device__ __forceinline__ bool fold_packets(uint32_t t, igdsp_chan_hold &g) const      // false (g untouched): no frame was folded
+    {
+        const uint32_t wa = counts[t], wb = level_sum[t];
+        if ((wa & 0xFFu) == 0u) return false;
+        fold_levels(t, g);
+        g.count += wa & 0xFFu; g.level_sum += wb & 0xFFFFu; g.samples += wb >> 16;
+        g.n_silent += (wa >> 8) & 0xFFu; g.n_clipped += (wa >> 16) & 0xFFu;
+        return true;
+    }
+    __device__ __forceinline__ void fold_levels(uint32_t t, igdsp_chan_hold &g) const
+    {
+        g.sumsq_acc += sumsq[t];
+        g.peak_hold = (uint16_t)max((uint32_t)g.peak_hold, peak[t]);
+        g.level_max = (uint8_t)max((uint32_t)g.level_max, level_max[t]);
+        g.level_min = (uint8_t)min((uint32_t)g.level_min, level_min[t]);
+    }
+};
+template <> struct BlkHoldWindowT<false> {}; // a kernel template's instantiations without the block-owned form reserve no LDS for it
+using BlkHoldWindow = BlkHoldWindowT<true>;
+static_assert(sizeof(BlkHoldWindow) == 7 * 4 * kBlkCh && alignof(BlkHoldWindow) == 8, "7 dwords of LDS per channel, the 64-bit plane aligned");
+
+// The item queue of the block-owned round trips.  Item id of the block (ids come in (frame, group) order from an LDS counter) is a
+// frame of group b_first + (id & (gpb - 1)): frame id >> gsh, or, in the odd blocks of a launch whose output is spread over two
+// memory classes (mid_start), that frame counted from the middle of the launch — at any moment half the chip then writes the first
+// half of the output and half the second.  A global load at the block's end waits ~5 us behind the other blocks' streams, so the
+// first gpb waves to start their last item (or to find they have none) fetch hold[c] of one group each, a whole item ahead, and fold it.
+struct BlkQueueLds { uint32_t next, ticket; };       // in LDS, zero before the first grab: items handed out, waves that have started their last item
+constexpr uint32_t kNoItem = 0xFFFFFFFFu;
+
+struct BlkItemQueue {
+    BlkQueueLds &q;
+    const uint32_t lane, gpb, gsh, F, b_first, b_items, f_shift;       // (all but lane wave-uniform)
+    igdsp_chan_hold e_hold = igdsp_chan_hold{};                        // hold[c] of group b_first + e_ticket, if its gate is open
+    uint32_t e_ticket = kNoItem;                                       // (kNoItem: not drawn yet)
+    bool e_open = false;
+    __device__ __forceinline__ BlkItemQueue(BlkQueueLds &q_, uint32_t lane_, uint32_t gpb_, uint32_t gsh_, uint32_t F_, bool mid_start)
+        : q(q_), lane(lane_), gpb(gpb_), gsh(gsh_), F(F_), b_first(blockIdx.x * gpb_), b_items(F_ * gpb_), f_shift((mid_start && (blockIdx.x & 1u)) ? F_ / 2u : 0u) {}
+    __device__ __forceinline__ uint32_t grab() { const uint32_t v = wave_draw(&q.next, lane); return v < b_items ? v : kNoItem; }   // block-local item number
+    __device__ __forceinline__ uint32_t frame_of(uint32_t id) const { const uint32_t f = (id >> gsh) + f_shift; return f >= F ? f - F : f; }
+    __device__ __forceinline__ uint32_t group_of(uint32_t id) const { return b_first + (id & (gpb - 1u)); }
+    __device__ __forceinline__ uint32_t chan_of(uint32_t id) const { return (id & (gpb - 1u)) * (uint32_t)kSuperFrames + lane; }   // this lane's channel within the block
+    __device__ __forceinline__ void end_prefetch(const igdsp_chan_hold *hold, const uint8_t *gate)     // when the wave starts its last item
+    {
+        e_ticket = wave_draw(&q.ticket, lane);
+        if (e_ticket < gpb) {
+            const uint32_t c = (b_first + e_ticket) * (uint32_t)kSuperFrames + lane;
+            e_open = gate == nullptr || gate[c] != 0;
+            if (e_open) e_hold = hold[c];
+        }
+    }
+    __device__ __forceinline__ void finish(const BlkHoldWindow &w, uint32_t n, igdsp_chan_hold *hold, const uint8_t *gate)
+    {   // every wave of the block, after its last item: the windows of F frames of n samples each go into hold[c]
+        if (e_ticket == kNoItem) end_prefetch(hold, gate);                     // a wave that never had an item
+        __syncthreads();
+        if (e_ticket < gpb && e_open) {
+            const uint32_t t = e_ticket * (uint32_t)kSuperFrames + lane;
+            w.fold(t, F, F * n, e_hold);
+            hold[b_first * (uint32_t)kSuperFrames + t] = e_hold;
+        }
+    }
+};
 
 // ============================================================================
 // a2 — G.711 compression.  ONE branch-free formulation serves both laws and both encoder lineages

@@ -30,7 +30,6 @@ struct WinArgs {
     igdsp_chan_probe *probe = nullptr;
 };
 constexpr int kWinRing = 16;                             // frames of a group that may be folded before an earlier one is (power of two)
-constexpr int kWinBlkCh = 256;                           // channels a block can own (7 dwords of LDS each)
 
 hipError_t init_device_attributes();       // per-device kernel attributes; igdsp_create calls it with its device current
 hipError_t launch_decode_meter(const LaunchCfg &cfg, int variant,

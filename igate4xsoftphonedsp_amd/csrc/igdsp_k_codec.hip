@@ -647,18 +647,12 @@ __global__ __launch_bounds__(kRtlWaves * 64) void k_roundtrip_lut64(
 
 // ============================================================================
 // Config #5, block-owned form — k_roundtrip_blk64 (late round 3): k_roundtrip_lut64's item body under the work distribution of the
-// block-owned window kernel (k_meter_rtp64<WIN = 2>, igdsp_k_packets.hip).  Block b owns the gpb = 4 (2, 1) consecutive channel
-// groups b * gpb ... for the launch and hands their F * gpb items — one frame of one group: 10 KiB in, 10 KiB out, 1 KiB of
-// records — to its waves one at a time from an LDS counter: a wave that falls behind draws fewer items, where the static walk
-// gives every wave a fixed third of a group's frames.  The windows of the block's <= 256 channels live in LDS and move by LDS
-// atomics (integer add / max / min: exact, any order — this kernel has no order-dependent state); at its end the block folds
-// them into hold[c] itself (it owns the channels: plain read-modify-write, hold[c] fetched one item ahead as in the window
-// kernel).  Blocks with an odd index walk the frames from the middle of the launch: at any moment half the chip writes the
-// first half of the output and half the second, which is what an output spread over two memory classes (IGDSP_IO_BULK)
-// needs, as the item orders of k_roundtrip_lut64 do.
+// block-owned window kernel (k_meter_rtp64<WIN = 2>, igdsp_k_packets.hip).  Block b owns gpb = 4 (2, 1) consecutive channel groups
+// for the launch and hands their F * gpb items — one frame of one group: 10 KiB in, 10 KiB out, 1 KiB of records — to its waves
+// one at a time from an LDS counter (BlkItemQueue, igdsp_device.h): a wave that falls behind draws fewer items, where the static walk
+// gives every wave a fixed third of a group's frames.  The windows of the block's channels live in LDS (BlkHoldWindow: integer
+// atomics, exact in any order — this kernel has no order-dependent state) and the block folds them into hold[c] itself at its end.
 // ============================================================================
-constexpr int kRtBlkCh = 256;                             // channels a block can own (7 dwords of LDS each)
-
 template <int VARIANT>
 __global__ __launch_bounds__(kRtbWaves * 64) void k_roundtrip_blk64(
     const uint8_t *__restrict__ payload, const uint8_t *__restrict__ codec, uint32_t C, uint32_t F,
@@ -666,12 +660,11 @@ __global__ __launch_bounds__(kRtbWaves * 64) void k_roundtrip_blk64(
     const uint8_t *__restrict__ gate, uint32_t gpb, uint32_t gsh, uint32_t mid_start)
 {
     __shared__ uint2 lds[kLutEntries + kRtbWaves * kStripEntries];
-    // {sum of squares (2 dwords), byte-mean sum, peak-hold, level max, level min, silent | clipped << 16} x kRtBlkCh channels
-    __shared__ uint32_t wst[7 * kRtBlkCh];
-    __shared__ uint32_t q_next, q_ticket;
+    __shared__ BlkHoldWindow wst;
+    __shared__ BlkQueueLds ql;
     fill_recode_lut<VARIANT>(lds);
-    for (uint32_t i = threadIdx.x; i < 7u * (uint32_t)kRtBlkCh; i += blockDim.x) wst[i] = (i >= 5u * (uint32_t)kRtBlkCh && i < 6u * (uint32_t)kRtBlkCh) ? 255u : 0u;
-    if (threadIdx.x == 0) { q_next = 0u; q_ticket = 0u; }
+    wst.init(threadIdx.x, blockDim.x);
+    if (threadIdx.x == 0) ql = BlkQueueLds{0u, 0u};
     __syncthreads();
 
     const uint32_t lane = threadIdx.x & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -680,49 +673,26 @@ __global__ __launch_bounds__(kRtbWaves * 64) void k_roundtrip_blk64(
     uint32_t fr5, pm5;
     pack_piece_consts(lane, fr5, pm5);
     const uint64_t fbytes = (uint64_t)C * kFrame;                  // bytes between two frames of one channel group
-    const uint32_t b_first = blockIdx.x * gpb, b_items = F * gpb;
-    const uint32_t f_shift = (mid_start != 0u && (blockIdx.x & 1u)) ? F / 2u : 0u;      // odd blocks start in the middle of the launch (spread outputs)
-    auto grab = [&]() -> uint32_t {                                // block-local item number, 0xFFFFFFFF = none left
-        uint32_t v = 0;
-        if (lane == 0) v = atomicAdd(&q_next, 1u);
-        v = (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
-        return v < b_items ? v : 0xFFFFFFFFu;
-    };
-    auto frame_of = [&](uint32_t id) { const uint32_t f = (id >> gsh) + f_shift; return f >= F ? f - F : f; };
-    auto group_of = [&](uint32_t id) { return b_first + (id & (gpb - 1u)); };
-    // hold[c] of one group, fetched by the first gpb waves to start their last item (a global load at the block's end waits ~5 us)
-    igdsp_chan_hold e_hold = igdsp_chan_hold{};
-    uint32_t e_ticket = 0xFFFFFFFFu;
-    bool e_open = false;
-    auto end_prefetch = [&]() {
-        uint32_t v = 0;
-        if (lane == 0) v = atomicAdd(&q_ticket, 1u);
-        e_ticket = (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
-        if (e_ticket < gpb) {
-            const uint32_t c = (b_first + e_ticket) * (uint32_t)kSuperFrames + lane;
-            e_open = gate == nullptr || gate[c] != 0;
-            if (e_open) e_hold = hold[c];
-        }
-    };
+    BlkItemQueue q(ql, lane, gpb, gsh, F, mid_start != 0u);
 
-    uint32_t id_cur = grab();
-    if (id_cur != 0xFFFFFFFFu) {
+    uint32_t id_cur = q.grab();
+    if (id_cur != kNoItem) {
         uint4 X[kLoadsPerChunk], Y[kLoadsPerChunk];
-        uint32_t cur_pt = codec[group_of(id_cur) * (uint32_t)kSuperFrames + lane];
+        uint32_t cur_pt = codec[q.group_of(id_cur) * (uint32_t)kSuperFrames + lane];
         {
-            const __amdgpu_buffer_rsrc_t r0 = make_rsrc(payload + (uint64_t)group_of(id_cur) * kSuperFrames * kFrame + (uint64_t)frame_of(id_cur) * fbytes);
+            const __amdgpu_buffer_rsrc_t r0 = make_rsrc(payload + (uint64_t)q.group_of(id_cur) * kSuperFrames * kFrame + (uint64_t)q.frame_of(id_cur) * fbytes);
 #pragma unroll
             for (int j = 0; j < kLoadsPerChunk; ++j) X[j] = buf_ld_stream(r0, voff, (uint32_t)j * 1024u);
 #pragma unroll
             for (int j = 0; j < kLoadsPerChunk; ++j) Y[j] = buf_ld_stream(r0, voff, (uint32_t)kChunkBytes + (uint32_t)j * 1024u);
         }
-        uint32_t id_next = grab();
+        uint32_t id_next = q.grab();
         for (;;) {
-            const bool more = id_next != 0xFFFFFFFFu;              // wave-uniform; the last item re-reads itself (cache hit)
-            if (!more) end_prefetch();                            // (once: the loop ends with this item)
+            const bool more = id_next != kNoItem;                  // wave-uniform; the last item re-reads itself (cache hit)
+            if (!more) q.end_prefetch(hold, gate);                // (once: the loop ends with this item)
             const uint32_t id_load = more ? id_next : id_cur;
-            const uint32_t cg = group_of(id_cur), f = frame_of(id_cur), c0 = cg * (uint32_t)kSuperFrames;
-            const uint32_t cg_n = group_of(id_load), f_n = frame_of(id_load);
+            const uint32_t cg = q.group_of(id_cur), f = q.frame_of(id_cur), c0 = cg * (uint32_t)kSuperFrames;
+            const uint32_t cg_n = q.group_of(id_load), f_n = q.frame_of(id_load);
             const bool my_alaw = cur_pt == IGDSP_PT_PCMA;
             const uint64_t amask = __ballot(my_alaw);
             const uint32_t nxt_pt = codec[cg_n * (uint32_t)kSuperFrames + lane];
@@ -730,7 +700,7 @@ __global__ __launch_bounds__(kRtbWaves * 64) void k_roundtrip_blk64(
             const __amdgpu_buffer_rsrc_t rout = make_rsrc(out + (uint64_t)c0 * kFrame + (uint64_t)f * fbytes);
             recode_half(lds, strip, X, (uint32_t)amask, fr5, pm5, off, lane, voff, 0u, rin, rout);
             recode_half(lds, strip + kPiecesPerChunk, Y, (uint32_t)(amask >> 32), fr5, pm5, off, lane, voff, (uint32_t)kChunkBytes, rin, rout);
-            const uint32_t id_after = more ? grab() : 0xFFFFFFFFu;  // its LDS round trip hides under the fold below
+            const uint32_t id_after = more ? q.grab() : kNoItem;    // its LDS round trip hides under the fold below
             wave_lds_fence();
             {
                 const uint4 *row = reinterpret_cast<const uint4 *>(strip + lane * kPiecesPerFrame);
@@ -747,33 +717,14 @@ __global__ __launch_bounds__(kRtbWaves * 64) void k_roundtrip_blk64(
                 uint32_t bm, fl;
                 const uint4 rec = pack_stats160(sq, peak, bsum, my_alaw, (fail >> 31) == 0u, bm, fl);
                 buf_st(make_rsrc(stats + ((uint64_t)f * C + c0)), voff, 0u, rec);       // 64 records = 1 KiB, lane * 16
-                const uint32_t cl = (id_cur & (gpb - 1u)) * (uint32_t)kSuperFrames + lane;
-                __hip_atomic_fetch_add(reinterpret_cast<unsigned long long *>(wst) + cl, (unsigned long long)(sq << 4), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                __hip_atomic_fetch_add(wst + 2 * kRtBlkCh + cl, bm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                __hip_atomic_fetch_max(wst + 3 * kRtBlkCh + cl, peak, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                __hip_atomic_fetch_max(wst + 4 * kRtBlkCh + cl, bm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                __hip_atomic_fetch_min(wst + 5 * kRtBlkCh + cl, bm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                const uint32_t sc = ((fl & IGDSP_FLAG_SILENT) ? 1u : 0u) + ((fl & IGDSP_FLAG_CLIPPED) ? 0x10000u : 0u);
-                if (sc != 0u) __hip_atomic_fetch_add(wst + 6 * kRtBlkCh + cl, sc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                wst.add(q.chan_of(id_cur), sq << 4, peak, bm, fl);
             }
             wave_lds_fence();
             if (!more) break;
             id_cur = id_next; id_next = id_after; cur_pt = nxt_pt;
         }
     }
-    if (e_ticket == 0xFFFFFFFFu) end_prefetch();                   // a wave that never had an item
-    __syncthreads();
-    if (e_ticket < gpb && e_open) {
-        const uint32_t t = e_ticket * (uint32_t)kSuperFrames + lane, c = b_first * (uint32_t)kSuperFrames + t;
-        igdsp_chan_hold g = e_hold;
-        const uint32_t sc = wst[6 * kRtBlkCh + t];
-        g.sumsq_acc += reinterpret_cast<const unsigned long long *>(wst)[t]; g.count += F; g.level_sum += wst[2 * kRtBlkCh + t]; g.samples += F * (uint32_t)kFrame;
-        g.peak_hold = (uint16_t)max((uint32_t)g.peak_hold, wst[3 * kRtBlkCh + t]);
-        g.level_max = (uint8_t)max((uint32_t)g.level_max, wst[4 * kRtBlkCh + t]);
-        g.level_min = (uint8_t)min((uint32_t)g.level_min, wst[5 * kRtBlkCh + t]);
-        g.n_silent += sc & 0xFFFFu; g.n_clipped += sc >> 16;
-        hold[c] = g;
-    }
+    q.finish(wst, (uint32_t)kFrame, hold, gate);
 }
 
 // ============================================================================
@@ -784,9 +735,8 @@ __global__ __launch_bounds__(kRtbWaves * 64) void k_roundtrip_blk64(
 // ============================================================================
 typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
 
-// BLK (late round 3): the work distribution of k_roundtrip_blk64 — block b owns n_seg (= gpb) consecutive channel groups for the
-// launch, hands their F * gpb items to its waves one at a time, keeps the windows in LDS (integer atomics) and folds them into
-// hold[c] itself; odd blocks walk the frames from the middle of the launch.  n_seg carries gpb and order log2(gpb) then.
+// BLK (late round 3): the work distribution of k_roundtrip_blk64 (BlkItemQueue, BlkHoldWindow: igdsp_device.h).  n_seg carries gpb
+// then, order log2(gpb) and, in bit 2, whether odd blocks start in the middle of the launch.
 template <int Q, bool TAIL, int VARIANT, bool BLK = false>
 __global__ __launch_bounds__((BLK ? (Q <= 1 ? 16 : kRtsbWaves) : kRtlWaves) * 64) void k_roundtrip_strided(
     const uint8_t *__restrict__ payload, const uint8_t *__restrict__ codec, uint32_t C, uint32_t F, uint32_t n,
@@ -804,12 +754,12 @@ __global__ __launch_bounds__((BLK ? (Q <= 1 ? 16 : kRtsbWaves) : kRtlWaves) * 64
     // (round 2: 4 % more HBM traffic than the algorithm needs at n = 164, and 0.67 of peak where n = 160 runs at 0.75).
     constexpr bool RING = TAIL;
     __shared__ uint2 lds[kLutEntries + kW * kStrip + (RING ? kW * 256 : 0)];
-    __shared__ uint32_t wst[BLK ? 7 * kRtBlkCh : 1];           // BLK: the windows of the block's channels, as in k_roundtrip_blk64
-    __shared__ uint32_t q_next, q_ticket;
+    __shared__ BlkHoldWindowT<BLK> wst;
+    __shared__ BlkQueueLds ql;
     fill_recode_lut<VARIANT>(lds);
-    if (BLK) {
-        for (uint32_t i = threadIdx.x; i < 7u * (uint32_t)kRtBlkCh; i += blockDim.x) wst[i] = (i >= 5u * (uint32_t)kRtBlkCh && i < 6u * (uint32_t)kRtBlkCh) ? 255u : 0u;
-        if (threadIdx.x == 0) { q_next = 0u; q_ticket = 0u; }
+    if constexpr (BLK) {
+        wst.init(threadIdx.x, blockDim.x);
+        if (threadIdx.x == 0) ql = BlkQueueLds{0u, 0u};
     }
     __syncthreads();
 
@@ -964,77 +914,35 @@ __global__ __launch_bounds__((BLK ? (Q <= 1 ? 16 : kRtsbWaves) : kRtlWaves) * 64
         }
         wave_lds_fence();
     };
-    if (BLK) {
-        const uint32_t gpb = n_seg, gsh = order & 3u, b_first = blockIdx.x * gpb, b_items = F * gpb;
-        const uint32_t f_shift = ((order & 4u) != 0u && (blockIdx.x & 1u)) ? F / 2u : 0u;      // (order bit 2: the output is spread over two classes)
-        auto grab = [&]() -> uint32_t {
-            uint32_t v = 0;
-            if (lane == 0) v = atomicAdd(&q_next, 1u);
-            v = (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
-            return v < b_items ? v : 0xFFFFFFFFu;
-        };
-        auto frame_of = [&](uint32_t id) { const uint32_t f = (id >> gsh) + f_shift; return f >= F ? f - F : f; };
-        auto group_of = [&](uint32_t id) { return b_first + (id & (gpb - 1u)); };
-        auto in_of = [&](uint32_t id) { return make_rsrc(payload + (uint64_t)group_of(id) * kSuperFrames * n + (uint64_t)frame_of(id) * fbytes); };
-        igdsp_chan_hold e_hold = igdsp_chan_hold{};
-        uint32_t e_ticket = 0xFFFFFFFFu;
-        bool e_open = false;
-        auto end_prefetch = [&]() {                               // hold[c] of one group, fetched a whole item before the block's end
-            uint32_t v = 0;
-            if (lane == 0) v = atomicAdd(&q_ticket, 1u);
-            e_ticket = (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
-            if (e_ticket < gpb) {
-                const uint32_t c = (b_first + e_ticket) * (uint32_t)kSuperFrames + lane;
-                e_open = gate == nullptr || gate[c] != 0;
-                if (e_open) e_hold = hold[c];
-            }
-        };
-        uint32_t id_cur = grab();
-        if (id_cur != 0xFFFFFFFFu) {
+    if constexpr (BLK) {
+        BlkItemQueue q(ql, lane, n_seg, order & 3u, F, (order & 4u) != 0u);
+        auto in_of = [&](uint32_t id) { return make_rsrc(payload + (uint64_t)q.group_of(id) * kSuperFrames * n + (uint64_t)q.frame_of(id) * fbytes); };
+        uint32_t id_cur = q.grab();
+        if (id_cur != kNoItem) {
             uint4 d[QP];
-            uint32_t cur_pt = codec[group_of(id_cur) * (uint32_t)kSuperFrames + lane];
+            uint32_t cur_pt = codec[q.group_of(id_cur) * (uint32_t)kSuperFrames + lane];
             {
                 const __amdgpu_buffer_rsrc_t r0 = in_of(id_cur);
 #pragma unroll
                 for (int j = 0; j < QP; ++j) d[j] = buf_ld_pieces(r0, po_of(j), 0u);
             }
-            uint32_t id_next = grab();
+            uint32_t id_next = q.grab();
             for (;;) {
-                const bool more = id_next != 0xFFFFFFFFu;          // the last item re-reads itself (cache hit)
-                if (!more) end_prefetch();
+                const bool more = id_next != kNoItem;              // the last item re-reads itself (cache hit)
+                if (!more) q.end_prefetch(hold, gate);
                 const uint32_t id_load = more ? id_next : id_cur;
                 const bool my_alaw = cur_pt == IGDSP_PT_PCMA;
                 const uint64_t amask = __ballot(my_alaw);
-                const uint32_t nxt_pt = codec[group_of(id_load) * (uint32_t)kSuperFrames + lane];
-                const uint32_t id_after = more ? grab() : 0xFFFFFFFFu;
-                const uint32_t cl = (id_cur & (gpb - 1u)) * (uint32_t)kSuperFrames + lane;
-                frame_body(group_of(id_cur) * (uint32_t)kSuperFrames, frame_of(id_cur), in_of(id_load), my_alaw, (uint32_t)amask, (uint32_t)(amask >> 32), d,
-                           [&](uint64_t s16, uint32_t peak, uint32_t bm, uint32_t fl) {
-                    __hip_atomic_fetch_add(reinterpret_cast<unsigned long long *>(wst) + cl, (unsigned long long)s16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    __hip_atomic_fetch_add(wst + 2 * kRtBlkCh + cl, bm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    __hip_atomic_fetch_max(wst + 3 * kRtBlkCh + cl, peak, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    __hip_atomic_fetch_max(wst + 4 * kRtBlkCh + cl, bm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    __hip_atomic_fetch_min(wst + 5 * kRtBlkCh + cl, bm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    const uint32_t sc = ((fl & IGDSP_FLAG_SILENT) ? 1u : 0u) + ((fl & IGDSP_FLAG_CLIPPED) ? 0x10000u : 0u);
-                    if (sc != 0u) __hip_atomic_fetch_add(wst + 6 * kRtBlkCh + cl, sc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                });
+                const uint32_t nxt_pt = codec[q.group_of(id_load) * (uint32_t)kSuperFrames + lane];
+                const uint32_t id_after = more ? q.grab() : kNoItem;
+                const uint32_t cl = q.chan_of(id_cur);
+                frame_body(q.group_of(id_cur) * (uint32_t)kSuperFrames, q.frame_of(id_cur), in_of(id_load), my_alaw, (uint32_t)amask, (uint32_t)(amask >> 32), d,
+                           [&](uint64_t s16, uint32_t peak, uint32_t bm, uint32_t fl) { wst.add(cl, s16, peak, bm, fl); });
                 if (!more) break;
                 id_cur = id_next; id_next = id_after; cur_pt = nxt_pt;
             }
         }
-        if (e_ticket == 0xFFFFFFFFu) end_prefetch();               // a wave that never had an item
-        __syncthreads();
-        if (e_ticket < gpb && e_open) {
-            const uint32_t t = e_ticket * (uint32_t)kSuperFrames + lane, c = b_first * (uint32_t)kSuperFrames + t;
-            igdsp_chan_hold g = e_hold;
-            const uint32_t sc = wst[6 * kRtBlkCh + t];
-            g.sumsq_acc += reinterpret_cast<const unsigned long long *>(wst)[t]; g.count += F; g.level_sum += wst[2 * kRtBlkCh + t]; g.samples += F * n;
-            g.peak_hold = (uint16_t)max((uint32_t)g.peak_hold, wst[3 * kRtBlkCh + t]);
-            g.level_max = (uint8_t)max((uint32_t)g.level_max, wst[4 * kRtBlkCh + t]);
-            g.level_min = (uint8_t)min((uint32_t)g.level_min, wst[5 * kRtBlkCh + t]);
-            g.n_silent += sc & 0xFFFFu; g.n_clipped += sc >> 16;
-            hold[c] = g;
-        }
+        q.finish(wst, n, hold, gate);
         return;
     }
     // item order as in k_roundtrip_lut64: consecutive groups per block in the first round when the output is spread over two classes

@@ -140,18 +140,11 @@ __device__ __forceinline__ void win_drain(uint32_t *commit, const uint32_t *flag
 // WIN == 2, one folded frame of one channel (this lane): the window's LDS atomics and the run's in-order commit.
 __device__ __forceinline__ void win_blk_item(const WinArgs &win, uint32_t id_cur, uint32_t lane, uint32_t l, bool metered, uint32_t ed, uint64_t sumsq16,
                                              uint32_t peak, uint32_t bm, uint32_t fl, uint32_t c_seen, uint32_t c_run, uint32_t c_al,
-                                             uint32_t *wst, uint32_t *w_commit, uint32_t *w_flag, uint4 *w_ring, uint32_t *w_run, uint32_t *w_alarms)
+                                             BlkHoldWindow &wst, uint32_t *w_commit, uint32_t *w_flag, uint4 *w_ring, uint32_t *w_run, uint32_t *w_alarms)
 {
     const uint32_t gj = id_cur & (win.gpb - 1u), cl = gj * 64u + lane;          // this lane's channel within the block
     const bool fold = metered && (win.gate_mask == 0u || (ed & win.gate_mask) != 0u);
-    if (fold) {                               // integer sums / max / min: any order
-        __hip_atomic_fetch_add(reinterpret_cast<unsigned long long *>(wst) + cl, (unsigned long long)sumsq16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __hip_atomic_fetch_add(wst + 2 * kWinBlkCh + cl, 1u | ((fl & IGDSP_FLAG_SILENT) ? 0x100u : 0u) | ((fl & IGDSP_FLAG_CLIPPED) ? 0x10000u : 0u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __hip_atomic_fetch_add(wst + 3 * kWinBlkCh + cl, bm | (l << 16), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __hip_atomic_fetch_max(wst + 4 * kWinBlkCh + cl, peak, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __hip_atomic_fetch_max(wst + 5 * kWinBlkCh + cl, bm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __hip_atomic_fetch_min(wst + 6 * kWinBlkCh + cl, bm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
+    if (fold) wst.add_packet(cl, sumsq16, peak, bm, fl, l);
 #ifdef IGDSP_BLK_NORUN            // A/B builds only (wrong runs on purpose): what the commit protocol costs
     if (win.probe != nullptr && l == 77777u) {
 #else
@@ -230,14 +223,12 @@ __global__ __launch_bounds__(kRtpWaves * 64) void k_meter_rtp64(
     __shared__ __attribute__((aligned(16))) uint2 lds[kLutEntries + kRtpWaves * kRtpStrip];
     __shared__ BlockQueue<kRtpWaves> bq;
     __shared__ AggBlock aggb;
-    // WIN == 2: the windows of the block's own channels {sum of squares (2 dwords), frames | silent << 8 | clipped << 16,
-    // byte-mean sum | samples << 16, peak-hold, level max, level min} x kWinBlkCh channels, moved by LDS atomics
-    __shared__ uint32_t wst[WIN == 2 ? 7 * kWinBlkCh : 1];
+    __shared__ BlkHoldWindowT<WIN == 2> wst;              // WIN == 2: the windows of the block's own channels, in their packet form
     __shared__ uint32_t w_ticket;                        // WIN == 2: order in which the waves start their last item
     // WIN == 2: the consecutive-silence run is order-dependent and the frames of a channel are folded by different waves: a group's
     // frames COMMIT in frame order (w_commit[j] = next frame of group j to commit), the run and the alarms of the block's channels
     // live here between the launch's start and end
-    __shared__ uint32_t w_run[WIN == 2 ? kWinBlkCh : 1], w_alarms[WIN == 2 ? kWinBlkCh : 1], w_commit[4];
+    __shared__ uint32_t w_run[WIN == 2 ? kBlkCh : 1], w_alarms[WIN == 2 ? kBlkCh : 1], w_commit[4];
     __shared__ __attribute__((aligned(16))) uint4 w_ring[WIN == 2 ? 4 * kWinRing : 1];       // probe / reset masks of frames not yet committed
     __shared__ uint32_t w_flag[WIN == 2 ? 4 * kWinRing : 1];                                  // frame + 1 once the slot holds that frame's masks
     uint32_t gb1 = 0;
@@ -249,8 +240,8 @@ __global__ __launch_bounds__(kRtpWaves * 64) void k_meter_rtp64(
     if (WIN == 2 && threadIdx.x < win.gpb * 64u && win.probe != nullptr) p0 = win.probe[blockIdx.x * win.gpb * 64u + threadIdx.x];
     fill_lut(lds);
     if (threadIdx.x == 0) { bq_init(bq, gqueue, gridDim.x, gb1); agg_block_init(aggb); if (WIN == 2) { bq.next = 0u; w_ticket = 0u; } }
-    if (WIN == 2) {
-        for (uint32_t i = threadIdx.x; i < 7u * (uint32_t)kWinBlkCh; i += blockDim.x) wst[i] = i >= 6u * (uint32_t)kWinBlkCh ? 255u : 0u;
+    if constexpr (WIN == 2) {
+        wst.init(threadIdx.x, blockDim.x);
         if (threadIdx.x < win.gpb * 64u) { w_run[threadIdx.x] = p0.run; w_alarms[threadIdx.x] = p0.alarms; }
         if (threadIdx.x < 4u) w_commit[threadIdx.x] = 0u;
         if (threadIdx.x < 4u * (uint32_t)kWinRing) w_flag[threadIdx.x] = 0u;
@@ -312,9 +303,7 @@ __global__ __launch_bounds__(kRtpWaves * 64) void k_meter_rtp64(
     auto grab = [&]() -> uint32_t {
         if (!WIN) return bq_grab(bq, gqueue, G, lane, n_batches);
         if (WIN == 2) {
-            uint32_t v = 0;
-            if (lane == 0) v = atomicAdd(&bq.next, 1u);
-            v = (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+            const uint32_t v = wave_draw(&bq.next, lane);
             return v < b_items ? v : 0xFFFFFFFFu;            // item v of the block = frame v >> gsh of its group v & (gpb - 1)
         }
 #ifdef IGDSP_WIN_ASC              // A/B builds only (wrong windows on purpose): the WIN code over the ascending static item order
@@ -349,9 +338,7 @@ __global__ __launch_bounds__(kRtpWaves * 64) void k_meter_rtp64(
     uint32_t e_ticket = 0xFFFFFFFFu;
     bool e_open = false;
     auto end_prefetch = [&]() {
-        uint32_t v = 0;
-        if (lane == 0) v = atomicAdd(&w_ticket, 1u);
-        e_ticket = (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+        e_ticket = wave_draw(&w_ticket, lane);
         if (e_ticket < win.gpb) {
             const uint32_t c = (b_first + e_ticket) * 64u + lane;
             e_hold = win.hold[c];
@@ -479,7 +466,7 @@ __global__ __launch_bounds__(kRtpWaves * 64) void k_meter_rtp64(
                     u_sil += (uint32_t)__builtin_popcountll(__ballot(metered && (fl & IGDSP_FLAG_SILENT) != 0u));
                     u_clip += (uint32_t)__builtin_popcountll(__ballot(metered && (fl & IGDSP_FLAG_CLIPPED) != 0u));
                 }
-                if (WIN == 2) {
+                if constexpr (WIN == 2) {
                     win_blk_item(win, id_cur, lane, whole ? (uint32_t)kFrame : plen, metered, ed, s << 4, peak, bm, fl, c_seen, c_run, c_al,
                                  wst, w_commit, w_flag, w_ring, w_run, w_alarms);
                 } else if (WIN) {
@@ -525,7 +512,7 @@ __global__ __launch_bounds__(kRtpWaves * 64) void k_meter_rtp64(
             cur_radio = nxt_radio;
         }
     }
-    if (WIN == 2) {
+    if constexpr (WIN == 2) {
         // Every item of the block's channels has been handed out; when all waves are here they have been folded and committed.
         // The gpb waves holding hold[c] of a group merge its window (the block owns the channel for the launch: plain
         // read-modify-write) and write the run back.
@@ -541,18 +528,7 @@ __global__ __launch_bounds__(kRtpWaves * 64) void k_meter_rtp64(
             __syncthreads();
         }
         if (mine) {
-            if (e_open) {
-                const uint32_t wa = wst[2 * kWinBlkCh + tch], wb = wst[3 * kWinBlkCh + tch];
-                if ((wa & 0xFFu) != 0u) {
-                    igdsp_chan_hold h = e_hold;
-                    h.sumsq_acc += reinterpret_cast<const unsigned long long *>(wst)[tch]; h.count += wa & 0xFFu; h.level_sum += wb & 0xFFFFu; h.samples += wb >> 16;
-                    h.peak_hold = (uint16_t)max((uint32_t)h.peak_hold, wst[4 * kWinBlkCh + tch]);
-                    h.level_max = (uint8_t)max((uint32_t)h.level_max, wst[5 * kWinBlkCh + tch]);
-                    h.level_min = (uint8_t)min((uint32_t)h.level_min, wst[6 * kWinBlkCh + tch]);
-                    h.n_silent += (wa >> 8) & 0xFFu; h.n_clipped += (wa >> 16) & 0xFFu;
-                    win.hold[c] = h;
-                }
-            }
+            if (e_open && wst.fold_packets(tch, e_hold)) win.hold[c] = e_hold;
             if (win.probe != nullptr) win.probe[c] = igdsp_chan_probe{w_run[tch], w_alarms[tch]};
         }
 #ifdef IGDSP_BLK_STAMP

@@ -137,8 +137,10 @@ constexpr bool aligned(uintptr_t p, uintptr_t a) { return (p & (a - 1u)) == 0u; 
 // ---- Block-owned form (round trip and fused window): a block owns gpb = 1 << gsh consecutive channel groups of 64 for the launch.
 // gpb: as many groups per block (<= 4: the LDS) as still give every CU a block; `force` (IGDSP_RT_GPB / IGDSP_WIN_GPB, tests) picks
 // 1, 2 or 4 where it divides n_groups.
+constexpr int kBlkCh = 256;                               // channels a block can own (7 dwords of LDS each: BlkHoldWindow, igdsp_device.h)
 inline uint32_t groups_per_block(uint32_t n_groups, uint32_t cus, std::optional<int> force)
 {
+    static_assert(4 * kSuperFrames <= kBlkCh, "the kernels' LDS windows hold the channels of the largest gpb");
     uint32_t gpb = 1u;
     for (uint32_t g = 4u; g > 1u; g >>= 1) if (n_groups % g == 0u && n_groups / g >= cus) { gpb = g; break; }
     if (force) { const uint32_t g = (uint32_t)*force; if ((g == 1u || g == 2u || g == 4u) && n_groups % g == 0u) gpb = g; }
