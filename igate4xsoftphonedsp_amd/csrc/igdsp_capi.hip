@@ -1361,8 +1361,10 @@ int igdsp_internal_stream_mix2(igdsp_ctx *ctx, const void *d_src, void *d_dst, v
     return IGDSP_OK;
 }
 
-// Diagnostic-only (not in include/igdsp.h): cycle stamps of the chunk32 kernel, 8 x u64 per wavefront
-// {t_begin, t_lut_ready, t_end, sum load-wait, sum process, iterations, sum frame-reduce, xcc id}.
+// Diagnostic-only (not in include/igdsp.h): stamps of the headline kernel's DIAG instantiation, kDiagWords = 16 x u64 per wavefront
+// (d_diag holds 16 x 8 bytes per wave of the grid): {t_begin, t_lut_ready, t_end, sum setup, sum half X, iterations, sum half Y, xcc id,
+// realtime begin, realtime end, sum frame-reduce, wave, t_prologue_loads_issued, realtime of the last batch draw, realtime of the
+// first draw past the end of the work, block}.
 int igdsp_internal_diag_chunk32(igdsp_ctx *ctx, const uint8_t *d_payload, const uint8_t *d_codec, uint32_t C, uint32_t F,
                                 igdsp_frame_stats *d_stats, uint64_t *d_diag, void *stream)
 {

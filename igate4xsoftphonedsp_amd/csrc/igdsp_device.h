@@ -100,6 +100,26 @@ __device__ __forceinline__ void buf_st(__amdgpu_buffer_rsrc_t r, uint32_t voff, 
     __builtin_amdgcn_raw_buffer_store_b128(t, r, (int)voff, (int)soff, 0);
 }
 
+// The 1 KiB record block of k_meter_chunk64 (64 lanes x 16 B at `base`).  0 = cached (st_stream), 1 = nontemporal, 2 = write-through:
+// a plain or nt store leaves its line dirty in the XCD's L2 and the launch's end then waits for the write-back of whatever is still
+// there; an sc1 store (buffer cache policy 16) goes through to memory and drops the line.  Whole 1 KiB blocks either way.
+// Measured: DESIGN 3.1, profiles/meter_launch_ledger.md.
+#ifndef IGDSP_RECORD_STORE
+#define IGDSP_RECORD_STORE 2
+#endif
+__device__ __forceinline__ void st_record_block(igdsp_frame_stats *base, uint32_t lane, const uint4 v)
+{
+#if IGDSP_RECORD_STORE == 2
+    u32x4_t t; t.x = v.x; t.y = v.y; t.z = v.z; t.w = v.w;
+    __builtin_amdgcn_raw_buffer_store_b128(t, make_rsrc(base), (int)(lane * 16u), 0, 16);            // aux 16 = sc1
+#elif IGDSP_RECORD_STORE == 1
+    u32x4_t t; t.x = v.x; t.y = v.y; t.z = v.z; t.w = v.w;
+    __builtin_nontemporal_store(t, reinterpret_cast<u32x4_t *>(base) + lane);
+#else
+    st_stream(reinterpret_cast<uint4 *>(base) + lane, v);
+#endif
+}
+
 __device__ __forceinline__ uint32_t full_scale(bool alaw) { return alaw ? 32256u : 32124u; }
 
 __device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int m)
@@ -322,6 +342,22 @@ __device__ __forceinline__ void fill_lut(uint2 *lut)
         const uint32_t ax = (e & 0x80u) ? alaw_abs(e) : ulaw_abs(e);
         const uint32_t m = ax >> 2;
         lut[i] = make_uint2(m * m, ax);
+    }
+}
+
+// The same table with each value computed ONCE per block (k_meter_chunk64, whose prologue is on the launch's critical path):
+// item i = (entry e = i >> 2, quarter r = i & 3) evaluates the segment formula of entry e and writes 8 of its 32 replicas as four 16-byte LDS stores (two replicas each).  Store k goes to 64-byte quarter (k + e) & 3 of the
+// 256-byte row, so the 16 lanes of four neighbouring entries cover all 64 banks once per instruction.
+__device__ __forceinline__ void fill_lut_once(uint2 *lut)                 // lut: 16-byte aligned
+{
+    for (uint32_t i = threadIdx.x; i < (uint32_t)kLutEntries / 8u; i += blockDim.x) {
+        const uint32_t e = i >> 2, r = i & 3u;     // e = law<<7 | code7
+        const uint32_t ax = (e & 0x80u) ? alaw_abs(e) : ulaw_abs(e);
+        const uint32_t m = ax >> 2;
+        const uint4 v = make_uint4(m * m, ax, m * m, ax);
+        uint4 *row = reinterpret_cast<uint4 *>(lut + e * 32u);      // 16 x 16 B
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; ++k) row[((k + e) & 3u) * 4u + r] = v;
     }
 }
 

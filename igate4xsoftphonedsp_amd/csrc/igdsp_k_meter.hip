@@ -211,6 +211,11 @@ __device__ __forceinline__ void process_half(const uint2 *lut, uint2 *strip_half
 
 // DIAG: a separate diagnostic instantiation (never the shipped path) that stamps where a
 // wave's cycles go; the stamps leave only through `diag`, no output is computed from them.
+#ifndef IGDSP_METER_EARLY_LOADS
+#define IGDSP_METER_EARLY_LOADS 1      // A/B: 0 = the first item's loads behind the LUT fill and its barrier, 16 formula evaluations per thread
+#endif
+constexpr int kDiagWords = 16;         // u64 stamps per wave of the DIAG instantiation (tools/launch_ledger.py reads them)
+
 template <bool STORE_PCM, bool AGG, bool DIAG = false>
 __global__ __launch_bounds__(ChunkGeom<STORE_PCM>::kWaves * 64) void k_meter_chunk64(
     const uint8_t *__restrict__ payload, const uint8_t *__restrict__ codec, uint32_t C, uint32_t n_frames,
@@ -218,32 +223,64 @@ __global__ __launch_bounds__(ChunkGeom<STORE_PCM>::kWaves * 64) void k_meter_chu
     uint64_t *__restrict__ diag = nullptr, uint32_t *__restrict__ gqueue = nullptr)
 {
     constexpr int kWaves = ChunkGeom<STORE_PCM>::kWaves;
-    __shared__ uint2 lds[kLutEntries + kWaves * kStripEntries + (STORE_PCM ? kWaves * 256 : 0)];        // LUT + 5 KiB strip per wave (+ 2 KiB PCM transposition scratch)
-    // Work queue.  A *batch* = kWaves consecutive super-chunks.  The block's first batch is static (its
-    // blockIdx); further batches come from ONE device-wide counter (gqueue[0], one atomic per batch, i.e.
-    // per ~160 KiB of input), so fast CUs take more and the launch has no inter-CU tail.  Inside the block
+    __shared__ __attribute__((aligned(16))) uint2 lds[kLutEntries + kWaves * kStripEntries + (STORE_PCM ? kWaves * 256 : 0)];        // LUT + 5 KiB strip per wave (+ 2 KiB PCM transposition scratch)
+    // Work queue.  A *batch* = kWaves consecutive super-chunks.  The block's first TWO batches are static (blockIdx,
+    // blockIdx + G: no device atomic, and no wait for one, stands between a wave's start and its first loads); further
+    // batches come from ONE device-wide counter (gqueue[0] + 2 G, one atomic per batch, i.e. per ~160 KiB of input), so
+    // fast CUs take more and the launch has no inter-CU tail.  Inside the block
     // the waves draw slots from an LDS counter; the wave that draws the first slot of local batch j
     // prefetches the id of batch j+1, so nobody waits for the device atomic's latency.
     constexpr int kRing = 8;
     __shared__ uint32_t q_next, q_batch[kRing], q_tag[kRing];
     __shared__ AggBlock aggb;
     uint64_t d_t0 = 0, d_t1 = 0, d_iter = 0, d_rt0 = 0, d_setup = 0, d_px = 0, d_py = 0, d_red = 0;
+    uint64_t *d_row = DIAG && diag != nullptr ? diag + (uint64_t)(blockIdx.x * kWaves + (threadIdx.x >> 6)) * (uint32_t)kDiagWords : nullptr;   // this wave's stamps
     if (DIAG) { d_t0 = now_cycles(); d_rt0 = __builtin_amdgcn_s_memrealtime(); }
     const uint32_t G = gridDim.x;
-    uint32_t gb1 = 0;
-    if (threadIdx.x == 0 && gqueue != nullptr) gb1 = atomicAdd(gqueue, 1u);   // id of this block's 2nd batch; lands under the LUT fill
+
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    // the two halves are only visited alternately when there is a bulk output to spread (PCM); for the meter alone the
+    // plain ascending order is as fast on average and steadier from launch to launch
+    const uint32_t n_batches = (STORE_PCM || IGDSP_SPREAD_METER) ? (n_frames / kSuperFrames + (uint32_t)kWaves - 1u) / (uint32_t)kWaves : 0u;
+    const uint32_t n_super = n_frames / kSuperFrames;             // the launcher hands over whole super-chunks only:
+    const uint4 *src16 = reinterpret_cast<const uint4 *>(payload); // no tail predicate anywhere in the loop
+    auto fetch_half = [&](uint4 (&dst)[kLoadsPerChunk], uint32_t sidx, uint32_t half) {
+        const uint4 *p0 = src16 + ((uint64_t)sidx * (uint32_t)kStripEntries + half * (uint32_t)kPiecesPerChunk + lane);   // 64-bit piece index
+#pragma unroll
+        for (int j = 0; j < kLoadsPerChunk; ++j) dst[j] = ld_stream(p0 + j * 64);
+    };
+    auto fetch_pt = [&](uint32_t sidx) {                         // codec id (RTP PT) of this lane's own frame
+        const uint32_t c = (sidx * (uint32_t)kSuperFrames + lane) % C;     // < 2^32: the ABI caps C*F
+        return (uint32_t)codec[c];
+    };
+
+    // The wave's first item is static (batch blockIdx.x, slot = wave) and its loads depend on nothing in LDS: they are issued
+    // BEFORE the LUT fill, so HBM works while the block sets itself up (the fill and its barrier used to pass with no load in
+    // flight).  A wave without a first item reads super-chunk 0 and drops it: no load is conditional.  Issue order pt, X, Y — the
+    // same as in the loop, so every wait up to the loop head stays counted (vmcnt(N), not 0).
+    uint32_t sidx = spread_batch(blockIdx.x, n_batches) * (uint32_t)kWaves + wave;   // batch blockIdx.x, slot = wave
+    const bool has_first = sidx < n_super;
+    uint4 X[kLoadsPerChunk], Y[kLoadsPerChunk];
+    uint32_t cur_pt = 0;
+#if IGDSP_METER_EARLY_LOADS
+    cur_pt = fetch_pt(has_first ? sidx : 0u);
+    fetch_half(X, has_first ? sidx : 0u, 0);
+    fetch_half(Y, has_first ? sidx : 0u, 1);
+    if (DIAG && d_row != nullptr && lane == 0u) d_row[12] = now_cycles();      // prologue loads issued
+    fill_lut_once(lds);
+#else
     fill_lut(lds);
+#endif
     if (threadIdx.x == 0) {
         q_next = kWaves;                                         // slots 0..kWaves-1 = the waves' first picks
         agg_block_init(aggb);
         for (int i = 0; i < kRing; ++i) q_tag[i] = 0xFFFFFFFFu;
         q_batch[0] = blockIdx.x; q_tag[0] = 0u;
-        q_batch[1] = gqueue ? gb1 + G : blockIdx.x + G; q_tag[1] = 1u;
+        q_batch[1] = blockIdx.x + G; q_tag[1] = 1u;
     }
     __syncthreads();
     if (DIAG) d_t1 = now_cycles();
 
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     uint2 *strip = lds + kLutEntries + wave * kStripEntries;
     uint4 *xpose = STORE_PCM ? reinterpret_cast<uint4 *>(lds + kLutEntries + kWaves * kStripEntries + wave * 256) : nullptr;
     const uint32_t off = (lane & 31u) * 8u;
@@ -256,12 +293,6 @@ __global__ __launch_bounds__(ChunkGeom<STORE_PCM>::kWaves * 64) void k_meter_chu
         pm[j] = probe_mask(p - fr[j] * 10u);
     }
 
-    // the two halves are only visited alternately when there is a bulk output to spread (PCM); for the meter alone the
-    // plain ascending order is as fast on average and steadier from launch to launch
-    const uint32_t n_batches = (STORE_PCM || IGDSP_SPREAD_METER) ? (n_frames / kSuperFrames + (uint32_t)kWaves - 1u) / (uint32_t)kWaves : 0u;
-    const uint32_t n_super = n_frames / kSuperFrames;             // the launcher hands over whole super-chunks only:
-    const uint4 *src16 = reinterpret_cast<const uint4 *>(payload); // no tail predicate anywhere in the loop
-
     // launch-aggregate partials.  Per-lane (VGPR): sum of squares, byte-mean sum, peak.  The three COUNTS are wave-uniform
     // (every iteration meters 64 frames; silent / clipped come from a ballot + popcount) and live in SGPRs, which keeps
     // the meter-only kernel inside its 128-VGPR budget without scratch.
@@ -269,24 +300,19 @@ __global__ __launch_bounds__(ChunkGeom<STORE_PCM>::kWaves * 64) void k_meter_chu
     uint32_t a_bm = 0, a_peak = 0;
     uint32_t u_frames = 0, u_sil = 0, u_clip = 0;
 
-    auto fetch_half = [&](uint4 (&dst)[kLoadsPerChunk], uint32_t sidx, uint32_t half) {
-        const uint4 *p0 = src16 + ((uint64_t)sidx * (uint32_t)kStripEntries + half * (uint32_t)kPiecesPerChunk + lane);   // 64-bit piece index
-#pragma unroll
-        for (int j = 0; j < kLoadsPerChunk; ++j) dst[j] = ld_stream(p0 + j * 64);
-    };
-    auto fetch_pt = [&](uint32_t sidx) {                         // codec id (RTP PT) of this lane's own frame
-        const uint32_t c = (sidx * (uint32_t)kSuperFrames + lane) % C;     // < 2^32: the ABI caps C*F
-        return (uint32_t)codec[c];
-    };
     auto grab = [&]() -> uint32_t {                              // next super-chunk for this wave (wave-uniform)
         uint32_t v = 0;
         if (lane == 0) {
             const uint32_t s = atomicAdd(&q_next, 1u);
             const uint32_t j = s / (uint32_t)kWaves, w = s - j * (uint32_t)kWaves;
             if (w == 0u) {                                       // first drawer of local batch j announces batch j + 1
-                const uint32_t nb = gqueue ? atomicAdd(gqueue, 1u) + G : blockIdx.x + (j + 1u) * G;
+                const uint32_t nb = gqueue ? atomicAdd(gqueue, 1u) + 2u * G : blockIdx.x + (j + 1u) * G;
                 __hip_atomic_store(&q_batch[(j + 1u) % kRing], nb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 __hip_atomic_store(&q_tag[(j + 1u) % kRing], j + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (DIAG && d_row != nullptr) {                  // realtime of this wave's last batch draw, and of its draw past the end of the work
+                    d_row[13] = __builtin_amdgcn_s_memrealtime();
+                    if ((uint64_t)nb * (uint32_t)kWaves >= n_super) d_row[14] = d_row[13];
+                }
             }
             while (__hip_atomic_load(&q_tag[j % kRing], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != j)
                 __builtin_amdgcn_s_sleep(2);                     // published by a wave of this block that never waits on us
@@ -295,12 +321,13 @@ __global__ __launch_bounds__(ChunkGeom<STORE_PCM>::kWaves * 64) void k_meter_chu
         return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
     };
 
-    uint32_t sidx = spread_batch(blockIdx.x, n_batches) * (uint32_t)kWaves + wave;   // batch blockIdx.x, slot = wave
-    if (sidx < n_super) {
-        uint4 X[kLoadsPerChunk], Y[kLoadsPerChunk];
-        uint32_t cur_pt = fetch_pt(sidx);          // issue order pt, X, Y — the same in the prologue and in the loop,
+    if (has_first) {
+#if !IGDSP_METER_EARLY_LOADS
+        cur_pt = fetch_pt(sidx);                   // issue order pt, X, Y — the same in the prologue and in the loop,
         fetch_half(X, sidx, 0);                    // so the waits at the loop head stay counted (vmcnt(N), not 0)
         fetch_half(Y, sidx, 1);
+        if (DIAG && d_row != nullptr && lane == 0u) d_row[12] = now_cycles();
+#endif
         uint32_t s_next = grab();                  // the item after this one (pulled one iteration ahead of use)
         for (;;) {
             uint64_t d_a = 0, d_b = 0, d_c = 0, d_d = 0;
@@ -337,7 +364,7 @@ __global__ __launch_bounds__(ChunkGeom<STORE_PCM>::kWaves * 64) void k_meter_chu
                     fail |= v.y | v.w;
                 }
                 uint32_t bm, fl;
-                st_stream(reinterpret_cast<uint4 *>(stats + (f0 + lane)), pack_stats160(s, peak, bsum, my_alaw, (fail >> 31) == 0u, bm, fl));
+                st_record_block(stats + f0, lane, pack_stats160(s, peak, bsum, my_alaw, (fail >> 31) == 0u, bm, fl));
                 if (AGG) {
                     a_sumsq += s << 4; a_bm += bm; a_peak = max(a_peak, peak);
                     u_frames += (uint32_t)kSuperFrames;
@@ -354,10 +381,11 @@ __global__ __launch_bounds__(ChunkGeom<STORE_PCM>::kWaves * 64) void k_meter_chu
         }
     }
     if (DIAG && lane == 0 && diag != nullptr) {
-        uint64_t *o = diag + (uint64_t)(blockIdx.x * kWaves + wave) * 12u;
+        uint64_t *o = d_row;
         o[0] = d_t0; o[1] = d_t1; o[2] = now_cycles(); o[3] = d_setup; o[4] = d_px; o[5] = d_iter; o[6] = d_py;
         o[7] = __builtin_amdgcn_s_getreg((4 << 11) | (0 << 6) | 20);   // HW_REG_XCC_ID, bits [3:0]
         o[8] = d_rt0; o[9] = __builtin_amdgcn_s_memrealtime(); o[10] = d_red; o[11] = wave;
+        o[15] = blockIdx.x;                      // (o[12..14]: written where they are taken)
     }
     // End of the wave's work, no barrier: its aggregate partials go into the block accumulator; the block's last wave out
     // commits the block totals and counts the block as finished (the last BLOCK out re-arms the device queue for the next launch).

@@ -22,12 +22,12 @@ ctx.gen_uniform(d_pl, d_pl.numel(), stream=s)
 d_cd = torch.zeros((C_,), dtype=torch.uint8, device="cuda")
 d_st = torch.zeros((F_ * C_ * 2,), dtype=torch.int64, device="cuda")
 nw = 256 * 16
-d_dg = torch.zeros((nw * 12,), dtype=torch.int64, device="cuda")
+d_dg = torch.zeros((nw * 16,), dtype=torch.int64, device="cuda")     # kDiagWords u64 per wave
 for _ in range(3):
     rc = L.igdsp_internal_diag_chunk32(ctx.h, d_pl.data_ptr(), d_cd.data_ptr(), C_, F_, d_st.data_ptr(), d_dg.data_ptr(), s)
     assert rc == 0
 torch.cuda.synchronize()
-d = d_dg.cpu().numpy().view(np.uint64).reshape(nw, 12).astype(np.float64)
+d = d_dg.cpu().numpy().view(np.uint64).reshape(nw, 16).astype(np.float64)
 rt = (d[:, 9] - d[:, 8])
 print(f"realtime (100 MHz) per wave: mean {rt.mean() / 100:.1f} us; kernel span by realtime {(d[:, 9].max() - d[:, 8].min()) / 100:.1f} us; begin spread {(d[:, 8].max() - d[:, 8].min()) / 100:.1f} us; end spread {(d[:, 9].max() - d[:, 9].min()) / 100:.1f} us")
 print(f"shader clock while alive: {np.mean((d[:, 2] - d[:, 0]) / rt) * 100:.0f} MHz")
