@@ -460,6 +460,23 @@ __device__ __forceinline__ uint4 pack_stats160(uint64_t s, uint32_t peak, uint32
 }
 
 constexpr int kStripEntries = kSuperFrames * kPiecesPerFrame;  // 640 x 8 B = 5 KiB per wave
+
+// Per-lane piece constants of a 32-frame half of 160-byte frames (five 16-byte pieces per lane), packed: five 5-bit frame
+// indices (frame-in-half of piece j) in `fr5`, five 5-bit probe shifts in `pm5` (the probe byte a piece is responsible for
+// sits at that bit of probe_fail's gathered word; 24 = none, that byte of the word is always zero).  Two registers instead
+// of ten; one v_bfe_u32 (+ one shift) per piece to unpack.  Used by k_roundtrip_lut64 and k_roundtrip_blk64.
+__device__ __forceinline__ void pack_piece_consts(uint32_t lane, uint32_t &fr5, uint32_t &pm5)
+{
+    fr5 = 0; pm5 = 0;
+#pragma unroll
+    for (int j = 0; j < kLoadsPerChunk; ++j) {
+        const uint32_t p = (uint32_t)j * 64u + lane, f = p / 10u, q = p - f * 10u;
+        const uint32_t sh = q == 1u ? 0u : (q == 3u ? 8u : (q == 2u ? 16u : 24u));
+        fr5 |= f << (5 * j);
+        pm5 |= sh << (5 * j);
+    }
+}
+
 // Order in which batches of work items are visited: the two halves of the item range alternately, so that at any
 // moment the launch reads and WRITES in two distant places of every buffer.  Write streams spread over two classes of
 // device memory run 11-22 % faster on MI355X than the same stream into one class (tools/stream_calib2.py, DESIGN.md

@@ -474,21 +474,6 @@ __device__ __forceinline__ void fill_recode_lut(uint2 *lut)
         if ((i & 31u) != 0u) lut[i] = lut[i & ~31u];
 }
 
-// Per-lane piece constants of a half, packed: five 5-bit frame indices (frame-in-half of piece j) in `fr5`, five 5-bit probe
-// shifts in `pm5` (the probe byte a piece is responsible for sits at that bit of probe_fail's gathered word; 24 = none, that
-// byte of the word is always zero).  Two registers instead of ten; one v_bfe_u32 (+ one shift) per piece to unpack.
-__device__ __forceinline__ void pack_piece_consts(uint32_t lane, uint32_t &fr5, uint32_t &pm5)
-{
-    fr5 = 0; pm5 = 0;
-#pragma unroll
-    for (int j = 0; j < kLoadsPerChunk; ++j) {
-        const uint32_t p = (uint32_t)j * 64u + lane, f = p / 10u, q = p - f * 10u;
-        const uint32_t sh = q == 1u ? 0u : (q == 3u ? 8u : (q == 2u ? 16u : 24u));
-        fr5 |= f << (5 * j);
-        pm5 |= sh << (5 * j);
-    }
-}
-
 // One half (32 frames) of a super-chunk: expand, meter, re-encode.  Same software pipeline as process_half (the LUT reads
 // of unit u + 1 are in flight while unit u is folded); the eight re-encoded bytes of a unit are assembled right in its fold.
 // All memory traffic goes through buffer instructions: `rin` describes the NEXT frame's super-chunk (refill), `rout` this
