@@ -25,6 +25,8 @@ ENC_SUN16, ENC_G191 = 0, 1
 FLAG_SILENT, FLAG_PROBE_D5, FLAG_CLIPPED, FLAG_EMPTY = 1, 2, 4, 8
 FLAG_SATURATED = 0x10        # igdsp_conf_mix
 BSS_VOTE_FRAMES = 10         # IGDSP_BSS_VOTE_FRAMES
+PTT_RELEASE_FRAMES = 12      # IGDSP_PTT_RELEASE_FRAMES
+PTT_ON, PTT_PRESS, PTT_RELEASE, PTT_TAKEOVER = 1, 2, 4, 8   # IGDSP_PTT_*
 JB_DEPTH, JB_DELAY = 16, 3   # IGDSP_JB_DEPTH, IGDSP_JB_DELAY
 JB_IDLE, JB_PLAYED, JB_LOST = 1, 2, 3
 JB_PKT_NONE, JB_PKT_INVALID, JB_PKT_KEEPALIVE, JB_PKT_PLACED, JB_PKT_LATE, JB_PKT_DUPLICATE, JB_PKT_RESTART = 0, 1, 2, 3, 4, 5, 6
@@ -51,6 +53,10 @@ CHAN_HOLD = np.dtype(
 )
 RTP_INFO = np.dtype([("ed137", "<u4"), ("payload_len", "<u2"), ("pt", "u1"), ("flags", "u1")], align=True)
 BSS_STATE = np.dtype([("count", "<u4"), ("voted", "<u4"), ("on", "<u4"), ("votes", "<u4")], align=True)   # igdsp_bss_state
+# PTT priority arbitration (igdsp_ptt_arbitrate)
+PTT_STATE = np.dtype([("level", "<u4"), ("holder", "<u4"), ("takeovers", "<u4"), ("reserved", "<u4")], align=True)   # igdsp_ptt_state
+PTT_SLOT = np.dtype([("word", "<u4"), ("last_tx", "u1"), ("release_cnt", "u1"), ("pressed", "u1"), ("reserved", "u1")], align=True)
+PTT_TICK = np.dtype([("sel", "<i4"), ("level", "u1"), ("ptt_id", "u1"), ("flags", "u1"), ("ctl", "u1")], align=True)
 CHAN_PROBE = np.dtype([("run", "<u4"), ("alarms", "<u4")], align=True)
 # the jitter buffer (igdsp_jb_receive / igdsp_jb_report)
 JB_STATE = np.dtype(
@@ -192,6 +198,8 @@ PROTOTYPES = [
     ("igdsp_conf_mix", _int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp]),
     ("igdsp_bss_select", _int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp,
                                 _vp]),
+    ("igdsp_ptt_arbitrate", _int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp,
+                                   _vp, _vp, _vp]),
     ("igdsp_jb_ring_bytes", C.c_size_t, [_u32, _u32]),
     ("igdsp_jb_report", _int, [_vp, _vp, _vp]),
     ("igdsp_jb_receive", _int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -469,6 +477,17 @@ class Context:
         self._ck(self.L.igdsp_bss_select(self.h, _ptr(info), _ptr(payload), _ptr(codec), _ptr(pcm), _ptr(length), _ptr(gain), _ptr(group_ptr),
                                          _ptr(members), n_members, _ptr(mute), C_, G_, F_, n, vote_frames, _ptr(state), _ptr(words), _ptr(sel),
                                          _ptr(out), _ptr(stats), stream), "igdsp_bss_select")
+
+    def ptt_arbitrate(self, info, group_ptr, members, n_members, state, slots, C_, G_, F_, n=160, payload=None, codec=None, pcm=None,
+                      length=None, gain=None, rxonly=None, release_frames=0, sel=None, tick=None, ctl_out=None, out=None, stats=None,
+                      stream=None):
+        """igdsp_ptt_arbitrate: info [F][C] RTP_INFO; at most one of payload [F][C][n] u8 (+ codec [C]) / pcm [F][C][n] int16; state [G]
+        PTT_STATE and slots [n_members] PTT_SLOT carried across calls; sel [F][G] int32, tick [F][G] PTT_TICK, ctl_out [F][G] u8, out
+        [F][G][n] int16, stats [F][G] (device buffers)."""
+        self._ck(self.L.igdsp_ptt_arbitrate(self.h, _ptr(info), _ptr(payload), _ptr(codec), _ptr(pcm), _ptr(length), _ptr(gain),
+                                            _ptr(group_ptr), _ptr(members), n_members, _ptr(rxonly), C_, G_, F_, n, release_frames,
+                                            _ptr(state), _ptr(slots), _ptr(sel), _ptr(tick), _ptr(ctl_out), _ptr(out), _ptr(stats), stream),
+                 "igdsp_ptt_arbitrate")
 
     def jb_receive(self, packets, radio, state, ring, payload, length, info, C_, T_, S_=1, stride=180, n=160, delay=JB_DELAY, sizes=None,
                    arrival=None, tick_flags=None, pkt_status=None, stream=None):

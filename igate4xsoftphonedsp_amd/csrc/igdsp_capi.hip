@@ -835,6 +835,48 @@ int igdsp_bss_select(igdsp_ctx *ctx, const igdsp_rtp_info *d_info, const uint8_t
                       d_state, d_words, d_sel, d_out, d_stats, stream, false);
 }
 
+// ---- PTT priority arbitration: the CLIENT-mode block of checkEvents (roip_ed137.cpp:6124-6231; get_IPRadioPttStatus,
+// Functions.cpp:1045-1139; the PTT id, Functions.cpp:1141-1151) ----
+// igdsp_ptt_arbitrate, or with yardstick its compute-free twin igdsp_internal_ptt_copy
+static int ptt_arbitrate(igdsp_ctx *ctx, const igdsp_rtp_info *d_info, const uint8_t *d_payload, const uint8_t *d_codec, const int16_t *d_pcm,
+                         const uint16_t *d_len, const uint16_t *d_gain, const uint32_t *d_group_ptr, const uint32_t *d_members,
+                         uint32_t n_members, const uint8_t *d_rxonly, uint32_t C, uint32_t G, uint32_t F, uint32_t n, uint32_t release_frames,
+                         igdsp_ptt_state *d_state, igdsp_ptt_slot *d_slots, int32_t *d_sel, igdsp_ptt_tick *d_tick, uint8_t *d_ctl_out,
+                         int16_t *d_out, igdsp_frame_stats *d_stats, void *stream, bool yardstick)
+{
+    if (!ctx) return IGDSP_EINVAL;
+    if (n == 0 || n > IGDSP_MAX_PAYLOAD || n_members > (1u << 24) || release_frames > 255u) return IGDSP_EINVAL;   // always checked
+    if ((uint64_t)G * F == 0) return IGDSP_OK;                                               // nothing to do
+    if (!d_info || !d_group_ptr || !d_state) return IGDSP_EINVAL;
+    if (n_members && (!d_members || !d_slots)) return IGDSP_EINVAL;
+    if (d_payload && d_pcm) return IGDSP_EINVAL;                                              // at most one input form
+    if (d_payload && !d_codec) return IGDSP_EINVAL;
+    if ((d_out || d_stats) && !d_payload && !d_pcm) return IGDSP_EINVAL;                      // audio outputs need audio
+    if (int rc = check_shape(C, F, n)) return rc;
+    if (int rc = check_shape(G, F, n)) return rc;
+    const uintptr_t a2 = reinterpret_cast<uintptr_t>(d_pcm) | reinterpret_cast<uintptr_t>(d_len) | reinterpret_cast<uintptr_t>(d_gain) |
+                         reinterpret_cast<uintptr_t>(d_out);
+    const uintptr_t a4 = reinterpret_cast<uintptr_t>(d_info) | reinterpret_cast<uintptr_t>(d_group_ptr) | reinterpret_cast<uintptr_t>(d_members) |
+                         reinterpret_cast<uintptr_t>(d_state) | reinterpret_cast<uintptr_t>(d_slots) | reinterpret_cast<uintptr_t>(d_sel) |
+                         reinterpret_cast<uintptr_t>(d_tick);
+    if ((a2 & 1u) || (a4 & 3u) || (reinterpret_cast<uintptr_t>(d_stats) & 7u)) return IGDSP_EINVAL;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, launch_ptt_arbitrate(cfg_of(ctx, pick(ctx, stream)), d_info, d_payload, d_codec, d_pcm, d_len, d_gain, d_group_ptr, d_members,
+                                      n_members, d_rxonly, C, G, F, n, release_frames, d_state, d_slots, d_sel, d_tick, d_ctl_out, d_out,
+                                      d_stats, yardstick, pick(ctx, stream)));
+    return IGDSP_OK;
+}
+
+int igdsp_ptt_arbitrate(igdsp_ctx *ctx, const igdsp_rtp_info *d_info, const uint8_t *d_payload, const uint8_t *d_codec, const int16_t *d_pcm,
+                        const uint16_t *d_len, const uint16_t *d_gain, const uint32_t *d_group_ptr, const uint32_t *d_members,
+                        uint32_t n_members, const uint8_t *d_rxonly, uint32_t C, uint32_t G, uint32_t F, uint32_t n, uint32_t release_frames,
+                        igdsp_ptt_state *d_state, igdsp_ptt_slot *d_slots, int32_t *d_sel, igdsp_ptt_tick *d_tick, uint8_t *d_ctl_out,
+                        int16_t *d_out, igdsp_frame_stats *d_stats, void *stream)
+{
+    return ptt_arbitrate(ctx, d_info, d_payload, d_codec, d_pcm, d_len, d_gain, d_group_ptr, d_members, n_members, d_rxonly, C, G, F, n,
+                         release_frames, d_state, d_slots, d_sel, d_tick, d_ctl_out, d_out, d_stats, stream, false);
+}
+
 // ---- jitter buffer: the pjmedia stream behind adapter->stream_rtp_cb (TransportAdapter.cpp:301): RFC 3550 A.1 / A.3 / A.8 and playout ----
 size_t igdsp_jb_ring_bytes(uint32_t n_channels, uint32_t samples_per_frame)
 {
@@ -1318,6 +1360,20 @@ int igdsp_internal_jb_copy(igdsp_ctx *ctx, const uint8_t *d_packets, const uint1
 {
     return jb_receive(ctx, d_packets, d_sizes, d_radio, d_arrival, C, T, S, pkt_stride, n, delay_frames, d_state, d_ring, d_payload_out, d_len_out,
                       d_info_out, d_tick_flags, d_pkt_status, stream, true);
+}
+
+// Calibration-only (not in include/igdsp.h): the compute-free yardstick of igdsp_ptt_arbitrate (tools/ptt_bench.py) — the same
+// traversal (info records, ops passes, the first member of every group emitted undecoded), the same bytes in and out, no debounce,
+// arbitration, decode or records.  Arguments as igdsp_ptt_arbitrate; the group state is not touched, the slots are stepped as by a
+// launch, and sel / out / stats hold raw bytes (tick and ctl_out are not written).
+int igdsp_internal_ptt_copy(igdsp_ctx *ctx, const igdsp_rtp_info *d_info, const uint8_t *d_payload, const uint8_t *d_codec, const int16_t *d_pcm,
+                            const uint16_t *d_len, const uint16_t *d_gain, const uint32_t *d_group_ptr, const uint32_t *d_members,
+                            uint32_t n_members, const uint8_t *d_rxonly, uint32_t C, uint32_t G, uint32_t F, uint32_t n, uint32_t release_frames,
+                            igdsp_ptt_state *d_state, igdsp_ptt_slot *d_slots, int32_t *d_sel, igdsp_ptt_tick *d_tick, uint8_t *d_ctl_out,
+                            int16_t *d_out, igdsp_frame_stats *d_stats, void *stream)
+{
+    return ptt_arbitrate(ctx, d_info, d_payload, d_codec, d_pcm, d_len, d_gain, d_group_ptr, d_members, n_members, d_rxonly, C, G, F, n,
+                         release_frames, d_state, d_slots, d_sel, d_tick, d_ctl_out, d_out, d_stats, stream, true);
 }
 
 // Calibration-only (not in include/igdsp.h): the compute-free yardstick of igdsp_plc_conceal (tools/plc_bench.py) — the same

@@ -93,6 +93,15 @@ hipError_t launch_bss_select(const LaunchCfg &cfg, const igdsp_rtp_info *info, c
                              const uint16_t *len, const uint16_t *gain, const uint32_t *group_ptr, const uint32_t *members, uint32_t n_members,
                              const uint8_t *mute, uint32_t C, uint32_t G, uint32_t F, uint32_t n, uint32_t vote_frames, igdsp_bss_state *state,
                              uint32_t *words, int32_t *sel, int16_t *out, igdsp_frame_stats *stats, bool yardstick, hipStream_t s);
+// igdsp_ptt_arbitrate: at most one of g711 (+ codec) / pcm; sel, tick, ctl_out, out, stats may each be nullptr (out and stats need an
+// input: the C ABI checks); gain nullptr = 256; release_frames 0 = IGDSP_PTT_RELEASE_FRAMES.  yardstick: the compute-free form, the same
+// traversal and bytes, no decode / scale / clamp / stats / debounce / arbitration; the group state is not touched, the slots are
+// stepped as by a launch
+hipError_t launch_ptt_arbitrate(const LaunchCfg &cfg, const igdsp_rtp_info *info, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm,
+                                const uint16_t *len, const uint16_t *gain, const uint32_t *group_ptr, const uint32_t *members,
+                                uint32_t n_members, const uint8_t *rxonly, uint32_t C, uint32_t G, uint32_t F, uint32_t n,
+                                uint32_t release_frames, igdsp_ptt_state *state, igdsp_ptt_slot *slots, int32_t *sel, igdsp_ptt_tick *tick,
+                                uint8_t *ctl_out, int16_t *out, igdsp_frame_stats *stats, bool yardstick, hipStream_t s);
 // igdsp_jb_receive: sizes, arrival, tick, pkt may each be nullptr; ring is igdsp_jb_ring_bytes(C, n) bytes, 16-byte aligned.
 // yardstick: the compute-free form, the same rows as an in-order lossless launch (arrival slot k = 0 of every tick played straight from
 // the packet), no header walk, state machine or ring store; the state is not touched

@@ -14,7 +14,7 @@
 //      frame loads in flight; decode, the Q7 level and the record as igdsp_conf_mix does them for a one-member port (igdsp_q7.h).
 // The stored words are only read here.  After each part k_bss_words writes every slot's last stored word (a thread per slot, a
 // backward scan that usually stops at the part's last frame), so slots shared by two groups of a bad table never race.
-#include "igdsp_q7.h"
+#include "igdsp_group.h"
 
 namespace igdsp {
 
@@ -41,22 +41,10 @@ struct BssArgs {
     uint32_t vec_in, vec_out;
 };
 
-constexpr uint32_t kBssNoChan = 0xFFFFFFFFu;
+constexpr uint32_t kBssNoChan = kGrpNoChan;
 
-// info[f][c] as two words: x = ed137, y = payload_len | pt << 16 | flags << 24 (igdsp_rtp_info is 4-byte aligned)
-__device__ __forceinline__ uint2 bss_info(const igdsp_rtp_info *info, uint32_t C, uint32_t f, uint32_t c)
-{
-    const uint32_t *p = reinterpret_cast<const uint32_t *>(info + ((uint64_t)f * C + c));
-    return make_uint2(p[0], p[1]);
-}
-
-// the frame stores its word on the channel (transport_rtp_cb: PT 0, 8, 18, 123 and not a runt)
-__device__ __forceinline__ bool bss_stores(uint2 r)
-{
-    const uint32_t pt = (r.y >> 16) & 0xFFu;
-    return ((r.y >> 24) & IGDSP_RTP_RUNT) == 0u && (pt == 0u || pt == 8u || pt == 18u || pt == 123u);
-}
-
+__device__ __forceinline__ uint2 bss_info(const igdsp_rtp_info *info, uint32_t C, uint32_t f, uint32_t c) { return grp_info(info, C, f, c); }
+__device__ __forceinline__ bool bss_stores(uint2 r) { return grp_stores(r); }
 __device__ __forceinline__ uint32_t bss_squ(uint32_t w) { return IGDSP_ED137_SQU(w); }
 
 template <int IN, bool COPY>
@@ -77,19 +65,10 @@ __global__ __launch_bounds__(kBssWaves * 64) void k_bss_select(const BssArgs a)
     for (uint32_t i = lane; i < kBssPart * kBssGroups; i += 64u) kw[i] = 0u;
 
     // the groups' slot ranges, clamped; lane i < ng holds group g0 + i
-    uint32_t b = 0, e = 0, muted = 0;
-    if (lane < ng) {
-        b = min(a.group_ptr[g0 + lane], a.n_members);
-        e = min(a.group_ptr[g0 + lane + 1u], a.n_members);
-        if (e < b) e = b;                                                  // a descending group_ptr: empty group
-        muted = (a.mute != nullptr && a.mute[g0 + lane] != 0u) ? 1u : 0u;
-    }
-    uint32_t V = 0, myoff = 0;                                             // slots of the wave; the lane's group's first one
-    for (uint32_t i = 0; i < ng; ++i) {
-        if (lane == i) myoff = V;
-        V += (uint32_t)__builtin_amdgcn_readlane((int)(e - b), (int)i);
-    }
-    if (lane < ng) { gbeg[w][lane] = b; goff[w][lane] = myoff; gmut[w][lane] = muted; }
+    uint32_t b, e, V, myoff;                                               // V: slots of the wave; myoff: the lane's group's first one
+    grp_ranges(a.group_ptr, a.n_members, g0, ng, lane, gbeg[w], goff[w], b, e, myoff, V);
+    const uint32_t muted = (lane < ng && a.mute != nullptr && a.mute[g0 + lane] != 0u) ? 1u : 0u;
+    if (lane < ng) gmut[w][lane] = muted;
 
     // the groups' state; the voted member's channel and the SQU bit of its stored word
     uint32_t count = 0, voted = 0, on = 0, votes = 0, cv = kBssNoChan, vw = 0;
@@ -109,27 +88,18 @@ __global__ __launch_bounds__(kBssWaves * 64) void k_bss_select(const BssArgs a)
         const uint32_t v = v0 + lane;
         uint32_t c = kBssNoChan, word = 0, gl = 0, pos = 0;
         if (v < V) {
-            for (uint32_t i = 1; i < ng; ++i) if (goff[w][i] <= v) gl = i;   // the last group starting at or before v (empty ones skipped)
-            pos = v - goff[w][gl];
-            const uint32_t k = gbeg[w][gl] + pos;
+            const uint32_t k = grp_locate(gbeg[w], goff[w], ng, v, gl, pos);
             c = a.members[k];
             word = a.words[k];
             if (c >= a.C || gmut[w][gl] != 0u) c = kBssNoChan;             // never open: nothing to read
         }
         if (__builtin_amdgcn_ballot_w64(c != kBssNoChan) == 0u) continue;
-        for (uint32_t t0 = 0; t0 < pf; t0 += kBssU) {
-            uint2 r[kBssU];
-#pragma unroll
-            for (uint32_t u = 0; u < kBssU; ++u)
-                r[u] = (c != kBssNoChan && t0 + u < pf) ? bss_info(a.info, a.C, a.f0 + t0 + u, c) : make_uint2(0u, (uint32_t)IGDSP_RTP_RUNT << 24);
-#pragma unroll
-            for (uint32_t u = 0; u < kBssU; ++u) {
-                if (COPY) { fold ^= r[u].x ^ r[u].y; continue; }
-                if (bss_stores(r[u])) word = r[u].x;
-                if (c != kBssNoChan && t0 + u < pf && bss_squ(word))
-                    atomicMax(&key[w][t0 + u][gl], ((IGDSP_ED137_BSS(word) + 1u) << 24) | (0xFFFFFFu - pos));
-            }
-        }
+        grp_frames(a.info, a.C, a.f0, 0u, pf, c, [&](uint32_t t, uint2 r) {
+            if (COPY) { fold ^= r.x ^ r.y; return; }
+            if (bss_stores(r)) word = r.x;
+            if (c != kBssNoChan && t < pf && bss_squ(word))
+                atomicMax(&key[w][t][gl], ((IGDSP_ED137_BSS(word) + 1u) << 24) | (0xFFFFFFu - pos));
+        });
     }
     if (COPY && fold == 0x9E3779B9u) kw[0] = 0u;                           // keeps the yardstick's loads
     wave_lds_fence();
@@ -183,78 +153,7 @@ __global__ __launch_bounds__(kBssWaves * 64) void k_bss_select(const BssArgs a)
     wave_lds_fence();
 
     // C. emit
-    const uint32_t n_items = pf * ng, off = (lane & 31u) * 8u, n = a.n;
-    for (uint32_t j0 = 0; j0 < n_items; j0 += 64u) {
-        const uint32_t cnt = min(n_items - j0, 64u);
-        // one item per lane: tg = t << 16 | group, cs = the selection (channel + 1, 0 = none), meta = gain | len << 16 | A-law << 25
-        uint32_t tg = 0, cs = 0, meta = 0;
-        if (lane < cnt) {
-            const uint32_t j = j0 + lane, t = j / ng, gl = j - t * ng;
-            tg = t << 16 | gl;
-            cs = key[w][t][gl];
-            if (a.sel != nullptr) a.sel[(uint64_t)(a.f0 + t) * a.G + g0 + gl] = (int32_t)(cs - 1u);
-            if (IN != kBssNone && cs != 0u) {
-                const uint32_t c = cs - 1u;
-                const uint32_t l = a.len ? min((uint32_t)a.len[(uint64_t)(a.f0 + t) * a.C + c], n) : n;
-                const uint32_t g = a.gain ? (uint32_t)a.gain[c] : 256u;
-                const uint32_t law = (IN == kConfG711 && a.codec[c] == IGDSP_PT_PCMA) ? 1u : 0u;
-                meta = g | l << 16 | law << 25;
-            }
-        }
-        if (IN == kBssNone) continue;
-#pragma nounroll
-        for (uint32_t k0 = 0; k0 < cnt; k0 += kBssU) {
-            uint2 v[kBssU];
-#pragma unroll
-            for (uint32_t u = 0; u < kBssU; ++u) {
-                const uint32_t idx = min(k0 + u, 63u);
-                const uint32_t m = (uint32_t)__builtin_amdgcn_readlane((int)meta, (int)idx);
-                const uint32_t s = (uint32_t)__builtin_amdgcn_readlane((int)cs, (int)idx);
-                const uint32_t t = (uint32_t)__builtin_amdgcn_readlane((int)tg, (int)idx) >> 16;
-                const bool load = k0 + u < cnt && s != 0u && (m & 0xFFFFu) != 0u && ((m >> 16) & 0x1FFu) != 0u;
-                v[u] = load ? q7_load<IN>(a.g711, a.pcm, n, a.vec_in, (uint64_t)(a.f0 + t) * a.C + (s - 1u), lane) : make_uint2(0u, 0u);
-            }
-#pragma unroll
-            for (uint32_t u = 0; u < kBssU; ++u) {
-                if (k0 + u >= cnt) break;                                  // wave-uniform
-                const uint32_t idx = k0 + u;
-                const uint32_t m = (uint32_t)__builtin_amdgcn_readlane((int)meta, (int)idx);
-                const uint32_t s = (uint32_t)__builtin_amdgcn_readlane((int)cs, (int)idx);
-                const uint32_t tgi = (uint32_t)__builtin_amdgcn_readlane((int)tg, (int)idx);
-                const uint64_t item = (uint64_t)(a.f0 + (tgi >> 16)) * a.G + g0 + (tgi & 0xFFFFu);
-                if (COPY) {                                                // the same bytes, undecoded
-                    const uint32_t b0 = 4u * lane;
-                    if (a.out != nullptr && b0 < n) {
-                        int16_t *dst = a.out + item * n + b0;
-                        const uint2 x = IN == kConfG711 ? make_uint2(v[u].x, v[u].x) : v[u];
-                        if (a.vec_out) *reinterpret_cast<uint2 *>(dst) = x;
-                        else for (uint32_t k = 0; k < 4u && b0 + k < n; ++k) dst[k] = (int16_t)((k < 2u ? x.x : x.y) >> (16u * (k & 1u)));
-                    }
-                    if (a.stats != nullptr && lane == 0u) {
-                        igdsp_frame_stats st;
-                        st.sumsq = ((uint64_t)v[u].y << 32) | v[u].x; st.rms = 0.f; st.peak = (uint16_t)m; st.byte_mean = 0; st.flags = (uint8_t)s;
-                        a.stats[item] = st;
-                    }
-                    continue;
-                }
-                const uint32_t g = m & 0xFFFFu, l = (m >> 16) & 0x1FFu, law80 = (m >> 25) ? 0x80808080u : 0u;
-                int32_t o[4];
-                uint32_t sat = 0, peak = 0;
-                uint64_t sq = 0;
-#pragma unroll
-                for (uint32_t k = 0; k < 4u; ++k) {
-                    uint32_t ax, neg;
-                    q7_sample<IN>(lut, v[u], law80, off, k, ax, neg);
-                    IGDSP_Q7_LEVEL(q, ax, neg, g, 4u * lane + k, l, sat);        // 0 past len (and past n)
-                    if (s == 0u) q = 0u;                                           // nothing voted
-                    o[k] = neg ? -(int32_t)q : (int32_t)q;
-                    sq += (uint64_t)q * q;
-                    peak = max(peak, q);
-                }
-                q7_store(a.out, a.stats, item, n, a.vec_out, lane, o, s == 0u || l == 0u, sat, sq, peak);
-            }
-        }
-    }
+    grp_emit<IN, COPY>(a, lut, kw, pf, ng, g0, lane);
 }
 
 // every member slot's last stored word of frames f0 .. f0 + pf - 1 (unchanged when no frame stores one, or the member is >= C)

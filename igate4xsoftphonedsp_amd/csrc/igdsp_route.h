@@ -480,6 +480,51 @@ inline BssRoute bss_route(uint32_t G, uint32_t F, uint32_t n, uint32_t n_members
     return r;
 }
 
+// ---- igdsp_ptt_arbitrate (launch_ptt_arbitrate): k_ptt_arbitrate<IN, COPY> + k_ptt_slots.  The wave geometry of bss_route:
+// a wave owns gpw consecutive groups for the frames of a part, about one chunk of 64 member slots.  Its lanes step the member slots
+// (one slot per lane: word, debounce, effective PTT type) through the part's frames and leave an op per (frame, slot) in LDS; lanes
+// 0 .. gpw-1 then walk their group's members in order, frame by frame, and the whole wave emits the holders' frames.  The ops of a
+// wave are kPttOps 16-bit entries: a window of W = min(its slots rounded up to 64, kPttOps) slots times kPttOps / W frames.  A wave
+// with more frames or slots than that takes the part in several passes (64 slots: 2 passes of 64 frames; more than kPttOps slots: a
+// frame at a time, window by window), every pass stepping its slots again from the part's first frame.  Nothing is read back within a
+// launch: the group state is read and written by its own lane, and the slots are only read; after each part k_ptt_slots (a thread
+// per member slot) steps every slot through the part and stores it, which the next part reads.
+constexpr int kPttWaves = 4;                              // waves per block: they share the 64 KiB LUT (+ 32 KiB selections, 32 KiB ops)
+constexpr uint32_t kPttGroups = 16;                       // groups per wave at most (decision lanes)
+constexpr uint32_t kPttPart = 128;                        // frames per part
+constexpr uint32_t kPttU = 8;                             // loads of a lane in flight together
+constexpr uint32_t kPttOps = 4096;                        // (frame, slot) ops of a wave in LDS
+constexpr uint32_t kPttSlotsThreads = 256;                // k_ptt_slots
+struct PttRoute {
+    int form = kBssNone;                   // kConfG711, kConfPcm, or no audio
+    uint32_t gpw = 0;                      // groups per wave
+    uint32_t vec_in = 0, vec_out = 0;      // as ConfRoute
+    uint32_t grid = 0, threads = 0;        // k_ptt_arbitrate, every part
+    uint32_t part_frames = 0, parts = 0;   // the last part takes the rest
+    uint32_t pass_frames = 0;              // frames per pass of a wave with the average slot count (a wider wave takes fewer)
+    uint32_t slots_grid = 0;               // k_ptt_slots, every part (0: no member slots)
+};
+inline PttRoute ptt_route(uint32_t G, uint32_t F, uint32_t n, uint32_t n_members, int form, uintptr_t in, uintptr_t out)
+{
+    PttRoute r;
+    if ((uint64_t)G * F == 0) return r;
+    r.form = form;
+    const uint64_t avg = std::max<uint64_t>(1u, ((uint64_t)n_members + G - 1) / G);
+    r.gpw = kPttGroups;
+    while (r.gpw > 1u && r.gpw * avg > 64u) r.gpw >>= 1;
+    r.vec_in = form != kBssNone && (n & 3u) == 0u && aligned(in, form == kConfPcm ? 8 : 4) ? 1u : 0u;
+    r.vec_out = form != kBssNone && (n & 3u) == 0u && aligned(out, 8) ? 1u : 0u;
+    const uint64_t waves = ((uint64_t)G + r.gpw - 1) / r.gpw;
+    r.grid = (uint32_t)((waves + kPttWaves - 1) / kPttWaves);
+    r.threads = kPttWaves * 64;
+    r.part_frames = std::min(F, kPttPart);
+    r.parts = (F + kPttPart - 1) / kPttPart;
+    const uint64_t window = std::min<uint64_t>(kPttOps, (r.gpw * avg + 63u) / 64u * 64u);
+    r.pass_frames = std::min(r.part_frames, (uint32_t)(kPttOps / window));
+    r.slots_grid = (uint32_t)(((uint64_t)n_members + kPttSlotsThreads - 1) / kPttSlotsThreads);
+    return r;
+}
+
 // ---- igdsp_jb_receive (launch_jb_receive): k_jb_receive<COPY>.  A wave owns kJbCh consecutive channels for the ticks
 // of one part (<= kJbPart ticks).  Lanes 0 .. kJbCh - 1 step their channel's state machine over the part's arrivals with the ring tags in
 // LDS and leave a source descriptor per (tick, channel) there: an arrival of the part, a ring slot, or none; then the whole wave writes

@@ -541,6 +541,100 @@ int igdsp_host_bss_state(void *v, int *count, int *on, unsigned *votes)
     return IGDSP_OK;
 }
 
+// ---- PTT priority arbitration (roip_ed137.cpp:6124-6231), no context needed
+PttArbiter::PttArbiter(int n_legs)
+    : nLegs(n_legs < 1 ? 1 : (n_legs > kMaxLegs ? (int)kMaxLegs : n_legs)), ptt_level(0), releaseTicks(IGDSP_PTT_RELEASE_FRAMES), takeovers(0),
+      lastFlags(0)
+{
+    for (int i = 0; i < kMaxLegs; ++i) {
+        leg[i].callState = false; leg[i].rxOnly = false; leg[i].lastTx = 0; leg[i].lastTxmsec = 0; leg[i].m_PttPressed = false;
+        leg[i].unmuted = false;
+    }
+}
+
+int PttArbiter::unmutedLeg() const
+{
+    for (int i = 0; i < nLegs; ++i)
+        if (leg[i].unmuted) return i;
+    return -1;
+}
+
+int PttArbiter::tick(const uint32_t *words, const bool *call_up)
+{
+    int flags = 0;
+    for (int i = 0; i < nLegs; ++i) {
+        Leg &l = leg[i];
+        l.callState = call_up[i];
+        if (l.callState == false) continue;                  // :6131
+        int ptt = l.rxOnly ? 0 : (int)IGDSP_ED137_PTT_TYPE(words[i]);   // :6134 get_IPRadioPttStatus, TRXMODE_RX
+        if (ptt != l.lastTx) {                               // :6139-6154 — a release is bridged, with type 1
+            if (ptt == 0) {
+                if (l.lastTxmsec < 255) l.lastTxmsec++;
+                if (l.lastTxmsec < releaseTicks) ptt = 1;
+            }
+        } else {
+            l.lastTxmsec = 0;
+        }
+        l.lastTx = ptt;
+        if (ptt > ptt_level) {                               // :6157-6177 — the highest type takes the transmitter
+            ptt_level = ptt;
+            for (int j = 0; j < nLegs; ++j) leg[j].unmuted = j == i;   // (every other leg MUTE, this one UNMUTE)
+            ++takeovers;
+            flags |= IGDSP_PTT_TAKEOVER;
+        }
+        if ((ptt > 0) && (l.m_PttPressed == false)) {        // :6191-6222
+            l.m_PttPressed = true;
+            flags |= IGDSP_PTT_PRESS;
+        } else if ((ptt == 0) && (l.m_PttPressed == true)) {
+            l.m_PttPressed = false;
+            l.unmuted = false;
+            ptt_level = 0;                                   // (on any pressed leg's release, not only the holder's)
+            flags |= IGDSP_PTT_RELEASE;
+        }
+    }
+    for (int i = 0; i < nLegs; ++i)
+        if (leg[i].callState && leg[i].m_PttPressed) flags |= IGDSP_PTT_ON;
+    lastFlags = flags;
+    return unmutedLeg();
+}
+
+void *igdsp_host_ptt_new(int n_legs, int release_ticks)
+{
+    if (n_legs < 1 || n_legs > PttArbiter::kMaxLegs || release_ticks < 0 || release_ticks > 255) return nullptr;
+    PttArbiter *v = new (std::nothrow) PttArbiter(n_legs);
+    if (v && release_ticks) v->releaseTicks = release_ticks;
+    return v;
+}
+void igdsp_host_ptt_free(void *v) { delete static_cast<PttArbiter *>(v); }
+int igdsp_host_ptt_tick(void *v, const uint32_t *words, const int *call_up, const int *rx_only)
+{
+    if (!v || !words || !call_up) return IGDSP_EINVAL;
+    PttArbiter *a = static_cast<PttArbiter *>(v);
+    bool up[PttArbiter::kMaxLegs];
+    for (int i = 0; i < a->nLegs; ++i) { up[i] = call_up[i] != 0; a->leg[i].rxOnly = rx_only && rx_only[i] != 0; }
+    return a->tick(words, up);
+}
+int igdsp_host_ptt_state(void *v, int *level, unsigned *takeovers, int *flags)
+{
+    if (!v) return IGDSP_EINVAL;
+    const PttArbiter *a = static_cast<const PttArbiter *>(v);
+    if (level) *level = a->ptt_level;
+    if (takeovers) *takeovers = a->takeovers;
+    if (flags) *flags = a->lastFlags;
+    return IGDSP_OK;
+}
+int igdsp_host_ptt_leg(void *v, int leg, int *last_tx, int *release_cnt, int *pressed, int *unmuted)
+{
+    if (!v) return IGDSP_EINVAL;
+    const PttArbiter *a = static_cast<const PttArbiter *>(v);
+    if (leg < 0 || leg >= a->nLegs) return IGDSP_EINVAL;
+    if (last_tx) *last_tx = a->leg[leg].lastTx;
+    if (release_cnt) *release_cnt = a->leg[leg].lastTxmsec;
+    if (pressed) *pressed = a->leg[leg].m_PttPressed ? 1 : 0;
+    if (unmuted) *unmuted = a->leg[leg].unmuted ? 1 : 0;
+    return IGDSP_OK;
+}
+
 // ---- conference receive levels, no context needed
 void *igdsp_host_levels_new(uint32_t n_channels)
 {

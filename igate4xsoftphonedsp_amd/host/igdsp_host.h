@@ -132,6 +132,33 @@ public:
     int voted() const;
 };
 
+// PTT priority arbitration, the CLIENT-mode block of RoIP_ED137::checkEvents (roip_ed137.cpp:6124-6231) over the call-in legs of one
+// frequency (trx_incall order), restated literally and without a context: per leg lastTx, lastTxmsec, m_PttPressed and a slot volume
+// (unmuted or not), one ptt_level.  A host that keeps the arbitration on the CPU calls tick() where checkEvents runs it;
+// igdsp_ptt_arbitrate is the same loop on the device, one tick per frame, with one holder in place of the volumes.
+class PttArbiter {
+public:
+    enum { kMaxLegs = 64 };
+    struct Leg {
+        bool callState;                      // the call is up (the per-leg block runs)
+        bool rxOnly;                         // TRXMODE_RX: never keys
+        int lastTx;                          // the (substituted) PTT type of the last tick
+        int lastTxmsec;                      // ticks of the release being debounced, saturating at 255
+        bool m_PttPressed;
+        bool unmuted;                        // the slot volume: UNMUTE (true) or MUTE
+    };
+    explicit PttArbiter(int n_legs);
+    Leg leg[kMaxLegs];
+    int nLegs;
+    int ptt_level;
+    int releaseTicks;                        // ticks a release is bridged for (IGDSP_PTT_RELEASE_FRAMES at one tick per frame)
+    unsigned takeovers;                      // takeovers so far (telemetry)
+    int lastFlags;                           // IGDSP_PTT_* of the last tick
+    // One tick: words[i] = the leg's stored ED-137 word (get_ed137_value), call_up[i] = its callState.  Returns the unmuted leg, or -1.
+    int tick(const uint32_t *words, const bool *call_up);
+    int unmutedLeg() const;
+};
+
 class RoIP_ED137 {
 public:
     // Unlike the reference singleton (roip_ed137.cpp:192) the instance owns an igdsp context; device < 0
@@ -211,6 +238,13 @@ void *igdsp_host_bss_new(int vote_ticks, int stale_last_rx);
 void  igdsp_host_bss_free(void *v);
 int   igdsp_host_bss_tick(void *v, const uint32_t *words4, const int *call_up4, int force_mute);
 int   igdsp_host_bss_state(void *v, int *count, int *on, unsigned *votes);
+// PTT priority arbitration without a context (PttArbiter, 1 .. 64 legs): tick returns the unmuted leg, -1 for none (IGDSP_EINVAL for a
+// NULL handle); rx_only may be NULL
+void *igdsp_host_ptt_new(int n_legs, int release_ticks);
+void  igdsp_host_ptt_free(void *v);
+int   igdsp_host_ptt_tick(void *v, const uint32_t *words, const int *call_up, const int *rx_only);
+int   igdsp_host_ptt_state(void *v, int *level, unsigned *takeovers, int *flags);
+int   igdsp_host_ptt_leg(void *v, int leg, int *last_tx, int *release_cnt, int *pressed, int *unmuted);
 // Meter output on the reference's other channel: AudioMeter (audiometer.cpp:11-34) reads ASCII decimal levels from the
 // FIFO /tmp/capturefifo<card>, 32 bytes per read, and emits onValueChanged(int(float(v*100.0/30000.0))).  These write
 // such records, so the reference's own meter consumer can be fed from igdsp_poll().rms.  open() waits up to

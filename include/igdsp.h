@@ -37,7 +37,8 @@ extern "C" {
  *    conference mix (igdsp_conf_level_q7, igdsp_conf_build, igdsp_conf_mix, IGDSP_FLAG_SATURATED); best signal selection
  *    (igdsp_bss_state, IGDSP_BSS_VOTE_FRAMES, igdsp_bss_select); the jitter buffer (igdsp_jb_state, igdsp_jb_prior, igdsp_jb_rr,
  *    IGDSP_JB_*, igdsp_jb_ring_bytes, igdsp_jb_report, igdsp_jb_receive); packet loss concealment (igdsp_plc_state, IGDSP_PLC_*,
- *    IGDSP_FLAG_CONCEALED, igdsp_plc_conceal). */
+ *    IGDSP_FLAG_CONCEALED, igdsp_plc_conceal); PTT priority arbitration (igdsp_ptt_state, igdsp_ptt_slot, igdsp_ptt_tick, IGDSP_PTT_*,
+ *    igdsp_ptt_arbitrate). */
 #define IGDSP_ABI_VERSION 3
 
 /* ---- error codes (0 == PJ_SUCCESS-style success) ------------------------- */
@@ -678,6 +679,90 @@ int igdsp_bss_select(igdsp_ctx *ctx, const igdsp_rtp_info *d_info,
                      const uint8_t *d_mute, uint32_t n_channels, uint32_t n_groups, uint32_t n_frames, uint32_t samples_per_frame,
                      uint32_t vote_frames, igdsp_bss_state *d_state, uint32_t *d_words,
                      int32_t *d_sel, int16_t *d_out, igdsp_frame_stats *d_stats, void *stream);
+
+/* ---- PTT priority arbitration: who may key a transmitter, the send-direction twin of the receiver vote ------------------------------
+ * Several call-in legs (consoles) may key one frequency.  The reference (inviteMode == CLIENT) arbitrates them in checkEvents
+ * (roip_ed137.cpp:6124-6231) by the PTT type of their ED-137 words (get_IPRadioPttStatus, Functions.cpp:1045-1139): the highest type
+ * takes the transmitter, every other pressed leg is muted by slot volume, and a release is debounced.  igdsp_ptt_arbitrate runs that
+ * loop for n_groups groups (one frequency or transmitter each) over n_frames frames, one tick per frame.
+ *
+ * A group's members are channels, as CSR: member slots k in [group_ptr[g], group_ptr[g + 1]); their ORDER is the reference's
+ * trx_incall order and decides ties.  group_ptr values are clamped to n_members and a descending pair is an empty group, as in
+ * igdsp_bss_select.  Persistent: d_state[g] (igdsp_ptt_state) and d_slots[k] (igdsp_ptt_slot); ALL-ZERO is the reset state of both.
+ * Both are read defensively, so that a garbage state stays in bounds: a holder larger than the group counts as 0, level is taken
+ * & 7, pressed != 0 counts as pressed.
+ *
+ * Per frame f, first per slot (every slot k < n_members steps once per frame, whichever groups list it):
+ *   1. Word.  With c = members[k] < n_channels: slot.word = info[f][c].ed137 iff the frame stores a word; igdsp_bss_select's step 1
+ *      verbatim (!(flags & IGDSP_RTP_RUNT) and pt 0, 8, 18 or 123).
+ *   2. Skip.  c >= n_channels: the leg has no call; the slot is left untouched and takes no part in the tick (:6131).
+ *   3. PTT type.  p = (d_rxonly && d_rxonly[c]) ? 0 : IGDSP_ED137_PTT_TYPE(slot.word)  (TRXMODE_RX, :6134).
+ *   4. Release debounce (:6139-6154, bug for bug):
+ *      - p != last_tx and p == 0: release_cnt = min(release_cnt + 1, 255); if release_cnt < release_frames then p = 1 (the value 1,
+ *        not the old type);
+ *      - p != last_tx and p != 0: release_cnt unchanged;
+ *      - p == last_tx: release_cnt = 0;
+ *      then last_tx = p (the substituted value).
+ * then per group, over its members in order (position pos), with the member's p:
+ *   5. Takeover (:6157-6177): p > level: level = p, holder = pos + 1, takeovers += 1.
+ *   6. Press and release (:6191-6222): p > 0 && !pressed: pressed = 1.  p == 0 && pressed: pressed = 0, holder = 0 if holder ==
+ *      pos + 1, and in either case level = 0.  The reference zeroes ptt_level on ANY pressed leg's release, not only the holder's;
+ *      another pressed leg then re-takes or steals the transmitter later in the same tick or in the next one.  Kept.
+ * After the tick: sel[f][g] = members[b + holder - 1] if a holder exists and that channel is < n_channels, else -1.  tick[f][g]:
+ * sel; level; ptt_id = IGDSP_ED137_PTT_ID of the holder's stored word (0 without a holder); flags = IGDSP_PTT_ON (some member with a
+ * call is pressed after the tick) | IGDSP_PTT_PRESS (some member went pressed in it) | IGDSP_PTT_RELEASE (some member released in
+ * it) | IGDSP_PTT_TAKEOVER (step 5 fired in it); ctl = IGDSP_TX_CTL_SET | (ON ? IGDSP_TX_CTL_PTT : 0).  d_ctl_out[f][g] is the ctl
+ * byte alone, dense: with n_channels = n_groups it is a valid d_ctl[f][c] of igdsp_tx_packetize (it holds sql at 0).
+ * Audio, optional, exactly as igdsp_bss_select's step 4: for the holder's channel c, out[f][g][s] = clamp16(trunc(x * gain[c] / 128))
+ * for s < len[f][c], 0 past it; the record [f][g] over out; zeros and IGDSP_FLAG_EMPTY when nothing is held or len is 0; gain NULL =
+ * 256.  The emit depends on holder only: a holder stays audible after another leg's release zeroed level, as the reference's slot
+ * volume does.
+ * release_frames 0 = IGDSP_PTT_RELEASE_FRAMES; valid 1..255, 1 = no debounce.  F launches of one frame give the same bits (outputs,
+ * state, slots) as one launch of F frames.  The state belongs to one table: rebuilding group_ptr / members means resetting both.
+ * A slot two groups list (only a bad table does) is one leg seen by both; a slot no group lists still steps, and nothing reads it.
+ *
+ * Fidelity.  PINNED to the reference: steps 3-6, the substitute value 1, the level reset on any release, member order.
+ * DIFFERENT ON PURPOSE: (a) the tick is one frame (the reference's 40 ms timer and audio edges), so IGDSP_PTT_RELEASE_FRAMES = 12 is
+ * 6 ticks of 40 ms at 20 ms frames; (b) a leg that was never unmuted is silent, where the reference starts every slot at SLOT_VOLUME
+ * 2.0; (c) one holder replaces the per-leg volumes: equivalent from a reset state, where an unmuted leg is always pressed and a
+ * takeover mutes every other pressed leg.  UNVERIFIED: pjmedia's Q7 level arithmetic, as for igdsp_conf_mix. */
+typedef struct igdsp_ptt_state {  /* per group, 16 bytes; ALL-ZERO = reset */
+    uint32_t level;               /* ptt_level: the PTT type that holds the transmitter (read & 7)                    */
+    uint32_t holder;              /* 1 + position of the unmuted member in the group's member list, 0 = none          */
+    uint32_t takeovers;           /* step 5 firings so far (telemetry, wraps)                                         */
+    uint32_t reserved;            /* kept as it is                                                                    */
+} igdsp_ptt_state;
+typedef struct igdsp_ptt_slot {   /* per member slot, 8 bytes; ALL-ZERO = reset */
+    uint32_t word;                /* the slot's stored ED-137 word                                                    */
+    uint8_t  last_tx;             /* lastTx: the (substituted) PTT type of the last tick                              */
+    uint8_t  release_cnt;         /* lastTxmsec: ticks of the release being debounced, saturating at 255              */
+    uint8_t  pressed;             /* m_PttPressed (any non-zero value is pressed; written as 0 / 1 on a change)       */
+    uint8_t  reserved;            /* kept as it is                                                                    */
+} igdsp_ptt_slot;
+typedef struct igdsp_ptt_tick {   /* per (frame, group), 8 bytes */
+    int32_t  sel;                 /* the unmuted channel, -1 = none                                                   */
+    uint8_t  level;               /* ptt_level after the tick                                                         */
+    uint8_t  ptt_id;              /* PTT id of the holder's stored word, 0 = no holder                                */
+    uint8_t  flags;               /* IGDSP_PTT_*                                                                      */
+    uint8_t  ctl;                 /* IGDSP_TX_CTL_SET | IGDSP_TX_CTL_PTT iff IGDSP_PTT_ON                             */
+} igdsp_ptt_tick;
+#define IGDSP_PTT_ON        0x01
+#define IGDSP_PTT_PRESS     0x02
+#define IGDSP_PTT_RELEASE   0x04
+#define IGDSP_PTT_TAKEOVER  0x08
+#define IGDSP_PTT_RELEASE_FRAMES 12  /* default debounce: 6 ticks of the reference's 40 ms timer at 20 ms frames */
+/* d_info[f][c], d_group_ptr[n_groups + 1], d_state[n_groups] and d_slots[n_members] required (d_members and d_slots may be NULL when
+ * n_members is 0; n_members <= 2^24).  Audio, at most one: d_payload[f][c][n] G.711 with d_codec[c], or d_pcm[f][c][n]; d_len, d_gain
+ * as igdsp_bss_select.  d_rxonly[c] optional.  Outputs, each optional: d_sel[f][g], d_tick[f][g], d_ctl_out[f][g], d_out[f][g][n],
+ * d_stats[f][g]; d_out and d_stats need an audio input.  n = 1..256 always.  n_groups == 0 or n_frames == 0: nothing to do.  Enqueued
+ * on `stream`, not synchronised. */
+int igdsp_ptt_arbitrate(igdsp_ctx *ctx, const igdsp_rtp_info *d_info,
+                        const uint8_t *d_payload, const uint8_t *d_codec, const int16_t *d_pcm, const uint16_t *d_len,
+                        const uint16_t *d_gain, const uint32_t *d_group_ptr, const uint32_t *d_members, uint32_t n_members,
+                        const uint8_t *d_rxonly, uint32_t n_channels, uint32_t n_groups, uint32_t n_frames, uint32_t samples_per_frame,
+                        uint32_t release_frames, igdsp_ptt_state *d_state, igdsp_ptt_slot *d_slots,
+                        int32_t *d_sel, igdsp_ptt_tick *d_tick, uint8_t *d_ctl_out, int16_t *d_out, igdsp_frame_stats *d_stats,
+                        void *stream);
 
 /* ---- Jitter buffer: RTP sequence tracking and playout between depayload and the vote / the bridge ---------------------------------
  * The reference hands every packet but the keep-alives to adapter->stream_rtp_cb (TransportAdapter.cpp:301): the pjmedia stream, which
