@@ -27,6 +27,11 @@ FLAG_SATURATED = 0x10        # igdsp_conf_mix
 BSS_VOTE_FRAMES = 10         # IGDSP_BSS_VOTE_FRAMES
 PTT_RELEASE_FRAMES = 12      # IGDSP_PTT_RELEASE_FRAMES
 PTT_ON, PTT_PRESS, PTT_RELEASE, PTT_TAKEOVER = 1, 2, 4, 8   # IGDSP_PTT_*
+# R2S link supervision (igdsp_link_watch): IGDSP_LINK_*
+LINK_R2S_PERIOD_MS, LINK_MISS_TICKS = 200, 12
+LINK_AUDIO_ON, LINK_AUDIO_OFF, LINK_MISSING, LINK_LATE, LINK_RECOVERED, LINK_CAME_UP = 1, 2, 4, 8, 0x10, 0x20   # kind bits
+LINK_EVENT_DEFAULT = 0x37
+LINK_UP, LINK_AUDIO, LINK_ALARMED = 1, 2, 4                  # state flags
 JB_DEPTH, JB_DELAY = 16, 3   # IGDSP_JB_DEPTH, IGDSP_JB_DELAY
 JB_IDLE, JB_PLAYED, JB_LOST = 1, 2, 3
 JB_PKT_NONE, JB_PKT_INVALID, JB_PKT_KEEPALIVE, JB_PKT_PLACED, JB_PKT_LATE, JB_PKT_DUPLICATE, JB_PKT_RESTART = 0, 1, 2, 3, 4, 5, 6
@@ -57,6 +62,9 @@ BSS_STATE = np.dtype([("count", "<u4"), ("voted", "<u4"), ("on", "<u4"), ("votes
 PTT_STATE = np.dtype([("level", "<u4"), ("holder", "<u4"), ("takeovers", "<u4"), ("reserved", "<u4")], align=True)   # igdsp_ptt_state
 PTT_SLOT = np.dtype([("word", "<u4"), ("last_tx", "u1"), ("release_cnt", "u1"), ("pressed", "u1"), ("reserved", "u1")], align=True)
 PTT_TICK = np.dtype([("sel", "<i4"), ("level", "u1"), ("ptt_id", "u1"), ("flags", "u1"), ("ctl", "u1")], align=True)
+# R2S link supervision (igdsp_link_watch)
+LINK_STATE = np.dtype([("last_ms", "<u8"), ("alarms", "<u4"), ("count", "<u2"), ("flags", "u1"), ("reserved", "u1")], align=True)   # igdsp_link_state
+LINK_EVENT = np.dtype([("channel", "<u4"), ("tick", "<u4"), ("word", "<u4"), ("count", "<u2"), ("kind", "u1"), ("reserved", "u1")], align=True)
 CHAN_PROBE = np.dtype([("run", "<u4"), ("alarms", "<u4")], align=True)
 # the jitter buffer (igdsp_jb_receive / igdsp_jb_report)
 JB_STATE = np.dtype(
@@ -200,6 +208,8 @@ PROTOTYPES = [
                                 _vp]),
     ("igdsp_ptt_arbitrate", _int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp,
                                    _vp, _vp, _vp]),
+    ("igdsp_link_work_bytes", C.c_size_t, [_u32, _u32]),
+    ("igdsp_link_watch", _int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u64, _u32, _u32, _u32, _vp, _vp, _vp, _u32, _vp, _vp, _vp]),
     ("igdsp_jb_ring_bytes", C.c_size_t, [_u32, _u32]),
     ("igdsp_jb_report", _int, [_vp, _vp, _vp]),
     ("igdsp_jb_receive", _int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -296,6 +306,11 @@ def conf_build(channel, port, n_channels: int, n_ports: int):
 def jb_ring_bytes(n_channels: int, n: int = SAMPLES_PER_FRAME) -> int:
     """igdsp_jb_ring_bytes (host only, no GPU): bytes of the jitter-buffer ring of n_channels at n samples per frame."""
     return int(load().igdsp_jb_ring_bytes(n_channels, n))
+
+
+def link_work_bytes(n_channels: int, n_ticks: int) -> int:
+    """igdsp_link_work_bytes (host only, no GPU): bytes of igdsp_link_watch's d_work for a launch of this shape."""
+    return int(load().igdsp_link_work_bytes(n_channels, n_ticks))
 
 
 def jb_report(state, prior) -> np.ndarray:
@@ -488,6 +503,15 @@ class Context:
                                             _ptr(group_ptr), _ptr(members), n_members, _ptr(rxonly), C_, G_, F_, n, release_frames,
                                             _ptr(state), _ptr(slots), _ptr(sel), _ptr(tick), _ptr(ctl_out), _ptr(out), _ptr(stats), stream),
                  "igdsp_ptt_arbitrate")
+
+    def link_watch(self, info, state, C_, T_, S_=1, t0_ms=0, tick_ms=20, sizes=None, up=None, period_ms=None, miss_ticks=0, event_mask=0,
+                   kind=None, events=None, event_cap=0, event_count=None, work=None, stream=None):
+        """igdsp_link_watch: info [T * S][C] RTP_INFO (arrival slots as jb_receive's), sizes [T * S][C] u16 (0 = no packet), up [C] u8,
+        period_ms [C] u16; state [C] LINK_STATE carried across calls; kind [T][C] u8, events [event_cap] LINK_EVENT, event_count [2] u32
+        {events of the launch, events stored}; work: link_work_bytes(C, T) bytes, 16-byte aligned, one per stream (device buffers)."""
+        self._ck(self.L.igdsp_link_watch(self.h, _ptr(info), _ptr(sizes), _ptr(up), _ptr(period_ms), C_, T_, S_, t0_ms & 0xFFFFFFFFFFFFFFFF, tick_ms,
+                                         miss_ticks, event_mask, _ptr(state), _ptr(kind), _ptr(events), event_cap, _ptr(event_count), _ptr(work),
+                                         stream), "igdsp_link_watch")
 
     def jb_receive(self, packets, radio, state, ring, payload, length, info, C_, T_, S_=1, stride=180, n=160, delay=JB_DELAY, sizes=None,
                    arrival=None, tick_flags=None, pkt_status=None, stream=None):

@@ -877,6 +877,43 @@ int igdsp_ptt_arbitrate(igdsp_ctx *ctx, const igdsp_rtp_info *d_info, const uint
                          release_frames, d_state, d_slots, d_sel, d_tick, d_ctl_out, d_out, d_stats, stream, false);
 }
 
+// ---- R2S link supervision and the device event list: the body of detectR2SPacketAndReconn (roip_ed137.cpp:1764-1780, :2009-2040) and
+// the rtpAudio edge of transport_rtp_cb (TransportAdapter.cpp:286-315) ----
+size_t igdsp_link_work_bytes(uint32_t n_channels, uint32_t n_ticks) { return (size_t)link_work_bytes(n_channels, n_ticks); }
+
+// igdsp_link_watch, or with yardstick its compute-free twin igdsp_internal_link_copy
+static int link_watch(igdsp_ctx *ctx, const igdsp_rtp_info *d_info, const uint16_t *d_sizes, const uint8_t *d_up, const uint16_t *d_period_ms,
+                      uint32_t C, uint32_t T, uint32_t S, uint64_t t0_ms, uint32_t tick_ms, uint32_t miss_ticks, uint32_t event_mask,
+                      igdsp_link_state *d_state, uint8_t *d_kind, igdsp_link_event *d_events, uint32_t event_cap, uint32_t *d_event_count,
+                      void *d_work, void *stream, bool yardstick)
+{
+    if (!ctx) return IGDSP_EINVAL;
+    if (S == 0 || S > IGDSP_STAGE_DEPTH || tick_ms == 0 || miss_ticks > 65535u) return IGDSP_EINVAL;   // always checked
+    if (!d_events && event_cap) return IGDSP_EINVAL;
+    const bool list = d_event_count != nullptr;
+    if (list && (!d_work || (reinterpret_cast<uintptr_t>(d_work) & 15u))) return IGDSP_EINVAL;
+    const uintptr_t a2 = reinterpret_cast<uintptr_t>(d_sizes) | reinterpret_cast<uintptr_t>(d_period_ms);
+    const uintptr_t a4 = reinterpret_cast<uintptr_t>(d_info) | reinterpret_cast<uintptr_t>(d_events) | reinterpret_cast<uintptr_t>(d_event_count);
+    if ((a2 & 1u) || (a4 & 3u) || (reinterpret_cast<uintptr_t>(d_state) & 7u)) return IGDSP_EINVAL;
+    const bool work = (uint64_t)C * T != 0;
+    if (work && (!d_info || !d_state)) return IGDSP_EINVAL;
+    if ((uint64_t)C * T * S >= 0xFFFFFFE0ull) return IGDSP_ERANGE;                             // list indices and counts are 32-bit
+    if (!work && !list) return IGDSP_OK;                                                     // nothing to do, nothing to write
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, launch_link_watch(cfg_of(ctx, pick(ctx, stream)), d_info, d_sizes, d_up, d_period_ms, C, T, S, t0_ms, tick_ms, miss_ticks, event_mask,
+                                   d_state, d_kind, d_events, event_cap, d_event_count, d_work, yardstick, pick(ctx, stream)));
+    return IGDSP_OK;
+}
+
+int igdsp_link_watch(igdsp_ctx *ctx, const igdsp_rtp_info *d_info, const uint16_t *d_sizes, const uint8_t *d_up, const uint16_t *d_period_ms,
+                     uint32_t n_channels, uint32_t n_ticks, uint32_t slots_per_tick, uint64_t t0_ms, uint32_t tick_ms, uint32_t miss_ticks,
+                     uint32_t event_mask, igdsp_link_state *d_state, uint8_t *d_kind, igdsp_link_event *d_events, uint32_t event_cap,
+                     uint32_t *d_event_count, void *d_work, void *stream)
+{
+    return link_watch(ctx, d_info, d_sizes, d_up, d_period_ms, n_channels, n_ticks, slots_per_tick, t0_ms, tick_ms, miss_ticks, event_mask, d_state,
+                      d_kind, d_events, event_cap, d_event_count, d_work, stream, false);
+}
+
 // ---- jitter buffer: the pjmedia stream behind adapter->stream_rtp_cb (TransportAdapter.cpp:301): RFC 3550 A.1 / A.3 / A.8 and playout ----
 size_t igdsp_jb_ring_bytes(uint32_t n_channels, uint32_t samples_per_frame)
 {
@@ -1374,6 +1411,18 @@ int igdsp_internal_ptt_copy(igdsp_ctx *ctx, const igdsp_rtp_info *d_info, const 
 {
     return ptt_arbitrate(ctx, d_info, d_payload, d_codec, d_pcm, d_len, d_gain, d_group_ptr, d_members, n_members, d_rxonly, C, G, F, n,
                          release_frames, d_state, d_slots, d_sel, d_tick, d_ctl_out, d_out, d_stats, stream, true);
+}
+
+// Calibration-only (not in include/igdsp.h): the compute-free yardstick of igdsp_link_watch (tools/link_bench.py) — the same passes
+// (count, scan and write with a list, one pass without), the same records and sizes read, the state stored as it was read, kind bytes
+// of 0 and an empty list; no state machine.  Arguments as igdsp_link_watch.
+int igdsp_internal_link_copy(igdsp_ctx *ctx, const igdsp_rtp_info *d_info, const uint16_t *d_sizes, const uint8_t *d_up, const uint16_t *d_period_ms,
+                             uint32_t n_channels, uint32_t n_ticks, uint32_t slots_per_tick, uint64_t t0_ms, uint32_t tick_ms, uint32_t miss_ticks,
+                             uint32_t event_mask, igdsp_link_state *d_state, uint8_t *d_kind, igdsp_link_event *d_events, uint32_t event_cap,
+                             uint32_t *d_event_count, void *d_work, void *stream)
+{
+    return link_watch(ctx, d_info, d_sizes, d_up, d_period_ms, n_channels, n_ticks, slots_per_tick, t0_ms, tick_ms, miss_ticks, event_mask, d_state,
+                      d_kind, d_events, event_cap, d_event_count, d_work, stream, true);
 }
 
 // Calibration-only (not in include/igdsp.h): the compute-free yardstick of igdsp_plc_conceal (tools/plc_bench.py) — the same

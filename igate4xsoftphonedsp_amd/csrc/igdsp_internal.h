@@ -102,6 +102,14 @@ hipError_t launch_ptt_arbitrate(const LaunchCfg &cfg, const igdsp_rtp_info *info
                                 uint32_t n_members, const uint8_t *rxonly, uint32_t C, uint32_t G, uint32_t F, uint32_t n,
                                 uint32_t release_frames, igdsp_ptt_state *state, igdsp_ptt_slot *slots, int32_t *sel, igdsp_ptt_tick *tick,
                                 uint8_t *ctl_out, int16_t *out, igdsp_frame_stats *stats, bool yardstick, hipStream_t s);
+// igdsp_link_watch: sizes, up, period, kind may each be nullptr; event_count nullptr = no list (one pass, work unused), else work is
+// igdsp_link_work_bytes(C, T) bytes, 16-byte aligned; miss_ticks 0 = IGDSP_LINK_MISS_TICKS, event_mask 0 = IGDSP_LINK_EVENT_DEFAULT.
+// C * T == 0 with a list: only the two counts are written (0).  yardstick: the compute-free form, the same passes, the same bytes read
+// and written, no state machine: the state is stored as it was read, the kind bytes are 0 and the list is empty
+hipError_t launch_link_watch(const LaunchCfg &cfg, const igdsp_rtp_info *info, const uint16_t *sizes, const uint8_t *up, const uint16_t *period,
+                             uint32_t C, uint32_t T, uint32_t S, uint64_t t0_ms, uint32_t tick_ms, uint32_t miss_ticks, uint32_t event_mask,
+                             igdsp_link_state *state, uint8_t *kind, igdsp_link_event *events, uint32_t event_cap, uint32_t *event_count,
+                             void *work, bool yardstick, hipStream_t s);
 // igdsp_jb_receive: sizes, arrival, tick, pkt may each be nullptr; ring is igdsp_jb_ring_bytes(C, n) bytes, 16-byte aligned.
 // yardstick: the compute-free form, the same rows as an in-order lossless launch (arrival slot k = 0 of every tick played straight from
 // the packet), no header walk, state machine or ring store; the state is not touched

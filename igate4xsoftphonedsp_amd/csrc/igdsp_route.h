@@ -525,6 +525,48 @@ inline PttRoute ptt_route(uint32_t G, uint32_t F, uint32_t n, uint32_t n_members
     return r;
 }
 
+// ---- igdsp_link_watch (launch_link_watch): k_link_watch<COPY, PASS, SIZES> + k_link_scan.  A lane owns a channel for the ticks of one part
+// (<= kLinkPart ticks) and walks the part's arrival slots in order, kLinkU record loads in flight; a wave is 64 consecutive channels.
+// Without an event list one pass (kLinkSingle) walks and stores the state and the kind bytes.  With a list a part takes three
+// launches: the count pass (kLinkCount) walks and leaves the number of event lanes per (tick, wave) in d_work, tick-major; k_link_scan
+// (one block) turns the counts into exclusive offsets in place, starting at the offset the launch's earlier parts reached (d_work's
+// header carries it) and writes the two totals after the last part; the write pass (kLinkWrite) replays the walk from the same state
+// and stores the state, the kind bytes and each event at its wave's offset plus the lane's rank among the wave's event lanes.
+// Nothing is read back within a kernel: the hand-offs are kernel boundaries on the stream.
+constexpr int kLinkWaves = 4;                             // waves per block, independent of each other
+constexpr uint32_t kLinkPart = 128;                       // ticks per part
+constexpr uint32_t kLinkU = 16;                           // record loads of a lane in flight together
+constexpr uint32_t kLinkScanThreads = 1024;               // k_link_scan: one block
+constexpr uint32_t kLinkWorkHead = 16;                    // d_work: {offset reached, 0, 0, 0}, then the counts / offsets [part ticks][waves]
+enum : int { kLinkSingle = 0, kLinkCount = 1, kLinkWrite = 2 };   // k_link_watch<COPY, PASS, SIZES>
+struct LinkRoute {
+    uint32_t waves = 0;                    // waves of 64 channels: the row of the counts
+    uint32_t grid = 0, threads = 0;        // k_link_watch, every pass of every part
+    uint32_t part_ticks = 0, parts = 0;    // the last part takes the rest
+    uint32_t passes = 0;                   // walks per part: 1, or 2 with a list
+    uint32_t scan_threads = 0;             // k_link_scan, every part (0: no list)
+    uint64_t work_bytes = 0;               // what the launch uses of d_work (0: no list)
+};
+inline uint32_t link_waves(uint32_t C) { return C / 64u + (C % 64u != 0u ? 1u : 0u); }
+inline uint64_t link_work_bytes(uint32_t C, uint32_t T)
+{
+    return kLinkWorkHead + (((uint64_t)std::min(T, kLinkPart) * link_waves(C) * 4u + 15u) & ~15ull);
+}
+inline LinkRoute link_route(uint32_t C, uint32_t T, bool list)
+{
+    LinkRoute r;
+    if ((uint64_t)C * T == 0) return r;
+    r.waves = link_waves(C);
+    r.grid = (r.waves + kLinkWaves - 1) / kLinkWaves;
+    r.threads = kLinkWaves * 64;
+    r.part_ticks = std::min(T, kLinkPart);
+    r.parts = (T + kLinkPart - 1) / kLinkPart;
+    r.passes = list ? 2u : 1u;
+    r.scan_threads = list ? kLinkScanThreads : 0u;
+    r.work_bytes = list ? link_work_bytes(C, T) : 0u;
+    return r;
+}
+
 // ---- igdsp_jb_receive (launch_jb_receive): k_jb_receive<COPY>.  A wave owns kJbCh consecutive channels for the ticks
 // of one part (<= kJbPart ticks).  Lanes 0 .. kJbCh - 1 step their channel's state machine over the part's arrivals with the ring tags in
 // LDS and leave a source descriptor per (tick, channel) there: an arrival of the part, a ring slot, or none; then the whole wave writes

@@ -635,6 +635,128 @@ int igdsp_host_ptt_leg(void *v, int leg, int *last_tx, int *release_cnt, int *pr
     return IGDSP_OK;
 }
 
+// ---- R2S link supervision (roip_ed137.cpp:1764-1780, :2009-2040; TransportAdapter.cpp:286-315), no context needed
+LinkWatch::LinkWatch(int n_legs) : nLegs(n_legs < 1 ? 1 : n_legs), missTicks(IGDSP_LINK_MISS_TICKS), now(0), leg(new Leg[n_legs < 1 ? 1 : n_legs])
+{
+    for (int i = 0; i < nLegs; ++i) {
+        Leg &l = leg[i];
+        l.callState = false; l.r2sPacket = 0; l.rtpAudio = false; l.r2sCount = 0; l.r2sPeriod = IGDSP_LINK_R2S_PERIOD_MS; l.alarmed = false;
+        l.alarms = 0; l.kind = 0; l.word = 0;
+    }
+}
+
+LinkWatch::~LinkWatch() { delete[] leg; }
+
+void LinkWatch::beginTick(unsigned long long now_ms, const bool *call_up)
+{
+    now = now_ms;
+    for (int i = 0; i < nLegs; ++i) {
+        Leg &l = leg[i];
+        const bool up = call_up ? call_up[i] : true;
+        l.kind = 0; l.word = 0;
+        if (up && !l.callState) {                            // transport_adapter_create (TransportAdapter.cpp:122, TransportAdapter.h:91)
+            l.r2sPacket = now; l.r2sCount = 0; l.rtpAudio = false; l.alarmed = false;
+            l.kind |= IGDSP_LINK_CAME_UP;
+        }
+        l.callState = up;
+    }
+}
+
+int LinkWatch::packet(int i, int pt, unsigned payload_len, bool runt, uint32_t ed137)
+{
+    if (i < 0 || i >= nLegs || !leg[i].callState) return 0;
+    Leg &l = leg[i];
+    l.r2sPacket = now;                                       // every return path of transport_rtp_cb
+    if (runt || (pt != 123 && payload_len >= 1024)) return 0;   // :286-291
+    if (pt != 123) {                                         // :298-307
+        if (l.rtpAudio == false) { l.rtpAudio = true; l.kind |= IGDSP_LINK_AUDIO_ON; l.word = ed137; return IGDSP_LINK_AUDIO_ON; }
+        l.rtpAudio = true;
+    } else {                                                 // :308-315
+        if (l.rtpAudio == true) { l.rtpAudio = false; l.kind |= IGDSP_LINK_AUDIO_OFF; l.word = ed137; return IGDSP_LINK_AUDIO_OFF; }
+        l.rtpAudio = false;
+    }
+    return 0;
+}
+
+int LinkWatch::endTick()
+{
+    int missing = 0;
+    for (int i = 0; i < nLegs; ++i) {
+        Leg &l = leg[i];
+        if (!l.callState) continue;
+        const long long secDiff = (long long)(now - l.r2sPacket);   // qint64, :1768
+        if (secDiff > (long long)l.r2sPeriod * 3) {          // :1769
+            l.kind |= IGDSP_LINK_LATE;
+            if (l.r2sCount == missTicks - 1) {               // :1771 r2sCount == 5
+                l.kind |= IGDSP_LINK_MISSING; l.alarmed = true; ++l.alarms; ++missing;
+            }
+            if (l.r2sCount < 65535) l.r2sCount++;
+        } else {
+            if (l.r2sCount > 0) l.kind |= IGDSP_LINK_RECOVERED;
+            l.r2sCount = 0;
+            l.alarmed = false;
+        }
+    }
+    return missing;
+}
+
+void *igdsp_host_link_new(int n_legs, int miss_ticks)
+{
+    if (n_legs < 1 || n_legs > 65536 || miss_ticks < 0 || miss_ticks > 65535) return nullptr;
+    LinkWatch *v = nullptr;
+    try { v = new LinkWatch(n_legs); } catch (...) { return nullptr; }
+    if (miss_ticks) v->missTicks = miss_ticks;
+    return v;
+}
+void igdsp_host_link_free(void *v) { delete static_cast<LinkWatch *>(v); }
+int igdsp_host_link_set_period(void *v, int leg, int period_ms)
+{
+    LinkWatch *a = static_cast<LinkWatch *>(v);
+    if (!a || leg < 0 || leg >= a->nLegs || period_ms < 0 || period_ms > 65535) return IGDSP_EINVAL;
+    a->leg[leg].r2sPeriod = period_ms;
+    return IGDSP_OK;
+}
+int igdsp_host_link_begin(void *v, unsigned long long now_ms, const int *call_up)
+{
+    LinkWatch *a = static_cast<LinkWatch *>(v);
+    if (!a) return IGDSP_EINVAL;
+    if (!call_up) { a->beginTick(now_ms, nullptr); return IGDSP_OK; }
+    bool *up = new (std::nothrow) bool[a->nLegs];
+    if (!up) return IGDSP_ENOMEM;
+    for (int i = 0; i < a->nLegs; ++i) up[i] = call_up[i] != 0;
+    a->beginTick(now_ms, up);
+    delete[] up;
+    return IGDSP_OK;
+}
+int igdsp_host_link_packet(void *v, int leg, int pt, unsigned payload_len, int runt, uint32_t ed137)
+{
+    LinkWatch *a = static_cast<LinkWatch *>(v);
+    if (!a || leg < 0 || leg >= a->nLegs) return IGDSP_EINVAL;
+    return a->packet(leg, pt, payload_len, runt != 0, ed137);
+}
+int igdsp_host_link_end(void *v, uint8_t *kinds, uint32_t *words)
+{
+    LinkWatch *a = static_cast<LinkWatch *>(v);
+    if (!a) return IGDSP_EINVAL;
+    const int missing = a->endTick();
+    for (int i = 0; i < a->nLegs; ++i) {
+        if (kinds) kinds[i] = (uint8_t)a->leg[i].kind;
+        if (words) words[i] = a->leg[i].word;
+    }
+    return missing;
+}
+int igdsp_host_link_leg(void *v, int leg, unsigned long long *last_ms, int *count, int *flags, unsigned *alarms)
+{
+    const LinkWatch *a = static_cast<const LinkWatch *>(v);
+    if (!a || leg < 0 || leg >= a->nLegs) return IGDSP_EINVAL;
+    const LinkWatch::Leg &l = a->leg[leg];
+    if (last_ms) *last_ms = l.r2sPacket;
+    if (count) *count = l.r2sCount;
+    if (flags) *flags = (l.callState ? IGDSP_LINK_UP : 0) | (l.rtpAudio ? IGDSP_LINK_AUDIO : 0) | (l.alarmed ? IGDSP_LINK_ALARMED : 0);
+    if (alarms) *alarms = l.alarms;
+    return IGDSP_OK;
+}
+
 // ---- conference receive levels, no context needed
 void *igdsp_host_levels_new(uint32_t n_channels)
 {

@@ -159,6 +159,41 @@ public:
     int unmutedLeg() const;
 };
 
+// R2S link supervision, the timer body of RoIP_ED137::detectR2SPacketAndReconn (roip_ed137.cpp:1764-1780, :2009-2040) and the tail of
+// transport_rtp_cb that feeds it (TransportAdapter.cpp:286-315), restated literally and without a context over tp_adapter-shaped legs:
+// r2sPacket, rtpAudio, r2sCount, r2sPeriod and callState.  A host that keeps the supervision on the CPU calls beginTick() where the
+// timer fires, packet() where transport_rtp_cb runs and endTick() where the timer checks; igdsp_link_watch is the same steps on the
+// device, one tick per frame, every packet stamped with its tick's time.
+class LinkWatch {
+public:
+    struct Leg {
+        bool callState;                      // the call is up (the per-leg block runs)
+        unsigned long long r2sPacket;        // ms of the last packet of any kind
+        bool rtpAudio;
+        int r2sCount;                        // saturating at 65535
+        int r2sPeriod;                       // ms, 200 in the reference
+        bool alarmed;                        // the hang-up condition fired in this outage
+        unsigned alarms;                     // times it fired (telemetry)
+        int kind;                            // IGDSP_LINK_* of the tick so far
+        uint32_t word;                       // ed137 of the tick's last edge packet, else 0
+    };
+    explicit LinkWatch(int n_legs);
+    ~LinkWatch();
+    int nLegs;
+    int missTicks;                           // 6 in the reference (r2sCount == 5); IGDSP_LINK_MISS_TICKS at one tick per frame
+    unsigned long long now;                  // the tick's time
+    Leg *leg;
+    // The tick begins: call_up[i] = the leg's callState (NULL: all up).  A leg that comes up is stamped and reset.
+    void beginTick(unsigned long long now_ms, const bool *call_up);
+    // One received packet (transport_rtp_cb): returns the edge it made, IGDSP_LINK_AUDIO_ON / _OFF or 0.
+    int packet(int i, int pt, unsigned payload_len, bool runt, uint32_t ed137);
+    // The timer's check: returns the number of legs whose hang-up condition fired; leg[i].kind holds every leg's kind byte.
+    int endTick();
+private:
+    LinkWatch(const LinkWatch &);
+    LinkWatch &operator=(const LinkWatch &);
+};
+
 class RoIP_ED137 {
 public:
     // Unlike the reference singleton (roip_ed137.cpp:192) the instance owns an igdsp context; device < 0
@@ -245,6 +280,15 @@ void  igdsp_host_ptt_free(void *v);
 int   igdsp_host_ptt_tick(void *v, const uint32_t *words, const int *call_up, const int *rx_only);
 int   igdsp_host_ptt_state(void *v, int *level, unsigned *takeovers, int *flags);
 int   igdsp_host_ptt_leg(void *v, int leg, int *last_tx, int *release_cnt, int *pressed, int *unmuted);
+// R2S link supervision without a context (LinkWatch, 1 .. 65 536 legs): begin / packet / end as the class; miss_ticks 0 = the default,
+// call_up and the outputs of _end may be NULL; _end returns the number of MISSING legs (IGDSP_EINVAL for a NULL handle or a bad leg)
+void *igdsp_host_link_new(int n_legs, int miss_ticks);
+void  igdsp_host_link_free(void *v);
+int   igdsp_host_link_set_period(void *v, int leg, int period_ms);
+int   igdsp_host_link_begin(void *v, unsigned long long now_ms, const int *call_up);
+int   igdsp_host_link_packet(void *v, int leg, int pt, unsigned payload_len, int runt, uint32_t ed137);
+int   igdsp_host_link_end(void *v, uint8_t *kinds, uint32_t *words);
+int   igdsp_host_link_leg(void *v, int leg, unsigned long long *last_ms, int *count, int *flags, unsigned *alarms);
 // Meter output on the reference's other channel: AudioMeter (audiometer.cpp:11-34) reads ASCII decimal levels from the
 // FIFO /tmp/capturefifo<card>, 32 bytes per read, and emits onValueChanged(int(float(v*100.0/30000.0))).  These write
 // such records, so the reference's own meter consumer can be fed from igdsp_poll().rms.  open() waits up to

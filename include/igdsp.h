@@ -38,7 +38,8 @@ extern "C" {
  *    (igdsp_bss_state, IGDSP_BSS_VOTE_FRAMES, igdsp_bss_select); the jitter buffer (igdsp_jb_state, igdsp_jb_prior, igdsp_jb_rr,
  *    IGDSP_JB_*, igdsp_jb_ring_bytes, igdsp_jb_report, igdsp_jb_receive); packet loss concealment (igdsp_plc_state, IGDSP_PLC_*,
  *    IGDSP_FLAG_CONCEALED, igdsp_plc_conceal); PTT priority arbitration (igdsp_ptt_state, igdsp_ptt_slot, igdsp_ptt_tick, IGDSP_PTT_*,
- *    igdsp_ptt_arbitrate). */
+ *    igdsp_ptt_arbitrate); R2S link supervision and the device event list (igdsp_link_state, igdsp_link_event, IGDSP_LINK_*,
+ *    igdsp_link_work_bytes, igdsp_link_watch). */
 #define IGDSP_ABI_VERSION 3
 
 /* ---- error codes (0 == PJ_SUCCESS-style success) ------------------------- */
@@ -763,6 +764,92 @@ int igdsp_ptt_arbitrate(igdsp_ctx *ctx, const igdsp_rtp_info *d_info,
                         uint32_t release_frames, igdsp_ptt_state *d_state, igdsp_ptt_slot *d_slots,
                         int32_t *d_sel, igdsp_ptt_tick *d_tick, uint8_t *d_ctl_out, int16_t *d_out, igdsp_frame_stats *d_stats,
                         void *stream);
+
+/* ---- R2S link supervision and the device event list: the body of the reference's 40 ms timer ------------------------------------------
+ * Every received packet refreshes a leg's timestamp (adapter->r2sPacket, TransportAdapter.cpp:122,289,302,311, read through
+ * get_R2SStatus); the reference's timer (detectR2SPacketAndReconn, roip_ed137.cpp:1756) hangs a call up with WG-67 cause 2001
+ * "missing R2S KeepAlive" when the timestamp is older than 3 * r2sPeriod for six ticks in a row (roip_ed137.cpp:1764-1780, :2009-2040).
+ * The same callback keeps adapter->rtpAudio: the first audio packet after keep-alives, or the first keep-alive after audio, is what
+ * makes the reference call setIncomingED137Value -> checkEvents (TransportAdapter.cpp:298-315).  igdsp_link_watch runs both per
+ * channel over n_ticks ticks on igdsp_depayload's records and hands back only what changed: a kind byte per (tick, channel) and a
+ * compacted list of the (tick, channel) pairs whose kind meets event_mask, small enough to copy back every tick.
+ *
+ * Layout.  Arrival slots are igdsp_jb_receive's: a = t * slots_per_tick + k, k = 0 .. slots_per_tick - 1 the arrival order within
+ * tick t, slots_per_tick = 1 .. IGDSP_STAGE_DEPTH.  d_info[a][c]: the records igdsp_depayload wrote for those slots.  d_sizes[a][c]
+ * == 0: no packet in the slot; d_sizes NULL: every slot holds one.  now(t) = t0_ms + (uint64_t)t * tick_ms in wrapping uint64
+ * arithmetic; every packet of tick t is stamped now(t).  Persistent: d_state[c] (igdsp_link_state); ALL-ZERO is the reset state (the
+ * call is not up).  Bits of flags other than IGDSP_LINK_UP | _AUDIO | _ALARMED, and reserved, are kept as they are.
+ *
+ * Per tick t and channel c, in tick order, with kind = 0, word = 0, period = d_period_ms ? d_period_ms[c] : IGDSP_LINK_R2S_PERIOD_MS:
+ *   1. Up.  d_up && !d_up[c]: clear IGDSP_LINK_UP, leave everything else, and end the tick with kind = 0 (the reference's else branch;
+ *      its reconnect counter stays on the host).  Otherwise, if IGDSP_LINK_UP is clear: last_ms = now, count = 0, clear AUDIO and
+ *      ALARMED, set UP, kind |= CAME_UP (transport_adapter_create, TransportAdapter.cpp:122 and TransportAdapter.h:91).
+ *   2. Arrivals, k in order.  Every slot that holds a packet sets last_ms = now (every return path of transport_rtp_cb refreshes it).
+ *      - keep-alive (!(flags & IGDSP_RTP_RUNT) && pt == 123): if AUDIO is set, clear it, kind |= AUDIO_OFF, word = info.ed137;
+ *      - audio (!(flags & IGDSP_RTP_RUNT) && pt != 123 && payload_len < 1024, TransportAdapter.cpp:286,298): if AUDIO is clear, set it,
+ *        kind |= AUDIO_ON, word = info.ed137;
+ *      - anything else (runts, payloads of 1024 or more) only refreshes last_ms.
+ *   3. Supervise (roip_ed137.cpp:1767-1780).  diff = (int64_t)(now - last_ms); a last_ms ahead of now gives a negative diff, which is
+ *      never late, as with the reference's qint64.  diff > 3 * (int64_t)period: kind |= LATE; if count == miss_ticks - 1 then kind |=
+ *      MISSING, set ALARMED, alarms += 1; count = min(count + 1, 65535).  Else: if count > 0 then kind |= RECOVERED; count = 0, clear
+ *      ALARMED.  MISSING fires once per outage, exactly where the reference's r2sCount == 5 does with miss_ticks 6 and tick_ms 40.
+ *
+ * Outputs.  d_kind[t][c] (optional): the kind byte.  (t, c) is an event iff kind & event_mask (event_mask 0 = IGDSP_LINK_EVENT_DEFAULT).
+ * Events are written to d_events in tick-major, then ascending channel order; d_event_count[0] = the number of events of the launch,
+ * d_event_count[1] = min(that, event_cap), the number stored: the first event_cap events in that order are kept and nothing is ever
+ * written past d_events[event_cap).  d_events may be NULL iff event_cap == 0; d_event_count may be NULL, then no list is produced.
+ * Each launch starts its list at index 0.
+ * State.  n_ticks launches of one tick, t0_ms advanced each time, give the same state bytes, kind bytes and events as one launch of
+ * n_ticks ticks (each event's tick shifted by its launch).
+ * Arguments.  miss_ticks 0 = IGDSP_LINK_MISS_TICKS, valid 1 .. 65535; tick_ms >= 1; d_work (igdsp_link_work_bytes bytes, 16-byte
+ * aligned) is required when a list is requested, and every stream that launches needs its own; d_info and d_state are required
+ * unless there is nothing to do.  n_channels == 0 or n_ticks == 0: nothing to do, the counts are written as 0.  Violations return
+ * IGDSP_EINVAL before any launch (n_channels * n_ticks * slots_per_tick >= 2^32 - 32: IGDSP_ERANGE).  Enqueued on `stream`, not
+ * synchronised.
+ *
+ * Fidelity.  PINNED to the reference: steps 2 and 3, the refresh on every packet (runts and oversize payloads included), the < 1024
+ * rule, the comparison of the count with miss_ticks - 1 before the increment.  DIFFERENT ON PURPOSE: (a) the tick is one frame, so
+ * IGDSP_LINK_MISS_TICKS = 12 is 6 ticks of the reference's 40 ms timer at 20 ms frames; (b) packets are stamped with their tick's
+ * time, not the wall clock; (c) count saturates at 65535 where r2sCount is an int; (d) non-radio legs follow the same < 1024 rule,
+ * where the reference reads a stale static rtphdr; (e) the hang-up itself, a SIP action, stays on the host: MISSING is its cue. */
+#define IGDSP_LINK_R2S_PERIOD_MS 200   /* roip_ed137.h:685 */
+#define IGDSP_LINK_MISS_TICKS     12   /* 6 ticks of the reference's 40 ms timer at 20 ms frames */
+/* kind bits, per (tick, channel) */
+#define IGDSP_LINK_AUDIO_ON   0x01     /* rtpAudio 0 -> 1 on an audio packet of this tick   */
+#define IGDSP_LINK_AUDIO_OFF  0x02     /* rtpAudio 1 -> 0 on a keep-alive of this tick      */
+#define IGDSP_LINK_MISSING    0x04     /* the hang-up condition fired in this tick          */
+#define IGDSP_LINK_LATE       0x08     /* diff > 3 * period at this tick's check            */
+#define IGDSP_LINK_RECOVERED  0x10     /* count went from > 0 to 0 in this tick             */
+#define IGDSP_LINK_CAME_UP    0x20     /* the call came up in this tick                     */
+#define IGDSP_LINK_EVENT_DEFAULT 0x37  /* every kind but LATE */
+/* state flags */
+#define IGDSP_LINK_UP       0x01
+#define IGDSP_LINK_AUDIO    0x02
+#define IGDSP_LINK_ALARMED  0x04
+typedef struct igdsp_link_state {      /* per channel, 16 bytes, ALL-ZERO = reset (call not up) */
+    uint64_t last_ms;                  /* adapter->r2sPacket                                   */
+    uint32_t alarms;                   /* MISSING firings so far (telemetry, wraps)            */
+    uint16_t count;                    /* r2sCount, saturating at 65535                        */
+    uint8_t  flags;                    /* IGDSP_LINK_UP | _AUDIO | _ALARMED; other bits kept   */
+    uint8_t  reserved;                 /* kept as it is                                        */
+} igdsp_link_state;
+typedef struct igdsp_link_event {      /* 16 bytes */
+    uint32_t channel;
+    uint32_t tick;                     /* t within this launch                                 */
+    uint32_t word;                     /* ed137 of the tick's last edge packet, else 0         */
+    uint16_t count;                    /* state count after the tick                           */
+    uint8_t  kind;                     /* the whole kind byte of (tick, channel)               */
+    uint8_t  reserved;                 /* 0 */
+} igdsp_link_event;
+/* bytes of d_work for a launch of this shape (host-only; grows with min(n_ticks, 128) and n_channels / 64) */
+size_t igdsp_link_work_bytes(uint32_t n_channels, uint32_t n_ticks);
+int igdsp_link_watch(igdsp_ctx *ctx, const igdsp_rtp_info *d_info, const uint16_t *d_sizes,
+                     const uint8_t *d_up, const uint16_t *d_period_ms,
+                     uint32_t n_channels, uint32_t n_ticks, uint32_t slots_per_tick,
+                     uint64_t t0_ms, uint32_t tick_ms, uint32_t miss_ticks, uint32_t event_mask,
+                     igdsp_link_state *d_state, uint8_t *d_kind,
+                     igdsp_link_event *d_events, uint32_t event_cap, uint32_t *d_event_count,
+                     void *d_work, void *stream);
 
 /* ---- Jitter buffer: RTP sequence tracking and playout between depayload and the vote / the bridge ---------------------------------
  * The reference hands every packet but the keep-alives to adapter->stream_rtp_cb (TransportAdapter.cpp:301): the pjmedia stream, which
