@@ -36,6 +36,7 @@ JB_DEPTH, JB_DELAY = 16, 3   # IGDSP_JB_DEPTH, IGDSP_JB_DELAY
 JB_IDLE, JB_PLAYED, JB_LOST = 1, 2, 3
 JB_PKT_NONE, JB_PKT_INVALID, JB_PKT_KEEPALIVE, JB_PKT_PLACED, JB_PKT_LATE, JB_PKT_DUPLICATE, JB_PKT_RESTART = 0, 1, 2, 3, 4, 5, 6
 JB_HEARD, JB_PLAYING, JB_TRANSIT = 1, 2, 4
+JB_ADAPT_MIN, JB_ADAPT_MAX, JB_ADAPT_MULT, JB_ADAPT_LATE_RESTART, JB_ADAPT_SET = 1, 12, 4, 3, 1   # IGDSP_JB_ADAPT_*
 PLC_PMIN, PLC_PMAX, PLC_SPAN, PLC_HIST, PLC_FLAT, PLC_STEP = 40, 120, 160, 280, 80, 82   # IGDSP_PLC_*
 FLAG_CONCEALED = 0x20        # igdsp_plc_conceal
 AGG_MAX_RANKS = 8
@@ -83,6 +84,11 @@ PLC_STATE = np.dtype(
 JB_PRIOR = np.dtype([("expected_prior", "<u4"), ("received_prior", "<u4"), ("epoch", "<u4"), ("reserved", "<u4")], align=True)
 JB_RR = np.dtype([("ssrc", "<u4"), ("ext_max_seq", "<u4"), ("cum_lost", "<i4"), ("jitter", "<u4"), ("fraction_lost", "u1"), ("valid", "u1"),
                   ("reserved", "<u2")], align=True)
+# the adaptive playout delay (igdsp_jb_receive_adaptive / igdsp_jb_adapt_next)
+JB_ADAPT_CFG = np.dtype([("min_frames", "u1"), ("max_frames", "u1"), ("init_frames", "u1"), ("jitter_mult", "u1"), ("late_restart", "u1"),
+                         ("reserved", "u1", (3,))], align=True)   # igdsp_jb_adapt_cfg
+JB_ADAPT = np.dtype([("delay", "u1"), ("flags", "u1"), ("need", "u1"), ("late_run", "u1"), ("grows", "<u2"), ("shrinks", "<u2")],
+                    align=True)   # igdsp_jb_adapt
 GATE_ALWAYS, GATE_SQU, GATE_PTT, GATE_SQU_OR_PTT = 0, 1, 2, 3
 PKT_SLOTS, PKT_PACKED, PKT_MIXED = 0, 1, 2
 PROBE_ALARM = 500
@@ -213,6 +219,10 @@ PROTOTYPES = [
     ("igdsp_jb_ring_bytes", C.c_size_t, [_u32, _u32]),
     ("igdsp_jb_report", _int, [_vp, _vp, _vp]),
     ("igdsp_jb_receive", _int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("igdsp_jb_adapt_cfg_default", None, [_vp]),
+    ("igdsp_jb_adapt_next", _int, [_vp, _u32, _u32, _vp]),
+    ("igdsp_jb_receive_adaptive", _int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                         _vp]),
     ("igdsp_plc_conceal", _int, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
     ("igdsp_g726_reorder", _int, [_vp, _vp, _vp, _u64, _int, _vp]),
     ("igdsp_gen_uniform", _int, [_vp, _vp, _u64, _u64, _u64, _vp]),
@@ -323,6 +333,36 @@ def jb_report(state, prior) -> np.ndarray:
     if rc != 0:
         raise IgdspError(rc, "igdsp_jb_report")
     return out
+
+
+def jb_adapt_cfg_default() -> np.ndarray:
+    """igdsp_jb_adapt_cfg_default (host only, no GPU): the default JB_ADAPT_CFG record."""
+    cfg = np.zeros((), dtype=JB_ADAPT_CFG)
+    load().igdsp_jb_adapt_cfg_default(cfg.ctypes.data_as(_vp))
+    return cfg
+
+
+def _jb_cfg(cfg) -> np.ndarray | None:
+    """a JB_ADAPT_CFG record from a record, a (min, max, init, mult, late_restart) sequence or None"""
+    if cfg is None:
+        return None
+    if isinstance(cfg, np.ndarray) and cfg.dtype == JB_ADAPT_CFG:
+        return np.ascontiguousarray(cfg.reshape(()))
+    out = np.zeros((), dtype=JB_ADAPT_CFG)
+    out["min_frames"], out["max_frames"], out["init_frames"], out["jitter_mult"], out["late_restart"] = cfg
+    return out
+
+
+def jb_adapt_next(cfg, jitter_q4: int, n: int, adapt) -> int:
+    """igdsp_jb_adapt_next (host only, no GPU): the Start rule of igdsp_jb_receive_adaptive for one channel: cfg (a JB_ADAPT_CFG record,
+    a (min, max, init, mult, late_restart) sequence or None for the defaults), the state's jitter (scaled by 16), n samples per frame;
+    adapt (a JB_ADAPT record) is updated in place.  Returns the new delay."""
+    c = _jb_cfg(cfg)
+    assert adapt.dtype == JB_ADAPT and adapt.flags["C_CONTIGUOUS"]
+    rc = load().igdsp_jb_adapt_next(None if c is None else c.ctypes.data_as(_vp), jitter_q4, n, adapt.ctypes.data_as(_vp))
+    if rc < 0:
+        raise IgdspError(rc, "igdsp_jb_adapt_next")
+    return rc
 
 
 def _ptr(x) -> int | None:
@@ -521,6 +561,17 @@ class Context:
         self._ck(self.L.igdsp_jb_receive(self.h, _ptr(packets), _ptr(sizes), _ptr(radio), _ptr(arrival), C_, T_, S_, stride, n, delay,
                                          _ptr(state), _ptr(ring), _ptr(payload), _ptr(length), _ptr(info), _ptr(tick_flags),
                                          _ptr(pkt_status), stream), "igdsp_jb_receive")
+
+    def jb_receive_adaptive(self, packets, radio, state, ring, adapt, payload, length, info, C_, T_, S_=1, stride=180, n=160, cfg=None,
+                            sizes=None, arrival=None, tick_flags=None, pkt_status=None, delay_out=None, stream=None):
+        """igdsp_jb_receive_adaptive: as jb_receive, with the playout delay of each channel adapted at every playout start: adapt [C]
+        JB_ADAPT carried across calls beside state and ring, cfg a JB_ADAPT_CFG record / (min, max, init, mult, late_restart) / None for
+        the defaults (host memory), delay_out [T][C] u8 out (optional)."""
+        c = _jb_cfg(cfg)
+        self._ck(self.L.igdsp_jb_receive_adaptive(self.h, _ptr(packets), _ptr(sizes), _ptr(radio), _ptr(arrival), C_, T_, S_, stride, n,
+                                                  None if c is None else c.ctypes.data_as(_vp), _ptr(state), _ptr(ring), _ptr(adapt),
+                                                  _ptr(payload), _ptr(length), _ptr(info), _ptr(tick_flags), _ptr(pkt_status), _ptr(delay_out),
+                                                  stream), "igdsp_jb_receive_adaptive")
 
     def plc_conceal(self, tick_flags, state, out, C_, T_, n=160, payload=None, codec=None, pcm=None, length=None, len_out=None, stats=None,
                     stream=None):

@@ -944,6 +944,20 @@ int igdsp_jb_report(const igdsp_jb_state *s, igdsp_jb_prior *prior, igdsp_jb_rr 
     return IGDSP_OK;
 }
 
+void igdsp_jb_adapt_cfg_default(igdsp_jb_adapt_cfg *cfg)
+{
+    if (cfg) *cfg = igdsp_jb_adapt_cfg{IGDSP_JB_ADAPT_MIN, IGDSP_JB_ADAPT_MAX, IGDSP_JB_DELAY, IGDSP_JB_ADAPT_MULT, IGDSP_JB_ADAPT_LATE_RESTART, {0, 0, 0}};
+}
+
+int igdsp_jb_adapt_next(const igdsp_jb_adapt_cfg *cfg, uint32_t jitter_q4, uint32_t samples_per_frame, igdsp_jb_adapt *a)
+{
+    igdsp_jb_adapt_cfg c;
+    igdsp_jb_adapt_cfg_default(&c);
+    if (cfg) c = *cfg;
+    if (!a || !jb_adapt_cfg_ok(c) || samples_per_frame == 0 || samples_per_frame > IGDSP_MAX_PAYLOAD) return IGDSP_EINVAL;
+    return (int)jb_adapt_start(c, jitter_q4, samples_per_frame, *a);
+}
+
 // igdsp_jb_receive, or with yardstick its compute-free twin igdsp_internal_jb_copy (which leaves d_pkt_status alone)
 static int jb_receive(igdsp_ctx *ctx, const uint8_t *d_packets, const uint16_t *d_sizes, const uint8_t *d_radio, const uint32_t *d_arrival,
                       uint32_t C, uint32_t T, uint32_t S, uint32_t stride, uint32_t n, uint32_t delay, igdsp_jb_state *d_state, void *d_ring,
@@ -974,6 +988,31 @@ int igdsp_jb_receive(igdsp_ctx *ctx, const uint8_t *d_packets, const uint16_t *d
 {
     return jb_receive(ctx, d_packets, d_sizes, d_radio, d_arrival, C, T, S, pkt_stride, n, delay_frames, d_state, d_ring, d_payload_out, d_len_out,
                       d_info_out, d_tick_flags, d_pkt_status, stream, false);
+}
+
+int igdsp_jb_receive_adaptive(igdsp_ctx *ctx, const uint8_t *d_packets, const uint16_t *d_sizes, const uint8_t *d_radio, const uint32_t *d_arrival,
+                              uint32_t C, uint32_t T, uint32_t S, uint32_t stride, uint32_t n, const igdsp_jb_adapt_cfg *cfg, igdsp_jb_state *d_state,
+                              void *d_ring, igdsp_jb_adapt *d_adapt, uint8_t *d_payload, uint16_t *d_len, igdsp_rtp_info *d_info,
+                              uint8_t *d_tick_flags, uint8_t *d_pkt_status, uint8_t *d_delay_out, void *stream)
+{
+    if (!ctx) return IGDSP_EINVAL;
+    if ((uint64_t)C * T == 0) return IGDSP_OK;                                               // nothing to do
+    if (!d_packets || !d_radio || !d_state || !d_ring || !d_adapt || !d_payload || !d_len || !d_info) return IGDSP_EINVAL;
+    igdsp_jb_adapt_cfg c;
+    igdsp_jb_adapt_cfg_default(&c);
+    if (cfg) c = *cfg;
+    if (S == 0 || S > IGDSP_STAGE_DEPTH || !jb_adapt_cfg_ok(c)) return IGDSP_EINVAL;
+    if (stride < 20u || (stride & 3u) || stride > 2048u) return IGDSP_EINVAL;
+    if (int rc = check_shape(C, T, n)) return rc;
+    if ((uint64_t)C * T * S >= 0xFFFFFFE0ull) return IGDSP_ERANGE;
+    const uintptr_t a2 = reinterpret_cast<uintptr_t>(d_sizes) | reinterpret_cast<uintptr_t>(d_len);
+    const uintptr_t a4 = reinterpret_cast<uintptr_t>(d_packets) | reinterpret_cast<uintptr_t>(d_arrival) | reinterpret_cast<uintptr_t>(d_state) |
+                         reinterpret_cast<uintptr_t>(d_info) | reinterpret_cast<uintptr_t>(d_adapt);
+    if ((a2 & 1u) || (a4 & 3u) || (reinterpret_cast<uintptr_t>(d_info) & 7u) || (reinterpret_cast<uintptr_t>(d_ring) & 15u)) return IGDSP_EINVAL;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, launch_jb_adaptive(cfg_of(ctx, pick(ctx, stream)), d_packets, d_sizes, d_radio, d_arrival, C, T, S, stride, n, c, d_state, d_ring, d_adapt,
+                                    d_payload, d_len, d_info, d_tick_flags, d_pkt_status, d_delay_out, pick(ctx, stream)));
+    return IGDSP_OK;
 }
 
 // ---- packet loss concealment between the jitter buffer and the bridge (the pjmedia stream's PLC; G.711 Appendix I's structure) ----

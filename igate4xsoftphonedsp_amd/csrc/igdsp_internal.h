@@ -116,6 +116,12 @@ hipError_t launch_link_watch(const LaunchCfg &cfg, const igdsp_rtp_info *info, c
 hipError_t launch_jb_receive(const LaunchCfg &cfg, const uint8_t *packets, const uint16_t *sizes, const uint8_t *radio, const uint32_t *arrival,
                              uint32_t C, uint32_t T, uint32_t S, uint32_t stride, uint32_t n, uint32_t delay, igdsp_jb_state *state, void *ring,
                              uint8_t *payload, uint16_t *len, igdsp_rtp_info *info, uint8_t *tick, uint8_t *pkt, bool yardstick, hipStream_t s);
+// igdsp_jb_receive_adaptive: as launch_jb_receive with the channel's delay from adapt [C] and cfg (checked by the C ABI); delay_out may
+// be nullptr.  No yardstick form: igdsp_internal_jb_copy is the yardstick of both entries
+hipError_t launch_jb_adaptive(const LaunchCfg &cfg, const uint8_t *packets, const uint16_t *sizes, const uint8_t *radio, const uint32_t *arrival,
+                              uint32_t C, uint32_t T, uint32_t S, uint32_t stride, uint32_t n, const igdsp_jb_adapt_cfg &acfg, igdsp_jb_state *state,
+                              void *ring, igdsp_jb_adapt *adapt, uint8_t *payload, uint16_t *len, igdsp_rtp_info *info, uint8_t *tick, uint8_t *pkt,
+                              uint8_t *delay_out, hipStream_t s);
 // igdsp_plc_conceal: exactly one of g711 (+ codec) / pcm; len, len_out, stats may each be nullptr.  yardstick: the compute-free form,
 // the same traversal with every tick taken as PLAIN, the input bits widened to the output, no decode, pitch search, synthesis or stats
 // (records carry only the length); the ring and the scalars are written as by a launch

@@ -12,6 +12,11 @@
 //   C. rows: 16-byte pieces of the payload rows, a piece per lane: from the packet (masked past len), from the ring slot, or zeros.
 //   D. ring: the packets of this part still in the ring are written into their slots (record head + masked payload), then every tag.
 // A packet that arrives and is played within one part never touches the ring.  The state is read once and written once per part.
+//
+// igdsp_jb_receive_adaptive (k_jb_adaptive) is the same body with ADAPT: phase A also carries the channel's igdsp_jb_adapt (8 bytes, read
+// and written once per part beside the state), takes the pre-roll of a Start from jb_adapt_start (igdsp_route.h) where the fixed entry
+// takes delay_frames, and lets the late_restart-th consecutive LATE packet start playout again; the delay after a tick's arrivals rides
+// in bits 28-31 of the tick's descriptor to phase B, which writes d_delay_out.  Independent restatement: tests/jb_adapt_model.py.
 #include "igdsp_rtp.h"
 
 namespace igdsp {
@@ -37,7 +42,15 @@ struct JbArgs {
     uint64_t slot_bytes;
 };
 
-// descriptor: kind | arrival or slot << 2 | flag << 12 | radio << 14 | len << 16
+// igdsp_jb_receive_adaptive: the fixed entry's arguments (delay unused), then its own
+struct JbAdaptArgs {
+    JbArgs a;
+    igdsp_jb_adapt *adapt;
+    uint8_t *delay_out;                    // nullptr: not wanted
+    igdsp_jb_adapt_cfg cfg;
+};
+
+// descriptor: kind | arrival or slot << 2 | flag << 12 | radio << 14 | len << 16 (9 bits) | ADAPT: delay << 28
 enum : uint32_t { kJdNone = 0, kJdKa = 1, kJdArr = 2, kJdRing = 3 };
 constexpr uint16_t kJbOld = 0xFFFFu;       // rsrc: the slot's packet is in the ring already
 constexpr uint32_t kJbTag = 0x10000u;      // tag = kJbTag | seq, 0 = empty
@@ -90,6 +103,21 @@ __device__ __forceinline__ uint4 jb_piece(const JbArgs &a, uint32_t al, uint32_t
     }
     return make_uint4(v[0], v[1], v[2], v[3]);
 }
+
+// one channel's igdsp_jb_adapt in registers, with what its rules need
+struct JbAdaptLane {
+    igdsp_jb_adapt a;
+    igdsp_jb_adapt_cfg cfg;
+    uint32_t n;
+
+    // a LATE packet, behind = -d frames behind the head; true: it is the late_restart-th in a row and starts playout again
+    __device__ __forceinline__ bool late(uint32_t behind)
+    {
+        a.need = (uint8_t)max((uint32_t)a.need, min((uint32_t)a.delay + behind, (uint32_t)cfg.max_frames));
+        a.late_run = (uint8_t)min((uint32_t)a.late_run + 1u, 255u);
+        return cfg.late_restart > 0u && a.late_run >= cfg.late_restart;
+    }
+};
 
 // one channel's state in registers, and its ring tags in LDS
 struct JbLane {
@@ -152,9 +180,11 @@ struct JbLane {
         ++s.received;
         return true;
     }
-    // a packet that is neither missing nor a runt; returns its IGDSP_JB_PKT_* status.  *ka: keep-alive of this tick (arrival al)
+    // a packet that is neither missing nor a runt; returns its IGDSP_JB_PKT_* status.  *ka: keep-alive of this tick (arrival al).
+    // ADAPT: ad holds the channel's igdsp_jb_adapt and delay is not used
+    template <bool ADAPT>
     __device__ __forceinline__ uint32_t packet(uint32_t al, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t arr, bool has_arr, uint32_t delay,
-                                               uint32_t *ka)
+                                               uint32_t *ka, JbAdaptLane *ad)
     {
         if (((w0 >> 6) & 3u) != 2u) { ++s.invalid; return IGDSP_JB_PKT_INVALID; }
         if (((w0 >> 8) & 0x7Fu) == 123u) { ++s.keepalives; *ka = al; return IGDSP_JB_PKT_KEEPALIVE; }
@@ -185,15 +215,20 @@ struct JbLane {
         const uint32_t slot = seq & (IGDSP_JB_DEPTH - 1u);
         const bool playing = (s.flags & IGDSP_JB_PLAYING) != 0u;
         const int32_t d = (int16_t)(uint16_t)(seq - s.head);
-        if (playing && !did_init && d < 0) { ++s.late; return IGDSP_JB_PKT_LATE; }
-        if (!playing || did_init || d >= IGDSP_JB_DEPTH) {      // Start
+        if (playing && !did_init && d < 0) {
+            ++s.late;
+            if (!ADAPT || !ad->late((uint32_t)-d)) return IGDSP_JB_PKT_LATE;
+        }
+        if (!playing || did_init || d >= IGDSP_JB_DEPTH || (ADAPT && d < 0)) {      // Start (ADAPT, d < 0: the late re-sync)
             drop_ring();
             if (playing) ++s.restarts;
+            if (ADAPT) delay = jb_adapt_start(ad->cfg, s.jitter, ad->n, ad->a);
             s.flags |= IGDSP_JB_PLAYING;
             s.head = (uint16_t)seq; s.wait = (uint8_t)delay; s.lost_run = 0;
             tag[slot] = kJbTag | seq; src[slot] = (uint16_t)al;
             return IGDSP_JB_PKT_RESTART;
         }
+        if (ADAPT) ad->a.late_run = 0;
         if (tag[slot] == (kJbTag | seq)) { ++s.duplicate; return IGDSP_JB_PKT_DUPLICATE; }
         tag[slot] = kJbTag | seq; src[slot] = (uint16_t)al;
         return IGDSP_JB_PKT_PLACED;
@@ -223,146 +258,16 @@ struct JbLane {
 template <bool COPY>
 __global__ __launch_bounds__(kJbWaves * 64) void k_jb_receive(const JbArgs a)
 {
-    __shared__ uint32_t desc[kJbWaves][kJbPart][kJbCh];
-    __shared__ uint32_t rtag[kJbWaves][kJbCh][IGDSP_JB_DEPTH];
-    __shared__ uint16_t rsrc[kJbWaves][kJbCh][IGDSP_JB_DEPTH];
-    __shared__ uint32_t todo[kJbWaves][kJbCh * IGDSP_JB_DEPTH];
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    const uint64_t c0l = ((uint64_t)blockIdx.x * kJbWaves + w) * kJbCh;
-    if (c0l >= a.C) return;                                                // waves are independent: no block barrier below
-    const uint32_t c0 = (uint32_t)c0l, nch = min(kJbCh, a.C - c0), pt = a.pt, ntag = nch * IGDSP_JB_DEPTH;
-    uint32_t *tags = reinterpret_cast<uint32_t *>(a.ring) + (uint64_t)c0 * IGDSP_JB_DEPTH;   // the wave's tags: contiguous
-    uint32_t *rt = &rtag[w][0][0];
-    uint16_t *rs = &rsrc[w][0][0];
-    for (uint32_t i = lane; i < ntag; i += 64u) { rt[i] = tags[i]; rs[i] = kJbOld; }
-    wave_lds_fence();
+    constexpr bool ADAPT = false;
+    constexpr JbAdaptArgs x{};                                             // the body reads x only where ADAPT
+#include "igdsp_k_jb_body.h"
+}
 
-    // A. decide
-    if (lane < nch) {
-        const uint32_t c = c0 + lane;
-        const bool radio = a.radio[c] != 0u;
-        if (COPY) {
-            for (uint32_t t = 0; t < pt; ++t) desc[w][t][lane] = jb_desc(kJdArr, t * a.S, IGDSP_JB_PLAYED) | (radio ? 1u << 14 : 0u);
-        } else {
-            JbLane L;
-            L.s = a.state[c];
-            L.tag = rt + lane * IGDSP_JB_DEPTH;
-            L.src = rs + lane * IGDSP_JB_DEPTH;
-            const uint32_t hdr = radio ? 20u : 12u, na = pt * a.S;
-            uint32_t ka = kJbOld, k = 0, t = 0;
-            for (uint32_t a0 = 0; a0 < na; a0 += kJbU) {
-                uint32_t sz[kJbU], w0[kJbU], w1[kJbU], w2[kJbU], ar[kJbU];
-#pragma unroll
-                for (uint32_t u = 0; u < kJbU; ++u) {                      // the headers of kJbU arrivals in flight
-                    const uint32_t al = min(a0 + u, na - 1u);
-                    const uint32_t *p = reinterpret_cast<const uint32_t *>(jb_pkt(a, al, c));
-                    sz[u] = jb_size(a, al, c);
-                    w0[u] = p[0]; w1[u] = p[1]; w2[u] = p[2];
-                    ar[u] = a.arrival ? a.arrival[(uint64_t)(a.t0 * a.S + al) * a.C + c] : 0u;
-                }
-#pragma unroll
-                for (uint32_t u = 0; u < kJbU; ++u) {
-                    const uint32_t al = a0 + u;
-                    if (al >= na) break;
-                    uint32_t st = IGDSP_JB_PKT_NONE;
-                    if (sz[u] != 0u) {
-                        if (sz[u] < hdr) { ++L.s.invalid; st = IGDSP_JB_PKT_INVALID; }
-                        else st = L.packet(al, w0[u], w1[u], w2[u], ar[u], a.arrival != nullptr, a.delay, &ka);
-                    }
-                    if (a.pkt) a.pkt[(uint64_t)(a.t0 * a.S + al) * a.C + c] = (uint8_t)st;
-                    if (++k == a.S) {                                      // the tick's last arrival: playout
-                        desc[w][t][lane] = L.tick(ka) | (radio ? 1u << 14 : 0u);
-                        k = 0; ++t; ka = kJbOld;
-                    }
-                }
-            }
-            a.state[c] = L.s;
-        }
-    }
-    wave_lds_fence();
-
-    // B. records
-    const uint32_t items = pt * nch;
-    for (uint32_t j = lane; j < items; j += 64u) {
-        const uint32_t t = j / nch, ch = j - t * nch, c = c0 + ch;
-        const uint32_t d = desc[w][t][ch], kind = d & 3u, idx = (d >> 2) & 0x3FFu, flag = (d >> 12) & 3u;
-        uint2 inf = make_uint2(0u, (uint32_t)IGDSP_RTP_RUNT << 24);
-        uint32_t l = 0;
-        if (kind == kJdRing) {
-            const uint4 h = *reinterpret_cast<const uint4 *>(jb_slot(a, c, idx));
-            inf = make_uint2(h.x, h.y); l = h.z;
-        } else if (kind != kJdNone) {
-            const FrameHdr h = jb_parse(a, idx, c, (d >> 14) & 1u);
-            inf = make_uint2(h.info.ed137, (uint32_t)h.info.payload_len | (uint32_t)h.info.pt << 16 | (uint32_t)h.info.flags << 24);
-            l = kind == kJdArr ? h.len : 0u;
-        }
-        const uint64_t o = (uint64_t)(a.t0 + t) * a.C + c;
-        a.len[o] = (uint16_t)l;
-        *reinterpret_cast<uint2 *>(a.info + o) = inf;
-        if (a.tick) a.tick[o] = (uint8_t)flag;
-        desc[w][t][ch] = d | l << 16;
-    }
-    wave_lds_fence();
-
-    // C. rows: piece q of frame (t, ch), kJbU pieces of a lane in flight
-    const uint32_t P = a.pieces, n = a.n, total = items * P;
-    for (uint32_t j0 = 0; j0 < total; j0 += 64u * kJbU) {
-        uint4 v[kJbU];
-        uint64_t dst[kJbU];
-        uint32_t b0s[kJbU];
-#pragma unroll
-        for (uint32_t u = 0; u < kJbU; ++u) {
-            const uint32_t j = j0 + u * 64u + lane;
-            v[u] = make_uint4(0u, 0u, 0u, 0u);
-            dst[u] = ~0ull;
-            if (j < total) {
-                const uint32_t row = j / P, q = j - row * P, t = row / nch, ch = row - t * nch, c = c0 + ch;
-                const uint32_t d = desc[w][t][ch], kind = d & 3u, idx = (d >> 2) & 0x3FFu, l = d >> 16;
-                if (kind == kJdArr) v[u] = jb_piece(a, idx, c, (d >> 14) & 1u ? 20u : 12u, l, 16u * q);
-                else if (kind == kJdRing) v[u] = *reinterpret_cast<const uint4 *>(jb_slot(a, c, idx) + kJbSlotHead + 16u * q);
-                dst[u] = ((uint64_t)(a.t0 + t) * a.C + c) * n;
-                b0s[u] = 16u * q;
-            }
-        }
-#pragma unroll
-        for (uint32_t u = 0; u < kJbU; ++u) {
-            if (dst[u] == ~0ull) continue;
-            uint8_t *o = a.payload + dst[u] + b0s[u];
-            if (a.vec) {
-                *reinterpret_cast<uint4 *>(o) = v[u];
-            } else {
-                const uint32_t x[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
-                for (uint32_t b = 0; b < 16u && b0s[u] + b < n; ++b) o[b] = (uint8_t)(x[b >> 2] >> (8u * (b & 3u)));
-            }
-        }
-    }
-
-    // D. ring: this part's unplayed packets into their slots, then the tags
-    if (!COPY) {
-        uint32_t cnt = 0;
-        for (uint32_t i0 = 0; i0 < ntag; i0 += 64u) {
-            const uint32_t i = i0 + lane;
-            const bool st = i < ntag && rt[i] != 0u && rs[i] != kJbOld;
-            const uint64_t m = __builtin_amdgcn_ballot_w64(st);
-            if (st) todo[w][cnt + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = i | (uint32_t)rs[i] << 16;
-            cnt += (uint32_t)__builtin_popcountll(m);
-        }
-        wave_lds_fence();
-        const uint32_t per = P + 1u;                                       // the record head, then P payload pieces
-        for (uint32_t j = lane; j < cnt * per; j += 64u) {
-            const uint32_t e = j / per, q = j - e * per, ent = todo[w][e];
-            const uint32_t ch = (ent & 0xFFFFu) / IGDSP_JB_DEPTH, s = ent & (IGDSP_JB_DEPTH - 1u), al = ent >> 16, c = c0 + ch;
-            const bool radio = a.radio[c] != 0u;
-            const FrameHdr h = jb_parse(a, al, c, radio);
-            uint8_t *slot = jb_slot(a, c, s);
-            if (q == 0u)
-                *reinterpret_cast<uint4 *>(slot) = make_uint4(h.info.ed137, (uint32_t)h.info.payload_len | (uint32_t)h.info.pt << 16 |
-                                                                                (uint32_t)h.info.flags << 24, h.len, 0u);
-            else
-                *reinterpret_cast<uint4 *>(slot + kJbSlotHead + 16u * (q - 1u)) = jb_piece(a, al, c, radio ? 20u : 12u, h.len, 16u * (q - 1u));
-        }
-        for (uint32_t i = lane; i < ntag; i += 64u) tags[i] = rt[i];
-    }
+__global__ __launch_bounds__(kJbWaves * 64) void k_jb_adaptive(const JbAdaptArgs x)
+{
+    constexpr bool COPY = false, ADAPT = true;
+    const JbArgs &a = x.a;
+#include "igdsp_k_jb_body.h"
 }
 
 hipError_t launch_jb_receive(const LaunchCfg &, const uint8_t *packets, const uint16_t *sizes, const uint8_t *radio, const uint32_t *arrival,
@@ -378,6 +283,24 @@ hipError_t launch_jb_receive(const LaunchCfg &, const uint8_t *packets, const ui
         a.t0 = p * kJbPart;
         a.pt = std::min(kJbPart, T - a.t0);
         hipLaunchKernelGGL(kernel, dim3(r.grid), dim3(r.threads), 0, s, a);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_jb_adaptive(const LaunchCfg &, const uint8_t *packets, const uint16_t *sizes, const uint8_t *radio, const uint32_t *arrival,
+                              uint32_t C, uint32_t T, uint32_t S, uint32_t stride, uint32_t n, const igdsp_jb_adapt_cfg &cfg, igdsp_jb_state *state,
+                              void *ring, igdsp_jb_adapt *adapt, uint8_t *payload, uint16_t *len, igdsp_rtp_info *info, uint8_t *tick, uint8_t *pkt,
+                              uint8_t *delay_out, hipStream_t s)
+{
+    const JbRoute r = jb_route(C, T, n, reinterpret_cast<uintptr_t>(payload));
+    if (r.grid == 0) return hipSuccess;
+    JbAdaptArgs x{{packets, sizes, radio, arrival, C, S, stride, n, 0u, r.pieces, r.vec, 0u, 0u, state, static_cast<uint8_t *>(ring), payload, len,
+                   info, tick, pkt, jb_slot_bytes(n)}, adapt, delay_out, cfg};
+    for (uint32_t p = 0; p < r.parts; ++p) {
+        x.a.t0 = p * kJbPart;
+        x.a.pt = std::min(kJbPart, T - x.a.t0);
+        hipLaunchKernelGGL(k_jb_adaptive, dim3(r.grid), dim3(r.threads), 0, s, x);
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     }
     return hipSuccess;

@@ -602,6 +602,30 @@ inline JbRoute jb_route(uint32_t C, uint32_t T, uint32_t n, uintptr_t payload_ou
     return r;
 }
 
+// igdsp_jb_receive_adaptive's Start rule (include/igdsp.h, "Jitter buffer, adaptive"): the new delay from the cfg, the A.8 jitter J
+// (scaled by 16) and n samples per frame; updates a.  constexpr, so k_jb_adaptive and igdsp_jb_adapt_next run the same function.
+constexpr bool jb_adapt_cfg_ok(const igdsp_jb_adapt_cfg &c)
+{
+    return c.min_frames <= c.init_frames && c.init_frames <= c.max_frames && c.max_frames <= IGDSP_JB_DEPTH - 1 && c.jitter_mult <= 16;
+}
+constexpr uint32_t jb_adapt_start(const igdsp_jb_adapt_cfg &cfg, uint32_t J, uint32_t n, igdsp_jb_adapt &a)
+{
+    const bool set = (a.flags & IGDSP_JB_ADAPT_SET) != 0;
+    const uint32_t cur = set ? a.delay : cfg.init_frames, lo = cfg.min_frames, hi = cfg.max_frames;
+    const uint64_t q = ((uint64_t)cfg.jitter_mult * J + 16u * n - 1u) / (16u * n);
+    const uint32_t tj = q < hi ? (uint32_t)q : hi;
+    const uint32_t want = tj > a.need ? tj : a.need;
+    uint32_t nw = want >= cur ? want : cur - 1u;
+    nw = nw < lo ? lo : (nw > hi ? hi : nw);
+    if (set && nw > a.delay && a.grows != 0xFFFFu) ++a.grows;
+    if (set && nw < a.delay && a.shrinks != 0xFFFFu) ++a.shrinks;
+    a.delay = (uint8_t)nw;
+    a.flags |= IGDSP_JB_ADAPT_SET;
+    a.need = 0;
+    a.late_run = 0;
+    return nw;
+}
+
 // ---- igdsp_plc_conceal (launch_plc_conceal): k_plc<COPY>.  A wave owns kPlcCh consecutive channels for the ticks of
 // one part (<= kPlcPart ticks).  Lanes 0 .. kPlcCh - 1 walk their channel's tick flags (no samples: which ticks are plain, which start
 // or continue a run, which recover) and leave a kind and a length per (tick, channel) in LDS; the whole wave then decodes and stores

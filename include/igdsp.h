@@ -36,7 +36,7 @@ extern "C" {
  *    igdsp_tx_packetize); the staged send path behind transport_send_rtp (igdsp_tx_open .. igdsp_tx_flush, igdsp_tx_packet); the
  *    conference mix (igdsp_conf_level_q7, igdsp_conf_build, igdsp_conf_mix, IGDSP_FLAG_SATURATED); best signal selection
  *    (igdsp_bss_state, IGDSP_BSS_VOTE_FRAMES, igdsp_bss_select); the jitter buffer (igdsp_jb_state, igdsp_jb_prior, igdsp_jb_rr,
- *    IGDSP_JB_*, igdsp_jb_ring_bytes, igdsp_jb_report, igdsp_jb_receive); packet loss concealment (igdsp_plc_state, IGDSP_PLC_*,
+ *    IGDSP_JB_*, igdsp_jb_ring_bytes, igdsp_jb_report, igdsp_jb_receive; igdsp_jb_adapt, igdsp_jb_adapt_cfg, igdsp_jb_receive_adaptive); packet loss concealment (igdsp_plc_state, IGDSP_PLC_*,
  *    IGDSP_FLAG_CONCEALED, igdsp_plc_conceal); PTT priority arbitration (igdsp_ptt_state, igdsp_ptt_slot, igdsp_ptt_tick, IGDSP_PTT_*,
  *    igdsp_ptt_arbitrate); R2S link supervision and the device event list (igdsp_link_state, igdsp_link_event, IGDSP_LINK_*,
  *    igdsp_link_work_bytes, igdsp_link_watch). */
@@ -899,8 +899,8 @@ int igdsp_link_watch(igdsp_ctx *ctx, const igdsp_rtp_info *d_info, const uint16_
  *
  * Fidelity.  PINNED to RFC 3550: A.1 (sequence validation), A.3 (igdsp_jb_report) and A.8 (jitter).  UNVERIFIED: that pjmedia's
  * rtp.c / rtcp.c use the same constants (pjmedia is a third-party dependency of the reference and is not in this tree).  DIFFERENT ON
- * PURPOSE: the buffer has a fixed delay (delay_frames at every playout start), where pjsua's default jbuf adapts; the buffer itself
- * does no concealment, LOST ticks come out as len 0 (igdsp_plc_conceal below fills them in); keep-alive words are not delayed by the
+ * PURPOSE: igdsp_jb_receive has a fixed delay (delay_frames at every playout start), where pjsua's default jbuf adapts
+ * (igdsp_jb_receive_adaptive below adapts it per talkspurt); the buffer itself does no concealment, LOST ticks come out as len 0 (igdsp_plc_conceal below fills them in); keep-alive words are not delayed by the
  * buffer. */
 #define IGDSP_JB_DEPTH   16      /* ring slots per channel: 320 ms at 20 ms frames */
 #define IGDSP_JB_DELAY    3      /* default delay_frames: 60 ms */
@@ -967,6 +967,68 @@ int igdsp_jb_receive(igdsp_ctx *ctx, const uint8_t *d_packets, const uint16_t *d
                      uint32_t n_channels, uint32_t n_ticks, uint32_t slots_per_tick, uint32_t pkt_stride, uint32_t samples_per_frame,
                      uint32_t delay_frames, igdsp_jb_state *d_state, void *d_ring, uint8_t *d_payload_out, uint16_t *d_len_out,
                      igdsp_rtp_info *d_info_out, uint8_t *d_tick_flags, uint8_t *d_pkt_status, void *stream);
+
+/* ---- Jitter buffer, adaptive: a playout delay chosen per talkspurt -------------------------------------------------------------------
+ * igdsp_jb_receive_adaptive is igdsp_jb_receive with the pre-roll of every playout start taken from the channel's own igdsp_jb_adapt
+ * record where igdsp_jb_receive takes delay_frames.  An ED-137 radio sends audio only while its squelch is open, so playout starts
+ * again at every talkspurt, and the delay is adapted there: the classic talkspurt rule (Ramjee, Kurose, Towsley, Schulzrinne, INFOCOM
+ * 1994: delay = d + 4 v at each talkspurt), with the RFC 3550 A.8 jitter of igdsp_jb_state as the variation estimate v.  No audio is
+ * stretched or dropped inside a talkspurt.
+ *
+ * Everything in igdsp_jb_receive's text above holds, except where delay_frames was used.  Let n = samples_per_frame and
+ * J = igdsp_jb_state.jitter (scaled by 16) after the packet's step 6.
+ *   Start rule.  It runs at every Start of step 7, whatever caused it: playout stopped, init_seq ran, d >= IGDSP_JB_DEPTH, or the late
+ *   re-sync below.  In order:
+ *     cur  = (flags & IGDSP_JB_ADAPT_SET) ? delay : init_frames
+ *     tj   = min(max_frames, (jitter_mult * J + 16 n - 1) / (16 n)), in 64-bit integer division
+ *     want = max(tj, need)
+ *     new  = want >= cur ? want : cur - 1          the delay grows at once and shrinks one frame per Start
+ *     new  = clamp(new, min_frames, max_frames)
+ *     if SET was on and new > delay: grows += 1; if SET was on and new < delay: shrinks += 1 (both saturate at 65535)
+ *     delay = new, flags |= SET, need = 0, late_run = 0
+ *     the state's wait = new, where igdsp_jb_receive writes delay_frames.
+ *   LATE packet (d < 0 while playing, no init_seq): late += 1 as in igdsp_jb_receive; need = max(need, min(delay + (-d), max_frames));
+ *   late_run = min(late_run + 1, 255).  If late_restart > 0 and late_run >= late_restart the packet is not dropped: it performs a Start
+ *   at its seq (the late re-sync): restarts += 1, the ring is discarded as at any Start, the packet is placed and its status is
+ *   RESTART.  Otherwise its status is LATE.
+ *   PLACED, DUPLICATE or RESTART: late_run = 0.
+ *   Other packets.  Keep-alives, invalid packets and missing slots touch nothing in igdsp_jb_adapt.  A new SSRC resets the source part
+ *   of igdsp_jb_state as in igdsp_jb_receive; igdsp_jb_adapt persists, because the path is the same.
+ *   d_delay_out[t][c] (optional) is igdsp_jb_adapt.delay after tick t's arrivals; 0 before the channel's first Start.
+ *   d_arrival == NULL: J stays 0, so only need drives the delay.
+ * Invariants.  With min_frames = max_frames = init_frames = D and late_restart = 0 every output, the state bytes and the ring bytes
+ * equal igdsp_jb_receive's with delay_frames = D.  n_ticks launches of one tick equal one launch of n_ticks ticks, d_adapt included.
+ * State: igdsp_jb_adapt[c] (device memory, 4-byte aligned) belongs to the caller beside d_state and d_ring; all-zero is its reset state.
+ *
+ * Fidelity.  PINNED: RFC 3550 A.8 as the variation estimate, and the talkspurt rule's structure (Ramjee et al., multiplier 4).
+ * UNVERIFIED: pjmedia's own algorithm (pjmedia is a third-party dependency of the reference and is not in this tree).  DIFFERENT ON
+ * PURPOSE: the delay changes only at playout starts, with no stretching or dropping of audio inside a talkspurt, so a continuous stream
+ * adapts only through the late re-sync; there is no mean-delay term, because arrivals are quantised to ticks by the caller. */
+#define IGDSP_JB_ADAPT_MIN           1
+#define IGDSP_JB_ADAPT_MAX          12
+#define IGDSP_JB_ADAPT_MULT          4   /* the 4 of d + 4 v */
+#define IGDSP_JB_ADAPT_LATE_RESTART  3
+#define IGDSP_JB_ADAPT_SET        0x01   /* igdsp_jb_adapt.flags: delay holds a value */
+typedef struct igdsp_jb_adapt_cfg {      /* host memory, read during the call; NULL = the defaults */
+    uint8_t min_frames, max_frames, init_frames, jitter_mult, late_restart, reserved[3];
+} igdsp_jb_adapt_cfg;
+typedef struct igdsp_jb_adapt {          /* per channel, 8 bytes, device, ALL-ZERO = reset */
+    uint8_t delay, flags, need, late_run;
+    uint16_t grows, shrinks;             /* saturate at 65535 */
+} igdsp_jb_adapt;
+/* The defaults: {IGDSP_JB_ADAPT_MIN, IGDSP_JB_ADAPT_MAX, IGDSP_JB_DELAY, IGDSP_JB_ADAPT_MULT, IGDSP_JB_ADAPT_LATE_RESTART}.  Host-only. */
+void igdsp_jb_adapt_cfg_default(igdsp_jb_adapt_cfg *cfg);
+/* The Start rule above for one channel: returns the new delay and updates *a exactly as the kernel does.  cfg NULL = the defaults.
+ * IGDSP_EINVAL for a NULL a, an invalid cfg or samples_per_frame outside 1..256.  Host-only, no GPU needed. */
+int igdsp_jb_adapt_next(const igdsp_jb_adapt_cfg *cfg, uint32_t jitter_q4, uint32_t samples_per_frame, igdsp_jb_adapt *a);
+/* Arguments, alignment and limits as igdsp_jb_receive's, without delay_frames.  d_adapt required, 4-byte aligned; d_delay_out
+ * optional.  cfg (NULL = the defaults) must satisfy min_frames <= init_frames <= max_frames <= IGDSP_JB_DEPTH - 1 and jitter_mult <=
+ * 16, else IGDSP_EINVAL.  n_channels == 0 or n_ticks == 0: nothing to do.  Enqueued on `stream`, not synchronised. */
+int igdsp_jb_receive_adaptive(igdsp_ctx *ctx, const uint8_t *d_packets, const uint16_t *d_sizes, const uint8_t *d_radio,
+                              const uint32_t *d_arrival, uint32_t n_channels, uint32_t n_ticks, uint32_t slots_per_tick, uint32_t pkt_stride,
+                              uint32_t samples_per_frame, const igdsp_jb_adapt_cfg *cfg, igdsp_jb_state *d_state, void *d_ring,
+                              igdsp_jb_adapt *d_adapt, uint8_t *d_payload_out, uint16_t *d_len_out, igdsp_rtp_info *d_info_out,
+                              uint8_t *d_tick_flags, uint8_t *d_pkt_status, uint8_t *d_delay_out, void *stream);
 
 /* ---- Packet loss concealment: between the jitter buffer and the bridge ------------------------------------------------------------
  * igdsp_plc_conceal turns the jitter buffer's playout ticks into continuous PCM: a LOST tick (or a PLAYED one that carries no audio)

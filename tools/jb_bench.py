@@ -2,6 +2,7 @@
 nominal HBM rate they represent, beside igdsp_depayload over the same arrival arrays and the compute-free yardstick, all in one process.
 
     python tools/jb_bench.py [--reps 20] [--warmup 5] [--out profiles/r08_jb_bench.json] [--only J1,J4]
+    python tools/jb_bench.py --adaptive [--only J1,J2,J3] [--out profiles/jb_adapt_bench.json]
 
 Shapes (180-byte ED-137 packets: 20-byte header + 160 G.711 bytes, 180-byte slots, delay_frames 3; packets built on the device):
     J1  C = 65 536, 128 ticks, 1 slot per tick, in order, no loss
@@ -14,7 +15,10 @@ Algorithmic bytes per channel-tick: the S sizes and the arrived packets (180 eac
 plus the 80-byte state and the 64 bytes of ring tags read and written once per channel and call.  Depayload does the same arrays with
 S slots per tick (T x S frames out).  The yardstick (igdsp_internal_jb_copy) writes the rows of an in-order lossless call (slot 0 of
 every tick copied as igdsp_depayload would) with no header walk, state machine or ring.  Kernel times: run this under
-`rocprofv3 --kernel-trace --stats` in a run of its own."""
+`rocprofv3 --kernel-trace --stats` in a run of its own.
+--adaptive times igdsp_jb_receive_adaptive (default cfg, no d_delay_out) beside igdsp_jb_receive instead: the two entries take turns, call
+by call, on the same stream of packets, the same state and ring and the same output buffers (the adaptive one with its igdsp_jb_adapt
+beside them).  Its bar: the fixed entry's median plus the fixed entry's own max - min spread in that run."""
 import argparse
 import ctypes
 import json
@@ -114,7 +118,23 @@ def timed(fn, s, reps, warmup, before=None):
     return float(np.median(t)), float(min(t))
 
 
-def run_case(ctx, name, reps, warmup):
+def timed_pair(fns, s, reps, warmup, before):
+    """the functions take turns, call by call; returns per function the sorted times in microseconds"""
+    ts = [[] for _ in fns]
+    for r in range(warmup + reps):
+        for i, fn in enumerate(fns):
+            before()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(s)
+            fn()
+            b.record(s)
+            b.synchronize()
+            if r >= warmup:
+                ts[i].append(a.elapsed_time(b) * 1000.0)
+    return [sorted(t) for t in ts]
+
+
+def run_case(ctx, name, reps, warmup, adaptive=False):
     C_, T, S = shape(name)
     tr = Traffic(C_, T, S, name == "J2", seed=C_ + T + S)
     cur = [tr.arrivals(0)]
@@ -155,6 +175,20 @@ def run_case(ctx, name, reps, warmup):
         pk, sz, _ = args()
         ctx.depayload(pk, sz, radio, C_, T * S, STRIDE, N, pay, ln, inf, stream=s.cuda_stream)
 
+    if adaptive:
+        adapt = torch.zeros(C_ * capi.JB_ADAPT.itemsize, dtype=torch.uint8, device="cuda")
+
+        def jba():
+            pk, sz, ar = args()
+            ctx.jb_receive_adaptive(pk, radio, state, ring, adapt, pay, ln, inf, C_, T, S, STRIDE, N, None, sizes=sz, arrival=ar, tick_flags=fl,
+                                    stream=s.cuda_stream)
+
+        tf, ta = timed_pair([jb, jba], s, reps, warmup, nxt)
+        med_f, med_a, spread = float(np.median(tf)), float(np.median(ta)), tf[-1] - tf[0]
+        return {"case": name, "C": C_, "T": T, "S": S, "fixed_us": round(med_f, 2), "fixed_min": round(tf[0], 2), "fixed_max": round(tf[-1], 2),
+                "adaptive_us": round(med_a, 2), "adaptive_min": round(ta[0], 2), "adaptive_max": round(ta[-1], 2),
+                "adaptive_over_fixed": round(med_a / med_f, 4), "bar_us": round(med_f + spread, 2), "bar_met": bool(med_a <= med_f + spread),
+                "reps": reps}
     us, us_min = timed(jb, s, reps, warmup, nxt)
     st = state.cpu().numpy().view(capi.JB_STATE)
     played = float(st["played"].sum()) / max(1.0, float(st["played"].sum() + st["lost"].sum()))
@@ -174,13 +208,15 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=None)
-    ap.add_argument("--only", default="J1,J2,J3,J4")
+    ap.add_argument("--only", default=None)
+    ap.add_argument("--adaptive", action="store_true", help="igdsp_jb_receive_adaptive beside igdsp_jb_receive (J1, J2, J3)")
     a = ap.parse_args()
+    a.only = a.only or ("J1,J2,J3" if a.adaptive else "J1,J2,J3,J4")
     torch.cuda.set_device(0)
     rows = []
     with capi.Context(device=0, max_channels=64) as ctx:
         for name in a.only.split(","):
-            r = run_case(ctx, name, a.reps, a.warmup)
+            r = run_case(ctx, name, a.reps, a.warmup, a.adaptive)
             print(json.dumps(r), flush=True)
             rows.append(r)
             torch.cuda.empty_cache()
