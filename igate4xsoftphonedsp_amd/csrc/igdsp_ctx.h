@@ -1,6 +1,8 @@
-// Private to the C-ABI translation units (igdsp_capi.hip, igdsp_io.hip): the context object and the small helpers every
-// entry uses.  Not part of the ABI (include/igdsp.h is).
+// Private to the C-ABI translation units (igdsp_capi.hip: the batched device entries; igdsp_capi_ctx.hip: context, routing, flush,
+// poll, memory, timers; igdsp_capi_tx.hip: the staged send path; igdsp_capi_bench.hip: calibration and diagnostics; igdsp_io.hip):
+// the context object and the small helpers every entry uses.  Not part of the ABI (include/igdsp.h is).
 #pragma once
+#include "igdsp_args.h"
 #include "igdsp_internal.h"
 #include "igdsp_rxstage.h"
 #include "igdsp_snappool.h"
@@ -78,7 +80,7 @@ struct igdsp_ctx {
     // few threads (csrc/igdsp_snappool.h); nullptr: the owner thread snapshots alone
     std::unique_ptr<igdsp::SnapshotPool> pool;
 
-    // the staged ED-137 send path (igdsp_tx_open .. igdsp_tx_flush, igdsp_capi.hip): its own staging rings, stream, pinned
+    // the staged ED-137 send path (igdsp_tx_open .. igdsp_tx_flush, igdsp_capi_tx.hip): its own staging rings, stream, pinned
     // blocks and device state, created by the first igdsp_tx_open so that RX-only users pay nothing for it
     struct TxSide;
     std::atomic<TxSide *> tx{nullptr};
@@ -113,6 +115,16 @@ const hipStream_t kFreeQueue = reinterpret_cast<hipStream_t>(~(uintptr_t)0);   /
 }
 
 void igdsp_io_drop_spares(igdsp_ctx *ctx);             // igdsp_io.hip: give the spare chunks back (igdsp_destroy, and before a new search)
+void igdsp_tx_drop(igdsp_ctx *ctx);                    // igdsp_capi_tx.hip: take the send path down, if one was created (igdsp_destroy)
+
+// a4 routing: the channel of call_id, or kNoChan
+static inline uint32_t lookup(igdsp_ctx *ctx, int32_t call_id)
+{
+    if (call_id >= 0 && call_id < kDirectCalls) return ctx->direct[(size_t)call_id].load(std::memory_order_acquire);
+    std::lock_guard<std::mutex> g(ctx->far_mu);
+    auto it = ctx->far.find(call_id);
+    return it == ctx->far.end() ? kNoChan : it->second;
+}
 
 static inline int fail(igdsp_ctx *ctx, int code, const char *what, hipError_t e = hipSuccess)
 {
@@ -129,6 +141,19 @@ static inline int fail(igdsp_ctx *ctx, int code, const char *what, hipError_t e 
     do {                                                                      \
         hipError_t e_ = (call);                                               \
         if (e_ != hipSuccess) return fail((ctx), IGDSP_EDEVICE, #call, e_);   \
+    } while (0)
+
+// A batched entry's way out on a verdict of igdsp_args.h that does not launch: its code, through fail() with "entry: rule" where the
+// rule names itself.
+static inline int refuse(igdsp_ctx *ctx, const char *entry, const igdsp::args::Verdict &v)
+{
+    return v.why ? fail(ctx, v.rc, (std::string(entry) + ": " + v.why).c_str()) : v.rc;
+}
+
+#define ARGS_TRY(ctx, entry, verdict)                                         \
+    do {                                                                      \
+        const igdsp::args::Verdict v_ = (verdict);                            \
+        if (!v_.run) return refuse((ctx), (entry), v_);                       \
     } while (0)
 
 // NULL means what it means everywhere in HIP: the legacy default (null) stream, so a caller that

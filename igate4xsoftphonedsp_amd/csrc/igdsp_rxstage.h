@@ -1,6 +1,6 @@
 // igdsp_rxstage.h — the staging half of the drop-in receive path (igdsp_on_rtp_frame / igdsp_set_ed137 / igdsp_flush_begin /
 // igdsp_flush_end / igdsp_poll): per-channel rings of received frames, the flush's snapshot into one compacted upload block, and
-// the double buffer the flush publishes its results in.  Host-only C++17, no HIP include: igdsp_capi.hip uses it (and allocates
+// the double buffer the flush publishes its results in.  Host-only C++17, no HIP include: igdsp_capi_ctx.hip uses it (and allocates
 // the pinned memory both halves work in), tests/rxstage/rx_stage_driver.cpp checks the upload block it builds, and
 // tests/san/rx_stage_tsan.cpp drives the staging under ThreadSanitizer.
 //

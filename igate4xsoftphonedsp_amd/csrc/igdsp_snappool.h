@@ -1,6 +1,6 @@
 // igdsp_snappool.h — the helper threads that share out a flush's host-side snapshot at many channels, for both flushes: the RX
 // flush (igdsp_flush_begin, csrc/igdsp_rxstage.h) and the TX flush (igdsp_tx_flush, csrc/igdsp_txstage.h).  Host-only C++17, no
-// HIP include: igdsp_capi.hip uses it, and tests/san/rx_stage_tsan.cpp drives it under ThreadSanitizer.
+// HIP include: igdsp_capi_ctx.hip and igdsp_capi_tx.hip use it, and tests/san/rx_stage_tsan.cpp drives it under ThreadSanitizer.
 //
 // A pool is sized once, when its owner is created (pool_threads), and is only ever run by that owner's flush, one run at a time.
 // for_each_part splits a channel range into the parts a run hands out; every part is a contiguous range of its own, so the

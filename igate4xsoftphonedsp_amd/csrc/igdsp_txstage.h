@@ -1,6 +1,6 @@
 // igdsp_txstage.h — the staging half of the ED-137 send path (igdsp_on_tx_frame / igdsp_tx_set_* / igdsp_tx_flush): per-leg
 // single-producer rings of pjmedia stream packets, the pending setter word, and the flush's snapshot into one compacted upload
-// block.  Host-only C++17, no HIP include: igdsp_capi.hip uses it, and tests/san/tx_stage_tsan.cpp drives it under ThreadSanitizer.
+// block.  Host-only C++17, no HIP include: igdsp_capi_tx.hip uses it, and tests/san/tx_stage_tsan.cpp drives it under ThreadSanitizer.
 //
 // One producer per leg (pjmedia serialises send_rtp per stream), one consumer (the flush's owner thread).  Staging is wait-free:
 // no lock or spin flag, only the leg's own head / tail and setter word.
