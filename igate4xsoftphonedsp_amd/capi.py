@@ -66,6 +66,10 @@ PTT_TICK = np.dtype([("sel", "<i4"), ("level", "u1"), ("ptt_id", "u1"), ("flags"
 # R2S link supervision (igdsp_link_watch)
 LINK_STATE = np.dtype([("last_ms", "<u8"), ("alarms", "<u4"), ("count", "<u2"), ("flags", "u1"), ("reserved", "u1")], align=True)   # igdsp_link_state
 LINK_EVENT = np.dtype([("channel", "<u4"), ("tick", "<u4"), ("word", "<u4"), ("count", "<u2"), ("kind", "u1"), ("reserved", "u1")], align=True)
+# sound-card splitter / combiner (igdsp_snd_combine / igdsp_snd_split / igdsp_snd_vu)
+SND_MAX_CHANNELS = 8
+SND_DB_FLOOR = -100.0
+SND_VU = np.dtype([("percent", "<i4"), ("reserved", "<u4"), ("db", "<f8")], align=True)   # igdsp_snd_vu_t
 CHAN_PROBE = np.dtype([("run", "<u4"), ("alarms", "<u4")], align=True)
 # the jitter buffer (igdsp_jb_receive / igdsp_jb_report)
 JB_STATE = np.dtype(
@@ -224,6 +228,9 @@ PROTOTYPES = [
     ("igdsp_jb_receive_adaptive", _int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                          _vp]),
     ("igdsp_plc_conceal", _int, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
+    ("igdsp_snd_combine", _int, [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp]),
+    ("igdsp_snd_split", _int, [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp]),
+    ("igdsp_snd_vu", _int, [_vp, _vp]),
     ("igdsp_g726_reorder", _int, [_vp, _vp, _vp, _u64, _int, _vp]),
     ("igdsp_gen_uniform", _int, [_vp, _vp, _u64, _u64, _u64, _vp]),
     ("igdsp_dev_alloc", _int, [_vp, C.POINTER(_vp), C.c_size_t]),
@@ -321,6 +328,16 @@ def jb_ring_bytes(n_channels: int, n: int = SAMPLES_PER_FRAME) -> int:
 def link_work_bytes(n_channels: int, n_ticks: int) -> int:
     """igdsp_link_work_bytes (host only, no GPU): bytes of igdsp_link_watch's d_work for a launch of this shape."""
     return int(load().igdsp_link_work_bytes(n_channels, n_ticks))
+
+
+def snd_vu(stats) -> dict:
+    """igdsp_snd_vu (host only, no GPU): the broadcastVUMeter numbers of one FRAME_STATS record: {"percent": int, "db": float}."""
+    st = np.ascontiguousarray(np.asarray(stats, dtype=FRAME_STATS).reshape(()))
+    out = np.zeros((), dtype=SND_VU)
+    rc = load().igdsp_snd_vu(st.ctypes.data_as(_vp), out.ctypes.data_as(_vp))
+    if rc != 0:
+        raise IgdspError(rc, "igdsp_snd_vu")
+    return {"percent": int(out["percent"]), "db": float(out["db"])}
 
 
 def jb_report(state, prior) -> np.ndarray:
@@ -524,6 +541,14 @@ class Context:
         stats [F][P] (device buffers)."""
         self._ck(self.L.igdsp_conf_mix(self.h, _ptr(payload), _ptr(codec), _ptr(pcm), _ptr(length), _ptr(gain), _ptr(port_ptr), _ptr(members),
                                        n_members, C_, P_, F_, n, _ptr(out), _ptr(stats), stream), "igdsp_conf_mix")
+
+    def snd_combine(self, pcm, D_, K_, F_, n=SAMPLES_PER_FRAME, frames=None, stats=None, stream=None):
+        """igdsp_snd_combine: pcm [F][D * K][n] int16 -> frames [F][D][n][K] int16 and / or stats [F][D * K] FRAME_STATS (the out VU)."""
+        self._ck(self.L.igdsp_snd_combine(self.h, _ptr(pcm), D_, K_, F_, n, _ptr(frames), _ptr(stats), stream), "igdsp_snd_combine")
+
+    def snd_split(self, frames, D_, K_, F_, n=SAMPLES_PER_FRAME, pcm=None, stats=None, stream=None):
+        """igdsp_snd_split: frames [F][D][n][K] int16 -> pcm [F][D * K][n] int16 and / or stats [F][D * K] FRAME_STATS (the in VU)."""
+        self._ck(self.L.igdsp_snd_split(self.h, _ptr(frames), D_, K_, F_, n, _ptr(pcm), _ptr(stats), stream), "igdsp_snd_split")
 
     def bss_select(self, info, group_ptr, members, n_members, state, words, C_, G_, F_, n=160, payload=None, codec=None, pcm=None,
                    length=None, gain=None, mute=None, vote_frames=0, sel=None, out=None, stats=None, stream=None):

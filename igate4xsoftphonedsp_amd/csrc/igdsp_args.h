@@ -352,4 +352,29 @@ inline Verdict plc_conceal(P d_tick_flags, P d_payload, P d_codec, P d_pcm, P d_
     return kRun;
 }
 
+// ---- sound-card splitter / combiner: one rule for both directions (d_in, d_bulk: d_pcm and d_frames in the entry's direction)
+inline Verdict snd_rule(P d_in, uint32_t D, uint32_t K, uint32_t F, uint32_t n, P d_bulk, P d_stats)
+{
+    if (empty(D, F)) return kNothing;
+    if (!d_in || (!d_bulk && !d_stats)) return kInvalid;
+    if (K == 0 || K > IGDSP_SND_MAX_CHANNELS) return kInvalid;
+    // check_shape(D * K, F, n) with the row count D * K taken in 64 bits (< 2^35, so the product with F is taken only where it fits)
+    if (n == 0 || n > IGDSP_MAX_PAYLOAD) return kInvalid;
+    const uint64_t rows = (uint64_t)D * K;
+    if (rows >= 0xFFFFFFE0ull || rows * F >= 0xFFFFFFE0ull) return reject(IGDSP_ERANGE);
+    if (misaligned(2, {d_in, d_bulk}) || misaligned(8, {d_stats})) return kInvalid;
+    if (d_in == d_bulk) return reject(IGDSP_EINVAL, "the output must not be the input");
+    return kRun;
+}
+
+inline Verdict snd_combine(P d_pcm, uint32_t D, uint32_t K, uint32_t F, uint32_t n, P d_frames, P d_stats)
+{
+    return snd_rule(d_pcm, D, K, F, n, d_frames, d_stats);
+}
+
+inline Verdict snd_split(P d_frames, uint32_t D, uint32_t K, uint32_t F, uint32_t n, P d_pcm, P d_stats)
+{
+    return snd_rule(d_frames, D, K, F, n, d_pcm, d_stats);
+}
+
 }  // namespace igdsp::args

@@ -128,6 +128,11 @@ hipError_t launch_jb_adaptive(const LaunchCfg &cfg, const uint8_t *packets, cons
 hipError_t launch_plc_conceal(const LaunchCfg &cfg, const uint8_t *flags, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm,
                               const uint16_t *len, uint32_t C, uint32_t T, uint32_t n, igdsp_plc_state *state, int16_t *out, uint16_t *len_out,
                               igdsp_frame_stats *stats, bool yardstick, hipStream_t s);
+// igdsp_snd_combine (dir kSndCombine: in = pcm [F][D * K][n], out = frames [F][D][n][K]) / igdsp_snd_split (kSndSplit: the reverse);
+// out and stats may be nullptr (not both: the C ABI checks).  yardstick: the compute-free form, the same items, the same bytes read
+// and written in memory order, no transpose and no records; it needs out
+hipError_t launch_snd(const LaunchCfg &cfg, int dir, const int16_t *in, uint32_t D, uint32_t K, uint32_t F, uint32_t n, int16_t *out,
+                      igdsp_frame_stats *stats, bool yardstick, hipStream_t s);
 hipError_t launch_wav_expand(const LaunchCfg &cfg, const uint8_t *payload, uint32_t C, uint32_t F, uint32_t n, uint32_t rate,
                              uint8_t *files, uint64_t file_stride, hipStream_t s);
 hipError_t launch_g726(const LaunchCfg &cfg, const uint8_t *in, uint8_t *out, uint64_t n_bytes, int mode, hipStream_t s);

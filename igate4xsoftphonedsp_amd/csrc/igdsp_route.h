@@ -660,6 +660,53 @@ inline PlcRoute plc_route(uint32_t C, uint32_t T, uint32_t n, bool pcm, uintptr_
     return r;
 }
 
+// ---- igdsp_snd_combine / igdsp_snd_split (launch_snd): k_snd<DIR, MODE, VEC>.  An item is one card-frame (frame f, card d): K rows
+// of n samples on the mono side, n samples of K channels on the card side, the same K * n * 2 bytes at the same offset of both buffers.
+// A wave takes kSndU consecutive items at a time (static, grid-stride): it issues the loads of all of them, then passes them one after
+// the other through its LDS tile, which always holds the item row-major ([k][s]); the records are read from the tile.
+//   vector form: K * n even and both buffers dword aligned.  16-byte pieces in memory order on both sides (16-byte aligned where the
+//             base and K * n * 2 are, dword aligned otherwise) and a last piece of 1 .. 3 dwords where K * n * 2 is no multiple of 16.
+//   general form: everything else (K * n odd, a buffer aligned to 2 only): the same tile, filled and emptied a sample at a time.
+// Interleaved index r = s * K + k of an item <-> row-major index k * n + s: s = r / K by snd_div, exact on the device's range.
+#ifndef IGDSP_SND_WAVES
+#define IGDSP_SND_WAVES 8
+#endif
+#ifndef IGDSP_SND_U
+#define IGDSP_SND_U 4
+#endif
+constexpr int kSndWaves = IGDSP_SND_WAVES;                // waves per block, independent of each other (a 4 KiB tile each)
+constexpr int kSndU = IGDSP_SND_U;                        // items of a wave in flight together
+constexpr uint32_t kSndTileBytes = IGDSP_SND_MAX_CHANNELS * IGDSP_MAX_PAYLOAD * 2u;   // the largest item: 4 KiB
+constexpr uint32_t kSndLanePieces = kSndTileBytes / 16u / 64u;                        // 16-byte pieces of a lane per item: 4
+enum : int { kSndCombine = 0, kSndSplit = 1 };            // k_snd<DIR>
+enum : int { kSndBoth = 0, kSndBulk = 1, kSndStats = 2, kSndCopy = 3 };   // k_snd<, MODE>: what is written; kSndCopy: the yardstick
+// r / d as (r * magic) >> 20 with magic = ceil(2^20 / d): exact for r < 4096 and d <= 256 (the error term r * (d * magic - 2^20) stays
+// below 2^20, and r * magic below 2^32).  constexpr: the kernel and tests/route/snd_route_driver.cpp run the same function.
+constexpr uint32_t snd_div_magic(uint32_t d) { return ((1u << 20) + d - 1u) / d; }
+constexpr uint32_t snd_div(uint32_t r, uint32_t magic) { return (r * magic) >> 20; }
+struct SndRoute {
+    int mode = kSndBoth;
+    uint32_t vec = 0;                      // the vector form
+    uint32_t pieces = 0, tail_dwords = 0;  // vector form: pieces per item (the last of tail_dwords dwords if that is not 0)
+    uint32_t items = 0, grid = 0, threads = 0;
+};
+inline SndRoute snd_route(uint32_t D, uint32_t K, uint32_t F, uint32_t n, bool bulk, bool stats, bool yardstick, uintptr_t in, uintptr_t out,
+                          uint32_t cus)
+{
+    SndRoute r;
+    const uint64_t items = (uint64_t)D * F;
+    if (items == 0 || K == 0 || K > IGDSP_SND_MAX_CHANNELS || n == 0 || n > IGDSP_MAX_PAYLOAD || items * K >= 0xFFFFFFE0ull) return r;
+    if (!bulk && !stats) return r;
+    r.mode = yardstick ? kSndCopy : (bulk && stats ? kSndBoth : (bulk ? kSndBulk : kSndStats));
+    const uint32_t bytes = K * n * 2u;
+    r.vec = (bytes & 3u) == 0u && aligned(in | out, 4) ? 1u : 0u;
+    if (r.vec) { r.tail_dwords = (bytes & 15u) >> 2; r.pieces = (bytes + 15u) >> 4; }
+    r.items = (uint32_t)items;
+    r.grid = blocks_for((items + kSndU - 1u) / kSndU, kSndWaves, std::max(1u, cus));
+    r.threads = kSndWaves * 64;
+    return r;
+}
+
 // ---- igdsp_tx_flush (launch_tx_staged): a wave owns kTsLegs staged legs (runs) of the flush; lanes 0 .. kTsLegs-1 decide, the
 // whole wave writes the packets.  No dynamic LDS: each wave's records (kTsLegs x IGDSP_STAGE_DEPTH) are static.
 constexpr int kTsWaves = 4;

@@ -757,6 +757,70 @@ int igdsp_host_link_leg(void *v, int leg, unsigned long long *last_ms, int *coun
     return IGDSP_OK;
 }
 
+// ---- the sound-card splitter / combiner, no context needed
+SplitComb::SplitComb(int channels, int samples_per_frame)
+    : K(channels < 1 ? 1 : (channels > IGDSP_SND_MAX_CHANNELS ? IGDSP_SND_MAX_CHANNELS : channels)),
+      n(samples_per_frame < 1 ? 1 : (samples_per_frame > IGDSP_MAX_PAYLOAD ? IGDSP_MAX_PAYLOAD : samples_per_frame))
+{
+}
+
+void SplitComb::combine(const int16_t *const *rows, int16_t *frame) const
+{
+    for (int s = 0; s < n; ++s)
+        for (int k = 0; k < K; ++k) frame[s * K + k] = rows[k][s];
+}
+
+void SplitComb::split(const int16_t *frame, int16_t *const *rows) const
+{
+    for (int s = 0; s < n; ++s)
+        for (int k = 0; k < K; ++k) rows[k][s] = frame[s * K + k];
+}
+
+igdsp_frame_stats SplitComb::vu(const int16_t *frame, int k) const
+{
+    igdsp_frame_stats st;
+    uint64_t sumsq = 0;
+    uint32_t peak = 0;
+    for (int s = 0; s < n; ++s) {
+        const int32_t x = frame[s * K + k];
+        const uint32_t ax = (uint32_t)(x < 0 ? -x : x);
+        sumsq += (uint64_t)ax * ax;
+        if (ax > peak) peak = ax;
+    }
+    st.sumsq = sumsq;
+    st.rms = std::sqrt((float)sumsq / (float)n);
+    st.peak = (uint16_t)peak;
+    st.byte_mean = 0;
+    st.flags = (uint8_t)(peak <= 8u ? IGDSP_FLAG_SILENT : 0);
+    return st;
+}
+
+void *igdsp_host_sc_new(int channels, int samples_per_frame)
+{
+    if (channels < 1 || channels > IGDSP_SND_MAX_CHANNELS || samples_per_frame < 1 || samples_per_frame > IGDSP_MAX_PAYLOAD) return nullptr;
+    return new (std::nothrow) SplitComb(channels, samples_per_frame);
+}
+void igdsp_host_sc_free(void *v) { delete static_cast<SplitComb *>(v); }
+int igdsp_host_sc_combine(void *v, const int16_t *const *rows, int16_t *frame)
+{
+    if (!v || !rows || !frame) return IGDSP_EINVAL;
+    static_cast<const SplitComb *>(v)->combine(rows, frame);
+    return IGDSP_OK;
+}
+int igdsp_host_sc_split(void *v, const int16_t *frame, int16_t *const *rows)
+{
+    if (!v || !rows || !frame) return IGDSP_EINVAL;
+    static_cast<const SplitComb *>(v)->split(frame, rows);
+    return IGDSP_OK;
+}
+int igdsp_host_sc_vu(void *v, const int16_t *frame, igdsp_frame_stats *out)
+{
+    const SplitComb *a = static_cast<const SplitComb *>(v);
+    if (!a || !frame || !out) return IGDSP_EINVAL;
+    for (int k = 0; k < a->K; ++k) out[k] = a->vu(frame, k);
+    return IGDSP_OK;
+}
+
 // ---- conference receive levels, no context needed
 void *igdsp_host_levels_new(uint32_t n_channels)
 {

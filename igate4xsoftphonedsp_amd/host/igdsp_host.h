@@ -194,6 +194,22 @@ private:
     LinkWatch &operator=(const LinkWatch &);
 };
 
+// The sound-card splitter / combiner, pjmedia_splitcomb as initSlaveSoundCard drives it (roip_ed137.cpp:3314-3435), without a context:
+// K mono rows of n samples <-> one card frame of n x K interleaved samples, and the per-channel VU of either side in plain loops.  A
+// gateway of the reference's size (one card) keeps the step on the CPU with this; igdsp_snd_combine / igdsp_snd_split are the same
+// steps on the device for thousands of cards.  No delay buffers: one call is one frame on one clock.
+class SplitComb {
+public:
+    SplitComb(int channels, int samples_per_frame);   // clamped to 1 .. IGDSP_SND_MAX_CHANNELS and 1 .. IGDSP_MAX_PAYLOAD
+    int K, n;
+    // playback: frame[s * K + k] = rows[k][s] (the splitcomb's get_frame over its reverse channels' put_frame)
+    void combine(const int16_t *const *rows, int16_t *frame) const;
+    // capture: rows[k][s] = frame[s * K + k] (the splitcomb's put_frame, the reverse channels' get_frame)
+    void split(const int16_t *frame, int16_t *const *rows) const;
+    // the record of card channel k of a frame, as igdsp_snd_combine / igdsp_snd_split write it
+    igdsp_frame_stats vu(const int16_t *frame, int k) const;
+};
+
 class RoIP_ED137 {
 public:
     // Unlike the reference singleton (roip_ed137.cpp:192) the instance owns an igdsp context; device < 0
@@ -289,6 +305,13 @@ int   igdsp_host_link_begin(void *v, unsigned long long now_ms, const int *call_
 int   igdsp_host_link_packet(void *v, int leg, int pt, unsigned payload_len, int runt, uint32_t ed137);
 int   igdsp_host_link_end(void *v, uint8_t *kinds, uint32_t *words);
 int   igdsp_host_link_leg(void *v, int leg, unsigned long long *last_ms, int *count, int *flags, unsigned *alarms);
+// the sound-card splitter / combiner without a context (SplitComb, 1 .. 8 channels of 1 .. 256 samples): rows = K pointers to n samples;
+// _vu writes the K records of a card frame (IGDSP_EINVAL for a NULL argument, NULL from _new for a bad shape)
+void *igdsp_host_sc_new(int channels, int samples_per_frame);
+void  igdsp_host_sc_free(void *v);
+int   igdsp_host_sc_combine(void *v, const int16_t *const *rows, int16_t *frame);
+int   igdsp_host_sc_split(void *v, const int16_t *frame, int16_t *const *rows);
+int   igdsp_host_sc_vu(void *v, const int16_t *frame, igdsp_frame_stats *out);
 // Meter output on the reference's other channel: AudioMeter (audiometer.cpp:11-34) reads ASCII decimal levels from the
 // FIFO /tmp/capturefifo<card>, 32 bytes per read, and emits onValueChanged(int(float(v*100.0/30000.0))).  These write
 // such records, so the reference's own meter consumer can be fed from igdsp_poll().rms.  open() waits up to

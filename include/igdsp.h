@@ -39,7 +39,8 @@ extern "C" {
  *    IGDSP_JB_*, igdsp_jb_ring_bytes, igdsp_jb_report, igdsp_jb_receive; igdsp_jb_adapt, igdsp_jb_adapt_cfg, igdsp_jb_receive_adaptive); packet loss concealment (igdsp_plc_state, IGDSP_PLC_*,
  *    IGDSP_FLAG_CONCEALED, igdsp_plc_conceal); PTT priority arbitration (igdsp_ptt_state, igdsp_ptt_slot, igdsp_ptt_tick, IGDSP_PTT_*,
  *    igdsp_ptt_arbitrate); R2S link supervision and the device event list (igdsp_link_state, igdsp_link_event, IGDSP_LINK_*,
- *    igdsp_link_work_bytes, igdsp_link_watch). */
+ *    igdsp_link_work_bytes, igdsp_link_watch); the sound-card splitter / combiner (IGDSP_SND_*, igdsp_snd_combine, igdsp_snd_split,
+ *    igdsp_snd_vu_t, igdsp_snd_vu). */
 #define IGDSP_ABI_VERSION 3
 
 /* ---- error codes (0 == PJ_SUCCESS-style success) ------------------------- */
@@ -1093,6 +1094,56 @@ int igdsp_plc_conceal(igdsp_ctx *ctx, const uint8_t *d_tick_flags,
                       uint32_t n_channels, uint32_t n_ticks, uint32_t samples_per_frame,
                       igdsp_plc_state *d_state, int16_t *d_out, uint16_t *d_len_out,
                       igdsp_frame_stats *d_stats, void *stream);
+
+/* ---- Sound-card splitter / combiner: the last step of the tick, between the bridge's ports and the card -------------------------------
+ * The reference hands the bridge's audio to its slave sound card through pjmedia's splitter / combiner: initSlaveSoundCard
+ * (roip_ed137.cpp:3314-3435) creates a 6-channel pjmedia_splitcomb at 8 kHz, puts the bridge's master port on channel 0, adds a reverse
+ * channel per further card channel as the conference ports sc_ch1_slot .. sc_ch5_slot and connects the combiner to the card's player;
+ * on_call_audio_state (:4907-4920) connects every call to every one of those ports in both directions.  The ports of igdsp_conf_mix
+ * are those card channels.
+ *
+ * A CARD has K channels, 1 <= K <= IGDSP_SND_MAX_CHANNELS (the reference's has 6).  A card frame is n samples of K interleaved int16:
+ * frames[f][d][s][k], n = 1..256.  The mono side is dense: card d, channel k is row d * K + k — port p of igdsp_conf_mix in the
+ * playback direction, channel c of a d_pcm input in the capture direction.  There is no map table: igdsp_conf_mix's CSR does the
+ * routing, and a port without members already comes out as zeros.
+ *   igdsp_snd_combine (playback: the splitcomb's get_frame over its reverse channels' put_frame)
+ *       frames[f][d][s][k] = pcm[f][d * K + k][s]
+ *   igdsp_snd_split   (capture: the splitcomb's put_frame, the reverse channels' get_frame)
+ *       pcm[f][d * K + k][s] = frames[f][d][s][k]
+ * Both are bit for bit, so split(combine(x)) == x.  Records [f][d * K + k] over that row's n samples, as igdsp_conf_mix writes them:
+ * sumsq exact, rms = sqrtf((float)sumsq / n), peak = max |x| (32768 for -32768), byte_mean 0, flags IGDSP_FLAG_SILENT when peak <= 8
+ * and nothing else.  igdsp_snd_combine's records are the OUT VU of the card's channels and igdsp_snd_split's the IN VU: the
+ * per-card-channel in1..in4 / out1..out4 numbers the reference receives from an outside process over its WebSocket
+ * (roip_ed137.cpp:7686-7716) and folds into the PTT window (keeplogAudioLevel).  Their [F][C] layout is what igdsp_hold_update takes
+ * with n_channels = n_cards * card_channels, so a PTT window over a card channel needs nothing new.
+ * At least one of the bulk output and d_stats must be given: records only is a pure meter over PCM, bulk only a pure transpose.  The
+ * input is required; n_cards == 0 or n_frames == 0: nothing to do.  n_cards * card_channels * n_frames < 2^32 - 32 (IGDSP_ERANGE).
+ * d_pcm and d_frames 2-byte, d_stats 8-byte aligned; the output must not be the input, and the buffers must not overlap at all.
+ * Enqueued on `stream`, not synchronised.
+ *
+ * Fidelity.  UNVERIFIED: the interleaving order s * K + k is the standard PCM layout the ALSA card takes; pjmedia's splitcomb.c is not
+ * in the reference tree.  DIFFERENT ON PURPOSE: pjmedia's reverse channels carry a delay buffer because the bridge and the card have
+ * separate clocks; here one launch is one clock and nothing is buffered.  The reference opens only a player on this card
+ * (pjmedia_snd_port_create_player; the bidirectional pjmedia_snd_port_create is commented out at :3411-3420), so its capture direction
+ * carries silence today although both directions are wired; igdsp_snd_split is the step that wiring implies. */
+#define IGDSP_SND_MAX_CHANNELS 8
+int igdsp_snd_combine(igdsp_ctx *ctx, const int16_t *d_pcm /* [F][D*K][n] */, uint32_t n_cards, uint32_t card_channels,
+                      uint32_t n_frames, uint32_t samples_per_frame,
+                      int16_t *d_frames /* [F][D][n][K] */, igdsp_frame_stats *d_stats /* [F][D*K] */, void *stream);
+int igdsp_snd_split(igdsp_ctx *ctx, const int16_t *d_frames /* [F][D][n][K] */, uint32_t n_cards, uint32_t card_channels,
+                    uint32_t n_frames, uint32_t samples_per_frame,
+                    int16_t *d_pcm /* [F][D*K][n] */, igdsp_frame_stats *d_stats /* [F][D*K] */, void *stream);
+
+/* Host only, no GPU: the numbers a broadcastVUMeter message carries for one card channel, from its record.  percent is
+ * int(float(rms * 100.0 / 30000.0)), exactly igdsp_level.percent; db = 20 * log10(rms / 32768.0) in double, IGDSP_SND_DB_FLOOR for
+ * rms == 0.  UNVERIFIED: the outside process's own dB scale is not in the reference tree.  IGDSP_EINVAL for a NULL argument. */
+#define IGDSP_SND_DB_FLOOR (-100.0)
+typedef struct igdsp_snd_vu_t {
+    int32_t percent;
+    uint32_t reserved;
+    double  db;
+} igdsp_snd_vu_t;
+int igdsp_snd_vu(const igdsp_frame_stats *st, igdsp_snd_vu_t *out);
 
 /* ---- synthetic input generators (device side; SURVEY 8(d) definitions) ---------
  * D-uniform: byte k of global byte index g is
