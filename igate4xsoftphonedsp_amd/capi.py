@@ -70,6 +70,17 @@ LINK_EVENT = np.dtype([("channel", "<u4"), ("tick", "<u4"), ("word", "<u4"), ("c
 SND_MAX_CHANNELS = 8
 SND_DB_FLOOR = -100.0
 SND_VU = np.dtype([("percent", "<i4"), ("reserved", "<u4"), ("db", "<f8")], align=True)   # igdsp_snd_vu_t
+# the tone generator (igdsp_tone_plan_build / igdsp_tone_frame / igdsp_tone_generate)
+TONE_MAX = 8
+TONE_VOLUME = 12288
+TONE_LOOP, TONE_NO_FADE = 1, 2
+TONE_PLAYING = 1
+TONE_CMD_REWIND, TONE_CMD_STOP, TONE_CMD_HOLD = 1, 2, 4
+TONE_DESC = np.dtype([("freq1", "<u2"), ("freq2", "<u2"), ("on_msec", "<u2"), ("off_msec", "<u2"), ("volume", "<u2"), ("reserved", "<u2")], align=True)
+TONE_SEG = np.dtype([("start", "<u4"), ("on", "<u4"), ("step1", "<u4"), ("step2", "<u4"), ("vol", "<u2"), ("fade_in", "<u2"), ("fade_out", "<u2"),
+                     ("reserved", "<u2")], align=True)                                             # igdsp_tone_seg, 24 bytes
+TONE_PLAN = np.dtype([("n_tones", "<u4"), ("options", "<u4"), ("cycle", "<u4"), ("clock_rate", "<u4"), ("seg", TONE_SEG, (TONE_MAX,))], align=True)   # 208 bytes
+TONE_STATE = np.dtype([("pos", "<u4"), ("flags", "<u4")], align=True)                            # igdsp_tone_state
 CHAN_PROBE = np.dtype([("run", "<u4"), ("alarms", "<u4")], align=True)
 # the jitter buffer (igdsp_jb_receive / igdsp_jb_report)
 JB_STATE = np.dtype(
@@ -231,6 +242,9 @@ PROTOTYPES = [
     ("igdsp_snd_combine", _int, [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp]),
     ("igdsp_snd_split", _int, [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp]),
     ("igdsp_snd_vu", _int, [_vp, _vp]),
+    ("igdsp_tone_plan_build", _int, [_vp, _u32, _u32, _u32, _vp]),
+    ("igdsp_tone_frame", _int, [_vp, _vp, _u32, _u32, _vp, _vp]),
+    ("igdsp_tone_generate", _int, [_vp, _vp, _u32, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp]),
     ("igdsp_g726_reorder", _int, [_vp, _vp, _vp, _u64, _int, _vp]),
     ("igdsp_gen_uniform", _int, [_vp, _vp, _u64, _u64, _u64, _vp]),
     ("igdsp_dev_alloc", _int, [_vp, C.POINTER(_vp), C.c_size_t]),
@@ -338,6 +352,35 @@ def snd_vu(stats) -> dict:
     if rc != 0:
         raise IgdspError(rc, "igdsp_snd_vu")
     return {"percent": int(out["percent"]), "db": float(out["db"])}
+
+
+def tone_plan_build(tones, clock_rate: int = 8000, options: int = TONE_LOOP) -> np.ndarray:
+    """igdsp_tone_plan_build (host only, no GPU): tones = a TONE_DESC array or a list of (freq1, freq2, on_msec, off_msec[, volume]);
+    returns one TONE_PLAN record."""
+    if not (isinstance(tones, np.ndarray) and tones.dtype == TONE_DESC):
+        d = np.zeros(len(tones), TONE_DESC)
+        for i, t in enumerate(tones):
+            d[i] = tuple(t) + (0,) * (6 - len(t))
+        tones = d
+    tones = np.ascontiguousarray(tones)
+    out = np.zeros((), TONE_PLAN)
+    rc = load().igdsp_tone_plan_build(tones.ctypes.data_as(_vp), len(tones), clock_rate, options, out.ctypes.data_as(_vp))
+    if rc != 0:
+        raise IgdspError(rc, "igdsp_tone_plan_build")
+    return out
+
+
+def tone_frame(plan, state, n: int = SAMPLES_PER_FRAME, cmd: int = 0):
+    """igdsp_tone_frame (host only, no GPU): one frame of one port.  plan a TONE_PLAN record, state a TONE_STATE record updated in
+    place.  Returns (samples [n] int16, len)."""
+    assert plan.dtype == TONE_PLAN and state.dtype == TONE_STATE and state.flags["C_CONTIGUOUS"] and state.flags["WRITEABLE"]
+    plan = np.ascontiguousarray(plan)
+    out = np.zeros(max(int(n), 0), np.int16)
+    ln = np.zeros((), np.uint16)
+    rc = load().igdsp_tone_frame(plan.ctypes.data_as(_vp), state.ctypes.data_as(_vp), cmd, n, out.ctypes.data_as(_vp), ln.ctypes.data_as(_vp))
+    if rc != 0:
+        raise IgdspError(rc, "igdsp_tone_frame")
+    return out, int(ln)
 
 
 def jb_report(state, prior) -> np.ndarray:
@@ -549,6 +592,13 @@ class Context:
     def snd_split(self, frames, D_, K_, F_, n=SAMPLES_PER_FRAME, pcm=None, stats=None, stream=None):
         """igdsp_snd_split: frames [F][D][n][K] int16 -> pcm [F][D * K][n] int16 and / or stats [F][D * K] FRAME_STATS (the in VU)."""
         self._ck(self.L.igdsp_snd_split(self.h, _ptr(frames), D_, K_, F_, n, _ptr(pcm), _ptr(stats), stream), "igdsp_snd_split")
+
+    def tone_generate(self, plans, n_plans, state, P_, F_, n=SAMPLES_PER_FRAME, plan_of=None, cmd=None, rows_per_frame=0, pcm=None, length=None,
+                      stats=None, stream=None):
+        """igdsp_tone_generate: plans [n_plans] TONE_PLAN, state [P] TONE_STATE (in and out), plan_of [P] u16 / None (plan 0), cmd [P] u8 /
+        None -> pcm [F][rows_per_frame or P][n] int16 rows [0, P) of each frame, length likewise u16, stats [F][P] FRAME_STATS."""
+        self._ck(self.L.igdsp_tone_generate(self.h, _ptr(plans), n_plans, _ptr(plan_of), _ptr(cmd), _ptr(state), P_, F_, n, rows_per_frame,
+                                            _ptr(pcm), _ptr(length), _ptr(stats), stream), "igdsp_tone_generate")
 
     def bss_select(self, info, group_ptr, members, n_members, state, words, C_, G_, F_, n=160, payload=None, codec=None, pcm=None,
                    length=None, gain=None, mute=None, vote_frames=0, sel=None, out=None, stats=None, stream=None):

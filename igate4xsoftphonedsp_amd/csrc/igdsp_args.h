@@ -377,4 +377,19 @@ inline Verdict snd_split(P d_frames, uint32_t D, uint32_t K, uint32_t F, uint32_
     return snd_rule(d_frames, D, K, F, n, d_pcm, d_stats);
 }
 
+// ---- tone generator (rows_per_frame 0 = n_ports; the rows of a frame that count are the larger of the two)
+inline Verdict tone_generate(P d_plans, uint32_t n_plans, P d_plan_of, P d_cmd, P d_state, uint32_t ports, uint32_t F, uint32_t n,
+                             uint32_t rows_per_frame, P d_pcm, P d_len, P d_stats)
+{
+    if (empty(ports, F)) return kNothing;
+    if (any_null({d_plans, d_state}) || n_plans == 0 || (!d_pcm && !d_stats)) return kInvalid;
+    if (rows_per_frame != 0 && rows_per_frame < ports) return kInvalid;
+    if (int rc = check_shape(rows_per_frame ? rows_per_frame : ports, F, n)) return reject(rc);
+    if (misaligned(2, {d_pcm, d_len, d_plan_of}) || misaligned(4, {d_plans, d_state}) || misaligned(8, {d_stats})) return kInvalid;
+    for (P out : {d_pcm, d_len, d_stats})
+        for (P in : {d_plans, d_plan_of, d_cmd, d_state})
+            if (out && out == in) return reject(IGDSP_EINVAL, "an output must not be an input or the state");
+    return kRun;
+}
+
 }  // namespace igdsp::args

@@ -133,6 +133,11 @@ hipError_t launch_plc_conceal(const LaunchCfg &cfg, const uint8_t *flags, const 
 // and written in memory order, no transpose and no records; it needs out
 hipError_t launch_snd(const LaunchCfg &cfg, int dir, const int16_t *in, uint32_t D, uint32_t K, uint32_t F, uint32_t n, int16_t *out,
                       igdsp_frame_stats *stats, bool yardstick, hipStream_t s);
+// igdsp_tone_generate: plan_of, cmd, len may each be nullptr; pcm and stats may be nullptr (not both: the C ABI checks); rows_per_frame 0 =
+// P.  yardstick: the compute-free form, the same items and stores, no plan, state or oscillator; it needs pcm
+hipError_t launch_tone(const LaunchCfg &cfg, const igdsp_tone_plan *plans, uint32_t n_plans, const uint16_t *plan_of, const uint8_t *cmd,
+                       igdsp_tone_state *state, uint32_t P, uint32_t F, uint32_t n, uint32_t rows_per_frame, int16_t *pcm, uint16_t *len,
+                       igdsp_frame_stats *stats, bool yardstick, hipStream_t s);
 hipError_t launch_wav_expand(const LaunchCfg &cfg, const uint8_t *payload, uint32_t C, uint32_t F, uint32_t n, uint32_t rate,
                              uint8_t *files, uint64_t file_stride, hipStream_t s);
 hipError_t launch_g726(const LaunchCfg &cfg, const uint8_t *in, uint8_t *out, uint64_t n_bytes, int mode, hipStream_t s);

@@ -11,6 +11,7 @@
 #include <utility>
 
 #include "igdsp.h"
+#include "igdsp_tone_tab.h"
 
 namespace igdsp {
 
@@ -704,6 +705,165 @@ inline SndRoute snd_route(uint32_t D, uint32_t K, uint32_t F, uint32_t n, bool b
     r.items = (uint32_t)items;
     r.grid = blocks_for((items + kSndU - 1u) / kSndU, kSndWaves, std::max(1u, cus));
     r.threads = kSndWaves * 64;
+    return r;
+}
+
+// ---- igdsp_tone_generate (launch_tone): the rules of include/igdsp.h, "Tone generator", as constexpr functions, so that the host
+// entries (igdsp_tone_plan_build, igdsp_tone_frame), k_tone and tests/route/tone_route_driver.cpp run the same code; then tone_route.
+// The oscillator reads the table as (value, delta) pairs: T[i] in the low half, T[i + 1] - T[i] (|delta| <= 202) in the high half, one
+// 4-byte lookup per oscillator sample.  kTonePairs is the host's copy; k_tone builds the same pairs in LDS from its own copy of the list.
+inline constexpr int16_t kToneSin[1024] = {IGDSP_TONE_SIN_VALUES};
+constexpr uint32_t tone_pair(int32_t v, int32_t next) { return (uint32_t)(uint16_t)v | ((uint32_t)(next - v) << 16); }
+struct TonePairs { uint32_t w[1024]; };
+constexpr TonePairs tone_make_pairs()
+{
+    TonePairs p{};
+    for (uint32_t i = 0; i < 1024u; ++i) p.w[i] = tone_pair(kToneSin[i], kToneSin[(i + 1u) & 1023u]);
+    return p;
+}
+inline constexpr TonePairs kTonePairs = tone_make_pairs();
+
+// T[i] + (((T[i + 1] - T[i]) * fr) >> 16) at phase ph: i = ph >> 22, fr = (ph >> 6) & 0xFFFF (>> of a negative value: arithmetic = floor).
+// tone_interp takes the pair already fetched: k_tone's whole-piece path issues the lookups of a piece together, then interpolates.
+constexpr int32_t tone_interp(uint32_t w, uint32_t ph)
+{
+    const int32_t v = (int16_t)(uint16_t)w, d = (int32_t)w >> 16, fr = (int32_t)((ph >> 6) & 0xFFFFu);
+    return v + ((d * fr) >> 16);
+}
+constexpr int32_t tone_osc(const uint32_t *pairs, uint32_t ph) { return tone_interp(pairs[ph >> 22], ph); }
+// the sample before the fades from the oscillators' values (the product in unsigned: a volume above 32767, which only a plan that
+// igdsp_tone_plan_build did not make can carry, wraps instead of overflowing)
+constexpr int32_t tone_scale1(const igdsp_tone_seg &sg, int32_t o1) { return (int32_t)((uint32_t)o1 * sg.vol) >> 15; }
+constexpr int32_t tone_scale2(const igdsp_tone_seg &sg, int32_t o1, int32_t o2) { return (int32_t)((uint32_t)(o1 + o2) * sg.vol) >> 16; }
+constexpr int32_t tone_amp(const uint32_t *pairs, const igdsp_tone_seg &sg, uint32_t ph1, uint32_t ph2)
+{
+    const int32_t o1 = tone_osc(pairs, ph1);
+    return sg.step2 == 0u ? tone_scale1(sg, o1) : tone_scale2(sg, o1, tone_osc(pairs, ph2));
+}
+constexpr int32_t tone_fade(const igdsp_tone_seg &sg, uint32_t k, int32_t a)
+{
+    if (k < sg.fade_in) a = a * (int32_t)k / (int32_t)sg.fade_in;
+    if (sg.fade_out != 0u && (uint64_t)k + sg.fade_out >= sg.on) a = a * (int32_t)(sg.on - 1u - k) / (int32_t)sg.fade_out;
+    return a;
+}
+// THE sample rule: offset k < sg.on inside a tone's ON period.  k_tone's whole-piece path runs the same tone_interp / tone_scale steps
+// with the phases advanced by addition ((k + 1) * step == k * step + step in 32 bits) and skips tone_fade where no sample of the piece
+// fades.
+constexpr int32_t tone_sample(const uint32_t *pairs, const igdsp_tone_seg &sg, uint32_t k)
+{
+    return tone_fade(sg, k, tone_amp(pairs, sg, k * sg.step1, k * sg.step2));
+}
+// A plan is read as it is (the device cannot reject one): more than IGDSP_TONE_MAX tones count as IGDSP_TONE_MAX, a cycle of 0 plays
+// nothing, a position no segment holds is silence.
+constexpr uint32_t tone_count(const igdsp_tone_plan &p) { return p.n_tones < IGDSP_TONE_MAX ? p.n_tones : (uint32_t)IGDSP_TONE_MAX; }
+constexpr uint32_t tone_seg_end(const igdsp_tone_plan &p, uint32_t i) { return i + 1u < tone_count(p) ? p.seg[i + 1u].start : p.cycle; }
+constexpr int32_t tone_seg_of(const igdsp_tone_plan &p, uint32_t q)          // the segment that holds cycle position q, or -1
+{
+    for (uint32_t i = 0; i < tone_count(p); ++i)
+        if (q >= p.seg[i].start && q < tone_seg_end(p, i)) return (int32_t)i;
+    return -1;
+}
+constexpr int32_t tone_at(const uint32_t *pairs, const igdsp_tone_plan &p, uint32_t q)   // the sample at cycle position q < p.cycle
+{
+    const int32_t i = tone_seg_of(p, q);
+    if (i < 0) return 0;
+    const uint32_t k = q - p.seg[i].start;
+    return k < p.seg[i].on ? tone_sample(pairs, p.seg[i], k) : 0;
+}
+// sample s of a live frame whose sample 0 is at q0 (pos + f * n; looping: any value, not looping: q0 < cycle)
+constexpr int32_t tone_frame_sample(const uint32_t *pairs, const igdsp_tone_plan &p, uint64_t q0, uint32_t s)
+{
+    uint64_t q = q0 + s;
+    if ((p.options & IGDSP_TONE_LOOP) != 0u && q >= p.cycle) { q -= p.cycle; if (q >= p.cycle) q %= p.cycle; }   // (mostly one subtraction)
+    return q < p.cycle ? tone_at(pairs, p, (uint32_t)q) : 0;
+}
+constexpr igdsp_tone_state tone_cmd(igdsp_tone_state st, uint32_t cmd)
+{
+    if ((cmd & IGDSP_TONE_CMD_STOP) != 0u) st.flags &= ~IGDSP_TONE_PLAYING;
+    else if ((cmd & IGDSP_TONE_CMD_REWIND) != 0u) { st.pos = 0u; st.flags |= IGDSP_TONE_PLAYING; }
+    return st;
+}
+// st: after tone_cmd.  A port that plays (not held, a plan, PLAYING) produces the frame at q0 = pos + f * n when this holds
+constexpr bool tone_plays(const igdsp_tone_plan &p, const igdsp_tone_state &st) { return (st.flags & IGDSP_TONE_PLAYING) != 0u && p.cycle != 0u; }
+constexpr bool tone_live(const igdsp_tone_plan &p, uint64_t q0) { return (p.options & IGDSP_TONE_LOOP) != 0u || q0 < p.cycle; }
+// the state after `samples` samples of a port that was not held (st: after tone_cmd)
+constexpr igdsp_tone_state tone_advance(const igdsp_tone_plan &p, igdsp_tone_state st, uint64_t samples)
+{
+    if (!tone_plays(p, st)) return st;
+    const uint64_t q = (uint64_t)st.pos + samples;
+    if ((p.options & IGDSP_TONE_LOOP) != 0u) { st.pos = (uint32_t)(q % p.cycle); return st; }
+    st.pos = q < p.cycle ? (uint32_t)q : p.cycle;
+    if (st.pos >= p.cycle) st.flags &= ~IGDSP_TONE_PLAYING;
+    return st;
+}
+// igdsp_tone_plan_build's rule; false: nothing written
+constexpr bool tone_plan_make(const igdsp_tone_desc *tones, uint32_t count, uint32_t clock_rate, uint32_t options, igdsp_tone_plan &out)
+{
+    if (!tones || count == 0u || count > IGDSP_TONE_MAX || clock_rate < 8000u || clock_rate > 48000u || clock_rate % 1000u != 0u) return false;
+    if ((options & ~(IGDSP_TONE_LOOP | IGDSP_TONE_NO_FADE)) != 0u) return false;
+    igdsp_tone_plan p{};
+    const uint32_t top = clock_rate / 2u - 1u;
+    uint32_t at = 0;
+    for (uint32_t i = 0; i < count; ++i) {
+        const igdsp_tone_desc &t = tones[i];
+        if (t.freq1 == 0u || t.freq1 > top || t.freq2 > top || t.volume > 32767u || t.reserved != 0u) return false;
+        igdsp_tone_seg &sg = p.seg[i];
+        const uint32_t on = t.on_msec * clock_rate / 1000u, off = t.off_msec * clock_rate / 1000u;
+        sg.start = at; sg.on = on;
+        sg.step1 = (uint32_t)((((uint64_t)t.freq1 << 32) + clock_rate / 2u) / clock_rate);
+        sg.step2 = t.freq2 ? (uint32_t)((((uint64_t)t.freq2 << 32) + clock_rate / 2u) / clock_rate) : 0u;
+        sg.vol = t.volume ? t.volume : (uint16_t)IGDSP_TONE_VOLUME;
+        const uint32_t fi = clock_rate / 1000u, fo = clock_rate / 500u;
+        const bool fade = (options & IGDSP_TONE_NO_FADE) == 0u && on >= fi + fo;
+        sg.fade_in = (uint16_t)(fade ? fi : 0u); sg.fade_out = (uint16_t)(fade ? fo : 0u);
+        at += on + off;
+    }
+    if (at == 0u) return false;
+    p.n_tones = count; p.options = options; p.cycle = at; p.clock_rate = clock_rate;
+    out = p;
+    return true;
+}
+
+// k_tone<VEC, MODE>.  A wave owns kTonePorts consecutive ports for the frames of one chunk: kToneLanes lanes per port.  The lanes of a
+// port read its plan index, cmd and state once per item, step the cycle position by n per frame and keep the segment that holds it in
+// registers; each takes the 8-sample pieces j, j + kToneLanes, .. of the row.  A piece that lies wholly in the un-faded part of an ON
+// period advances two phases by addition; one wholly in an OFF period or in an EMPTY row is zeros; the rest (a segment edge, a fade,
+// the wrap, the end of a plan that does not loop) goes sample by sample through tone_frame_sample.  Consecutive rows of a frame are
+// consecutive in memory, so a wave's stores of one frame cover one run of kTonePorts rows.  The lanes of a row fold their sums by DPP.
+//   vector form: n % 8 == 0 and d_pcm 16-byte aligned: one 16-byte store per piece.
+//   general form: everything else: the same pieces, the last one partial, stored a sample at a time.
+// Frames are cut into chunks only where the port groups alone would leave waves idle (few ports, many frames); a launch of one chunk
+// writes the state itself, otherwise k_tone_state (a thread per port) does, behind the kernel on the stream.
+constexpr int kToneWaves = 16;                            // waves per block: they share the 4 KiB pair table
+constexpr uint32_t kToneLanes = 4;                        // lanes per port
+constexpr uint32_t kTonePorts = 64u / kToneLanes;         // ports per wave: 16
+constexpr uint32_t kToneStateThreads = 256;               // k_tone_state
+enum : int { kToneBoth = 0, kTonePcm = 1, kToneStats = 2, kToneFill = 3 };   // k_tone<, MODE>: what is written; kToneFill: the yardstick
+struct ToneRoute {
+    int mode = kToneBoth;
+    uint32_t vec = 0;                      // the vector form
+    uint32_t pieces = 0;                   // 8-sample pieces per row
+    uint32_t groups = 0;                   // port groups of kTonePorts
+    uint32_t chunk_frames = 0, chunks = 0; // frames per chunk (the last takes the rest); items = groups * chunks
+    uint32_t grid = 0, threads = 0;
+    uint32_t state_grid = 0;               // k_tone_state behind the kernel (0: the kernel writes the state, or the yardstick: nobody does)
+};
+inline ToneRoute tone_route(uint32_t P, uint32_t F, uint32_t n, bool pcm, bool stats, bool yardstick, uintptr_t out, uint32_t cus)
+{
+    ToneRoute r;
+    if ((uint64_t)P * F == 0 || n == 0 || n > IGDSP_MAX_PAYLOAD || (uint64_t)P * F >= 0xFFFFFFE0ull) return r;
+    if (!pcm && !stats) return r;
+    r.mode = yardstick ? kToneFill : (pcm && stats ? kToneBoth : (pcm ? kTonePcm : kToneStats));
+    r.vec = (n & 7u) == 0u && aligned(out, 16) ? 1u : 0u;
+    r.pieces = (n + 7u) / 8u;
+    r.groups = (uint32_t)(((uint64_t)P + kTonePorts - 1u) / kTonePorts);
+    const uint32_t want = std::max(1u, cus) * (uint32_t)kToneWaves;
+    const uint32_t cuts = r.groups >= want ? 1u : std::min(F, (want + r.groups - 1u) / r.groups);
+    r.chunk_frames = (F + cuts - 1u) / cuts;
+    r.chunks = (F + r.chunk_frames - 1u) / r.chunk_frames;
+    r.grid = blocks_for((uint64_t)r.groups * r.chunks, kToneWaves, std::max(1u, cus));
+    r.threads = kToneWaves * 64;
+    r.state_grid = !yardstick && r.chunks > 1u ? (P + kToneStateThreads - 1u) / kToneStateThreads : 0u;
     return r;
 }
 

@@ -821,6 +821,90 @@ int igdsp_host_sc_vu(void *v, const int16_t *frame, igdsp_frame_stats *out)
     return IGDSP_OK;
 }
 
+// ---- the ring tone, no context needed
+RingTone::RingTone(uint32_t clock_rate, uint32_t samples_per_frame)
+    : n(samples_per_frame < 1 ? 1 : (samples_per_frame > IGDSP_MAX_PAYLOAD ? IGDSP_MAX_PAYLOAD : samples_per_frame)), connected_(false), rewind_(false)
+{
+    static const uint16_t off_msec[3] = {1000, 4000, 3000};                       // Functions.cpp:542-553
+    for (int i = 0; i < 3; ++i) {
+        tone[i].freq1 = 440; tone[i].freq2 = 480; tone[i].on_msec = 2000; tone[i].off_msec = off_msec[i];
+        tone[i].volume = 0; tone[i].reserved = 0;
+    }
+    std::memset(&plan, 0, sizeof(plan));
+    ok = igdsp_tone_plan_build(tone, 1, clock_rate, IGDSP_TONE_LOOP, &plan) == IGDSP_OK;   // count = 1, as pjmedia_tonegen_play(.., 1, tone, ..)
+    state.pos = 0;
+    state.flags = IGDSP_TONE_PLAYING;
+}
+
+void RingTone::playRing() { connected_ = true; }
+
+void RingTone::stopRing()
+{
+    connected_ = false;
+    rewind_ = true;
+}
+
+uint32_t RingTone::connections(uint32_t tone_channel, uint32_t *channel, uint32_t *port) const
+{
+    if (!connected_ || !channel || !port) return 0;
+    channel[0] = tone_channel;
+    port[0] = 0;
+    return 1;
+}
+
+uint32_t RingTone::cmd()
+{
+    const uint32_t c = (rewind_ ? IGDSP_TONE_CMD_REWIND : 0u) | (connected_ ? 0u : IGDSP_TONE_CMD_HOLD);
+    rewind_ = false;
+    return c;
+}
+
+int RingTone::frame(int16_t *out, uint16_t *len)
+{
+    if (!ok) return IGDSP_EINVAL;
+    return igdsp_tone_frame(&plan, &state, cmd(), n, out, len);
+}
+
+void *igdsp_host_ring_new(uint32_t clock_rate, uint32_t samples_per_frame)
+{
+    if (samples_per_frame < 1 || samples_per_frame > IGDSP_MAX_PAYLOAD) return nullptr;
+    RingTone *r = new (std::nothrow) RingTone(clock_rate, samples_per_frame);
+    if (r && !r->ok) { delete r; r = nullptr; }
+    return r;
+}
+void igdsp_host_ring_free(void *v) { delete static_cast<RingTone *>(v); }
+int igdsp_host_ring_play(void *v)
+{
+    if (!v) return IGDSP_EINVAL;
+    static_cast<RingTone *>(v)->playRing();
+    return IGDSP_OK;
+}
+int igdsp_host_ring_stop(void *v)
+{
+    if (!v) return IGDSP_EINVAL;
+    static_cast<RingTone *>(v)->stopRing();
+    return IGDSP_OK;
+}
+int igdsp_host_ring_connections(void *v, uint32_t tone_channel, uint32_t *channel, uint32_t *port)
+{
+    if (!v || !channel || !port) return IGDSP_EINVAL;
+    return (int)static_cast<const RingTone *>(v)->connections(tone_channel, channel, port);
+}
+int igdsp_host_ring_cmd(void *v) { return v ? (int)static_cast<RingTone *>(v)->cmd() : IGDSP_EINVAL; }
+int igdsp_host_ring_frame(void *v, int16_t *out, uint16_t *len)
+{
+    if (!v || !out || !len) return IGDSP_EINVAL;
+    return static_cast<RingTone *>(v)->frame(out, len);
+}
+int igdsp_host_ring_get(void *v, igdsp_tone_plan *plan, igdsp_tone_state *state)
+{
+    const RingTone *r = static_cast<const RingTone *>(v);
+    if (!r || !plan || !state) return IGDSP_EINVAL;
+    *plan = r->plan;
+    *state = r->state;
+    return IGDSP_OK;
+}
+
 // ---- conference receive levels, no context needed
 void *igdsp_host_levels_new(uint32_t n_channels)
 {

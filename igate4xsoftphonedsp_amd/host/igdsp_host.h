@@ -210,6 +210,32 @@ public:
     igdsp_frame_stats vu(const int16_t *frame, int k) const;
 };
 
+// The ring tone, RoIP_ED137::init_ringTone / playRing / stopRing (Functions.cpp:523-571), without a context: the tonegen port's plan and
+// state, and whether the port is connected to port 0 of the bridge.  The reference fills three descriptors (440 + 480 Hz, 2 s on, then
+// 1 s / 4 s / 3 s off) and plays count = 1 with PJMEDIA_TONEGEN_LOOP: the cadence is 2 s on / 1 s off, and so it is here.  The bridge
+// pulls a port only while something listens to it, so a ring that is not connected is held (IGDSP_TONE_CMD_HOLD) and stays where
+// stopRing's rewind left it.  A gateway of the reference's size calls frame() once per tick; igdsp_tone_generate takes plan, cmd() and
+// the state for thousands of consoles.
+class RingTone {
+public:
+    explicit RingTone(uint32_t clock_rate = 8000, uint32_t samples_per_frame = IGDSP_SAMPLES_PER_FRAME);   // init_ringTone
+    igdsp_tone_desc tone[3];                 // as the reference fills them; tone[1] and tone[2] are never played
+    igdsp_tone_plan plan;                    // igdsp_tone_plan_build(tone, 1, clock_rate, IGDSP_TONE_LOOP)
+    igdsp_tone_state state;                  // pjmedia_tonegen_play at init: PLAYING from position 0
+    uint32_t n;
+    bool ok;                                 // the plan was built (a clock rate igdsp_tone_plan_build takes)
+    void playRing();                         // pjsua_conf_connect(in_ring_slot_, 0)
+    void stopRing();                         // pjsua_conf_disconnect(in_ring_slot_, 0), pjmedia_tonegen_rewind
+    bool connected() const { return connected_; }
+    // the (tone row -> port 0) connection for igdsp_conf_build: writes channel[0] = tone_channel, port[0] = 0 and returns 1 while
+    // connected, else returns 0
+    uint32_t connections(uint32_t tone_channel, uint32_t *channel, uint32_t *port) const;
+    uint32_t cmd();                          // the d_cmd byte of the next launch: REWIND once after stopRing, HOLD while not connected
+    int frame(int16_t *out, uint16_t *len);  // one tick on the CPU: igdsp_tone_frame with cmd()
+private:
+    bool connected_, rewind_;
+};
+
 class RoIP_ED137 {
 public:
     // Unlike the reference singleton (roip_ed137.cpp:192) the instance owns an igdsp context; device < 0
@@ -312,6 +338,16 @@ void  igdsp_host_sc_free(void *v);
 int   igdsp_host_sc_combine(void *v, const int16_t *const *rows, int16_t *frame);
 int   igdsp_host_sc_split(void *v, const int16_t *frame, int16_t *const *rows);
 int   igdsp_host_sc_vu(void *v, const int16_t *frame, igdsp_frame_stats *out);
+// the ring tone without a context (RingTone): NULL from _new for a clock rate igdsp_tone_plan_build rejects or samples_per_frame outside
+// 1 .. 256; _connections as RingTone::connections; _cmd as RingTone::cmd; _frame one tick (IGDSP_EINVAL for a NULL argument)
+void *igdsp_host_ring_new(uint32_t clock_rate, uint32_t samples_per_frame);
+void  igdsp_host_ring_free(void *v);
+int   igdsp_host_ring_play(void *v);
+int   igdsp_host_ring_stop(void *v);
+int   igdsp_host_ring_connections(void *v, uint32_t tone_channel, uint32_t *channel, uint32_t *port);
+int   igdsp_host_ring_cmd(void *v);
+int   igdsp_host_ring_frame(void *v, int16_t *out, uint16_t *len);
+int   igdsp_host_ring_get(void *v, igdsp_tone_plan *plan, igdsp_tone_state *state);
 // Meter output on the reference's other channel: AudioMeter (audiometer.cpp:11-34) reads ASCII decimal levels from the
 // FIFO /tmp/capturefifo<card>, 32 bytes per read, and emits onValueChanged(int(float(v*100.0/30000.0))).  These write
 // such records, so the reference's own meter consumer can be fed from igdsp_poll().rms.  open() waits up to

@@ -40,7 +40,8 @@ extern "C" {
  *    IGDSP_FLAG_CONCEALED, igdsp_plc_conceal); PTT priority arbitration (igdsp_ptt_state, igdsp_ptt_slot, igdsp_ptt_tick, IGDSP_PTT_*,
  *    igdsp_ptt_arbitrate); R2S link supervision and the device event list (igdsp_link_state, igdsp_link_event, IGDSP_LINK_*,
  *    igdsp_link_work_bytes, igdsp_link_watch); the sound-card splitter / combiner (IGDSP_SND_*, igdsp_snd_combine, igdsp_snd_split,
- *    igdsp_snd_vu_t, igdsp_snd_vu). */
+ *    igdsp_snd_vu_t, igdsp_snd_vu); the tone generator (IGDSP_TONE_*, igdsp_tone_desc, igdsp_tone_seg, igdsp_tone_plan,
+ *    igdsp_tone_state, igdsp_tone_plan_build, igdsp_tone_frame, igdsp_tone_generate). */
 #define IGDSP_ABI_VERSION 3
 
 /* ---- error codes (0 == PJ_SUCCESS-style success) ------------------------- */
@@ -1144,6 +1145,79 @@ typedef struct igdsp_snd_vu_t {
     double  db;
 } igdsp_snd_vu_t;
 int igdsp_snd_vu(const igdsp_frame_stats *st, igdsp_snd_vu_t *out);
+
+/* ---- Tone generator: the bridge's last source, the ring tone --------------------------------------------------------------------------
+ * RoIP_ED137::init_ringTone (Functions.cpp:532-571, called at roip_ed137.cpp:3082) creates a pjmedia_tonegen port (8 kHz, mono, 160
+ * samples, 16 bit, PJMEDIA_TONEGEN_LOOP), plays a 440 + 480 Hz dual tone of 2 000 ms on / 1 000 ms off and adds the port to the bridge;
+ * playRing / stopRing (Functions.cpp:523-531) connect and disconnect it to port 0 and rewind it.  A tone PORT here is one such
+ * generator: a row of PCM per frame that igdsp_conf_mix takes as one more d_pcm channel.  Everything is integer.
+ *
+ * PLAN (igdsp_tone_plan_build, host only, no GPU): count = 1..IGDSP_TONE_MAX descriptors with pjmedia_tone_desc's fields; clock_rate a
+ * multiple of 1 000 in 8 000..48 000; freq1 in 1..clock_rate / 2 - 1, freq2 0 (single tone) or in the same range; volume <= 32767,
+ * 0 = IGDSP_TONE_VOLUME; reserved 0; options a combination of IGDSP_TONE_LOOP and IGDSP_TONE_NO_FADE.  Per tone i:
+ *   on = on_msec * clock_rate / 1000, off likewise (integer division); start_i = sum over j < i of (on_j + off_j);
+ *   step(f) = ((f << 32) + clock_rate / 2) / clock_rate in 64 bits, step2 = 0 for a single tone;
+ *   fade_in = clock_rate / 1000, fade_out = clock_rate / 500, both 0 with IGDSP_TONE_NO_FADE or when on < fade_in + fade_out.
+ * cycle = sum of (on_i + off_i) must be >= 1.  Anything else: IGDSP_EINVAL, nothing written.
+ *
+ * OSCILLATOR.  T[i] = floor(32767 sin(2 pi i / 1024) + 0.5), i = 0..1023, a list of constants in the source (no libm at run time;
+ * T[256] = 32767, T[i] = -T[1024 - i]).  For sample offset k >= 0 inside a tone's ON period, per oscillator:
+ *   ph = (uint32_t)(k * step);  i = ph >> 22;  fr = (ph >> 6) & 0xFFFF
+ *   osc = T[i] + (((T[(i + 1) & 1023] - T[i]) * fr) >> 16)                  arithmetic shift = floor
+ *   single: a = (osc1 * vol) >> 15          dual: a = ((osc1 + osc2) * vol) >> 16
+ *   k < fade_in:        a = a * k / fade_in                                 C division, toward zero
+ *   k >= on - fade_out: a = a * (on - 1 - k) / fade_out
+ * The phase restarts at 0 at every tone start.  Against float64 the oscillator is within 2 of 32767 sin(2 pi ph / 2^32) and the output
+ * within 4 of vol sin (single) / vol (sin + sin) / 2 (dual); a step is within clock_rate / 2^33 Hz of its frequency.
+ *
+ * PORT-FRAME.  Port p, frame f, sample s of a launch of F frames of n samples (n = 1..256).  d_cmd[p], if given, is applied first:
+ * IGDSP_TONE_CMD_STOP clears IGDSP_TONE_PLAYING; IGDSP_TONE_CMD_REWIND without STOP sets pos = 0 and PLAYING (pjmedia_tonegen_play and
+ * pjmedia_tonegen_rewind); IGDSP_TONE_CMD_HOLD: the bridge does not pull this port in this launch: every frame is EMPTY and pos does not
+ * advance (STOP and REWIND still take effect).  A port whose d_plan_of[p] >= n_plans is EMPTY in every frame, its plan is never
+ * dereferenced and its state is written back unchanged apart from the cmd.  With PLAYING set, q0 = pos + f * n in 64 bits:
+ *   looping:      q = (q0 + s) mod cycle; the frame is always produced;
+ *   not looping:  produced when q0 < cycle, with q = q0 + s and samples with q >= cycle 0; EMPTY when q0 >= cycle.
+ * In a produced frame the segment with start_i <= q < start_i + on_i + off_i gives k = q - start_i: the oscillator rule when k < on_i,
+ * else 0.  EMPTY: zeros, len 0 and igdsp_decode_meter's len-0 record (all 0, IGDSP_FLAG_EMPTY).  Produced: len n and the record as
+ * igdsp_conf_mix writes it (sumsq exact, rms = sqrtf((float)sumsq / n), peak, byte_mean 0, IGDSP_FLAG_SILENT when peak <= 8).
+ * State after the launch of a port that was not held and is PLAYING: looping pos' = (pos + F * n) mod cycle; not looping
+ * pos' = min(pos + F * n, cycle), and PLAYING stays set only while pos' < cycle.  A port that is not PLAYING does not move.  So F frames
+ * in one launch, F launches of one frame and any split in between give the same rows and the same final state.
+ * A plan that igdsp_tone_plan_build did not make is read as it is and is safe: n_tones above IGDSP_TONE_MAX counts as IGDSP_TONE_MAX, a
+ * cycle of 0 plays nothing, a position that no segment holds is silence.
+ *
+ * igdsp_tone_frame (host only): one frame of one port by the same rule, the state advanced; plan, st, out and len required, cmd as
+ * d_cmd[p], samples_per_frame 1..256 (else IGDSP_EINVAL).
+ * igdsp_tone_generate: d_plans [n_plans] (n_plans >= 1), d_state [P] required, 4-byte aligned; d_plan_of [P] optional (NULL: plan 0),
+ * 2-byte aligned; d_cmd [P] optional.  rows_per_frame is the frame stride of d_pcm and d_len in rows: 0 means n_ports, otherwise
+ * >= n_ports; tone rows can so be written beside the calls' rows of a [F][C + P][n] array that igdsp_conf_mix reads with
+ * n_channels = C + P; rows outside [0, P) of each frame are not touched.  d_stats is dense [F][P].  At least one of d_pcm and d_stats;
+ * d_len optional.  d_pcm and d_len 2-byte, d_stats 8-byte aligned; an output must not be one of the inputs or the state, and the
+ * buffers must not overlap at all.  n_ports == 0 or n_frames == 0: nothing to do, the state is untouched.
+ * max(rows_per_frame, n_ports) * n_frames < 2^32 - 32 (IGDSP_ERANGE).  Enqueued on `stream`, not synchronised.
+ *
+ * Fidelity.  UNVERIFIED: pjmedia's tonegen.c is not in the reference tree, so its default amplitude (IGDSP_TONE_VOLUME), the shape and
+ * length of its fades and the restart of the phase at every tone are this library's own rules, not compared with it.  The reference
+ * fills three descriptors and plays count = 1 (Functions.cpp:542-560): its cadence is 2 s on / 1 s off. */
+#define IGDSP_TONE_MAX      8        /* tones per plan */
+#define IGDSP_TONE_VOLUME   12288    /* used when a desc's volume is 0 (pjmedia's default amplitude; UNVERIFIED) */
+#define IGDSP_TONE_LOOP     1u       /* plan option: PJMEDIA_TONEGEN_LOOP */
+#define IGDSP_TONE_NO_FADE  2u       /* plan option */
+#define IGDSP_TONE_PLAYING  1u       /* state flag */
+#define IGDSP_TONE_CMD_REWIND 1u     /* d_cmd bits, applied before frame 0 of a launch */
+#define IGDSP_TONE_CMD_STOP   2u
+#define IGDSP_TONE_CMD_HOLD   4u
+typedef struct igdsp_tone_desc { uint16_t freq1, freq2, on_msec, off_msec, volume, reserved; } igdsp_tone_desc;   /* pjmedia_tone_desc's fields */
+typedef struct igdsp_tone_seg { uint32_t start, on, step1, step2; uint16_t vol, fade_in, fade_out, reserved; } igdsp_tone_seg;   /* 24 bytes */
+typedef struct igdsp_tone_plan { uint32_t n_tones, options, cycle, clock_rate; igdsp_tone_seg seg[IGDSP_TONE_MAX]; } igdsp_tone_plan;   /* 208 bytes */
+typedef struct igdsp_tone_state { uint32_t pos, flags; } igdsp_tone_state;   /* 8 bytes per port; all-zero: stopped at the start */
+int igdsp_tone_plan_build(const igdsp_tone_desc *tones, uint32_t count, uint32_t clock_rate, uint32_t options, igdsp_tone_plan *out);
+int igdsp_tone_frame(const igdsp_tone_plan *plan, igdsp_tone_state *st, uint32_t cmd, uint32_t samples_per_frame, int16_t *out,
+                     uint16_t *len);
+int igdsp_tone_generate(igdsp_ctx *ctx, const igdsp_tone_plan *d_plans, uint32_t n_plans, const uint16_t *d_plan_of /* [P], NULL: plan 0 */,
+                        const uint8_t *d_cmd /* [P], optional */, igdsp_tone_state *d_state /* [P], in and out */,
+                        uint32_t n_ports, uint32_t n_frames, uint32_t samples_per_frame, uint32_t rows_per_frame,
+                        int16_t *d_pcm, uint16_t *d_len, igdsp_frame_stats *d_stats /* [F][P], dense */, void *stream);
 
 /* ---- synthetic input generators (device side; SURVEY 8(d) definitions) ---------
  * D-uniform: byte k of global byte index g is
