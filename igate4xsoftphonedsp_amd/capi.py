@@ -81,6 +81,12 @@ TONE_SEG = np.dtype([("start", "<u4"), ("on", "<u4"), ("step1", "<u4"), ("step2"
                      ("reserved", "<u2")], align=True)                                             # igdsp_tone_seg, 24 bytes
 TONE_PLAN = np.dtype([("n_tones", "<u4"), ("options", "<u4"), ("cycle", "<u4"), ("clock_rate", "<u4"), ("seg", TONE_SEG, (TONE_MAX,))], align=True)   # 208 bytes
 TONE_STATE = np.dtype([("pos", "<u4"), ("flags", "<u4")], align=True)                            # igdsp_tone_state
+# the rate converter (igdsp_rs_taps / igdsp_rs_frame / igdsp_resample)
+RS_UP, RS_DOWN = 0, 1
+RS_ROWS, RS_SUBFRAMES = 0, 1
+RS_TAPS, RS_HIST = 24, 144
+RS_FACTORS = (2, 3, 4, 6)
+RS_STATE = np.dtype([("hist", "<i2", (RS_HIST,)), ("flags", "<u4"), ("frames", "<u4")], align=True)   # igdsp_rs_state, 296 bytes
 CHAN_PROBE = np.dtype([("run", "<u4"), ("alarms", "<u4")], align=True)
 # the jitter buffer (igdsp_jb_receive / igdsp_jb_report)
 JB_STATE = np.dtype(
@@ -245,6 +251,9 @@ PROTOTYPES = [
     ("igdsp_tone_plan_build", _int, [_vp, _u32, _u32, _u32, _vp]),
     ("igdsp_tone_frame", _int, [_vp, _vp, _u32, _u32, _vp, _vp]),
     ("igdsp_tone_generate", _int, [_vp, _vp, _u32, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp]),
+    ("igdsp_rs_taps", _int, [_u32, _u32, C.POINTER(_vp), C.POINTER(_u32)]),
+    ("igdsp_rs_frame", _int, [_vp, _u32, _u32, _vp, _u32, _vp]),
+    ("igdsp_resample", _int, [_vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp]),
     ("igdsp_g726_reorder", _int, [_vp, _vp, _vp, _u64, _int, _vp]),
     ("igdsp_gen_uniform", _int, [_vp, _vp, _u64, _u64, _u64, _vp]),
     ("igdsp_dev_alloc", _int, [_vp, C.POINTER(_vp), C.c_size_t]),
@@ -381,6 +390,29 @@ def tone_frame(plan, state, n: int = SAMPLES_PER_FRAME, cmd: int = 0):
     if rc != 0:
         raise IgdspError(rc, "igdsp_tone_frame")
     return out, int(ln)
+
+
+def rs_taps(direction: int, factor: int) -> np.ndarray:
+    """igdsp_rs_taps (host only, no GPU): a copy of the Q14 table of a direction and factor: U_R as [R][24] for RS_UP, D_R as [24 R] for
+    RS_DOWN."""
+    p, n = _vp(), _u32()
+    rc = load().igdsp_rs_taps(direction, factor, C.byref(p), C.byref(n))
+    if rc != 0:
+        raise IgdspError(rc, "igdsp_rs_taps")
+    t = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int16)), (n.value,)).copy()
+    return t.reshape(factor, RS_TAPS) if direction == RS_UP else t
+
+
+def rs_frame(state, direction: int, factor: int, x) -> np.ndarray:
+    """igdsp_rs_frame (host only, no GPU): one frame of one channel.  state an RS_STATE record updated in place, x the frame's input
+    (int16: n for RS_UP, n * factor for RS_DOWN).  Returns the output samples (n * factor / n)."""
+    assert state.dtype == RS_STATE and state.flags["C_CONTIGUOUS"] and state.flags["WRITEABLE"]
+    x = np.ascontiguousarray(x, np.int16)
+    out = np.zeros(len(x) * factor if direction == RS_UP else len(x) // max(factor, 1), np.int16)
+    rc = load().igdsp_rs_frame(state.ctypes.data_as(_vp), direction, factor, x.ctypes.data_as(_vp), len(x), out.ctypes.data_as(_vp))
+    if rc != 0:
+        raise IgdspError(rc, "igdsp_rs_frame")
+    return out
 
 
 def jb_report(state, prior) -> np.ndarray:
@@ -599,6 +631,14 @@ class Context:
         None -> pcm [F][rows_per_frame or P][n] int16 rows [0, P) of each frame, length likewise u16, stats [F][P] FRAME_STATS."""
         self._ck(self.L.igdsp_tone_generate(self.h, _ptr(plans), n_plans, _ptr(plan_of), _ptr(cmd), _ptr(state), P_, F_, n, rows_per_frame,
                                             _ptr(pcm), _ptr(length), _ptr(stats), stream), "igdsp_tone_generate")
+
+    def resample(self, direction, factor, state, C_, F_, n=SAMPLES_PER_FRAME, layout=RS_ROWS, payload=None, codec=None, pcm=None, length=None,
+                 rows_narrow=0, rows_wide=0, out=None, stats=None, stream=None):
+        """igdsp_resample: RS_UP takes payload [F][C][n] u8 (+ codec [C]) or pcm [F][rows_narrow or C][n] int16 to the wide side, RS_DOWN takes
+        pcm from the wide side to [F][rows_narrow or C][n]; the wide side is [F][rows_wide or C][n * factor] (RS_ROWS) or
+        [F * factor][rows_wide or C][n] (RS_SUBFRAMES); state [C] RS_STATE (in and out); stats dense, one per output row."""
+        self._ck(self.L.igdsp_resample(self.h, direction, factor, layout, _ptr(payload), _ptr(codec), _ptr(pcm), _ptr(length), _ptr(state), C_, F_, n,
+                                       rows_narrow, rows_wide, _ptr(out), _ptr(stats), stream), "igdsp_resample")
 
     def bss_select(self, info, group_ptr, members, n_members, state, words, C_, G_, F_, n=160, payload=None, codec=None, pcm=None,
                    length=None, gain=None, mute=None, vote_frames=0, sel=None, out=None, stats=None, stream=None):

@@ -392,4 +392,25 @@ inline Verdict tone_generate(P d_plans, uint32_t n_plans, P d_plan_of, P d_cmd, 
     return kRun;
 }
 
+// ---- rate converter.  The direction, the factor and the layout are checked whether or not there is work.  rows_narrow / rows_wide
+// 0 = n_channels; the rows that count on a side are its stride times its frames (n_frames, times the factor for a wide side in sub-frames)
+inline Verdict resample(uint32_t dir, uint32_t factor, uint32_t layout, P d_payload, P d_codec, P d_pcm, P d_len, P d_state, uint32_t C, uint32_t F,
+                        uint32_t n, uint32_t rows_narrow, uint32_t rows_wide, P d_out, P d_stats)
+{
+    if (!rs_dir_ok(dir) || !rs_factor_ok(factor) || layout > IGDSP_RS_SUBFRAMES) return kInvalid;
+    if (empty(C, F)) return kNothing;
+    if (dir == IGDSP_RS_UP ? (!exactly_one(d_payload, d_pcm) || (d_payload && !d_codec)) : (!d_pcm || d_payload)) return kInvalid;
+    if (!d_state || (!d_out && !d_stats)) return kInvalid;
+    if ((rows_narrow != 0 && rows_narrow < C) || (rows_wide != 0 && rows_wide < C)) return kInvalid;
+    if (n == 0 || n > IGDSP_MAX_PAYLOAD) return kInvalid;
+    const uint64_t wide_frames = (uint64_t)F * (layout == IGDSP_RS_SUBFRAMES ? factor : 1u);
+    if ((uint64_t)(rows_narrow ? rows_narrow : C) * F >= 0xFFFFFFE0ull || (uint64_t)(rows_wide ? rows_wide : C) * wide_frames >= 0xFFFFFFE0ull)
+        return reject(IGDSP_ERANGE);
+    if (misaligned(2, {d_pcm, d_len, d_out}) || misaligned(4, {d_state}) || misaligned(8, {d_stats})) return kInvalid;
+    for (P out : {d_out, d_stats})
+        for (P in : {d_payload, d_codec, d_pcm, d_len, d_state})
+            if (out && out == in) return reject(IGDSP_EINVAL, "an output must not be an input or the state");
+    return kRun;
+}
+
 }  // namespace igdsp::args

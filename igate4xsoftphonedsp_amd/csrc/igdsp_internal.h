@@ -138,6 +138,12 @@ hipError_t launch_snd(const LaunchCfg &cfg, int dir, const int16_t *in, uint32_t
 hipError_t launch_tone(const LaunchCfg &cfg, const igdsp_tone_plan *plans, uint32_t n_plans, const uint16_t *plan_of, const uint8_t *cmd,
                        igdsp_tone_state *state, uint32_t P, uint32_t F, uint32_t n, uint32_t rows_per_frame, int16_t *pcm, uint16_t *len,
                        igdsp_frame_stats *stats, bool yardstick, hipStream_t s);
+// igdsp_resample: exactly one of g711 (+ codec, UP only) / pcm; len may be nullptr; out and stats may be nullptr (not both: the C ABI
+// checks); rows_narrow / rows_wide 0 = C.  yardstick: the compute-free form, the same loads, LDS traffic and stores, no filter, zero
+// records, the state neither read nor written
+hipError_t launch_rs(const LaunchCfg &cfg, uint32_t dir, uint32_t R, uint32_t layout, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm,
+                     const uint16_t *len, igdsp_rs_state *state, uint32_t C, uint32_t F, uint32_t n, uint32_t rows_narrow, uint32_t rows_wide,
+                     int16_t *out, igdsp_frame_stats *stats, bool yardstick, hipStream_t s);
 hipError_t launch_wav_expand(const LaunchCfg &cfg, const uint8_t *payload, uint32_t C, uint32_t F, uint32_t n, uint32_t rate,
                              uint8_t *files, uint64_t file_stride, hipStream_t s);
 hipError_t launch_g726(const LaunchCfg &cfg, const uint8_t *in, uint8_t *out, uint64_t n_bytes, int mode, hipStream_t s);

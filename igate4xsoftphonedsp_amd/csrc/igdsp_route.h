@@ -11,6 +11,7 @@
 #include <utility>
 
 #include "igdsp.h"
+#include "igdsp_rs_tab.h"
 #include "igdsp_tone_tab.h"
 
 namespace igdsp {
@@ -864,6 +865,129 @@ inline ToneRoute tone_route(uint32_t P, uint32_t F, uint32_t n, bool pcm, bool s
     r.grid = blocks_for((uint64_t)r.groups * r.chunks, kToneWaves, std::max(1u, cus));
     r.threads = kToneWaves * 64;
     r.state_grid = !yardstick && r.chunks > 1u ? (P + kToneStateThreads - 1u) / kToneStateThreads : 0u;
+    return r;
+}
+
+// ---- igdsp_resample (launch_rs): the rules of include/igdsp.h, "Rate converter", as constexpr functions, so that the host entries
+// (igdsp_rs_frame, igdsp_rs_taps), k_rs and tests/route/rs_route_driver.cpp run the same code; then rs_route.
+inline constexpr int16_t kRsUp2[2 * IGDSP_RS_TAPS] = {IGDSP_RS_UP2_VALUES}, kRsDown2[2 * IGDSP_RS_TAPS] = {IGDSP_RS_DOWN2_VALUES};
+inline constexpr int16_t kRsUp3[3 * IGDSP_RS_TAPS] = {IGDSP_RS_UP3_VALUES}, kRsDown3[3 * IGDSP_RS_TAPS] = {IGDSP_RS_DOWN3_VALUES};
+inline constexpr int16_t kRsUp4[4 * IGDSP_RS_TAPS] = {IGDSP_RS_UP4_VALUES}, kRsDown4[4 * IGDSP_RS_TAPS] = {IGDSP_RS_DOWN4_VALUES};
+inline constexpr int16_t kRsUp6[6 * IGDSP_RS_TAPS] = {IGDSP_RS_UP6_VALUES}, kRsDown6[6 * IGDSP_RS_TAPS] = {IGDSP_RS_DOWN6_VALUES};
+constexpr uint32_t kRsTaps = IGDSP_RS_TAPS, kRsHist = IGDSP_RS_HIST;
+constexpr bool rs_factor_ok(uint32_t R) { return R == 2u || R == 3u || R == 4u || R == 6u; }
+constexpr bool rs_dir_ok(uint32_t dir) { return dir == IGDSP_RS_UP || dir == IGDSP_RS_DOWN; }
+// U_R in [p][k] order or D_R, 24 R values each; nullptr for a direction or factor that does not exist
+constexpr const int16_t *rs_table(uint32_t dir, uint32_t R)
+{
+    if (!rs_dir_ok(dir)) return nullptr;
+    const bool up = dir == IGDSP_RS_UP;
+    return R == 2u ? (up ? kRsUp2 : kRsDown2) : R == 3u ? (up ? kRsUp3 : kRsDown3) : R == 4u ? (up ? kRsUp4 : kRsDown4)
+         : R == 6u ? (up ? kRsUp6 : kRsDown6) : nullptr;
+}
+constexpr int32_t rs_clamp16(int32_t v) { return v > 32767 ? 32767 : (v < -32768 ? -32768 : v); }
+constexpr int32_t rs_round(int32_t acc) { return (acc + 8192) >> 14; }     // arithmetic shift: a floor
+// THE sample rules, before the clamp.  xg points at x[g] (UP) / x[g R + R - 1] (DOWN) of a stream with its predecessors in front of it
+constexpr int32_t rs_up_raw(const int16_t *tab, uint32_t p, const int16_t *xg)
+{
+    int32_t acc = 0;
+    for (uint32_t k = 0; k < kRsTaps; ++k) acc += (int32_t)tab[p * kRsTaps + k] * xg[-(int32_t)k];
+    return rs_round(acc);
+}
+constexpr int32_t rs_down_raw(const int16_t *tab, uint32_t R, const int16_t *xe)
+{
+    int32_t acc = 0;
+    for (uint32_t j = 0; j < kRsTaps * R; ++j) acc += (int32_t)tab[j] * xe[-(int32_t)j];
+    return rs_round(acc);
+}
+// k_rs reads a window oldest sample first, two samples per dword: the taps of window samples t0 (low half) and t0 + 1 (high half) of
+// the 24 (UP, phase p) / 24 R (DOWN) samples that end at x[g] / x[g R + R - 1]
+constexpr uint32_t rs_pair(uint32_t dir, uint32_t R, uint32_t p, uint32_t t0)
+{
+    const int16_t *tab = rs_table(dir, R);
+    const uint32_t last = dir == IGDSP_RS_UP ? p * kRsTaps + kRsTaps - 1u : kRsTaps * R - 1u;
+    return (uint32_t)(uint16_t)tab[last - t0] | ((uint32_t)(uint16_t)tab[last - t0 - 1u] << 16);
+}
+// igdsp_rs_frame's rule: one frame of one channel, n_in input samples (checked by the caller), the state advanced; *sat (optional):
+// the clamp fired
+inline void rs_frame_run(igdsp_rs_state &st, uint32_t dir, uint32_t R, const int16_t *in, uint32_t n_in, int16_t *out, bool *sat = nullptr)
+{
+    int16_t x[kRsHist + IGDSP_MAX_PAYLOAD * 6u];
+    for (uint32_t i = 0; i < kRsHist; ++i) x[i] = st.hist[i];
+    for (uint32_t i = 0; i < n_in; ++i) x[kRsHist + i] = in[i];
+    const int16_t *tab = rs_table(dir, R);
+    bool clamped = false;
+    const uint32_t n_out = dir == IGDSP_RS_UP ? n_in * R : n_in / R;
+    for (uint32_t q = 0; q < n_out; ++q) {
+        const int32_t v = dir == IGDSP_RS_UP ? rs_up_raw(tab, q % R, x + kRsHist + q / R) : rs_down_raw(tab, R, x + kRsHist + q * R + R - 1u);
+        clamped |= v != rs_clamp16(v);
+        out[q] = (int16_t)rs_clamp16(v);
+    }
+    for (uint32_t i = 0; i < kRsHist; ++i) st.hist[i] = x[n_in + i];
+    st.frames += 1u;
+    if (sat) *sat = clamped;
+}
+
+// k_rs<DIR, R, COPY, VEC>.  A wave owns ch consecutive channels for the frames of one chunk, lanes lanes per channel, and keeps each
+// channel's input row with its hist = 24 (UP) / 24 R (DOWN) predecessors in a tile of LDS: the predecessors of a chunk's first frame
+// come sample by sample from the state or the earlier rows, those of every later frame are the tile's own tail moved to its front.  A
+// lane takes units of 8 narrow samples: UP it reads the 32 tile samples that end with its 8 inputs and writes R 16-byte pieces, DOWN
+// it reads the 32 R tile samples that end with its 8 R inputs and writes one.  The taps are compile-time constants of the
+// instantiation (rs_pair), the samples come as dwords in both packings (the odd one by a funnel shift of two neighbours).
+//   vector form: n % 8 == 0, the input base 16-byte (G.711: 8-byte) and d_out 16-byte aligned: 16-byte loads and stores;
+//   general form: everything else: the same units, loaded and stored a sample at a time.
+// Records: per output piece packed dot products and min / max of the values before the clamp, folded per output row in LDS.
+// The grid is sized for the blocks a CU holds (rs_resident); frames are cut into chunks until a wave has about kRsItemsPerWave items.
+// The state is written by k_rs_state behind the kernel on the stream (the chunks of a channel all read it).
+constexpr int kRsWaves = 4;                               // waves per block, one per SIMD, independent of each other: the largest tiles (DOWN by 6) stay below 64 KiB
+constexpr uint32_t kRsMaxResident = 3;                    // blocks per CU the grid is sized for where the LDS admits them: 12 waves per CU (the sweep: DESIGN 3.18)
+constexpr uint32_t kRsItemsPerWave = 4;                   // frames are cut until a wave has about this many items: the grid-stride tail is a quarter at most
+constexpr uint32_t kRsStateThreads = 192;                 // k_rs_state: a block takes a channel at a time, a thread per history sample
+constexpr uint32_t rs_ch(uint32_t dir) { return dir == IGDSP_RS_UP ? 16u : 4u; }          // channels of a wave
+constexpr uint32_t rs_lanes(uint32_t dir) { return 64u / rs_ch(dir); }                     // lanes per channel
+constexpr uint32_t rs_hist(uint32_t dir, uint32_t R) { return dir == IGDSP_RS_UP ? kRsTaps : kRsTaps * R; }   // predecessors kept in the tile
+constexpr uint32_t rs_tile(uint32_t dir, uint32_t R) { return rs_hist(dir, R) + (dir == IGDSP_RS_UP ? IGDSP_MAX_PAYLOAD : IGDSP_MAX_PAYLOAD * R); }          // samples per channel
+// LDS of a block: the tiles, a 16-byte slot per channel and output sub-frame for the records, the 1 KiB G.711 table (UP)
+constexpr uint32_t rs_lds_bytes(uint32_t dir, uint32_t R)
+{
+    return (uint32_t)kRsWaves * rs_ch(dir) * (rs_tile(dir, R) * 2u + R * 16u) + (dir == IGDSP_RS_UP ? 1024u : 0u);
+}
+// blocks of k_rs a CU holds: what 160 KiB of LDS admit, kRsMaxResident at most; k_rs's launch bound gives each wave 512 / this many VGPRs
+constexpr uint32_t rs_resident(uint32_t dir, uint32_t R) { return std::min(kRsMaxResident, 163840u / (rs_lds_bytes(dir, R) + 16u)); }
+// IGDSP_RS_BLOCKS: blocks per CU of k_rs's grid, for tools/rs_bench.py's sweep, which changes it between launches of one process: the one
+// variable is looked up per launch, nothing else is parsed
+inline std::optional<int> rs_blocks_from_env()
+{
+    if (const char *e = std::getenv("IGDSP_RS_BLOCKS")) return std::atoi(e);
+    return std::nullopt;
+}
+struct RsRoute {
+    uint32_t vec = 0;                      // the vector form
+    uint32_t pieces = 0;                   // units of 8 narrow samples per row
+    uint32_t ch = 0, groups = 0;           // channels per wave; channel groups
+    uint32_t chunk_frames = 0, chunks = 0; // frames per chunk (the last takes the rest); items = groups * chunks
+    uint32_t grid = 0, threads = 0, lds = 0;
+    uint32_t state_grid = 0;               // k_rs_state behind the kernel (0: the yardstick: nobody writes the state)
+};
+inline RsRoute rs_route(uint32_t dir, uint32_t R, uint32_t C, uint32_t F, uint32_t n, bool g711, bool yardstick, uintptr_t in, uintptr_t out,
+                        uint32_t cus, std::optional<int> blocks = std::nullopt)
+{
+    RsRoute r;
+    if (!rs_dir_ok(dir) || !rs_factor_ok(R) || (uint64_t)C * F == 0 || n == 0 || n > IGDSP_MAX_PAYLOAD || (uint64_t)C * F >= 0xFFFFFFE0ull) return r;
+    if (g711 && dir != IGDSP_RS_UP) return r;
+    r.vec = (n & 7u) == 0u && aligned(in, g711 ? 8 : 16) && aligned(out, 16) ? 1u : 0u;
+    r.pieces = (n + 7u) / 8u;
+    r.ch = rs_ch(dir);
+    r.groups = (uint32_t)(((uint64_t)C + r.ch - 1u) / r.ch);
+    const uint32_t per_cu = blocks && *blocks >= 1 && *blocks <= 8 ? (uint32_t)*blocks : rs_resident(dir, R);
+    const uint32_t want = std::max(1u, cus) * per_cu * (uint32_t)kRsWaves * kRsItemsPerWave;
+    const uint32_t cuts = r.groups >= want ? 1u : std::min(F, (want + r.groups - 1u) / r.groups);
+    r.chunk_frames = (F + cuts - 1u) / cuts;
+    r.chunks = (F + r.chunk_frames - 1u) / r.chunk_frames;
+    r.grid = blocks_for((uint64_t)r.groups * r.chunks, kRsWaves, std::max(1u, cus) * per_cu);
+    r.threads = kRsWaves * 64;
+    r.lds = rs_lds_bytes(dir, R);
+    r.state_grid = yardstick ? 0u : std::min(C, std::max(1u, cus) * 8u);
     return r;
 }
 

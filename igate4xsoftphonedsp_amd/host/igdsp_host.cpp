@@ -905,6 +905,42 @@ int igdsp_host_ring_get(void *v, igdsp_tone_plan *plan, igdsp_tone_state *state)
     return IGDSP_OK;
 }
 
+// ---- a call port's rate converters, no context needed
+Resampler::Resampler(uint32_t bridge_rate, uint32_t samples_per_frame) : factor(bridge_rate / 8000u), n(samples_per_frame)
+{
+    ok = bridge_rate % 8000u == 0 && (factor == 2 || factor == 3 || factor == 4 || factor == 6) && n >= 1 && n <= IGDSP_MAX_PAYLOAD;
+    std::memset(&to_bridge, 0, sizeof(to_bridge));
+    std::memset(&from_bridge, 0, sizeof(from_bridge));
+}
+
+int Resampler::up(const int16_t *narrow, int16_t *wide)
+{
+    return ok ? igdsp_rs_frame(&to_bridge, IGDSP_RS_UP, factor, narrow, n, wide) : IGDSP_EINVAL;
+}
+
+int Resampler::down(const int16_t *wide, int16_t *narrow)
+{
+    return ok ? igdsp_rs_frame(&from_bridge, IGDSP_RS_DOWN, factor, wide, n * factor, narrow) : IGDSP_EINVAL;
+}
+
+void *igdsp_host_rs_new(uint32_t bridge_rate, uint32_t samples_per_frame)
+{
+    Resampler *r = new (std::nothrow) Resampler(bridge_rate, samples_per_frame);
+    if (r && !r->ok) { delete r; r = nullptr; }
+    return r;
+}
+void igdsp_host_rs_free(void *v) { delete static_cast<Resampler *>(v); }
+int igdsp_host_rs_up(void *v, const int16_t *narrow, int16_t *wide)
+{
+    if (!v || !narrow || !wide) return IGDSP_EINVAL;
+    return static_cast<Resampler *>(v)->up(narrow, wide);
+}
+int igdsp_host_rs_down(void *v, const int16_t *wide, int16_t *narrow)
+{
+    if (!v || !wide || !narrow) return IGDSP_EINVAL;
+    return static_cast<Resampler *>(v)->down(wide, narrow);
+}
+
 // ---- conference receive levels, no context needed
 void *igdsp_host_levels_new(uint32_t n_channels)
 {

@@ -236,6 +236,19 @@ private:
     bool connected_, rewind_;
 };
 
+// A call port's rate conversion, as pjmedia's bridge does it when media_cfg.clock_rate (roip_ed137.cpp:3031) is not the streams' 8 kHz,
+// without a context: one channel's two converters, towards the bridge (up) and back (down), each with its own history.  A gateway of
+// the reference's size calls up() / down() once per tick and call; igdsp_resample takes the same states for thousands of calls.
+class Resampler {
+public:
+    explicit Resampler(uint32_t bridge_rate = 16000, uint32_t samples_per_frame = IGDSP_SAMPLES_PER_FRAME);   // the narrow side: 8 kHz, n samples
+    uint32_t factor, n;                      // bridge_rate / 8000
+    bool ok;                                 // a factor igdsp_resample takes (2, 3, 4, 6) and n in 1 .. 256
+    igdsp_rs_state to_bridge, from_bridge;
+    int up(const int16_t *narrow, int16_t *wide);      // n samples -> n * factor (igdsp_rs_frame, IGDSP_RS_UP)
+    int down(const int16_t *wide, int16_t *narrow);    // n * factor samples -> n (IGDSP_RS_DOWN)
+};
+
 class RoIP_ED137 {
 public:
     // Unlike the reference singleton (roip_ed137.cpp:192) the instance owns an igdsp context; device < 0
@@ -348,6 +361,12 @@ int   igdsp_host_ring_connections(void *v, uint32_t tone_channel, uint32_t *chan
 int   igdsp_host_ring_cmd(void *v);
 int   igdsp_host_ring_frame(void *v, int16_t *out, uint16_t *len);
 int   igdsp_host_ring_get(void *v, igdsp_tone_plan *plan, igdsp_tone_state *state);
+// a call port's rate converters without a context (Resampler): NULL from _new for a bridge rate other than 16 000, 24 000, 32 000,
+// 48 000 or samples_per_frame outside 1 .. 256; _up / _down one tick (IGDSP_EINVAL for a NULL argument)
+void *igdsp_host_rs_new(uint32_t bridge_rate, uint32_t samples_per_frame);
+void  igdsp_host_rs_free(void *v);
+int   igdsp_host_rs_up(void *v, const int16_t *narrow, int16_t *wide);
+int   igdsp_host_rs_down(void *v, const int16_t *wide, int16_t *narrow);
 // Meter output on the reference's other channel: AudioMeter (audiometer.cpp:11-34) reads ASCII decimal levels from the
 // FIFO /tmp/capturefifo<card>, 32 bytes per read, and emits onValueChanged(int(float(v*100.0/30000.0))).  These write
 // such records, so the reference's own meter consumer can be fed from igdsp_poll().rms.  open() waits up to

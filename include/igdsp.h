@@ -41,7 +41,8 @@ extern "C" {
  *    igdsp_ptt_arbitrate); R2S link supervision and the device event list (igdsp_link_state, igdsp_link_event, IGDSP_LINK_*,
  *    igdsp_link_work_bytes, igdsp_link_watch); the sound-card splitter / combiner (IGDSP_SND_*, igdsp_snd_combine, igdsp_snd_split,
  *    igdsp_snd_vu_t, igdsp_snd_vu); the tone generator (IGDSP_TONE_*, igdsp_tone_desc, igdsp_tone_seg, igdsp_tone_plan,
- *    igdsp_tone_state, igdsp_tone_plan_build, igdsp_tone_frame, igdsp_tone_generate). */
+ *    igdsp_tone_state, igdsp_tone_plan_build, igdsp_tone_frame, igdsp_tone_generate); the rate converter (IGDSP_RS_*, igdsp_rs_state,
+ *    igdsp_resample, igdsp_rs_frame, igdsp_rs_taps). */
 #define IGDSP_ABI_VERSION 3
 
 /* ---- error codes (0 == PJ_SUCCESS-style success) ------------------------- */
@@ -1218,6 +1219,78 @@ int igdsp_tone_generate(igdsp_ctx *ctx, const igdsp_tone_plan *d_plans, uint32_t
                         const uint8_t *d_cmd /* [P], optional */, igdsp_tone_state *d_state /* [P], in and out */,
                         uint32_t n_ports, uint32_t n_frames, uint32_t samples_per_frame, uint32_t rows_per_frame,
                         int16_t *d_pcm, uint16_t *d_len, igdsp_frame_stats *d_stats /* [F][P], dense */, void *stream);
+
+/* ---- Rate converter: a bridge that does not run at the streams' 8 kHz ------------------------------------------------------------------
+ * initSoftPhone takes the bridge's clock rate from the control command (roip_ed137.cpp:227-241, 7269, 7419) and puts it into
+ * media_cfg.clock_rate and media_cfg.snd_clock_rate (:3031-3032); the splitcomb, the player port, the null port and the tone generator
+ * all use it (:3318-3424, Functions.cpp:555, 1198), and an older settings line defaulted it to 48 000 (Functions.cpp:503).  G.711
+ * streams are always 8 kHz, so with any other bridge rate pjmedia's bridge resamples every call port in both directions at
+ * media_cfg.quality = 5 (its large filter).  igdsp_resample is that step for every call of a launch: IGDSP_RS_UP takes a call's rows to
+ * the bridge's rate (towards igdsp_conf_mix / igdsp_snd_combine), IGDSP_RS_DOWN takes a port's rows back (towards igdsp_encode /
+ * igdsp_tx_packetize).  Everything is integer.
+ *
+ * RULE.  Factor R in {2, 3, 4, 6} (8 <-> 16, 24, 32, 48 kHz; 16 <-> 48), T = IGDSP_RS_TAPS = 24 taps per phase, prototype length
+ * N = 24 R, coefficients Q14.  The prototype is a Kaiser-windowed sinc: c_j = j - (N - 1) / 2,
+ *   h[j] = sinc(0.95 c_j / R) * kaiser_N(beta = 6.0)[j],   sinc(x) = sin(pi x) / (pi x)
+ * in float64, and fix(v): q = floor(16384 v / sum(v) + 0.5), then 16384 - sum(q) added to the entry of largest |q| (the lowest index
+ * on a tie), so that every table sums to exactly 16384 and a constant input reproduces itself.  U_R[p][k] = fix(h[p::R])[k] (p < R,
+ * k < 24), D_R[j] = fix(h)[j] (j < N).  The formula is how the constants were made (tools/rs_tables.py); the committed constants of
+ * csrc/igdsp_rs_tab.h ARE the definition, and igdsp_rs_taps returns them.
+ * A channel's input is one stream x[g], g = f * n_in + s over the launch; x[g] for g < 0 comes from the state's history; with d_len a
+ * sample with s >= len of its input row is 0 (as igdsp_conf_mix reads a short row).
+ *   UP    narrow row n samples, wide row n R:   y[g R + p] = clamp16((sum_{k < 24} U_R[p][k] x[g - k]           + 8192) >> 14)
+ *   DOWN  wide row n R samples, narrow row n:   y[g]       = clamp16((sum_{j < N}  D_R[j]    x[g R + R - 1 - j] + 8192) >> 14)
+ * >> is arithmetic (a floor).  DOWN has no lookahead: a frame's last output uses the frame's last input.  With |x| <= 32768 and
+ * sum |q| <= 34 960 the sum plus 8192 stays below 2^31: 32-bit accumulators are exact (Q15 would not fit).  The clamp is real: the
+ * worst output before it is about 69 900.  The group delay of (N - 1) / 2 wide samples (23.5 at R = 2, 71.5 at R = 6: just under 12
+ * narrow samples, 1.5 ms at 8 kHz) is NOT compensated: the output is the delayed signal.  The filter is non-recursive: every frame of
+ * a launch depends on the input only, and only inputs with g < 0 come from the state.
+ *
+ * STATE.  hist is the channel's last IGDSP_RS_HIST = 144 input samples, oldest first (UP uses the last 23, DOWN the last N - 1).  After
+ * a launch hist is the last 144 entries of (old hist, the launch's input) and frames += n_frames; flags is reserved and kept as it is.
+ * F frames in one launch, F launches of one frame and any split in between give the same outputs and the same final state.
+ *
+ * LAYOUTS.  samples_per_frame n = 1..256 counts the NARROW side.  The narrow side is [F][rows_narrow][n].  The wide side is
+ *   IGDSP_RS_ROWS       [F][rows_wide][n R]
+ *   IGDSP_RS_SUBFRAMES  [F R][rows_wide][n]: wide sample q of (f, c) is sample q % n of frame f R + q / n,
+ * so that igdsp_conf_mix, igdsp_snd_* and tone ports built at R * 8000 Hz with samples_per_frame = n consume or produce the rows
+ * directly.  rows_narrow / rows_wide are each side's frame stride in rows (as rows_per_frame of igdsp_tone_generate): 0 means
+ * n_channels, otherwise >= n_channels; rows outside [0, n_channels) are never touched.
+ * INPUT.  UP takes exactly one of d_payload ([f][c][n] G.711 with d_codec[c]: PT 8 A-law, anything else mu-law; igdsp_decode_meter's
+ * expansion) and d_pcm (int16); DOWN takes d_pcm only.  d_len is optional and is laid out as the input rows are (their frame count
+ * and row stride).
+ * OUTPUT.  At least one of d_out and d_stats.  d_stats is dense, one record per output row as laid out ([F][C], or [F R][C] for UP into
+ * IGDSP_RS_SUBFRAMES) over that row's samples: sumsq exact, rms = sqrtf((float)sumsq / count), peak = max |y| (32768 for -32768),
+ * byte_mean 0, flags IGDSP_FLAG_SILENT (peak <= 8) | IGDSP_FLAG_SATURATED (the clamp fired in that row).
+ * A bad direction, factor or layout is IGDSP_EINVAL with nothing written.  d_state required, 4-byte aligned; d_pcm, d_len, d_out
+ * 2-byte, d_stats 8-byte aligned; an output must not be an input or the state and the buffers must not overlap at all.
+ * n_channels == 0 or n_frames == 0: nothing to do, the state is untouched.  max(rows, n_channels) * n_frames * (R in the sub-frame
+ * layout) < 2^32 - 32 on both sides (IGDSP_ERANGE).  Enqueued on `stream`, not synchronised.
+ *
+ * igdsp_rs_frame (host only, no GPU): one frame of one channel by the same rule, the state advanced.  n_in input samples: 1..256 for
+ * UP (n_in R written), a multiple of R in R..256 R for DOWN (n_in / R written).  igdsp_rs_taps (host only): the table of a direction and
+ * factor (UP: R * 24 values in [p][k] order, DOWN: 24 R) and its length.  Both: IGDSP_EINVAL for a NULL or anything out of range.
+ *
+ * Fidelity.  UNVERIFIED: pjmedia's resampler (libresample: resample.c / resamplesubs.c, a Kaiser-windowed sinc table with linear
+ * interpolation between entries) is third-party and not in the reference tree; the filter length, cutoff, window, rounding and
+ * delay above are this library's own rules and are not compared with it. */
+#define IGDSP_RS_UP         0u
+#define IGDSP_RS_DOWN       1u
+#define IGDSP_RS_ROWS       0u       /* wide side [F][rows][n R] */
+#define IGDSP_RS_SUBFRAMES  1u       /* wide side [F R][rows][n] */
+#define IGDSP_RS_TAPS       24       /* taps per phase */
+#define IGDSP_RS_HIST       144      /* history samples per channel: N - 1 = 143 at R = 6, rounded up */
+typedef struct igdsp_rs_state {
+    int16_t  hist[IGDSP_RS_HIST];    /* the channel's last 144 input samples, oldest first */
+    uint32_t flags;                  /* reserved, kept as it is */
+    uint32_t frames;                 /* frames converted, wrapping */
+} igdsp_rs_state;                    /* 296 bytes; all-zero = silence */
+int igdsp_resample(igdsp_ctx *ctx, uint32_t direction, uint32_t factor, uint32_t layout,
+                   const uint8_t *d_payload, const uint8_t *d_codec, const int16_t *d_pcm, const uint16_t *d_len,
+                   igdsp_rs_state *d_state /* [C], in and out */, uint32_t n_channels, uint32_t n_frames, uint32_t samples_per_frame,
+                   uint32_t rows_narrow, uint32_t rows_wide, int16_t *d_out, igdsp_frame_stats *d_stats /* dense */, void *stream);
+int igdsp_rs_frame(igdsp_rs_state *st, uint32_t direction, uint32_t factor, const int16_t *in, uint32_t n_in, int16_t *out);
+int igdsp_rs_taps(uint32_t direction, uint32_t factor, const int16_t **taps, uint32_t *count);
 
 /* ---- synthetic input generators (device side; SURVEY 8(d) definitions) ---------
  * D-uniform: byte k of global byte index g is
