@@ -11,6 +11,7 @@
 //   hold / window aggregate       : Functions.cpp:2126-2145, 2155-2167.
 #pragma once
 #include "igdsp_internal.h"
+#include "igdsp_pcmrec.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -212,22 +213,17 @@ __device__ __forceinline__ igdsp_frame_stats make_stats(uint64_t sumsq, uint32_t
     return st;
 }
 
-// Wave64 reductions on the VALU's DPP path (no LDS round trips): an inclusive scan inside each row of 16
-// lanes (row_shr 1/2/4/8), then row_bcast15 / row_bcast31 carry the row totals upward; lane 63 ends up
+// Wave64 reductions on the VALU's DPP path (no LDS round trips): group_fold's inclusive scan inside each row of 16
+// lanes (igdsp_pcmrec.h), then row_bcast15 / row_bcast31 carry the row totals upward; lane 63 ends up
 // with the wave total and is read out with v_readlane.  Identity 0 suits unsigned add and max.
 template <typename Op>
 __device__ __forceinline__ uint32_t wave_reduce_dpp(uint32_t v, Op op)
 {
-    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false));   // row_shr:1
-    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false));   // row_shr:2
-    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, false));   // row_shr:4
-    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, false));   // row_shr:8
+    v = group_fold<16>(v, op);
     v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false));   // row_bcast:15 -> rows 1, 3
     v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false));   // row_bcast:31 -> rows 2, 3
     return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
 }
-struct OpAdd { __device__ __forceinline__ uint32_t operator()(uint32_t a, uint32_t b) const { return a + b; } };
-struct OpMax { __device__ __forceinline__ uint32_t operator()(uint32_t a, uint32_t b) const { return max(a, b); } };
 
 // Barrier-free launch-aggregate commit for the persistent kernels: a wave that has run out of work reduces its partials with DPP (no LDS, no shuffle tree), lane 0 adds the
 // wave totals into a 48-byte block accumulator with seven LDS atomics and bumps a counter; the
@@ -401,9 +397,6 @@ __device__ __forceinline__ uint32_t isqrt_m2(uint32_t v)
 {
     return (uint32_t)(__builtin_amdgcn_sqrtf((float)v) + 0.5f);
 }
-
-typedef short v2i16 __attribute__((ext_vector_type(2)));
-typedef unsigned short v2u16_t __attribute__((ext_vector_type(2)));
 
 // two magnitudes -> one dword of signed int16 PCM (codes k and k + 1 of word w; a code is negative iff its bit 7 is
 // clear).  Packed 16-bit math: one v_perm puts the two inverted sign bits at bits 15 / 31, a packed arithmetic shift

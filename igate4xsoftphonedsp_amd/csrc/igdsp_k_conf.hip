@@ -139,31 +139,7 @@ __device__ __forceinline__ void conf_finish(const ConfArgs &a, uint64_t item, ui
         sq += (uint64_t)ax * ax;
         peak = max(peak, ax);
     }
-    if (a.out != nullptr && b0 < n) {
-        int16_t *dst = a.out + item * n + b0;
-        if (a.vec_out) {
-            *reinterpret_cast<uint2 *>(dst) = make_uint2(((uint32_t)o[0] & 0xFFFFu) | ((uint32_t)o[1] << 16), ((uint32_t)o[2] & 0xFFFFu) | ((uint32_t)o[3] << 16));
-        } else {
-            for (uint32_t k = 0; k < 4u && b0 + k < n; ++k) dst[k] = (int16_t)o[k];
-        }
-    }
-    if (a.stats == nullptr) return;
-    const uint64_t sumsq = wave_sum_u64(sq);
-    peak = wave_reduce_dpp(peak, OpMax{});
-    const uint32_t any_sat = __builtin_amdgcn_ballot_w64(sat != 0u) != 0u ? 1u : 0u;
-    if (lane == 0u) {
-        igdsp_frame_stats st;
-        if (empty) {
-            st.sumsq = 0; st.rms = 0.f; st.peak = 0; st.byte_mean = 0; st.flags = IGDSP_FLAG_EMPTY;
-        } else {
-            st.sumsq = sumsq;
-            st.rms = sqrtf((float)sumsq / (float)n);
-            st.peak = (uint16_t)peak;
-            st.byte_mean = 0;
-            st.flags = (uint8_t)((peak <= 8u ? IGDSP_FLAG_SILENT : 0u) | (any_sat ? IGDSP_FLAG_SATURATED : 0u));
-        }
-        a.stats[item] = st;
-    }
+    q7_store(a.out, a.stats, item, n, a.vec_out, lane, o, empty, sat, sq, peak);
 }
 
 template <int IN, bool COPY>

@@ -21,6 +21,7 @@
 // COPY (the compute-free yardstick, tools/plc_bench.py): phases A, B and D with every tick taken as PLAIN and no decode, stats or
 // ring arithmetic: the input bits are widened to the output, the records carry only the length.
 #include "igdsp_device.h"
+#include "igdsp_pcmrec.h"
 
 namespace igdsp {
 
@@ -84,17 +85,7 @@ __device__ __forceinline__ void plc_record(const PlcArgs &a, uint64_t o, uint64_
 {
     if (a.len_out) a.len_out[o] = idle ? 0u : (uint16_t)a.n;
     if (!a.stats) return;
-    igdsp_frame_stats st;
-    if (idle) {
-        st.sumsq = 0; st.rms = 0.f; st.peak = 0; st.byte_mean = 0; st.flags = IGDSP_FLAG_EMPTY;
-    } else {
-        st.sumsq = sumsq;
-        st.rms = sqrtf((float)sumsq / (float)a.n);
-        st.peak = (uint16_t)peak;
-        st.byte_mean = 0;
-        st.flags = (uint8_t)((peak <= 8u ? IGDSP_FLAG_SILENT : 0u) | flags);
-    }
-    a.stats[o] = st;
+    a.stats[o] = as_stats(idle ? pcm_record_empty() : pcm_record(sumsq, peak, a.n, flags));
 }
 
 // the output sample j of the part (j = t * n + i; j < 0: before the part) of a channel whose loss rows are in L.ring

@@ -23,6 +23,7 @@
 // COPY (the compute-free yardstick, tools/rs_bench.py): steps 1 - 3 with the same loads, LDS traffic and stores, an xor instead of the
 // dot products, zero records, no state.
 #include "igdsp_device.h"
+#include "igdsp_pcmrec.h"
 
 namespace igdsp {
 
@@ -274,19 +275,13 @@ __global__ __launch_bounds__(kRsWaves * 64, rs_resident(DIR, R)) void k_rs(const
                     const uint32_t kk = u / a.SO, sub = u - kk * a.SO, cc = c0 + kk;
                     if (cc >= a.C) continue;
                     const RsSlot sl = slots[kk][sub];
-                    igdsp_frame_stats st;
-                    if (COPY) {
-                        st.sumsq = 0; st.rms = 0.f; st.peak = 0; st.byte_mean = 0; st.flags = 0;
-                    } else {
+                    uint4 rec = make_uint4(0u, 0u, 0u, 0u);                    // COPY: a zero record, flags 0
+                    if (!COPY) {
                         const int32_t hi = rs_clamp16(sl.mx), lo = rs_clamp16(sl.mn);
                         const uint32_t peak = (uint32_t)max(hi < 0 ? -hi : hi, lo < 0 ? -lo : lo);
-                        st.sumsq = sl.sq;
-                        st.rms = sqrtf((float)sl.sq / (float)a.LO);
-                        st.peak = (uint16_t)peak;
-                        st.byte_mean = 0;
-                        st.flags = (uint8_t)((peak <= 8u ? IGDSP_FLAG_SILENT : 0u) | (sl.mx > 32767 || sl.mn < -32768 ? IGDSP_FLAG_SATURATED : 0u));
+                        rec = pcm_record(sl.sq, peak, a.LO, sl.mx > 32767 || sl.mn < -32768 ? (uint32_t)IGDSP_FLAG_SATURATED : 0u);
                     }
-                    a.stats[((uint64_t)f * a.SO + sub) * a.C + cc] = st;
+                    a.stats[((uint64_t)f * a.SO + sub) * a.C + cc] = as_stats(rec);
                 }
             }
             wave_lds_fence();                                                  // the tile and the slots are rewritten next

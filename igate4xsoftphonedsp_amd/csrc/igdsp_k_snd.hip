@@ -18,6 +18,7 @@
 // record: the K records of an item are one contiguous run.  Integer sums: any order gives the same bits.  Nothing is read back from
 // memory.  The general form (K * n odd, or a buffer aligned to 2 only) fills and empties the same tile a sample at a time.
 #include "igdsp_device.h"
+#include "igdsp_pcmrec.h"
 
 namespace igdsp {
 
@@ -91,33 +92,6 @@ __device__ __forceinline__ void snd_scatter(uint4 *tile, const uint32_t (&slot)[
     }
 }
 
-__device__ __forceinline__ void snd_acc(uint32_t x, uint64_t &sq, uint32_t &pk)    // one sample, as its 16 bits
-{
-    const int32_t s = (int16_t)x;
-    const uint32_t ax = (uint32_t)(s < 0 ? -s : s);
-    sq += ax * ax;                                                                 // <= 2^30
-    pk = max(pk, ax);
-}
-// two samples in one dword, packed math: x . x as one dot product (2^31 for two -32768: the 32 bits hold it), |x| as max(x, 0 - x)
-// in 16 bits (-32768 stays 0x8000 = 32768 unsigned) folded into two running unsigned maxima
-__device__ __forceinline__ void snd_acc2(uint32_t w, uint64_t &sq, v2u16_t &pk)
-{
-    const v2i16 x = __builtin_bit_cast(v2i16, w);
-    sq += (uint32_t)__builtin_amdgcn_sdot2(x, x, 0, false);
-    const v2u16_t neg = (v2u16_t)(0) - __builtin_bit_cast(v2u16_t, w);             // wraps: well defined
-    pk = __builtin_elementwise_max(pk, __builtin_bit_cast(v2u16_t, __builtin_elementwise_max(x, __builtin_bit_cast(v2i16, neg))));
-}
-
-// lane 8 g + 7 gets op over lanes 8 g .. 8 g + 7: the first three steps of wave_reduce_dpp's scan (a lane without a source adds 0)
-template <typename Op>
-__device__ __forceinline__ uint32_t snd_row8(uint32_t v, Op op)
-{
-    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false));   // row_shr:1
-    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false));   // row_shr:2
-    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, false));   // row_shr:4
-    return v;
-}
-
 // The K records of item `item` from its row-major tile (every lane of the wave active).
 __device__ __forceinline__ void snd_records(const SndArgs &a, const uint4 *tile, uint64_t item, uint32_t lane)
 {
@@ -131,21 +105,23 @@ __device__ __forceinline__ void snd_records(const SndArgs &a, const uint4 *tile,
             v2u16_t pk2 = (v2u16_t)(0);
             for (uint32_t c = j; c < (n >> 3); c += 8u) {
                 const uint4 v = row[c];
-                snd_acc2(v.x, sq, pk2); snd_acc2(v.y, sq, pk2); snd_acc2(v.z, sq, pk2); snd_acc2(v.w, sq, pk2);
+                pcm_acc2(v.x, sq, pk2); pcm_acc2(v.y, sq, pk2); pcm_acc2(v.z, sq, pk2); pcm_acc2(v.w, sq, pk2);
             }
             pk = max((uint32_t)pk2.x, (uint32_t)pk2.y);
         } else {
-            for (uint32_t s = j; s < n; s += 8u) snd_acc(tile16[k * n + s], sq, pk);
+            for (uint32_t s = j; s < n; s += 8u) pcm_acc(tile16[k * n + s], sq, pk);
         }
     }
-    const uint32_t lo = snd_row8((uint32_t)sq & 0xFFFFFFu, OpAdd{});               // 24-bit limbs: eight of them fit 32 bits
-    const uint32_t hi = snd_row8((uint32_t)(sq >> 24), OpAdd{});
-    pk = snd_row8(pk, OpMax{});
+    const uint2 limbs = group_limbs<8>(sq);                                        // lane 8 k + 7 gets row k's
+    pk = group_fold<8>(pk, OpMax{});
     if (j == 7u && k < a.K) {
-        const uint64_t sumsq = (uint64_t)lo + ((uint64_t)hi << 24);
-        const float rms = sqrtf((float)sumsq / (float)n);
-        const uint32_t flags = pk <= 8u ? (uint32_t)IGDSP_FLAG_SILENT : 0u;
-        st_record_block(a.stats + item * a.K, k, make_uint4((uint32_t)sumsq, (uint32_t)(sumsq >> 32), __float_as_uint(rms), pk | (flags << 24)));
+        // pcm_record's steps one by one, the sum joined in the storing lane: in this order k_snd compiles to the instructions it had;
+        // as one pcm_record(group_sum_u64<8>(sq), ..) call the vector forms scheduled differently and S1 split measured 0.4 % slower
+        // (profiles/pcm_record_isa.md)
+        const uint64_t sumsq = limbs_u64(limbs);
+        const float rms = pcm_rms(sumsq, n);
+        const uint32_t flags = pcm_flags(pk, 0u);
+        st_record_block(a.stats + item * a.K, k, pcm_pack(sumsq, rms, pk, flags));
     }
 }
 

@@ -17,6 +17,7 @@
 // A launch of one chunk writes the state from the lanes that read it; a launch cut into chunks leaves that to k_tone_state behind it
 // (the chunks of a port read the state the kernel must not have written yet).
 #include "igdsp_device.h"
+#include "igdsp_pcmrec.h"
 
 namespace igdsp {
 
@@ -36,24 +37,6 @@ struct ToneArgs {
     uint32_t pieces, groups, chunk_frames, chunks;
     uint32_t write_state;              // one chunk: the kernel writes the state
 };
-
-// two samples in one dword, packed math (k_snd's snd_acc2): x . x as one dot product, |x| as max(x, 0 - x) in 16 bits
-__device__ __forceinline__ void tone_acc2(uint32_t w, uint64_t &sq, v2u16_t &pk)
-{
-    const v2i16 x = __builtin_bit_cast(v2i16, w);
-    sq += (uint32_t)__builtin_amdgcn_sdot2(x, x, 0, false);
-    const v2u16_t neg = (v2u16_t)(0) - __builtin_bit_cast(v2u16_t, w);
-    pk = __builtin_elementwise_max(pk, __builtin_bit_cast(v2u16_t, __builtin_elementwise_max(x, __builtin_bit_cast(v2i16, neg))));
-}
-
-// lane 4 g + 3 gets op over lanes 4 g .. 4 g + 3: the first two steps of wave_reduce_dpp's scan (a lane without a source adds 0)
-template <typename Op>
-__device__ __forceinline__ uint32_t tone_row4(uint32_t v, Op op)
-{
-    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false));   // row_shr:1
-    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false));   // row_shr:2
-    return v;
-}
 
 // the segment a port's lanes keep in registers: [start, end) of the cycle, and what tone_amp / tone_fade read
 struct ToneSeg {
@@ -166,7 +149,7 @@ __global__ __launch_bounds__(kToneWaves * 64) void k_tone(const ToneArgs a)
                     auto keep = [&](uint32_t first) { return valid > first + 1u ? 0xFFFFFFFFu : (valid > first ? 0xFFFFu : 0u); };
                     v.x &= keep(0u); v.y &= keep(2u); v.z &= keep(4u); v.w &= keep(6u);
                 }
-                if constexpr (STATS && !FILL) { tone_acc2(v.x, sq, pk2); tone_acc2(v.y, sq, pk2); tone_acc2(v.z, sq, pk2); tone_acc2(v.w, sq, pk2); }
+                if constexpr (STATS && !FILL) { pcm_acc2(v.x, sq, pk2); pcm_acc2(v.y, sq, pk2); pcm_acc2(v.z, sq, pk2); pcm_acc2(v.w, sq, pk2); }
                 if constexpr (PCM) {
                     if (port) {
                         int16_t *dst = a.pcm + row * n + s0;
@@ -183,16 +166,11 @@ __global__ __launch_bounds__(kToneWaves * 64) void k_tone(const ToneArgs a)
             if (a.len && port && j == 0u) a.len[row] = (uint16_t)(live || FILL ? n : 0u);
             if constexpr (STATS) {
                 // every lane of the wave is here: the fold's DPP steps read the neighbours' registers
-                const uint32_t lo = tone_row4((uint32_t)sq & 0xFFFFFFu, OpAdd{});  // 24-bit limbs: four of them fit 32 bits
-                const uint32_t hi = tone_row4((uint32_t)(sq >> 24), OpAdd{});      // a lane's sum is below 64 * 2^30
-                const uint32_t pk = tone_row4(max((uint32_t)pk2.x, (uint32_t)pk2.y), OpMax{});
+                const uint64_t sumsq = group_sum_u64<kToneLanes>(sq);              // a lane's sum is below 64 * 2^30
+                const uint32_t pk = group_fold<kToneLanes>(max((uint32_t)pk2.x, (uint32_t)pk2.y), OpMax{});
                 if (j == 3u && port && a.stats) {
-                    uint4 rec = make_uint4(0u, 0u, 0u, (uint32_t)IGDSP_FLAG_EMPTY << 24);
-                    if (live) {
-                        const uint64_t sumsq = (uint64_t)lo + ((uint64_t)hi << 24);
-                        const float rms = sqrtf((float)sumsq / (float)n);
-                        rec = make_uint4((uint32_t)sumsq, (uint32_t)(sumsq >> 32), __float_as_uint(rms), pk | ((pk <= 8u ? (uint32_t)IGDSP_FLAG_SILENT : 0u) << 24));
-                    }
+                    uint4 rec = pcm_record_empty();                                // (as a conditional expression this schedules differently:
+                    if (live) rec = pcm_record(sumsq, pk, n, 0u);                  // profiles/pcm_record_isa.md)
                     st_record_block(a.stats + (uint64_t)f * a.P + (uint64_t)g * kTonePorts, r, rec);
                 }
             }

@@ -3,6 +3,7 @@
 // "Conference mix").  A lane owns samples 4 lane .. 4 lane + 3 of the row.
 #pragma once
 #include "igdsp_device.h"
+#include "igdsp_pcmrec.h"
 
 namespace igdsp {
 
@@ -60,7 +61,7 @@ __device__ __forceinline__ void q7_sample(const uint2 *lut, uint2 v, uint32_t la
 
 // The frame's PCM row out[item][n] and record stats[item] from the lane's output samples o (samples 4 lane + k), the lane's sum of
 // squares sq and peak, a clamp flag sat; empty: the len-0 record.  Either pointer may be nullptr; every lane of the wave active.
-// (The same stores and reductions as conf_finish in igdsp_k_conf.hip, which keeps its own copy so that its ISA stays as it was.)
+// (igdsp_conf_mix's conf_finish ends here too.)
 __device__ __forceinline__ void q7_store(int16_t *out, igdsp_frame_stats *stats, uint64_t item, uint32_t n, uint32_t vec_out, uint32_t lane,
                                          const int32_t (&o)[4], bool empty, uint32_t sat, uint64_t sq, uint32_t peak)
 {
@@ -77,19 +78,7 @@ __device__ __forceinline__ void q7_store(int16_t *out, igdsp_frame_stats *stats,
     const uint64_t sumsq = wave_sum_u64(sq);
     peak = wave_reduce_dpp(peak, OpMax{});
     const uint32_t any_sat = __builtin_amdgcn_ballot_w64(sat != 0u) != 0u ? 1u : 0u;
-    if (lane == 0u) {
-        igdsp_frame_stats st;
-        if (empty) {
-            st.sumsq = 0; st.rms = 0.f; st.peak = 0; st.byte_mean = 0; st.flags = IGDSP_FLAG_EMPTY;
-        } else {
-            st.sumsq = sumsq;
-            st.rms = sqrtf((float)sumsq / (float)n);
-            st.peak = (uint16_t)peak;
-            st.byte_mean = 0;
-            st.flags = (uint8_t)((peak <= 8u ? IGDSP_FLAG_SILENT : 0u) | (any_sat ? IGDSP_FLAG_SATURATED : 0u));
-        }
-        stats[item] = st;
-    }
+    if (lane == 0u) stats[item] = as_stats(empty ? pcm_record_empty() : pcm_record(sumsq, peak, n, any_sat ? (uint32_t)IGDSP_FLAG_SATURATED : 0u));
 }
 
 }  // namespace igdsp

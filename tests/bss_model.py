@@ -4,6 +4,7 @@ G.711 tables and scales with conf_model.scale (the Q7 rule of igdsp_conf_mix).""
 import numpy as np
 
 from tests import conf_model as cm
+from tests import record_model
 
 RTP_RUNT = 0x40
 STORE_PTS = (0, 8, 18, 123)
@@ -73,9 +74,7 @@ def emit(sel, x, n, gain=None, length=None):
     256), length [F][C] (None: n).  A voted frame is igdsp_conf_mix of a one-member port."""
     F_, G_ = sel.shape
     out = np.zeros((F_, G_, n), np.int16)
-    st = {k: np.zeros((F_, G_), t) for k, t in (("sumsq", np.uint64), ("rms", np.float32), ("peak", np.uint16), ("byte_mean", np.uint8),
-                                                   ("flags", np.uint8))}
-    st["flags"][:] = cm.FLAG_EMPTY
+    live, sat = np.zeros((F_, G_), bool), np.zeros((F_, G_), bool)
     s_idx = np.arange(n)
     for f in range(F_):
         for g in range(G_):
@@ -86,15 +85,10 @@ def emit(sel, x, n, gain=None, length=None):
             if ln == 0:
                 continue
             gq = 256 if gain is None else int(gain[c])
-            o, fired = cm.scale(np.where(s_idx < ln, x[f, c], 0), gq)
-            out[f, g] = o
-            sq = int((o.astype(np.int64) ** 2).sum())
-            peak = int(np.abs(o).max())
-            st["sumsq"][f, g] = sq
-            st["rms"][f, g] = np.float32(np.sqrt(sq / n))
-            st["peak"][f, g] = peak
-            st["flags"][f, g] = (cm.FLAG_SILENT if peak <= 8 else 0) | (cm.FLAG_SATURATED if fired.any() else 0)
-    return out, st
+            out[f, g], fired = cm.scale(np.where(s_idx < ln, x[f, c], 0), gq)
+            live[f, g], sat[f, g] = True, fired.any()
+    rec = record_model.records(out, live=live, extra=np.where(sat, cm.FLAG_SATURATED, 0))
+    return out, {k: rec[k].astype(np.float32 if k == "rms" else rec.dtype[k]) for k in rec.dtype.names}
 
 
 def word(squelch, bss_q, ptt_type=0):

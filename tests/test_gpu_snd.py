@@ -70,13 +70,6 @@ def run_snd(ctx, direction, src, D_, K_, F_, n, bulk=True, stats=True, in_off=0,
     return o, s
 
 
-def check_stats(s, es):
-    for k in ("sumsq", "peak", "byte_mean", "flags"):
-        np.testing.assert_array_equal(s[k], es[k], err_msg=k)
-    ref = es["rms"]
-    assert np.all(np.abs(s["rms"].astype(np.float64) - ref) <= 1e-5 * ref + 1e-30)
-
-
 def check_dir(ctx, direction, pcm, D_, K_, **kw):
     """pcm [F][D * K][n]: combine takes it, split takes the model's frames of it; both give the model's other side and records"""
     F_, _, n = pcm.shape
@@ -86,7 +79,7 @@ def check_dir(ctx, direction, pcm, D_, K_, **kw):
     if o is not None:
         np.testing.assert_array_equal(o, want.reshape(-1))
     if s is not None:
-        check_stats(s, sm.records(pcm))
+        gu.assert_stats_equal(s, sm.records(pcm))
 
 
 @pytest.mark.parametrize("K_", KS)
@@ -168,7 +161,7 @@ def test_chain_depayload_mix_combine(ctx, orc):
     raw = d_fr.cpu().numpy()
     assert np.all(raw[F_ * P_ * n * 2:] == 0xA5)
     np.testing.assert_array_equal(raw[:F_ * P_ * n * 2].view("<i2"), sm.combine(eo, D_, K_).reshape(-1))
-    check_stats(gu.to_host(d_st, capi.FRAME_STATS, (F_, P_)), sm.records(eo))
+    gu.assert_stats_equal(gu.to_host(d_st, capi.FRAME_STATS, (F_, P_)), sm.records(eo))
     assert np.all(eo[:, P_ - 1] == 0)
 
 
@@ -190,7 +183,7 @@ def test_chain_split_mix_and_hold(ctx, orc):
     ctx.hold_update(d_st, C_, F_, n, d_hold)
     torch.cuda.synchronize()
     st = gu.to_host(d_st, capi.FRAME_STATS, (F_, C_))
-    check_stats(st, sm.records(mic))
+    gu.assert_stats_equal(st, sm.records(mic))
     assert (st["flags"] & sm.FLAG_SILENT).any()
     eo, es = cm.mix(mic.astype(np.int64), gain, ptr, mem, len(mem), P_)
     np.testing.assert_array_equal(gu.to_host(d_out, "<i2", (F_, P_, n)), eo)

@@ -71,13 +71,6 @@ def run_tone(ctx, plans, pos, flags, F_, n, plan_of=None, cmd=None, rpf=0, pcm=T
     return o, ln, s, d_state.cpu().numpy().view(capi.TONE_STATE), d_state
 
 
-def check_stats(s, es):
-    for k in ("sumsq", "peak", "byte_mean", "flags"):
-        np.testing.assert_array_equal(s[k], es[k], err_msg=k)
-    ref = es["rms"]
-    assert np.all(np.abs(s["rms"].astype(np.float64) - ref) <= 1e-5 * ref + 1e-30)
-
-
 def check_launch(ctx, plans, pos, flags, F_, n, plan_of=None, cmd=None, **kw):
     """a launch equals the model: the rows [0, P) of every frame, the canaries in the others, lengths, records, state"""
     P_ = len(pos)
@@ -90,7 +83,7 @@ def check_launch(ctx, plans, pos, flags, F_, n, plan_of=None, cmd=None, **kw):
         np.testing.assert_array_equal(ln[:, :P_], eln)
         assert np.all(ln[:, P_:] == 0xEEEE), "lengths outside [0, P) written"
     if s is not None:
-        check_stats(s, es)
+        gu.assert_stats_equal(s, es)
     np.testing.assert_array_equal(st["pos"], epos)
     np.testing.assert_array_equal(st["flags"], eflags)
     return eo, eln

@@ -5,13 +5,14 @@ import math
 
 import numpy as np
 
+from tests import record_model
+from tests.record_model import FLAG_EMPTY, FLAG_SILENT, STATS  # noqa: F401  (re-exported)
+
 TONE_MAX, VOLUME = 8, 12288
 LOOP, NO_FADE = 1, 2
 PLAYING = 1
 REWIND, STOP, HOLD = 1, 2, 4
-FLAG_SILENT, FLAG_EMPTY = 0x01, 0x08
 TABLE = np.array([math.floor(32767 * math.sin(2 * math.pi * i / 1024) + 0.5) for i in range(1024)], np.int64)
-STATS = np.dtype([("sumsq", "<u8"), ("rms", "<f8"), ("peak", "<u2"), ("byte_mean", "u1"), ("flags", "u1")])   # rms in float64: the reference value
 
 
 def step_of(freq, clock_rate):
@@ -83,14 +84,7 @@ def cycle_wave(plan):
 
 def records(pcm, live):
     """records over rows pcm [..][n] with live [..] bool: a live row's sumsq / rms / peak / SILENT, an EMPTY row's len-0 record"""
-    x = pcm.astype(np.int64)
-    st = np.zeros(pcm.shape[:-1], STATS)
-    st["sumsq"] = (x * x).sum(axis=-1).astype(np.uint64)
-    st["rms"] = np.sqrt(st["sumsq"].astype(np.float64) / pcm.shape[-1])
-    peak = np.abs(x).max(axis=-1)
-    st["peak"] = peak
-    st["flags"] = np.where(live, np.where(peak <= 8, FLAG_SILENT, 0), FLAG_EMPTY)
-    return st
+    return record_model.records(pcm, live=live)
 
 
 def apply_cmd(pos, flags, cmd):
