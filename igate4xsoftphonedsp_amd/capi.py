@@ -275,7 +275,33 @@ PROTOTYPES = [
     ("igdsp_set_variant", _int, [_vp, _int]),
 ]
 
+# The compute-free yardsticks (igdsp_internal_*, not in include/igdsp.h; tools/*_bench.py and the tests call them).  Nine take the
+# arguments of a public entry and are derived from that entry's row above; igdsp_internal_tx_copy has no twin.
+INTERNAL_TWIN = {
+    "igdsp_internal_conf_copy": "igdsp_conf_mix",
+    "igdsp_internal_bss_copy": "igdsp_bss_select",
+    "igdsp_internal_ptt_copy": "igdsp_ptt_arbitrate",
+    "igdsp_internal_link_copy": "igdsp_link_watch",
+    "igdsp_internal_jb_copy": "igdsp_jb_receive",
+    "igdsp_internal_plc_copy": "igdsp_plc_conceal",
+    "igdsp_internal_snd_copy": "igdsp_snd_combine",
+    "igdsp_internal_tone_fill": "igdsp_tone_generate",
+    "igdsp_internal_rs_copy": "igdsp_resample",
+}
+_PUBLIC = {name: (res, args) for name, res, args in PROTOTYPES}
+INTERNAL = {name: _PUBLIC[twin] for name, twin in INTERNAL_TWIN.items()}
+INTERNAL["igdsp_internal_tx_copy"] = (_int, [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp])
+
 _lib = None
+
+
+def internal(name: str):
+    """The bound function of a yardstick entry of INTERNAL ("igdsp_internal_rs_copy", or short "rs_copy"); it returns the raw code."""
+    name = name if name.startswith("igdsp_internal_") else "igdsp_internal_" + name
+    res, args = INTERNAL[name]                      # KeyError == not a yardstick entry
+    fn = getattr(load(), name)
+    fn.restype, fn.argtypes = res, list(args)
+    return fn
 
 
 def load() -> C.CDLL:
@@ -806,6 +832,12 @@ class Context:
     def sync(self, stream=None):
         self._ck(self.L.igdsp_sync(self.h, stream), "igdsp_sync")
 
+    def via(self, entry: str) -> "Context":
+        """A view of this context whose stage method (conf_mix, resample, ...) calls the yardstick `entry` of INTERNAL_TWIN in place of
+        the public twin whose arguments it takes (igdsp_internal_snd_copy: both directions); everything else is this context's.  The
+        view owns nothing; a failing call raises IgdspError under the twin's name."""
+        return _Via(self, entry)
+
     # -- timers
     def probe_placement(self, buf, n_bytes, out=None, reps=10, stream=None) -> float:
         ms = C.c_float(0)
@@ -866,3 +898,22 @@ class Timer:
         if self.t:
             self.ctx.L.igdsp_timer_destroy(self.ctx.h, self.t)
             self.t = None
+
+
+class _ViaLib:
+    def __init__(self, lib, entry):
+        name = entry if entry.startswith("igdsp_internal_") else "igdsp_internal_" + entry
+        twin = INTERNAL_TWIN[name]
+        self._lib, self._fn = lib, internal(name)
+        self._twins = {twin, "igdsp_snd_split"} if twin == "igdsp_snd_combine" else {twin}
+
+    def __getattr__(self, name):
+        return self._fn if name in self._twins else getattr(self._lib, name)
+
+
+class _Via(Context):
+    def __init__(self, ctx: Context, entry: str):
+        self.L, self.h, self.max_channels = _ViaLib(ctx.L, entry), ctx.h, ctx.max_channels
+
+    def close(self):
+        self.h = None                               # the handle is the context's

@@ -250,7 +250,7 @@ int igdsp_tx_packetize(igdsp_ctx *ctx, const int16_t *d_pcm, const uint8_t *d_g7
 }
 
 // Calibration-only (not in include/igdsp.h): the compute-free packet writer that moves the bytes of an all-audio igdsp_tx_packetize launch
-// in the same traversal (tools/tx_bench.py --ab).  Exactly one of d_pcm / d_g711; n % 4 == 0.
+// in the same traversal and the same grid (tx_copy_route) (tools/tx_bench.py --ab).  Exactly one of d_pcm / d_g711; n % 4 == 0.
 int igdsp_internal_tx_copy(igdsp_ctx *ctx, const int16_t *d_pcm, const uint8_t *d_g711, uint32_t C, uint32_t F, uint32_t n, uint8_t *d_packets,
                            uint32_t pkt_stride, void *stream)
 {
@@ -354,7 +354,8 @@ int igdsp_bss_select(igdsp_ctx *ctx, const igdsp_rtp_info *d_info, const uint8_t
 
 // Calibration-only (not in include/igdsp.h): the compute-free yardstick of igdsp_bss_select (tools/bss_bench.py) — the same traversal,
 // the same bytes read and written, no decode / scale / clamp / stats / state machine (every non-empty group "selects" its first
-// member).  Arguments as igdsp_bss_select; the state is not touched, and sel / out / stats hold raw bytes.
+// member).  Arguments as igdsp_bss_select; the group state is not touched, the stored words are written as by a launch (the words
+// pass runs behind the yardstick too), and sel / out / stats hold raw bytes.
 int igdsp_internal_bss_copy(igdsp_ctx *ctx, const igdsp_rtp_info *d_info, const uint8_t *d_payload, const uint8_t *d_codec, const int16_t *d_pcm,
                             const uint16_t *d_len, const uint16_t *d_gain, const uint32_t *d_group_ptr, const uint32_t *d_members,
                             uint32_t n_members, const uint8_t *d_mute, uint32_t C, uint32_t G, uint32_t F, uint32_t n, uint32_t vote_frames,

@@ -21,7 +21,8 @@
 // The accumulator starts at 8192 (the rounding term), so a sample is 12 (or 12 R) dot products, a shift and a v_med3.
 // The state is written by k_rs_state behind the kernel on the stream: a block per channel at a time, a thread per history sample.
 // COPY (the compute-free yardstick, tools/rs_bench.py): steps 1 - 3 with the same loads, LDS traffic and stores, an xor instead of the
-// dot products, zero records, no state.
+// dot products, zero records, no state (the samples ahead of a launch's first frame are zeros; in the general form so are the tile
+// samples between a row's end and its last unit's end).
 #include "igdsp_device.h"
 #include "igdsp_pcmrec.h"
 
@@ -207,9 +208,12 @@ __global__ __launch_bounds__(kRsWaves * 64, rs_resident(DIR, R)) void k_rs(const
                     *reinterpret_cast<uint4 *>(&tile[kk][HIST + s0]) = v;
                 }
             } else {
-                for (uint32_t u = lane; u < CH * n_in; u += 64u) {
-                    const uint32_t kk = u / n_in, s = u - kk * n_in, cc = c0 + kk;
-                    if (cc < a.C) tile[kk][HIST + s] = rs_x(a, g711, dec, f, cc, s);
+                // (the yardstick folds whole units: it takes the samples between the row's end and its last unit's end as zeros, not as
+                // what the LDS held; the filter's windows end at a valid sample and never read them)
+                const uint32_t n_row = COPY ? a.pieces * (UP ? 8u : 8u * R) : n_in;
+                for (uint32_t u = lane; u < CH * n_row; u += 64u) {
+                    const uint32_t kk = u / n_row, s = u - kk * n_row, cc = c0 + kk;
+                    if (cc < a.C) tile[kk][HIST + s] = (!COPY || s < n_in) ? rs_x(a, g711, dec, f, cc, s) : (int16_t)0;
                 }
             }
             if (a.stats)

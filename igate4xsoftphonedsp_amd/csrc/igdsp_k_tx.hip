@@ -377,16 +377,6 @@ __global__ __launch_bounds__(kTxWaves * 64) void k_tx_copy_ab(const TxArgs a)
     }
 }
 
-hipError_t launch_tx_copy_ab(const LaunchCfg &cfg, const int16_t *pcm, const uint8_t *g711, uint32_t C, uint32_t F, uint32_t n,
-                             uint8_t *packets, uint32_t stride, hipStream_t s)
-{
-    TxArgs a{pcm, g711, nullptr, C, F, n, 0, 0, nullptr, nullptr, packets, stride, nullptr, nullptr, nullptr, (C + kTxCh - 1) / kTxCh, 1u};
-    const uint32_t grid = blocks_for(a.n_groups, kTxWaves, (uint32_t)cfg.compute_units * (pcm ? 1u : 2u));   // as k_tx_packetize
-    if (pcm) hipLaunchKernelGGL((k_tx_copy_ab<kTxPcmTab>), dim3(grid), dim3(kTxWaves * 64), 0, s, a);
-    else     hipLaunchKernelGGL((k_tx_copy_ab<kTxG711>), dim3(grid), dim3(kTxWaves * 64), 0, s, a);
-    return hipGetLastError();
-}
-
 // The 128 KiB of dynamic LDS the table form asks for exceeds the default limit.  Raised on the first large PCM launch on each device
 // (igdsp_create does not depend on it); if that fails the launch takes the enc_uni form instead — same bytes, slower.
 static bool tab_lds_ready()
@@ -405,6 +395,18 @@ static bool tab_lds_ready()
         state[dev].store(st, std::memory_order_release);
     }
     return st == 1;
+}
+
+// The grid is tx_route's for the same arguments (the table form included), so the yardstick runs the blocks of the launch it is compared with
+hipError_t launch_tx_copy_ab(const LaunchCfg &cfg, const int16_t *pcm, const uint8_t *g711, uint32_t C, uint32_t F, uint32_t n,
+                             uint8_t *packets, uint32_t stride, hipStream_t s)
+{
+    const bool tab_lds = tx_wants_table(pcm != nullptr, C, F, n) && tab_lds_ready();
+    const TxRoute r = tx_copy_route(C, F, n, reinterpret_cast<uintptr_t>(pcm), reinterpret_cast<uintptr_t>(g711), (uint32_t)cfg.compute_units, tab_lds);
+    TxArgs a{pcm, g711, nullptr, C, F, n, 0, 0, nullptr, nullptr, packets, stride, nullptr, nullptr, nullptr, r.n_groups, 1u};
+    if (pcm) hipLaunchKernelGGL((k_tx_copy_ab<kTxPcmTab>), dim3(r.grid), dim3(r.threads), 0, s, a);
+    else     hipLaunchKernelGGL((k_tx_copy_ab<kTxG711>), dim3(r.grid), dim3(r.threads), 0, s, a);
+    return hipGetLastError();
 }
 
 hipError_t launch_tx_packetize(const LaunchCfg &cfg, const int16_t *pcm, const uint8_t *g711, const uint8_t *ctl, uint32_t C, uint32_t F,

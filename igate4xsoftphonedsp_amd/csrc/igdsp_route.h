@@ -416,6 +416,16 @@ inline TxRoute tx_route(uint32_t C, uint32_t F, uint32_t n, uintptr_t pcm, uintp
     return r;
 }
 
+// igdsp_internal_tx_copy (launch_tx_copy_ab): the groups, grid and block of the igdsp_tx_packetize launch of the same arguments; the
+// yardstick has no send buffer, no LDS table of its own and always the vector loads (args::tx_copy asks for n % 4 == 0)
+inline TxRoute tx_copy_route(uint32_t C, uint32_t F, uint32_t n, uintptr_t pcm, uintptr_t g711, uint32_t cus, bool tab_lds)
+{
+    TxRoute r = tx_route(C, F, n, pcm, g711, 0, cus, tab_lds);
+    r.vec = 1u;
+    r.lds = 0u;
+    return r;
+}
+
 // ---- igdsp_conf_mix (launch_conf_mix): k_conf_mix<IN, COPY>.  An item is one (frame, port); a block of kConfWaves
 // waves takes groups of kConfWaves consecutive items.  Which ports are narrow (a wave mixes the port-frame alone) and which are wide
 // (the block splits the member list among its waves) is decided per item on the device from the CSR, so a launch with a skewed

@@ -27,6 +27,34 @@ def to_host(t, dtype, shape=None):
     return a.reshape(shape) if shape is not None else a
 
 
+FILL_A, FILL_B = 0xEE, 0x11
+
+
+def written_mask(run):
+    """The bytes a deterministic launch stores.  run(fill) makes the launch with every output buffer (guard bytes and foreign rows
+    included) pre-filled with `fill` and returns {name: the whole buffer's bytes after the launch}; it is called with 0xEE and with 0x11.
+    Returns {name: after_A != 0xEE | after_B != 0x11}: no byte can equal both fills, so a byte is in the mask iff it was stored."""
+    a, b = run(FILL_A), run(FILL_B)
+    assert a.keys() == b.keys()
+    mask = {}
+    for k in a:
+        ba, bb = np.ascontiguousarray(a[k]).view(np.uint8).reshape(-1), np.ascontiguousarray(b[k]).view(np.uint8).reshape(-1)
+        assert ba.shape == bb.shape, k
+        mask[k] = (ba != FILL_A) | (bb != FILL_B)
+    return mask
+
+
+def assert_same_footprint(yard, real, not_written=()):
+    """masks of written_mask: the yardstick stores exactly the bytes the entry stores, but nothing at all in the buffers of not_written"""
+    for k in yard:
+        if k in not_written:
+            assert not yard[k].any(), f"{k}: the yardstick wrote {int(yard[k].sum())} bytes, first at {int(np.flatnonzero(yard[k])[0])}"
+        else:
+            diff = np.flatnonzero(yard[k] != real[k])
+            assert diff.size == 0, (f"{k}: {diff.size} bytes differ in the footprint, first at {int(diff[0])} "
+                                    f"(yardstick {'wrote' if yard[k][diff[0]] else 'skipped'} it)")
+
+
 def new_hold(C_):
     h = np.zeros((C_,), dtype=capi.CHAN_HOLD)
     h["level_min"] = 255

@@ -77,6 +77,11 @@ int main()
             const TxRoute r = tx_route(C, F, n, pcm, g711, g("last", 0x1000), cus, g("tab_lds", 1) != 0);
             std::printf("form=%s vec=%u n_groups=%u grid=%u threads=%u lds=%u table=%d\n", tx_name(r.form), r.vec, r.n_groups, r.grid, r.threads, r.lds,
                         tx_wants_table(pcm != 0, C, F, n));
+        } else if (entry == "tx_copy") {   // the yardstick of tx (launch_tx_copy_ab)
+            const uint64_t pcm = g("pcm"), g711 = g("g711");
+            const TxRoute r = tx_copy_route(C, F, n, pcm, g711, cus, g("tab_lds", 1) != 0);
+            std::printf("form=%s vec=%u n_groups=%u grid=%u threads=%u lds=%u table=%d\n", tx_name(r.form), r.vec, r.n_groups, r.grid, r.threads, r.lds,
+                        tx_wants_table(pcm != 0, C, F, n));
         } else if (entry == "bss") {   // form 0 G.711 / 1 PCM / 2 none; in, out: buffer addresses, alignment only
             const BssRoute r = bss_route((uint32_t)g("G"), F, n, (uint32_t)g("members"), (int)g("form"), g("in", 0x1000), g("out", 0x1000));
             std::printf("form=%d gpw=%u vec_in=%u vec_out=%u grid=%u threads=%u part_frames=%u parts=%u words_grid=%u\n", r.form, r.gpw, r.vec_in,

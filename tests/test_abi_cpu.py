@@ -32,6 +32,62 @@ def test_header_symbols_all_exported_and_bound(lib):
     assert lib.igdsp_abi_version() == capi.ABI_VERSION == 3
 
 
+def _param_types(text, name):
+    """the parameter-type list of the one declaration / definition `int name(...)` in C text: comments dropped, names dropped"""
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+    found = re.findall(rf"^\s*int\s+{name}\s*\(([^)]*)\)", text, flags=re.M)
+    assert len(found) == 1, (name, len(found))
+    types = []
+    for p in found[0].split(","):
+        m = re.fullmatch(r"\s*(.*?)\s*\b[A-Za-z_]\w*\s*", p, flags=re.S)           # everything ahead of the parameter's name
+        assert m and m.group(1), (name, p)
+        types.append(re.sub(r"\s*\*\s*", " *", " ".join(m.group(1).split())))
+    return types
+
+
+def _ctype_of(t):
+    if t.endswith("*"):
+        return ctypes.c_void_p
+    return {"uint32_t": ctypes.c_uint32, "uint64_t": ctypes.c_uint64, "int32_t": ctypes.c_int32, "int": ctypes.c_int}[t]
+
+
+def _csrc():
+    d = os.path.join(ROOT, "igate4xsoftphonedsp_amd", "csrc")
+    return "\n".join(open(os.path.join(d, f)).read() for f in sorted(os.listdir(d)) if f.startswith("igdsp_capi") and f.endswith(".hip"))
+
+
+@pytest.mark.parametrize("name", sorted(capi.INTERNAL_TWIN))
+def test_yardstick_signature_is_its_twins(name):
+    """a yardstick entry takes "arguments as" its public twin: the parameter types of its extern "C" definition equal those the header
+    declares for the twin, and the binding's row (derived from the twin's) is that list"""
+    twin = capi.INTERNAL_TWIN[name]
+    got = _param_types(_csrc(), name)
+    exp = _param_types(open(os.path.join(ROOT, "include", "igdsp.h")).read(), twin)
+    assert got == exp, (name, twin)
+    res, args = capi.INTERNAL[name]
+    assert res is ctypes.c_int and list(args) == [_ctype_of(t) for t in got]
+
+
+def test_yardstick_table_is_complete():
+    """every igdsp_internal_*_copy / _fill the library defines is in the table, and tx_copy's own row matches its definition"""
+    src = re.sub(r"//[^\n]*", "", _csrc())
+    defined = set(re.findall(r"^int\s+(igdsp_internal_\w+_(?:copy|fill))\s*\(", src, flags=re.M))
+    assert defined == set(capi.INTERNAL) and len(defined) == 10, defined ^ set(capi.INTERNAL)
+    res, args = capi.INTERNAL["igdsp_internal_tx_copy"]
+    assert res is ctypes.c_int and list(args) == [_ctype_of(t) for t in _param_types(_csrc(), "igdsp_internal_tx_copy")]
+    with pytest.raises(KeyError):
+        capi.internal("igdsp_internal_stream_rw")
+
+
+def test_tools_bind_their_yardstick_through_the_table():
+    """tools/<stage>_bench.py takes its yardstick from capi.internal and writes no argtypes of its own"""
+    for name in capi.INTERNAL:
+        stage = name[len("igdsp_internal_"):].split("_")[0]
+        text = open(os.path.join(ROOT, "tools", f"{stage}_bench.py")).read()
+        assert f'capi.internal("{name}")' in text and ".argtypes" not in text, stage
+
+
 def test_struct_layouts_agree(orc):
     assert capi.FRAME_STATS.itemsize == orc.FRAME_STATS.itemsize == 16
     assert capi.CHAN_HOLD.itemsize == orc.CHAN_HOLD.itemsize == 32

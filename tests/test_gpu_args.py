@@ -38,7 +38,8 @@ def entries(ctx):
         if ac.SYMBOL[entry] in declared:
             assert list(fn.argtypes) == argtypes, entry             # the table's parameter list is the binding's
         else:
-            fn.restype, fn.argtypes = C.c_int, argtypes
+            fn = capi.internal(ac.SYMBOL[entry])
+            assert list(fn.argtypes) == argtypes, entry
         fns[entry] = fn
     return fns
 
@@ -78,4 +79,20 @@ def test_replay(ctx, a, entries):
         got = _call(entries[entry], ctx.h, entry, kv, a)
         if got != rc:
             wrong.append((ac.case_id((entry, kv, rc, 0)), "expected", rc, "got", got))
+    assert not wrong, wrong
+
+
+YARDSTICK_OF = {"conf_mix": "conf_copy", "bss_select": "bss_copy", "ptt_arbitrate": "ptt_copy", "link_watch": "link_copy", "jb_receive": "jb_copy",
+                "plc_conceal": "plc_copy"}
+
+
+@pytest.mark.parametrize("entry", sorted(YARDSTICK_OF))
+def test_yardstick_rejects_what_its_twin_rejects(ctx, a, entry):
+    """a yardstick takes its public entry's rule: every IGDSP_EINVAL row of the twin that launches nothing (at least three per stage),
+    and the nothing-to-do rows, give the same code through the igdsp_internal_* entry.  (igdsp_internal_tx_copy has rows of its own
+    above; rs, snd and tone: their own test files.)"""
+    fn = capi.internal(YARDSTICK_OF[entry])
+    rows = [c for c in REPLAYED if c[0] == entry]
+    assert sum(1 for c in rows if c[2] == ac.EINVAL) >= 3
+    wrong = [(ac.case_id(c), "got", got) for c in rows if (got := _call(fn, ctx.h, entry, c[1], a)) != c[2]]
     assert not wrong, wrong

@@ -33,16 +33,18 @@ def _dev(a):
 
 
 def run_bss(ctx, info, ptr, mem, C_, G_, n, state, words, payload=None, codec=None, pcm=None, length=None, gain=None, mute=None, vf=0,
-            sel=True, out=True, stats=True, stream=None, F_=None):
+            sel=True, out=True, stats=True, stream=None, F_=None, entry=None, fill=None, raw=None):
     """igdsp_bss_select through the C ABI with guard bytes after every output; returns (sel, out, stats, state, words) (None where not
-    asked for)"""
+    asked for).  entry: through that yardstick of capi.INTERNAL_TWIN instead; fill: the byte every output and its guard hold before the
+    launch; raw: a dict that takes the whole output buffers' bytes after it."""
     torch = gu.torch_cuda()
     F_ = info.shape[0] if F_ is None else F_
     nm = len(mem)
     audio = payload is not None or pcm is not None
-    d_sel = gu.dev_zeros(F_ * G_ * 4 + GUARD, 0x3C) if sel else None
-    d_out = gu.dev_zeros(F_ * G_ * n * 2 + GUARD, 0xA5) if out and audio else None
-    d_st = gu.dev_zeros(F_ * G_ * 16 + GUARD, 0x5A) if stats and audio else None
+    fsel, fout, fst = (0x3C, 0xA5, 0x5A) if fill is None else (fill,) * 3
+    d_sel = gu.dev_zeros(F_ * G_ * 4 + GUARD, fsel) if sel else None
+    d_out = gu.dev_zeros(F_ * G_ * n * 2 + GUARD, fout) if out and audio else None
+    d_st = gu.dev_zeros(F_ * G_ * 16 + GUARD, fst) if stats and audio else None
     d_state = _dev(np.concatenate([np.ascontiguousarray(state, np.uint32).reshape(-1).view(np.uint8), np.full(GUARD, 0x77, np.uint8)]))
     d_words = _dev(np.concatenate([np.ascontiguousarray(words, np.uint32).view(np.uint8), np.full(GUARD, 0x66, np.uint8)]))
     # (the inputs are named so that they live until the launch is through: a temporary is freed when the call returns, and with
@@ -50,8 +52,8 @@ def run_bss(ctx, info, ptr, mem, C_, G_, n, state, words, payload=None, codec=No
     d_info, d_ptr, d_mem = _dev(info), _dev(ptr), _dev(mem) if nm else None
     ins = {k: _dev(v) if v is not None else None for k, v in (("payload", payload), ("codec", codec), ("pcm", pcm), ("length", length),
                                                                ("gain", gain), ("mute", mute))}
-    ctx.bss_select(d_info, d_ptr, d_mem, nm, d_state, d_words if nm else None, C_, G_, F_, n, vote_frames=vf, sel=d_sel, out=d_out,
-                   stats=d_st, stream=stream, **ins)
+    (ctx.via(entry) if entry else ctx).bss_select(d_info, d_ptr, d_mem, nm, d_state, d_words if nm else None, C_, G_, F_, n, vote_frames=vf,
+                                                  sel=d_sel, out=d_out, stats=d_st, stream=stream, **ins)
     if stream is None:
         torch.cuda.synchronize()
     else:
@@ -62,11 +64,13 @@ def run_bss(ctx, info, ptr, mem, C_, G_, n, state, words, payload=None, codec=No
         assert np.all(raw[nbytes:] == fill), f"guard bytes after {what} written"
         return raw[:nbytes]
 
-    s = take(d_sel, F_ * G_ * 4, 0x3C, "d_sel").view("<i4").reshape(F_, G_) if sel else None
-    o = take(d_out, F_ * G_ * n * 2, 0xA5, "d_out").view("<i2").reshape(F_, G_, n) if d_out is not None else None
-    r = take(d_st, F_ * G_ * 16, 0x5A, "d_stats").view(capi.FRAME_STATS).reshape(F_, G_) if d_st is not None else None
+    s = take(d_sel, F_ * G_ * 4, fsel, "d_sel").view("<i4").reshape(F_, G_) if sel else None
+    o = take(d_out, F_ * G_ * n * 2, fout, "d_out").view("<i2").reshape(F_, G_, n) if d_out is not None else None
+    r = take(d_st, F_ * G_ * 16, fst, "d_stats").view(capi.FRAME_STATS).reshape(F_, G_) if d_st is not None else None
     st = take(d_state, G_ * 16, 0x77, "d_state").view("<u4").reshape(G_, 4)
     wd = take(d_words, nm * 4, 0x66, "d_words").view("<u4").copy()
+    if raw is not None:
+        raw.update({k: t.cpu().numpy() for k, t in (("sel", d_sel), ("out", d_out), ("stats", d_st)) if t is not None})
     return s, o, r, st, wd
 
 
@@ -375,3 +379,81 @@ def test_arguments(ctx):
     with pytest.raises(capi.IgdspError):
         ctx.bss_select(info, ptr, mem, 8, None, words, C_, G_, F_, n)
     torch.cuda.synchronize()
+
+
+# ---- the compute-free yardstick (igdsp_internal_bss_copy, tools/bss_bench.py) against its promise in csrc/igdsp_capi.hip: "the same
+# traversal, the same bytes read and written, no decode / scale / clamp / stats / state machine (every non-empty group selects its first
+# member); the group state is not touched, the stored words are written as by a launch, and sel / out / stats hold raw bytes"
+
+def _yard_inputs(rng, form, F_, C_, n):
+    if form == "g711":
+        return dict(payload=rng.integers(0, 256, (F_, C_, n), dtype=np.uint8), codec=np.where(rng.random(C_) < 0.5, 8, 0).astype(np.uint8))
+    return dict(pcm=rng.integers(-32768, 32768, (F_, C_, n)).astype(np.int16)) if form == "pcm" else {}
+
+
+@pytest.mark.parametrize("form", ["g711", "pcm", "none"])
+@pytest.mark.parametrize("F_", [3, 131])
+def test_yardstick_footprint_and_independence(ctx, form, F_):
+    """igdsp_internal_bss_copy, group counts around a wave's, one part and two, the three input forms: it stores the bytes
+    igdsp_bss_select stores in sel, out and stats and leaves the stored words as the entry does; the group state is not written, and
+    whether it holds zeros or garbage the outputs are the same bytes"""
+    rng = np.random.default_rng(800 + F_ + len(form))
+    C_, n = 48, 160
+    for G_ in (1, 15, 17, 65):
+        info = random_info(rng, F_, C_)
+        ptr, mem = random_table(rng, C_, G_)
+        kw = _yard_inputs(rng, form, F_, C_, n)
+        _, wd0 = start_state(rng, G_, ptr, len(mem))
+        got = {}
+
+        def launch(entry):
+            def run(fill):
+                raw = {}
+                st0 = np.full((G_, 4), fill * 0x01010101, np.uint32) if entry else np.zeros((G_, 4), np.uint32)
+                got[entry, fill] = run_bss(ctx, info, ptr, mem, C_, G_, n, st0, wd0, entry=entry, fill=fill, raw=raw, **kw)
+                return raw
+            return run
+
+        yard, real = gu.written_mask(launch("bss_copy")), gu.written_mask(launch(None))
+        assert all(real[k][:-GUARD].all() for k in real)
+        gu.assert_same_footprint(yard, real)
+        zero = run_bss(ctx, info, ptr, mem, C_, G_, n, np.zeros((G_, 4), np.uint32), wd0, entry="bss_copy", fill=gu.FILL_A, **kw)
+        a, b = got["bss_copy", gu.FILL_A], got["bss_copy", gu.FILL_B]
+        assert (a[3].view(np.uint8) == gu.FILL_A).all() and (b[3].view(np.uint8) == gu.FILL_B).all() and not zero[3].any()    # the state as it was
+        for x in (b, zero):
+            assert all(p is None or p.tobytes() == q.tobytes() for p, q in zip(x[:3], a[:3]))
+            np.testing.assert_array_equal(x[4], got[None, gu.FILL_A][4])                                          # the words as the entry's
+        first = np.where(ptr[1:] > ptr[:-1], mem[np.minimum(ptr[:-1], len(mem) - 1)].astype(np.int64), -1)
+        np.testing.assert_array_equal(a[0], np.broadcast_to(first, (F_, G_)))                                    # sel: the first member
+
+
+@pytest.mark.parametrize("form", ["g711", "pcm"])
+def test_yardstick_reads_the_first_members_rows(ctx, form):
+    """one channel's whole row of one frame replaced by fresh random bytes: out (and the raw bytes in the record) of exactly the groups
+    whose first member it is change, in that frame; every other output byte is the same.  One d_info record replaced: every output
+    byte is the same and the launch completes — the promise says the records are read, but nothing the yardstick stores depends on
+    them (the kernel keeps the loads alive through a fold it compares with a constant), and a load that was dropped cannot be seen
+    from outside, so this is as far as a test can go."""
+    rng = np.random.default_rng(820 + len(form))
+    C_, G_, F_, n, f = 48, 65, 3, 160, 1
+    info = random_info(rng, F_, C_)
+    ptr, mem = random_table(rng, C_, G_)
+    kw = _yard_inputs(rng, form, F_, C_, n)
+    st0, wd0 = np.zeros((G_, 4), np.uint32), np.zeros(len(mem), np.uint32)
+    c = int(mem[ptr[G_ // 2]])
+    consumers = [g for g in range(G_) if mem[ptr[g]] == c]
+    base = run_bss(ctx, info, ptr, mem, C_, G_, n, st0, wd0, entry="bss_copy", **kw)
+    key = "payload" if form == "g711" else "pcm"
+    rows = kw[key].copy()
+    rows[f, c] = rng.integers(0, 256, n, dtype=np.uint8) if form == "g711" else rng.integers(-32768, 32768, n).astype(np.int16)
+    got = run_bss(ctx, info, ptr, mem, C_, G_, n, st0, wd0, entry="bss_copy", **{**kw, key: rows})
+    want = np.zeros((F_, G_), bool)
+    want[f, consumers] = True
+    np.testing.assert_array_equal((got[1] != base[1]).any(axis=2), want)
+    rec = lambda r: np.ascontiguousarray(r).view(np.uint8).reshape(F_, G_, 16)   # noqa: E731
+    assert got[0].tobytes() == base[0].tobytes() and not (rec(got[2]) != rec(base[2])).any(axis=2)[~want].any()
+    info2 = info.copy()
+    info2[f, c] = random_info(rng, 1, 1)[0, 0]
+    info2["ed137"][f, c] ^= 0x5A5A5A5A
+    got = run_bss(ctx, info2, ptr, mem, C_, G_, n, st0, wd0, entry="bss_copy", **kw)
+    assert all(p.tobytes() == q.tobytes() for p, q in zip(got[:3], base[:3]))

@@ -31,28 +31,34 @@ def _dev(a):
 
 
 def run_mix(ctx, C_, P_, F_, n, gain, ptr, mem, payload=None, codec=None, pcm=None, length=None, n_members=None, out=True, stats=True,
-            stream=None):
-    """igdsp_conf_mix through the C ABI with guard bytes after both outputs; returns (out [F][P][n] | None, stats [F][P] | None)."""
+            stream=None, entry=None, fill=None, raw=None):
+    """igdsp_conf_mix through the C ABI with guard bytes after both outputs; returns (out [F][P][n] | None, stats [F][P] | None).
+    entry: through that yardstick of capi.INTERNAL_TWIN instead; fill: the byte both outputs and their guards hold before the launch;
+    raw: a dict that takes the whole output buffers' bytes after it."""
     torch = gu.torch_cuda()
     nm = len(mem) if n_members is None else n_members
-    d_out = gu.dev_zeros(F_ * P_ * n * 2 + GUARD, 0xA5) if out else None
-    d_st = gu.dev_zeros(F_ * P_ * 16 + GUARD, 0x5A) if stats else None
+    fo, fs = (0xA5, 0x5A) if fill is None else (fill, fill)
+    d_out = gu.dev_zeros(F_ * P_ * n * 2 + GUARD, fo) if out else None
+    d_st = gu.dev_zeros(F_ * P_ * 16 + GUARD, fs) if stats else None
     args = dict(payload=_dev(payload) if payload is not None else None, codec=_dev(codec) if codec is not None else None,
                 pcm=_dev(pcm) if pcm is not None else None, length=_dev(length) if length is not None else None)
-    ctx.conf_mix(_dev(gain), _dev(ptr), _dev(mem) if nm else None, nm, C_, P_, F_, n, out=d_out, stats=d_st, stream=stream, **args)
+    (ctx.via(entry) if entry else ctx).conf_mix(_dev(gain), _dev(ptr), _dev(mem) if nm else None, nm, C_, P_, F_, n, out=d_out, stats=d_st,
+                                                stream=stream, **args)
     if stream is None:
         torch.cuda.synchronize()
     else:
         ctx.sync(stream)
     o = s = None
     if out:
-        raw = d_out.cpu().numpy()
-        assert np.all(raw[F_ * P_ * n * 2:] == 0xA5), "guard bytes after d_out written"
-        o = raw[:F_ * P_ * n * 2].view("<i2").reshape(F_, P_, n)
+        b = d_out.cpu().numpy()
+        assert np.all(b[F_ * P_ * n * 2:] == fo), "guard bytes after d_out written"
+        o = b[:F_ * P_ * n * 2].view("<i2").reshape(F_, P_, n)
     if stats:
-        raw = d_st.cpu().numpy()
-        assert np.all(raw[F_ * P_ * 16:] == 0x5A), "guard bytes after d_stats written"
-        s = raw[:F_ * P_ * 16].view(capi.FRAME_STATS).reshape(F_, P_)
+        b = d_st.cpu().numpy()
+        assert np.all(b[F_ * P_ * 16:] == fs), "guard bytes after d_stats written"
+        s = b[:F_ * P_ * 16].view(capi.FRAME_STATS).reshape(F_, P_)
+    if raw is not None:
+        raw.update({k: t.cpu().numpy() for k, t in (("out", d_out), ("stats", d_st)) if t is not None})
     return o, s
 
 
@@ -338,3 +344,80 @@ def test_argument_paths(ctx):
     torch.cuda.synchronize()
     assert np.all(gu.to_host(st, capi.FRAME_STATS)[:F_ * P_]["flags"] == capi.FLAG_EMPTY)
     assert np.all(out.cpu().numpy()[F_ * P_ * n * 2:] == 0xA5) and np.all(st.cpu().numpy()[F_ * P_ * 16:] == 0x5A)
+
+
+# ---- the compute-free yardstick (igdsp_internal_conf_copy, tools/conf_bench.py) against its promise in csrc/igdsp_capi.hip: "the
+# same traversal, the same bytes read and written, no decode / scale / clamp / stats"
+
+def _yard_case(rng, C_, P_, F_, n, form, wide=None):
+    """a table of unique members (every port lists 0 .. 6 channels, port `wide` 130), full gains but for two muted channels, d_len with
+    short and empty rows"""
+    sizes = rng.integers(0, 7, P_)
+    if wide is not None:
+        sizes[wide] = 130
+    chan = np.concatenate([rng.choice(C_, k, replace=False) for k in sizes] + [np.zeros(0, np.int64)]).astype(np.uint32)
+    port = np.repeat(np.arange(P_), sizes).astype(np.uint32)
+    ptr, mem = cm.build(chan, port, C_, P_)
+    gain = GAINS[rng.integers(1, len(GAINS), C_)]
+    gain[[C_ // 3, C_ // 2]] = 0
+    length = np.where(rng.integers(0, 4, (F_, C_)) == 0, rng.integers(0, n + 1, (F_, C_)), n).astype(np.uint16)
+    codec = np.where(rng.integers(0, 2, C_) == 1, 8, 0).astype(np.uint8)
+    kw = dict(payload=rng.integers(0, 256, (F_, C_, n), dtype=np.uint8), codec=codec) if form == "g711" else \
+        dict(pcm=rng.integers(-32768, 32768, (F_, C_, n)).astype(np.int16))
+    return gain, ptr, mem, length, kw
+
+
+YARD_ITEMS = [(1, 1), (5, 3), (16, 1), (17, 1), (11, 3)]                   # P x F = 1, 15, 16, 17, 33 items: a block takes 16 at a time
+
+
+@pytest.mark.parametrize("form", ["g711", "pcm"])
+@pytest.mark.parametrize("n", [1, 160, 164])
+def test_yardstick_footprint(ctx, n, form):
+    """igdsp_internal_conf_copy stores exactly the bytes igdsp_conf_mix stores on the same arguments: every port-frame's row and record,
+    narrow ports and a block-wide one, and nothing behind them"""
+    rng = np.random.default_rng(500 + n + len(form))
+    for P_, F_ in YARD_ITEMS + [(3, 2)]:
+        C_ = 140
+        gain, ptr, mem, length, kw = _yard_case(rng, C_, P_, F_, n, form, wide=1 if (P_, F_) == (3, 2) else None)
+
+        def launch(entry):
+            def run(fill):
+                raw = {}
+                run_mix(ctx, C_, P_, F_, n, gain, ptr, mem, length=length, entry=entry, fill=fill, raw=raw, **kw)
+                return raw
+            return run
+
+        yard, real = gu.written_mask(launch("conf_copy")), gu.written_mask(launch(None))
+        assert real["out"][:F_ * P_ * n * 2].all() and real["stats"][:F_ * P_ * 16].all()
+        gu.assert_same_footprint(yard, real)
+
+
+@pytest.mark.parametrize("form", ["g711", "pcm"])
+@pytest.mark.parametrize("wide", [False, True], ids=["narrow", "wide"])
+def test_yardstick_reads_every_member_row(ctx, form, wide):
+    """one member channel's whole row of one frame replaced by fresh random bytes (not complemented: the fold is an xor): the output
+    rows of exactly the ports that list the channel change, in that frame; every other output byte is the same.  Once through the
+    narrow form, once for a port of 130 members (> kConfWideMin: the block splits the list)"""
+    rng = np.random.default_rng(520 + len(form) + wide)
+    C_, P_, F_, n = 140, 11, 3, 160
+    gain, ptr, mem, length, kw = _yard_case(rng, C_, P_, F_, n, form, wide=4 if wide else None)
+    f = 1
+    lists = [mem[ptr[p]:ptr[p + 1]] for p in range(P_)]
+    pool = lists[4] if wide else np.concatenate([lists[p] for p in range(P_) if p != 4])
+    c = int(next(x for x in pool if gain[x] and (wide or x not in lists[4])))
+    length[f, c] = n
+    consumers = [p for p in range(P_) if c in lists[p]]
+    assert consumers and (4 in consumers) == wide and (len(lists[4]) == 130) == wide
+    base = run_mix(ctx, C_, P_, F_, n, gain, ptr, mem, length=length, entry="conf_copy", **kw)
+    key = "payload" if form == "g711" else "pcm"
+    rows = kw[key].copy()
+    rows[f, c] = rng.integers(0, 256, n, dtype=np.uint8) if form == "g711" else rng.integers(-32768, 32768, n).astype(np.int16)
+    assert (rows[f, c] != kw[key][f, c]).any()
+    got = run_mix(ctx, C_, P_, F_, n, gain, ptr, mem, length=length, entry="conf_copy", **{**kw, key: rows})
+    changed = (got[0] != base[0]).any(axis=2)
+    want = np.zeros((F_, P_), bool)
+    want[f, consumers] = True
+    np.testing.assert_array_equal(changed, want)
+    assert got[1].tobytes() == base[1].tobytes()                            # the records do not depend on the samples
+    again = run_mix(ctx, C_, P_, F_, n, gain, ptr, mem, length=length, entry="conf_copy", **kw)
+    assert again[0].tobytes() == base[0].tobytes() and again[1].tobytes() == base[1].tobytes()

@@ -35,12 +35,12 @@ def _take(d, nbytes, fill, what):
 
 
 class Dev:
-    """device state + ring of C channels (zero = reset), carried across run() calls"""
+    """device state + ring of C channels (zero = reset; fill: every byte of both holds it), carried across run() calls"""
 
-    def __init__(self, C_, n=160):
+    def __init__(self, C_, n=160, fill=0):
         self.C, self.n = C_, n
-        self.state = _guarded(C_ * capi.JB_STATE.itemsize, 0)
-        self.ring = _guarded(capi.jb_ring_bytes(C_, n), 0)
+        self.state = _guarded(C_ * capi.JB_STATE.itemsize, fill)
+        self.ring = _guarded(capi.jb_ring_bytes(C_, n), fill)
         self.state[C_ * capi.JB_STATE.itemsize:] = 0x77
         self.ring[capi.jb_ring_bytes(C_, n):] = 0x66
 
@@ -51,26 +51,34 @@ class Dev:
         return _take(self.ring, capi.jb_ring_bytes(self.C, self.n), 0x66, "d_ring")
 
 
-def run_jb(ctx, dev, packets, sizes, radio, S, delay, arrival=None, stream=None, status=True, flags=True):
-    """one igdsp_jb_receive launch over packets [T*S][C][stride]; returns (payload, len, info, flags, status) numpy"""
+def run_jb(ctx, dev, packets, sizes, radio, S, delay, arrival=None, stream=None, status=True, flags=True, entry=None, fill=None, raw=None):
+    """one igdsp_jb_receive launch over packets [T*S][C][stride]; returns (payload, len, info, flags, status) numpy.  entry: through
+    that yardstick of capi.INTERNAL_TWIN instead; fill: the byte every output and its guard hold before the launch; raw: a dict that
+    takes the whole output buffers' bytes after it."""
     torch = gu.torch_cuda()
     A, C_, stride = packets.shape
     T, n = A // S, dev.n
-    d_pay, d_len, d_inf = _guarded(T * C_ * n, 0xA5), _guarded(T * C_ * 2, 0x5A), _guarded(T * C_ * 8, 0x3C)
-    d_fl = _guarded(T * C_, 0x11) if flags else None
-    d_st = _guarded(A * C_, 0x22) if status else None
-    ctx.jb_receive(gu.to_dev(packets), gu.to_dev(np.asarray(radio, np.uint8)), dev.state, dev.ring, d_pay, d_len, d_inf, C_, T, S, stride, n,
-                   delay, sizes=None if sizes is None else gu.to_dev(np.asarray(sizes, "<u2")),
-                   arrival=None if arrival is None else gu.to_dev(np.asarray(arrival, "<u4")), tick_flags=d_fl, pkt_status=d_st, stream=stream)
+    fp, fn, fi, ff, fs = (0xA5, 0x5A, 0x3C, 0x11, 0x22) if fill is None else (fill,) * 5
+    d_pay, d_len, d_inf = _guarded(T * C_ * n, fp), _guarded(T * C_ * 2, fn), _guarded(T * C_ * 8, fi)
+    d_fl = _guarded(T * C_, ff) if flags else None
+    d_st = _guarded(A * C_, fs) if status else None
+    (ctx.via(entry) if entry else ctx).jb_receive(
+        gu.to_dev(packets), gu.to_dev(np.asarray(radio, np.uint8)), dev.state, dev.ring, d_pay, d_len, d_inf, C_, T, S, stride, n, delay,
+        sizes=None if sizes is None else gu.to_dev(np.asarray(sizes, "<u2")),
+        arrival=None if arrival is None else gu.to_dev(np.asarray(arrival, "<u4")), tick_flags=d_fl, pkt_status=d_st, stream=stream)
     if stream is None:
         torch.cuda.synchronize()
     else:
         ctx.sync(stream)
-    pay = _take(d_pay, T * C_ * n, 0xA5, "payload").reshape(T, C_, n)
-    ln = _take(d_len, T * C_ * 2, 0x5A, "len").view("<u2").reshape(T, C_)
-    inf = _take(d_inf, T * C_ * 8, 0x3C, "info").view(capi.RTP_INFO).reshape(T, C_)
-    fl = _take(d_fl, T * C_, 0x11, "tick flags").reshape(T, C_) if flags else None
-    st = _take(d_st, A * C_, 0x22, "packet status").reshape(A, C_) if status else None
+    pay = _take(d_pay, T * C_ * n, fp, "payload").reshape(T, C_, n)
+    ln = _take(d_len, T * C_ * 2, fn, "len").view("<u2").reshape(T, C_)
+    inf = _take(d_inf, T * C_ * 8, fi, "info").view(capi.RTP_INFO).reshape(T, C_)
+    fl = _take(d_fl, T * C_, ff, "tick flags").reshape(T, C_) if flags else None
+    st = _take(d_st, A * C_, fs, "packet status").reshape(A, C_) if status else None
+    if raw is not None:
+        raw.update({k: t.cpu().numpy() for k, t in (("payload", d_pay), ("len", d_len), ("info", d_inf), ("tick_flags", d_fl), ("pkt_status", d_st))
+                    if t is not None})
+        raw.update(state=dev.host_state().view(np.uint8), ring=dev.ring_bytes())      # (their guards hold bytes of their own, checked there)
     return pay, ln, inf, fl, st
 
 
@@ -350,3 +358,59 @@ def test_full_size_in_order(ctx):
     # the ring holds the three packets of the pre-roll
     tags = ring[:C_ * 64].view(torch.int32).view(C_, 16).cpu().numpy()
     assert np.all((tags != 0).sum(axis=1) == 3)
+
+
+# ---- the compute-free yardstick (igdsp_internal_jb_copy, tools/jb_bench.py) against its promise in csrc/igdsp_capi.hip: "the rows of
+# an in-order lossless launch (arrival slot 0 of every tick copied as igdsp_depayload would), with no header walk, state machine or
+# ring store; the state, the ring and d_pkt_status are not touched"
+
+def slot0_traffic(C_, T, n, S=2, seed=5):
+    """in order, lossless: the tick's packet in arrival slot 0 (payloads of n bytes, and some shorter), junk bytes of size 0 in the others"""
+    rng = np.random.default_rng(seed)
+    stride = (20 + n + 3) // 4 * 4
+    radio = (np.arange(C_) % 3 != 0).astype(np.uint8)
+    arrivals = {}
+    for c in range(C_):
+        s0, ssrc = int(rng.integers(0, 65536)), int(rng.integers(0, 1 << 32))
+        for t in range(T):
+            ln = n if rng.random() < 0.9 else int(rng.integers(0, n))
+            arrivals[(t, c)] = [jm.rtp_header(8, s0 + t, n * t, ssrc, bool(radio[c]), 1 << 28 | (c & 31) << 3) + rng.integers(0, 256, ln, dtype=np.uint8).tobytes()]
+    packets, sizes = jm.pack(arrivals, C_, T, S, stride)
+    junk = rng.integers(0, 256, packets.shape, dtype=np.uint8)
+    for k in range(1, S):
+        packets[k::S] = junk[k::S]
+    return packets, sizes, radio
+
+
+@pytest.mark.parametrize("T", [3, 131])
+@pytest.mark.parametrize("n", [160, 24, 13])
+def test_yardstick_footprint_values_independence(ctx, orc, n, T):
+    """igdsp_internal_jb_copy on an in-order lossless launch, two arrival slots per tick, channel counts around the wave's, one part and
+    two: it stores the bytes igdsp_jb_receive stores in the rows, lengths, records and tick flags and not a byte of the state, the ring
+    or d_pkt_status; the state and the ring may hold any garbage; rows, lengths and records are igdsp_depayload's of slot 0"""
+    S = 2
+    for C_ in (1, 15, 17, 65):
+        packets, sizes, radio = slot0_traffic(C_, T, n, S, seed=C_ + T)
+        got = {}
+
+        def yard(fill):
+            raw = {}
+            got[fill] = run_jb(ctx, Dev(C_, n, fill), packets, sizes, radio, S, 0, entry="jb_copy", fill=fill, raw=raw)
+            return raw
+
+        def real(fill):
+            raw = {}
+            run_jb(ctx, Dev(C_, n), packets, sizes, radio, S, 0, fill=fill, raw=raw)
+            return raw
+
+        outs = ("payload", "len", "info", "tick_flags")
+        ym, rmk = gu.written_mask(yard), gu.written_mask(real)
+        assert all(rmk[k][:-GUARD].all() for k in outs)
+        gu.assert_same_footprint(ym, rmk, not_written=("state", "ring", "pkt_status"))
+        dpay, dln, dinf = orc.depayload(packets[0::S], sizes[0::S], radio, n)
+        zero = run_jb(ctx, Dev(C_, n), packets, sizes, radio, S, 0, entry="jb_copy")
+        for pay, ln, inf, fl, _ in (got[gu.FILL_A], got[gu.FILL_B], zero):
+            np.testing.assert_array_equal(pay, dpay)
+            np.testing.assert_array_equal(ln, dln)
+            np.testing.assert_array_equal(inf.view(np.uint64), dinf.view(np.uint64))
+            assert (fl == jm.PLAYED).all()

@@ -2,7 +2,6 @@
 kind bytes, the event list and its two counts: shapes around the wave, the block and the part; every optional input given and NULL;
 event_cap around the total with guard bytes behind the list; the masks; no list; no kind; launch-split equivalence on the device; d_up
 toggled between launches; two streams; nothing to do; every argument rule; and the compute-free yardstick's promise."""
-import ctypes
 import threading
 
 import numpy as np
@@ -265,10 +264,7 @@ def test_argument_rules(ctx):
 def test_yardstick_same_passes_no_state_machine(ctx):
     """igdsp_internal_link_copy (tools/link_bench.py's yardstick) walks the same passes and stores the state as it read it, kind bytes of
     0 and an empty list"""
-    cp = ctx.L.igdsp_internal_link_copy
-    cp.restype = ctypes.c_int
-    vp, u32 = ctypes.c_void_p, ctypes.c_uint32
-    cp.argtypes = [vp] * 5 + [u32] * 3 + [ctypes.c_uint64] + [u32] * 3 + [vp] * 3 + [u32] + [vp] * 3
+    cp = capi.internal("igdsp_internal_link_copy")
     C, T, S = 257, PART + 3, 2
     info, sz, up, per, st0, t0 = make_case(71, C, T, S)
     for want_list in (True, False):

@@ -103,22 +103,28 @@ class Dev:
         return _take(self.state, self.C * SB, 0x77, "d_state").view(capi.PLC_STATE)
 
 
-def run_plc(ctx, dev, fl, ln, inp, n, stream=None, with_len=True, outs=True):
+def run_plc(ctx, dev, fl, ln, inp, n, stream=None, with_len=True, outs=True, entry=None, fill=None, raw=None):
+    """one launch; entry: through that yardstick of capi.INTERNAL_TWIN instead; fill: the byte every output and its guard hold before
+    the launch; raw: a dict that takes the whole output buffers' bytes after it"""
     torch = gu.torch_cuda()
     T, C_ = fl.shape
-    d_out = _guarded(T * C_ * n * 2, 0xA5)
-    d_lo = _guarded(T * C_ * 2, 0x5A) if outs else None
-    d_st = _guarded(T * C_ * 16, 0x3C) if outs else None
+    fo, fl_, fs = (0xA5, 0x5A, 0x3C) if fill is None else (fill,) * 3
+    d_out = _guarded(T * C_ * n * 2, fo)
+    d_lo = _guarded(T * C_ * 2, fl_) if outs else None
+    d_st = _guarded(T * C_ * 16, fs) if outs else None
     kw = dict(pcm=gu.to_dev(inp.pcm)) if inp.pcm is not None else dict(payload=gu.to_dev(inp.payload), codec=gu.to_dev(inp.codec))
-    ctx.plc_conceal(gu.to_dev(fl), dev.state, d_out, C_, T, n, length=gu.to_dev(np.asarray(ln, "<u2")) if with_len else None, len_out=d_lo,
-                    stats=d_st, stream=stream, **kw)
+    (ctx.via(entry) if entry else ctx).plc_conceal(gu.to_dev(fl), dev.state, d_out, C_, T, n,
+                                                   length=gu.to_dev(np.asarray(ln, "<u2")) if with_len else None, len_out=d_lo, stats=d_st,
+                                                   stream=stream, **kw)
     if stream is None:
         torch.cuda.synchronize()
     else:
         ctx.sync(stream)
-    out = _take(d_out, T * C_ * n * 2, 0xA5, "out").view("<i2").reshape(T, C_, n)
-    lo = _take(d_lo, T * C_ * 2, 0x5A, "len_out").view("<u2").reshape(T, C_) if outs else None
-    st = _take(d_st, T * C_ * 16, 0x3C, "stats").view(capi.FRAME_STATS).reshape(T, C_) if outs else None
+    out = _take(d_out, T * C_ * n * 2, fo, "out").view("<i2").reshape(T, C_, n)
+    lo = _take(d_lo, T * C_ * 2, fl_, "len_out").view("<u2").reshape(T, C_) if outs else None
+    st = _take(d_st, T * C_ * 16, fs, "stats").view(capi.FRAME_STATS).reshape(T, C_) if outs else None
+    if raw is not None:
+        raw.update({k: t.cpu().numpy() for k, t in (("out", d_out), ("len_out", d_lo), ("stats", d_st)) if t is not None})
     return out, lo, st
 
 
@@ -348,3 +354,57 @@ def test_full_size_lossy_sample_vs_model(ctx, orc):
     assert (est["flags"] & pm.FLAG_CONCEALED).any()
     del pl, out, stats
     torch.cuda.empty_cache()
+
+
+# ---- the compute-free yardstick (igdsp_internal_plc_copy, tools/plc_bench.py) against its promise in csrc/igdsp_capi.hip: "the same
+# traversal with every tick taken as PLAIN: the input bits widened to the output, no decode, pitch search, synthesis or stats (the
+# records carry only the length); the state's ring and scalars are written"
+
+def _valid_state(rng, C_):
+    st = garbage_state(rng, C_)
+    st["head"], st["pitch"] = rng.integers(0, capi.PLC_HIST, C_), rng.integers(capi.PLC_PMIN, capi.PLC_PMAX + 1, C_)
+    st["pos"], st["missing"] = st["pitch"] // 2, 0
+    return st
+
+
+@pytest.mark.parametrize("T", [3, 131])
+@pytest.mark.parametrize("form", ["mix", "pcm"])
+def test_yardstick_footprint_values_independence(ctx, form, T):
+    """igdsp_internal_plc_copy, channel counts around the wave's, one part and two, every n of (160, 24, 13): on all-PLAIN tick flags
+    it stores the bytes igdsp_plc_conceal stores in the rows, lengths and records; lossy flags and short lengths give the same bytes
+    (every tick is taken as PLAIN); a row is the input code byte zero-extended or the input sample, a record that of n zeros, and the
+    state's ring ends with the last 280 widened input samples behind the advanced head, the other scalars as they were"""
+    from tests import record_model
+
+    for n in (160, 24, 13):
+        for C_ in (1, 15, 17, 65):
+            rng = np.random.default_rng(700 + n + C_ + T)
+            inp = Inputs(rng, T, C_, n, form)
+            plain, full = np.full((T, C_), pm.PLAYED, np.uint8), np.full((T, C_), n, np.uint16)
+            init = _valid_state(rng, C_)
+            got = {}
+
+            def launch(entry):
+                def run(fill):
+                    raw, dev = {}, Dev(C_, init)
+                    got[entry, fill] = run_plc(ctx, dev, plain, full, inp, n, entry=entry, fill=fill, raw=raw), dev.host()
+                    return raw
+                return run
+
+            yard, real = gu.written_mask(launch("plc_copy")), gu.written_mask(launch(None))
+            assert all(real[k][:-GUARD].all() for k in real)
+            gu.assert_same_footprint(yard, real)
+            wide = inp.pcm if inp.pcm is not None else inp.payload.astype(np.int16)
+            fl, ln = ticks(rng, T, C_, n, loss=0.3)
+            dev = Dev(C_, init)
+            lossy = run_plc(ctx, dev, fl, ln, inp, n, entry="plc_copy"), dev.host()
+            exp_st = init.copy()
+            x = wide.transpose(1, 0, 2).reshape(C_, T * n)
+            for k in range(max(0, T * n - capi.PLC_HIST), T * n):
+                exp_st["hist"][np.arange(C_), (init["head"].astype(np.int64) + k) % capi.PLC_HIST] = x[:, k]
+            exp_st["head"] = (init["head"].astype(np.int64) + T * n) % capi.PLC_HIST
+            for (out, lo, st), state in (got["plc_copy", gu.FILL_A], got["plc_copy", gu.FILL_B], lossy):
+                np.testing.assert_array_equal(out, wide)
+                assert (lo == n).all()
+                gu.assert_stats_equal(st, record_model.records(np.zeros((T, C_, n), np.int64)))
+                assert state.tobytes() == exp_st.tobytes(), [k for k in capi.PLC_STATE.names if not np.array_equal(state[k], exp_st[k])]

@@ -55,25 +55,27 @@ class Guarded:
 
 
 def run_ptt(ctx, info, ptr, mem, C_, G_, n, state, slots, payload=None, codec=None, pcm=None, length=None, gain=None, rxonly=None, rf=0,
-            sel=True, tick=True, ctl=True, out=True, stats=True, stream=None):
+            sel=True, tick=True, ctl=True, out=True, stats=True, stream=None, entry=None, fill=None, raw=None):
     """igdsp_ptt_arbitrate through the C ABI with guard bytes around every output, the state and the slots; returns (sel, tick, ctl, out,
-    stats, state, slots) (None where not asked for)"""
+    stats, state, slots) (None where not asked for).  entry: through that yardstick of capi.INTERNAL_TWIN instead; fill: the byte every
+    output and its guards hold before the launch; raw: a dict that takes the output buffers' bytes, guards included, after it."""
     torch = gu.torch_cuda()
     F_, nm = info.shape[0], len(mem)
     audio = payload is not None or pcm is not None
-    b_sel = Guarded(F_ * G_ * 4, 0x3C) if sel else None
-    b_tick = Guarded(F_ * G_ * 8, 0x4D) if tick else None
-    b_ctl = Guarded(F_ * G_, 0x2B) if ctl else None
-    b_out = Guarded(F_ * G_ * n * 2, 0xA5) if out and audio else None
-    b_st = Guarded(F_ * G_ * 16, 0x5A) if stats and audio else None
+    f5 = (0x3C, 0x4D, 0x2B, 0xA5, 0x5A) if fill is None else (fill,) * 5
+    b_sel = Guarded(F_ * G_ * 4, f5[0]) if sel else None
+    b_tick = Guarded(F_ * G_ * 8, f5[1]) if tick else None
+    b_ctl = Guarded(F_ * G_, f5[2]) if ctl else None
+    b_out = Guarded(F_ * G_ * n * 2, f5[3]) if out and audio else None
+    b_st = Guarded(F_ * G_ * 16, f5[4]) if stats and audio else None
     b_state = Guarded(G_ * 16, 0x77, state)
     b_slots = Guarded(nm * 8, 0x66, slots)
     keep = [_dev(x) if x is not None else None for x in (info, ptr, mem if nm else None, payload, codec, pcm, length, gain, rxonly)]
     d_info, d_ptr, d_mem, d_pl, d_cd, d_pcm, d_len, d_gain, d_rx = keep
     p = lambda b: b.ptr if b is not None else None                  # noqa: E731
-    ctx.ptt_arbitrate(d_info, d_ptr, d_mem, nm, b_state.ptr, b_slots.ptr if nm else None, C_, G_, F_, n, payload=d_pl, codec=d_cd, pcm=d_pcm,
-                      length=d_len, gain=d_gain, rxonly=d_rx, release_frames=rf, sel=p(b_sel), tick=p(b_tick), ctl_out=p(b_ctl), out=p(b_out),
-                      stats=p(b_st), stream=stream)
+    (ctx.via(entry) if entry else ctx).ptt_arbitrate(
+        d_info, d_ptr, d_mem, nm, b_state.ptr, b_slots.ptr if nm else None, C_, G_, F_, n, payload=d_pl, codec=d_cd, pcm=d_pcm, length=d_len,
+        gain=d_gain, rxonly=d_rx, release_frames=rf, sel=p(b_sel), tick=p(b_tick), ctl_out=p(b_ctl), out=p(b_out), stats=p(b_st), stream=stream)
     if stream is None:
         torch.cuda.synchronize()
     else:
@@ -85,6 +87,9 @@ def run_ptt(ctx, info, ptr, mem, C_, G_, n, state, slots, payload=None, codec=No
     r = b_st.take("d_stats").view(capi.FRAME_STATS).reshape(F_, G_) if b_st is not None else None
     st = b_state.take("d_state").view(capi.PTT_STATE)
     sl = b_slots.take("d_slots").view(capi.PTT_SLOT)
+    if raw is not None:
+        raw.update({k: b.t.cpu().numpy() for k, b in (("sel", b_sel), ("tick", b_tick), ("ctl_out", b_ctl), ("out", b_out), ("stats", b_st))
+                    if b is not None})
     return s, t, c, o, r, st, sl
 
 
@@ -471,3 +476,90 @@ def test_arguments(ctx):
     with pytest.raises(capi.IgdspError):
         ctx.ptt_arbitrate(info, ptr, mem, 8, None, slots, C_, G_, F_, n)
     torch.cuda.synchronize()
+
+
+# ---- the compute-free yardstick (igdsp_internal_ptt_copy, tools/ptt_bench.py) against its promise in csrc/igdsp_capi.hip: "the same
+# traversal (info records, ops passes, the first member of every group emitted undecoded), the same bytes in and out, no debounce,
+# arbitration, decode or records; the group state is not touched, the slots are stepped as by a launch, and sel / out / stats hold raw
+# bytes (tick and ctl_out are not written)"
+
+def _yard_inputs(rng, form, F_, C_, n):
+    if form == "g711":
+        return dict(payload=rng.integers(0, 256, (F_, C_, n), dtype=np.uint8), codec=np.where(rng.random(C_) < 0.5, 8, 0).astype(np.uint8))
+    return dict(pcm=rng.integers(-32768, 32768, (F_, C_, n)).astype(np.int16)) if form == "pcm" else {}
+
+
+def _yard_table(rng, C_, G_, wide=False):
+    """groups of 1 .. 6 members; wide: one of 70 (more than the 64 slots of an ops window: two passes)"""
+    sizes = rng.integers(1, 7, G_)
+    if wide:
+        sizes[G_ // 2] = 70
+    ptr = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint32)
+    return ptr, rng.integers(0, C_, int(ptr[-1])).astype(np.uint32)
+
+
+@pytest.mark.parametrize("form", ["g711", "pcm", "none"])
+@pytest.mark.parametrize("F_", [3, 131])
+def test_yardstick_footprint_and_independence(ctx, form, F_):
+    """igdsp_internal_ptt_copy, group counts around a wave's (G = 17 with a group of 70 slots: two passes), one part and two, the three
+    input forms: it stores the bytes igdsp_ptt_arbitrate stores in sel, out and stats, nothing in d_tick and d_ctl_out, leaves the slots
+    as the entry does and the group state as it was; whether that holds zeros or garbage, the outputs are the same bytes"""
+    rng = np.random.default_rng(840 + F_ + len(form))
+    C_, n = 48, 160
+    for G_ in (1, 15, 17, 65):
+        info = random_info(rng, F_, C_)
+        ptr, mem = _yard_table(rng, C_, G_, wide=G_ == 17)
+        kw = _yard_inputs(rng, form, F_, C_, n)
+        _, sl0 = garbage(rng, G_, len(mem))
+        got = {}
+
+        def launch(entry):
+            def run(fill):
+                raw = {}
+                st0 = np.full(G_ * 16, fill, np.uint8).view(capi.PTT_STATE) if entry else np.zeros(G_, capi.PTT_STATE)
+                got[entry, fill] = run_ptt(ctx, info, ptr, mem, C_, G_, n, st0, sl0, entry=entry, fill=fill, raw=raw, **kw)
+                return raw
+            return run
+
+        yard, real = gu.written_mask(launch("ptt_copy")), gu.written_mask(launch(None))
+        assert all(real[k][GUARD:-GUARD].all() for k in real if k in ("sel", "out", "stats"))
+        gu.assert_same_footprint(yard, real, not_written=("tick", "ctl_out"))
+        zero = run_ptt(ctx, info, ptr, mem, C_, G_, n, np.zeros(G_, capi.PTT_STATE), sl0, entry="ptt_copy", fill=gu.FILL_A, **kw)
+        a, b = got["ptt_copy", gu.FILL_A], got["ptt_copy", gu.FILL_B]
+        assert (a[5].view(np.uint8) == gu.FILL_A).all() and (b[5].view(np.uint8) == gu.FILL_B).all() and not zero[5].view(np.uint8).any()
+        for x in (b, zero):
+            assert all(p is None or p.tobytes() == q.tobytes() for p, q in zip((x[0], x[3], x[4]), (a[0], a[3], a[4])))
+            assert x[6].tobytes() == got[None, gu.FILL_A][6].tobytes()                                            # the slots as the entry's
+        np.testing.assert_array_equal(a[0], np.broadcast_to(mem[ptr[:-1]].astype(np.int64), (F_, G_)))           # sel: the first member
+
+
+@pytest.mark.parametrize("form", ["g711", "pcm"])
+def test_yardstick_reads_the_first_members_rows(ctx, form):
+    """one channel's whole row of one frame replaced by fresh random bytes: out (and the raw bytes in the record) of exactly the groups
+    whose first member it is change, in that frame; every other output byte is the same.  One d_info record replaced: every output
+    byte is the same and the launch completes — the promise says the records are read, but nothing the yardstick stores in sel, out or
+    stats depends on them (the kernel keeps the loads alive through a fold it compares with a constant), and a load that was dropped
+    cannot be seen from outside, so this is as far as a test can go."""
+    rng = np.random.default_rng(860 + len(form))
+    C_, G_, F_, n, f = 48, 65, 3, 160, 1
+    info = random_info(rng, F_, C_)
+    ptr, mem = _yard_table(rng, C_, G_, wide=True)
+    kw = _yard_inputs(rng, form, F_, C_, n)
+    st0, sl0 = np.zeros(G_, capi.PTT_STATE), np.zeros(len(mem), capi.PTT_SLOT)
+    c = int(mem[ptr[G_ // 2]])                                             # the wide group's first member
+    consumers = [g for g in range(G_) if mem[ptr[g]] == c]
+    base = run_ptt(ctx, info, ptr, mem, C_, G_, n, st0, sl0, entry="ptt_copy", **kw)
+    key = "payload" if form == "g711" else "pcm"
+    rows = kw[key].copy()
+    rows[f, c] = rng.integers(0, 256, n, dtype=np.uint8) if form == "g711" else rng.integers(-32768, 32768, n).astype(np.int16)
+    got = run_ptt(ctx, info, ptr, mem, C_, G_, n, st0, sl0, entry="ptt_copy", **{**kw, key: rows})
+    want = np.zeros((F_, G_), bool)
+    want[f, consumers] = True
+    np.testing.assert_array_equal((got[3] != base[3]).any(axis=2), want)
+    rec = lambda r: np.ascontiguousarray(r).view(np.uint8).reshape(F_, G_, 16)   # noqa: E731
+    assert got[0].tobytes() == base[0].tobytes() and not (rec(got[4]) != rec(base[4])).any(axis=2)[~want].any()
+    info2 = info.copy()
+    info2[f, c] = random_info(rng, 1, 1)[0, 0]
+    info2["ed137"][f, c] ^= 0x5A5A5A5A
+    got = run_ptt(ctx, info2, ptr, mem, C_, G_, n, st0, sl0, entry="ptt_copy", **kw)
+    assert all(p.tobytes() == q.tobytes() for p, q in zip((got[0], got[3], got[4]), (base[0], base[3], base[4])))

@@ -37,8 +37,10 @@ def strided(rows, stride):
     return buf
 
 
-def run_rs(ctx, direction, R, layout, rows, n, codec=None, length=None, hist=None, rn=0, rw=0, off=0, out=True, stats=True, d_state=None):
-    """One launch through the C ABI.  rows: the input as laid out ([F][C][n] int16 or G.711 uint8 for UP; the wide side for DOWN).  The
+def run_rs(ctx, direction, R, layout, rows, n, codec=None, length=None, hist=None, rn=0, rw=0, off=0, out=True, stats=True, d_state=None,
+           entry=None, fill=0xEE, raw=None):
+    """One launch through the C ABI (entry: through that yardstick of capi.INTERNAL_TWIN instead; fill: the byte the outputs and their
+    surroundings hold before the launch; raw: a dict that takes the whole output buffers' bytes after it).  rows: the input as laid out ([F][C][n] int16 or G.711 uint8 for UP; the wide side for DOWN).  The
     input rows, d_len and the output sit in strided buffers whose foreign rows and surroundings hold 0xEE, the input and the output
     `off` bytes behind a 256-byte aligned base.  Returns (out as laid out [frames][C][len] | None, stats | None, state [C], the state
     tensor)."""
@@ -61,24 +63,26 @@ def run_rs(ctx, direction, R, layout, rows, n, codec=None, length=None, hist=Non
         st["flags"], st["frames"] = 0xA5, 0xFFFFFFFE
         d_state = gu.to_dev(st)
     nb = fr_out * s_out * len_out * 2
-    d_out = gu.dev_zeros(nb + 64 + GUARD, 0xEE) if out else None
-    d_st = gu.dev_zeros(fr_out * C_ * 16 + GUARD, 0xEE) if stats else None
+    d_out = gu.dev_zeros(nb + 64 + GUARD, fill) if out else None
+    d_st = gu.dev_zeros(fr_out * C_ * 16 + GUARD, fill) if stats else None
     assert d_in.data_ptr() % 256 == 0 and (d_out is None or d_out.data_ptr() % 256 == 0)
-    ctx.resample(direction, R, d_state, C_, F_, n, layout=layout, payload=d_in.data_ptr() + off if g711 else None, codec=d_codec,
+    (ctx.via(entry) if entry else ctx).resample(direction, R, d_state, C_, F_, n, layout=layout, payload=d_in.data_ptr() + off if g711 else None, codec=d_codec,
                  pcm=None if g711 else d_in.data_ptr() + off, length=d_len, rows_narrow=rn, rows_wide=rw,
                  out=d_out.data_ptr() + off if out else None, stats=d_st)
     torch.cuda.synchronize()
     o = s = None
     if out:
-        raw = d_out.cpu().numpy()
-        assert np.all(raw[:off] == 0xEE) and np.all(raw[off + nb:] == 0xEE), "bytes around the rows written"
-        o = raw[off:off + nb].copy().view("<i2").reshape(fr_out, s_out, len_out)
-        assert np.all(o[:, C_:].view(np.uint16) == 0xEEEE), "rows outside [0, C) written"
+        b = d_out.cpu().numpy()
+        assert np.all(b[:off] == fill) and np.all(b[off + nb:] == fill), "bytes around the rows written"
+        o = b[off:off + nb].copy().view("<i2").reshape(fr_out, s_out, len_out)
+        assert np.all(o[:, C_:].view(np.uint8) == fill), "rows outside [0, C) written"
         o = o[:, :C_]
     if stats:
-        raw = d_st.cpu().numpy()
-        assert np.all(raw[fr_out * C_ * 16:] == 0xEE), "bytes after d_stats written"
-        s = raw[:fr_out * C_ * 16].view(capi.FRAME_STATS).reshape(fr_out, C_)
+        b = d_st.cpu().numpy()
+        assert np.all(b[fr_out * C_ * 16:] == fill), "bytes after d_stats written"
+        s = b[:fr_out * C_ * 16].view(capi.FRAME_STATS).reshape(fr_out, C_)
+    if raw is not None:
+        raw.update({k: t.cpu().numpy() for k, t in (("out", d_out), ("stats", d_st), ("state", d_state)) if t is not None})
     return o, s, d_state.cpu().numpy().view(capi.RS_STATE), d_state
 
 
@@ -309,3 +313,144 @@ def test_up_beside_a_16k_tone_into_conf_mix(ctx):
     s = d_st.cpu().numpy().view(capi.FRAME_STATS).reshape(2, 7)
     for k in ("sumsq", "peak", "flags"):
         np.testing.assert_array_equal(s[k], es[k], err_msg=k)
+
+
+# ---- the compute-free yardstick (igdsp_internal_rs_copy, tools/rs_bench.py) against its promise: csrc/igdsp_capi_rs.hip and the head
+# of csrc/igdsp_k_rs.hip.  "The same items, loads, tile traffic and stores, an xor in place of the filter, zero records; d_out is
+# required, the state is neither read nor written."
+
+def rs_chunk_frames(direction, R, C_, F_, cus, blocks=None):
+    """rs_route's frames per chunk (csrc/igdsp_route.h), restated: a wave keeps its channels for this many frames"""
+    up = direction == rm.UP
+    ch, u = (16, 1) if up else (4, R)
+    lds = 4 * ch * ((24 * u + 256 * u) * 2 + R * 16) + (1024 if up else 0)
+    per_cu = blocks if blocks is not None and 1 <= blocks <= 8 else min(3, 163840 // (lds + 16))
+    want, groups = max(1, cus) * per_cu * 4 * 4, -(-C_ // ch)
+    cuts = 1 if groups >= want else min(F_, -(-want // groups))
+    return -(-F_ // cuts)
+
+
+def rs_copy_model(direction, R, layout, rows, n, length=None, codec=None, chunk_frames=1, vec=True):
+    """What the yardstick stores, from the input rows as laid out.  Per channel and frame the tile holds the 24 (UP) / 24 R (DOWN)
+    samples ahead of the frame, the frame's samples and zeros up to the last unit's end; unit q folds the 32 (32 R) tile samples from
+    8 q (8 R q) on: x[d & 3] ^= E[d] over its dwords, i.e. output sample i of the unit is the xor of the tile samples i, i + 8, ...; UP
+    stores the eight samples R times.  The samples ahead of a chunk's first frame are the earlier rows' (decoded, cut at d_len; zeros
+    ahead of the launch), those ahead of a later frame are the tile's own tail.  A G.711 row in the vector form is not decoded: its 8
+    code bytes are stored as 4 samples, twice."""
+    up = direction == rm.UP
+    u = 1 if up else R
+    SI = R if (not up and layout == rm.SUBFRAMES) else 1
+    fr_in, C_, LI = rows.shape
+    F_, n_in, HIST, pieces, g711 = fr_in // SI, n * u, 24 * u, (n + 7) // 8, rows.dtype == np.uint8
+    valid = np.arange(LI)[None, None, :] < (np.full(rows.shape[:2], LI) if length is None else np.asarray(length))[:, :, None]
+    D = W = np.where(valid, rm.decode(rows, codec) if g711 else rows.astype(np.int64), 0)
+    if g711 and vec:
+        b = rows.astype(np.int64)
+        w = (b[..., 0::2] | b[..., 1::2] << 8).reshape(fr_in, C_, LI // 8, 4)
+        W = np.where(valid, np.concatenate([w, w], axis=-1).reshape(fr_in, C_, LI), 0)
+    stream = lambda x: (x.reshape(F_, SI, C_, LI).transpose(0, 2, 1, 3).reshape(F_, C_, n_in) & 0xFFFF).astype(np.uint16)   # noqa: E731
+    D, W = stream(D), stream(W)
+    n_rep = R if up else 1
+    y = np.zeros((F_, C_, pieces * 8 * n_rep), np.uint16)
+    tile = None
+    for f in range(F_):
+        if f % chunk_frames == 0:
+            ahead = np.concatenate([np.zeros((C_, HIST), np.uint16)] + [D[g] for g in range(max(0, f - HIST), f)], axis=1)[:, -HIST:]
+        else:
+            ahead = tile[:, n_in:n_in + HIST]
+        tile = np.concatenate([ahead, W[f], np.zeros((C_, pieces * 8 * u - n_in), np.uint16)], axis=1)
+        for q in range(pieces):
+            fold = np.bitwise_xor.reduce(tile[:, q * 8 * u:q * 8 * u + 32 * u].reshape(C_, 4 * u, 8), axis=1)
+            y[f, :, q * 8 * n_rep:(q + 1) * 8 * n_rep] = np.tile(fold, (1, n_rep))
+    n_out = n * R if up else n
+    SO = R if (up and layout == rm.SUBFRAMES) else 1
+    y = np.ascontiguousarray(y[:, :, :n_out]).view(np.int16)
+    return y.reshape(F_, C_, SO, n_out // SO).transpose(0, 2, 1, 3).reshape(F_ * SO, C_, n_out // SO)
+
+
+def yardstick_case(ctx, rng, direction, R, layout, C_, F_, n, g711=False, with_len=False, chunk_frames=1, **kw):
+    """footprint, values and independence of one yardstick launch"""
+    rows, _, codec = make_input(rng, direction, R, layout, C_, F_, n, g711)
+    length = None
+    if with_len:
+        length = rng.integers(0, rows.shape[2] + 40, rows.shape[:2])
+        length[rng.random(rows.shape[:2]) < 0.2] = 0
+    got = {}
+
+    def yard(fill):                                                       # the state holds the fill: garbage the yardstick must not read
+        raw = {}
+        got[fill] = run_rs(ctx, direction, R, layout, rows, n, codec=codec, length=length, d_state=gu.dev_zeros(C_ * 296, fill), entry="rs_copy",
+                           fill=fill, raw=raw, **kw)[:2]
+        return raw
+
+    def real(fill):
+        raw = {}
+        run_rs(ctx, direction, R, layout, rows, n, codec=codec, length=length, fill=fill, raw=raw, **kw)
+        return {k: raw[k] for k in ("out", "stats")}
+
+    ym = gu.written_mask(yard)
+    gu.assert_same_footprint(ym, gu.written_mask(real), not_written=("state",))       # (a) rows and records as the entry's, no state
+    off = kw.get("off", 0)
+    vec = n % 8 == 0 and off % 16 == 0
+    exp = rs_copy_model(direction, R, layout, rows, n, length, codec, chunk_frames, vec)
+    for fill in (gu.FILL_A, gu.FILL_B):                                   # (c) the fold of the right tile dwords; zero records
+        np.testing.assert_array_equal(got[fill][0], exp)
+        assert not got[fill][1].tobytes().strip(b"\0")
+    o, s, st, _ = run_rs(ctx, direction, R, layout, rows, n, codec=codec, length=length, entry="rs_copy", **kw)   # (b) a zero state
+    np.testing.assert_array_equal(o, exp)
+    assert not s.tobytes().strip(b"\0") and not st["hist"].any() and (st["flags"] == 0xA5).all() and (st["frames"] == 0xFFFFFFFE).all()
+
+
+@pytest.mark.parametrize("R", rm.FACTORS)
+@pytest.mark.parametrize("direction", (rm.UP, rm.DOWN), ids=("up", "down"))
+def test_yardstick_footprint_values_independence(ctx, direction, R):
+    """igdsp_internal_rs_copy at F = 3, every n of (8, 25, 160) (25: the general form), both layouts and the channel counts around a
+    wave's and a block's: it stores the bytes igdsp_resample stores and none of the state (which holds garbage, other garbage, or
+    zeros: the rows are the same), the records are zero, and every output piece is the xor fold of its unit's tile dwords"""
+    rng = np.random.default_rng(80 + 10 * R + direction)
+    cus = ctx.device_info()["compute_units"]
+    for layout in (rm.ROWS, rm.SUBFRAMES):
+        for n in (8, 25, 160):
+            for C_ in ((1, 17, 65) if direction == rm.UP else (1, 5, 17)):
+                assert rs_chunk_frames(direction, R, C_, 3, cus) == 1
+                yardstick_case(ctx, rng, direction, R, layout, C_, 3, n)
+                if direction == rm.UP and C_ == 17:
+                    yardstick_case(ctx, rng, direction, R, layout, C_, 3, n, g711=True)
+        yardstick_case(ctx, rng, direction, R, layout, 17, 3, 160, off=2)                                   # a base 2 bytes off: the general form
+        yardstick_case(ctx, rng, direction, R, layout, 5, 3, 160, with_len=True, rn=7, rw=9)                # d_len and row strides
+        yardstick_case(ctx, rng, direction, R, layout, 5, 3, 25, with_len=True, rn=6, rw=5, off=2, g711=direction == rm.UP)
+
+
+@pytest.mark.parametrize("direction,R", [(rm.UP, 2), (rm.DOWN, 3)], ids=("up", "down"))
+def test_yardstick_wave_keeps_its_channels_for_two_frames(ctx, monkeypatch, direction, R):
+    """one block per CU in the grid and a sixth of the groups rs_route wants: the frames are cut into chunks of two, so from a chunk's
+    second frame on the samples ahead of the row are the tile's own tail, moved to its front"""
+    assert rs_chunk_frames(rm.UP, 2, 32805, 9, 256) == 2 and rs_chunk_frames(rm.DOWN, 2, 8229, 7, 256) == 2            # rows of the route
+    assert rs_chunk_frames(rm.UP, 6, 65536, 128, 256, 1) == 128 and rs_chunk_frames(rm.UP, 6, 65536, 128, 256, 2) == 64   # table
+    monkeypatch.setenv("IGDSP_RS_BLOCKS", "1")
+    cus, ch = ctx.device_info()["compute_units"], 16 if direction == rm.UP else 4
+    C_ = (cus * 16 // 6 + 1) * ch - 3
+    cf = rs_chunk_frames(direction, R, C_, 9, cus, 1)
+    assert cf >= 2, (cus, C_, cf)
+    yardstick_case(ctx, np.random.default_rng(90 + direction), direction, R, rm.ROWS, C_, 9, 8, chunk_frames=cf)
+
+
+def test_yardstick_argument_rules(ctx):
+    """igdsp_internal_rs_copy rejects what igdsp_resample rejects, and a NULL d_out, with nothing written"""
+    fn = capi.internal("rs_copy")
+    d_state, d_pcm = gu.dev_zeros(4 * 296 + 64, 0xEE), gu.dev_zeros(2 * 4 * 960 * 2 + 64)
+    d_out, d_st = gu.dev_zeros(2 * 4 * 960 * 2 + 64, 0xEE), gu.dev_zeros(2 * 4 * 6 * 16, 0xEE)
+    stt, pcm, out, st = (t.data_ptr() for t in (d_state, d_pcm, d_out, d_st))
+
+    def call(direction=0, R=2, layout=0, pcm_=pcm, state=stt, C_=4, F_=2, n=160, out_=out, st_=st, h=ctx.h):
+        return fn(h, direction, R, layout, None, None, pcm_, None, state, C_, F_, n, 0, 0, out_, st_, None)
+
+    for kw in (dict(h=None), dict(direction=2), dict(R=5), dict(layout=2), dict(pcm_=None), dict(state=None), dict(n=257), dict(out_=out + 1),
+               dict(out_=pcm), dict(out_=None)):
+        assert call(**kw) == EINVAL, kw
+    gu.torch_cuda().cuda.synchronize()
+    assert (d_out.cpu().numpy() == 0xEE).all() and (d_st.cpu().numpy() == 0xEE).all() and (d_state.cpu().numpy() == 0xEE).all()
+    assert call() == 0
+    gu.torch_cuda().cuda.synchronize()
+    rec = d_st.cpu().numpy()
+    assert (d_state.cpu().numpy() == 0xEE).all() and not rec[:2 * 4 * 16].any() and (rec[2 * 4 * 16:] == 0xEE).all()

@@ -41,17 +41,21 @@ def make_pcm(rng, F_, rows, n):
     return pcm
 
 
-def run_snd(ctx, direction, src, D_, K_, F_, n, bulk=True, stats=True, in_off=0, out_off=0, stream=None):
+def run_snd(ctx, direction, src, D_, K_, F_, n, bulk=True, stats=True, in_off=0, out_off=0, stream=None, entry=None, fill=None, raw=None):
     """One direction through the C ABI with guard bytes behind both outputs and the buffers offset by in_off / out_off bytes from a
-    256-byte aligned base.  src: the input as int16 (any shape).  Returns (bulk int16 flat | None, stats [F][D * K] | None)."""
+    256-byte aligned base.  src: the input as int16 (any shape).  Returns (bulk int16 flat | None, stats [F][D * K] | None).  entry:
+    through that yardstick of capi.INTERNAL_TWIN instead; fill: the byte both outputs and their surroundings hold before the launch;
+    raw: a dict that takes the whole output buffers' bytes after it."""
     torch = gu.torch_cuda()
     nb = F_ * D_ * K_ * n * 2
+    fb, fs = (0xA5, 0x5A) if fill is None else (fill, fill)
     d_in = gu.dev_zeros(nb + 64)
     d_in[in_off:in_off + nb] = gu.to_dev(src)
-    d_out = gu.dev_zeros(nb + 64 + GUARD, 0xA5) if bulk else None
-    d_st = gu.dev_zeros(F_ * D_ * K_ * 16 + GUARD, 0x5A) if stats else None
+    d_out = gu.dev_zeros(nb + 64 + GUARD, fb) if bulk else None
+    d_st = gu.dev_zeros(F_ * D_ * K_ * 16 + GUARD, fs) if stats else None
     assert d_in.data_ptr() % 256 == 0 and (d_out is None or d_out.data_ptr() % 256 == 0)
-    fn = ctx.snd_combine if direction == "combine" else ctx.snd_split
+    c = ctx.via(entry) if entry else ctx
+    fn = c.snd_combine if direction == "combine" else c.snd_split
     kw = {("frames" if direction == "combine" else "pcm"): (d_out.data_ptr() + out_off if bulk else None)}
     fn(d_in.data_ptr() + in_off, D_, K_, F_, n, stats=d_st, stream=stream, **kw)
     if stream is None:
@@ -60,13 +64,15 @@ def run_snd(ctx, direction, src, D_, K_, F_, n, bulk=True, stats=True, in_off=0,
         ctx.sync(stream)
     o = s = None
     if bulk:
-        raw = d_out.cpu().numpy()
-        assert np.all(raw[:out_off] == 0xA5) and np.all(raw[out_off + nb:] == 0xA5), "bytes around the bulk output written"
-        o = raw[out_off:out_off + nb].copy().view("<i2")
+        b = d_out.cpu().numpy()
+        assert np.all(b[:out_off] == fb) and np.all(b[out_off + nb:] == fb), "bytes around the bulk output written"
+        o = b[out_off:out_off + nb].copy().view("<i2")
     if stats:
-        raw = d_st.cpu().numpy()
-        assert np.all(raw[F_ * D_ * K_ * 16:] == 0x5A), "guard bytes after d_stats written"
-        s = raw[:F_ * D_ * K_ * 16].view(capi.FRAME_STATS).reshape(F_, D_ * K_)
+        b = d_st.cpu().numpy()
+        assert np.all(b[F_ * D_ * K_ * 16:] == fs), "guard bytes after d_stats written"
+        s = b[:F_ * D_ * K_ * 16].view(capi.FRAME_STATS).reshape(F_, D_ * K_)
+    if raw is not None:
+        raw.update({k: t.cpu().numpy() for k, t in (("bulk", d_out), ("stats", d_st)) if t is not None})
     return o, s
 
 
@@ -293,16 +299,22 @@ ARG_ROWS = [
 ]
 
 
-@pytest.mark.parametrize("entry", ["igdsp_snd_combine", "igdsp_snd_split"])
+@pytest.mark.parametrize("entry", ["igdsp_snd_combine", "igdsp_snd_split", "igdsp_internal_snd_copy"])
 def test_argument_clauses(ctx, entry):
+    """(the yardstick takes igdsp_snd_combine's rule and name, and also rejects a NULL bulk output)"""
+    if entry == "igdsp_internal_snd_copy":
+        return _argument_clauses(ctx, capi.internal(entry), "igdsp_snd_combine", [(o, -22 if o == dict(bulk=None) else c, t) for o, c, t in ARG_ROWS])
+    return _argument_clauses(ctx, getattr(ctx.L, entry), entry, ARG_ROWS)
+
+
+def _argument_clauses(ctx, fn, entry, rows):
     torch = gu.torch_cuda()
     L = ctx.L
     D_, K_, F_, n = 3, 6, 2, 160
     nb = F_ * D_ * K_ * n * 2
     src = gu.dev_zeros(nb + 64, 1)
     out, st = gu.dev_zeros(nb + 64, 0xA5), gu.dev_zeros(F_ * D_ * K_ * 16 + 64, 0x5A)
-    fn = getattr(L, entry)
-    for over, code, text in ARG_ROWS:
+    for over, code, text in rows:
         a = dict(ctx=ctx.h, src=src.data_ptr(), bulk=out.data_ptr(), st=st.data_ptr(), D=D_, K=K_, F=F_, n=n, src_off=0, bulk_off=0, st_off=0, alias=False)
         a.update(over)
         p_src = a["src"] + a["src_off"] if a["src"] else None
@@ -331,3 +343,39 @@ def test_snd_vu_of_device_records(ctx):
         vu = capi.snd_vu(rec)
         p, db = sm.snd_vu(rec["rms"])
         assert vu["percent"] == p and abs(vu["db"] - db) <= 1e-9
+
+
+# ---- the compute-free yardstick (igdsp_internal_snd_copy, tools/snd_bench.py) against its promise in csrc/igdsp_capi_snd.hip: "the
+# same items, the same bytes read and written in memory order, no transpose and no records; d_out is required and d_stats is not
+# written"
+
+@pytest.mark.parametrize("K_", KS)
+@pytest.mark.parametrize("direction", ["combine", "split"])
+def test_yardstick_footprint_and_values(ctx, direction, K_):
+    """igdsp_internal_snd_copy with the arguments of either direction, D x F = 1, 31, 33, 65 items (a block takes 32), n of the vector
+    form, its tail and (K n odd) the general form: it stores the bulk bytes the direction stores, none of d_stats, and the bulk output is
+    the input, byte for byte"""
+    rng = np.random.default_rng(300 + K_)
+    for D_, F_ in ((1, 1), (31, 1), (11, 3), (65, 1)):
+        for n in (160, 164, 3):
+            src = make_pcm(rng, F_, D_ * K_, n)
+            got = {}
+
+            def yard(fill):
+                raw = {}
+                got[fill] = run_snd(ctx, direction, src, D_, K_, F_, n, entry="snd_copy", fill=fill, raw=raw)
+                return raw
+
+            def real(fill):
+                raw = {}
+                run_snd(ctx, direction, src, D_, K_, F_, n, fill=fill, raw=raw)
+                return raw
+
+            gu.assert_same_footprint(gu.written_mask(yard), gu.written_mask(real), not_written=("stats",))
+            for fill in (gu.FILL_A, gu.FILL_B):
+                np.testing.assert_array_equal(got[fill][0], src.reshape(-1))
+    for in_off, out_off in ((2, 0), (0, 2), (8, 8)):                      # misaligned bases: the general form and the tail
+        src = make_pcm(rng, 2, 5 * K_, 160)
+        o, s = run_snd(ctx, direction, src, 5, K_, 2, 160, entry="snd_copy", in_off=in_off, out_off=out_off, fill=0xEE)
+        np.testing.assert_array_equal(o, src.reshape(-1))
+        assert (s.view(np.uint8) == 0xEE).all()

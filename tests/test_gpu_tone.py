@@ -34,10 +34,12 @@ def plan_array(plans):
     return np.array([tm.plan_record(p, capi.TONE_PLAN) for p in plans], capi.TONE_PLAN)
 
 
-def run_tone(ctx, plans, pos, flags, F_, n, plan_of=None, cmd=None, rpf=0, pcm=True, length=True, stats=True, off=0, d_state=None):
+def run_tone(ctx, plans, pos, flags, F_, n, plan_of=None, cmd=None, rpf=0, pcm=True, length=True, stats=True, off=0, d_state=None, entry=None,
+             fill=0xEE, raw=None):
     """One launch through the C ABI.  The rows and lengths sit in buffers filled with 0xEE (the canary of foreign rows and of the bytes
     around), the rows `off` bytes behind a 256-byte aligned base.  Returns (pcm [F][R][n] | None, len [F][R] | None, stats [F][P] | None,
-    state [P], the state tensor)."""
+    state [P], the state tensor).  entry: through that yardstick of capi.INTERNAL_TWIN instead; fill: another canary byte; raw: a dict
+    that takes the whole output buffers' bytes after the launch."""
     torch = gu.torch_cuda()
     P_ = len(pos)
     R_ = rpf or P_
@@ -48,26 +50,28 @@ def run_tone(ctx, plans, pos, flags, F_, n, plan_of=None, cmd=None, rpf=0, pcm=T
     d_of = gu.to_dev(np.asarray(plan_of, np.uint16)) if plan_of is not None else None
     d_cmd = gu.to_dev(np.asarray(cmd, np.uint8)) if cmd is not None else None
     nb = F_ * R_ * n * 2
-    d_pcm = gu.dev_zeros(nb + 64 + GUARD, 0xEE) if pcm else None
-    d_len = gu.dev_zeros(F_ * R_ * 2 + GUARD, 0xEE) if length else None
-    d_st = gu.dev_zeros(F_ * P_ * 16 + GUARD, 0xEE) if stats else None
+    d_pcm = gu.dev_zeros(nb + 64 + GUARD, fill) if pcm else None
+    d_len = gu.dev_zeros(F_ * R_ * 2 + GUARD, fill) if length else None
+    d_st = gu.dev_zeros(F_ * P_ * 16 + GUARD, fill) if stats else None
     assert d_pcm is None or d_pcm.data_ptr() % 256 == 0
-    ctx.tone_generate(d_plans, len(plans), d_state, P_, F_, n, plan_of=d_of, cmd=d_cmd, rows_per_frame=rpf,
-                      pcm=d_pcm.data_ptr() + off if pcm else None, length=d_len, stats=d_st)
+    (ctx.via(entry) if entry else ctx).tone_generate(d_plans, len(plans), d_state, P_, F_, n, plan_of=d_of, cmd=d_cmd, rows_per_frame=rpf,
+                                                     pcm=d_pcm.data_ptr() + off if pcm else None, length=d_len, stats=d_st)
     torch.cuda.synchronize()
     o = ln = s = None
     if pcm:
-        raw = d_pcm.cpu().numpy()
-        assert np.all(raw[:off] == 0xEE) and np.all(raw[off + nb:] == 0xEE), "bytes around the rows written"
-        o = raw[off:off + nb].copy().view("<i2").reshape(F_, R_, n)
+        b = d_pcm.cpu().numpy()
+        assert np.all(b[:off] == fill) and np.all(b[off + nb:] == fill), "bytes around the rows written"
+        o = b[off:off + nb].copy().view("<i2").reshape(F_, R_, n)
     if length:
-        raw = d_len.cpu().numpy()
-        assert np.all(raw[F_ * R_ * 2:] == 0xEE), "bytes after d_len written"
-        ln = raw[:F_ * R_ * 2].view("<u2").reshape(F_, R_)
+        b = d_len.cpu().numpy()
+        assert np.all(b[F_ * R_ * 2:] == fill), "bytes after d_len written"
+        ln = b[:F_ * R_ * 2].view("<u2").reshape(F_, R_)
     if stats:
-        raw = d_st.cpu().numpy()
-        assert np.all(raw[F_ * P_ * 16:] == 0xEE), "bytes after d_stats written"
-        s = raw[:F_ * P_ * 16].view(capi.FRAME_STATS).reshape(F_, P_)
+        b = d_st.cpu().numpy()
+        assert np.all(b[F_ * P_ * 16:] == fill), "bytes after d_stats written"
+        s = b[:F_ * P_ * 16].view(capi.FRAME_STATS).reshape(F_, P_)
+    if raw is not None:
+        raw.update({k: t.cpu().numpy() for k, t in (("pcm", d_pcm), ("len", d_len), ("stats", d_st), ("state", d_state)) if t is not None})
     return o, ln, s, d_state.cpu().numpy().view(capi.TONE_STATE), d_state
 
 
@@ -279,3 +283,61 @@ def test_ring_into_conf_mix(ctx):
     for k in ("sumsq", "peak", "flags"):
         np.testing.assert_array_equal(s[k], es[k], err_msg=k)
     assert s["flags"][0, 1] & cm.FLAG_SATURATED
+
+
+# ---- the compute-free yardstick (igdsp_internal_tone_fill, tools/tone_bench.py) against its promise in csrc/igdsp_capi_tone.hip: "the
+# same items in the same order, the same rows, lengths and records stored, no plan, no state, no oscillator; d_pcm is required, the
+# state is neither read nor written, the rows hold a pattern and the records are the len-0 record"
+
+@pytest.mark.parametrize("n", [1, 160, 255])
+def test_yardstick_footprint_values_independence(ctx, n):
+    """igdsp_internal_tone_fill at F = 3 with P = 1, 17, 65 ports, a row stride, a base 2 bytes off: it stores the bytes
+    igdsp_tone_generate stores in the rows, lengths and records (foreign rows and the surroundings stay), none of the state, which may
+    hold anything; the lengths are those of a launch whose ports all play, the records the len-0 record"""
+    from tests import record_model
+
+    rng = np.random.default_rng(400 + n)
+    for P_, kw in ((1, {}), (17, {}), (65, {}), (17, dict(rpf=23)), (5, dict(off=2)), (17, dict(rpf=19, off=2))):
+        pos, fl = spread(rng, RING, P_), np.full(P_, tm.PLAYING)
+        got = {}
+
+        def yard(fill):
+            raw = {}
+            got[fill] = run_tone(ctx, [RING], pos, fl, 3, n, d_state=gu.dev_zeros(P_ * 8, fill), entry="tone_fill", fill=fill, raw=raw, **kw)
+            return raw
+
+        def real(fill):
+            raw = {}
+            got["real", fill] = run_tone(ctx, [RING], pos, fl, 3, n, fill=fill, raw=raw, **kw)
+            return {k: v for k, v in raw.items() if k != "state"}
+
+        gu.assert_same_footprint(gu.written_mask(yard), gu.written_mask(real), not_written=("state",))
+        zero = run_tone(ctx, [RING], np.zeros(P_, np.int64), np.zeros(P_, np.int64), 3, n, entry="tone_fill", cmd=np.full(P_, 7, np.uint8), **kw)
+        empty = record_model.records(np.zeros((3, P_, n), np.int64), live=np.zeros((3, P_), bool))
+        for o, ln, st, _, _ in (got[gu.FILL_A], got[gu.FILL_B], zero):
+            np.testing.assert_array_equal(o[:, :P_], got[gu.FILL_A][0][:, :P_])
+            np.testing.assert_array_equal(ln[:, :P_], got["real", gu.FILL_A][1][:, :P_])
+            assert (ln[:, :P_] == n).all()
+            gu.assert_stats_equal(st, empty)
+            assert (st["rms"] == 0).all()
+        assert not zero[3].tobytes().strip(b"\0")
+
+
+def test_yardstick_argument_rules(ctx):
+    """igdsp_internal_tone_fill rejects what igdsp_tone_generate rejects, and a NULL d_pcm, with nothing written"""
+    fn = capi.internal("tone_fill")
+    d_plans, d_state = gu.to_dev(plan_array([EDGES])), gu.dev_zeros(64, 0xEE)
+    d_pcm, d_len, d_st = gu.dev_zeros(4 * 160 * 2 * 2 + 64, 0xEE), gu.dev_zeros(64, 0xEE), gu.dev_zeros(4 * 16 * 2, 0xEE)
+    pl, stt, pcm, ln, st = (t.data_ptr() for t in (d_plans, d_state, d_pcm, d_len, d_st))
+
+    def call(plans=pl, n_plans=1, state=stt, P_=4, F_=2, n=160, rpf=0, pcm_=pcm, len_=ln, st_=st, h=ctx.h):
+        return fn(h, plans, n_plans, None, None, state, P_, F_, n, rpf, pcm_, len_, st_, None)
+
+    for kw in (dict(h=None), dict(plans=None), dict(state=None), dict(n_plans=0), dict(rpf=3), dict(n=257), dict(pcm_=pcm + 1), dict(st_=st + 4),
+               dict(pcm_=stt), dict(pcm_=None), dict(pcm_=None, len_=None)):
+        assert call(**kw) == EINVAL, kw
+    gu.torch_cuda().cuda.synchronize()
+    assert all((t.cpu().numpy() == 0xEE).all() for t in (d_state, d_pcm, d_len, d_st))
+    assert call() == 0
+    gu.torch_cuda().cuda.synchronize()
+    assert (d_state.cpu().numpy() == 0xEE).all()

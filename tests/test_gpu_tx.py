@@ -237,3 +237,60 @@ def test_two_streams_disjoint_halves(orc):
             d.run(ctx, g711=d_g, ctl=d_ctl, t0=t0, f0=f, nf=1, c0=h, nc=h, stream=s2.cuda_stream)
         torch.cuda.synchronize()
         check(d.host(), exp, "two streams")
+
+
+# ---- the compute-free packet writer (igdsp_internal_tx_copy, tools/tx_bench.py --ab) against its promise in csrc/igdsp_capi.hip and
+# csrc/igdsp_k_tx.hip: "the same traversal and the same bytes moved as an all-audio igdsp_tx_packetize launch — every packet 20 + n bytes,
+# its payload read from the frame's input — no encoder (PCM: the low byte of each sample is stored) and no records"
+
+def run_tx_copy(ctx, C_, F_, n, stride, pcm=None, g711=None, fill=0xA5, guard=256):
+    """one launch; returns the packet buffer's bytes with `guard` bytes ahead of and behind the F * C slots"""
+    torch = torch_cuda()
+    d_pk = dev_zeros(F_ * C_ * stride + 2 * guard, fill)
+    d_in = to_dev(pcm if pcm is not None else g711)
+    assert d_pk.data_ptr() % 256 == 0 and d_in.data_ptr() % 256 == 0
+    rc = capi.internal("tx_copy")(ctx.h, d_in.data_ptr() if pcm is not None else None, d_in.data_ptr() if g711 is not None else None, C_, F_, n,
+                                  d_pk.data_ptr() + guard, stride, None)
+    assert rc == 0, rc
+    torch.cuda.synchronize()
+    return d_pk.cpu().numpy()
+
+
+@pytest.mark.parametrize("form", ["g711", "pcm"])
+@pytest.mark.parametrize("n", [4, 160, 236])
+def test_yardstick_packets(n, form):
+    """channels at and around a wave's 16 and a block's four groups, frames at and around a chunk's 8, the slot stride 256 and the
+    smallest multiple of 4 that holds a packet: the bytes stored are exactly [0, 20 + n) of every slot (nothing past a packet, nothing
+    around the buffer); the five header dwords are row * 0x9E3779B9 + o, the payload the G.711 bytes or the low byte of each sample"""
+    rng = np.random.default_rng(900 + n + len(form))
+    guard = 256
+    with capi.Context(device=0, max_channels=64) as ctx:
+        _yardstick_packets(ctx, rng, n, form, guard)
+
+
+def _yardstick_packets(ctx, rng, n, form, guard):
+    from tests import gpu_util as gu
+
+    for C_ in (15, 16, 17, 63, 64, 65):
+        for F_ in (7, 8, 9):
+            for stride in (256, (20 + n + 3) // 4 * 4):
+                pcm = rng.integers(-32768, 32768, (F_, C_, n)).astype(np.int16) if form == "pcm" else None
+                g711 = rng.integers(0, 256, (F_, C_, n), dtype=np.uint8) if form == "g711" else None
+                got = {}
+
+                def run(fill):
+                    got[fill] = run_tx_copy(ctx, C_, F_, n, stride, pcm, g711, fill, guard)
+                    return {"packets": got[fill]}
+
+                mask = gu.written_mask(run)["packets"]
+                assert not mask[:guard].any() and not mask[-guard:].any(), "bytes around the packets written"
+                mask = mask[guard:-guard].reshape(F_ * C_, stride)
+                assert mask[:, :20 + n].all(), "a packet byte was not stored"
+                assert not mask[:, 20 + n:].any(), "bytes past 20 + n of a slot written"
+                row = np.arange(F_ * C_, dtype=np.uint64)
+                hdr = ((row[:, None] * np.uint64(0x9E3779B9) + np.arange(5, dtype=np.uint64)[None, :]) & np.uint64(0xFFFFFFFF)).astype("<u4")
+                pay = (g711 if pcm is None else (pcm & 0xFF).astype(np.uint8)).reshape(F_ * C_, n)
+                for fill in (gu.FILL_A, gu.FILL_B):
+                    pk = got[fill][guard:-guard].reshape(F_ * C_, stride)
+                    np.testing.assert_array_equal(pk[:, :20].copy().view("<u4"), hdr)
+                    np.testing.assert_array_equal(pk[:, 20:20 + n], pay)

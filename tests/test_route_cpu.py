@@ -87,3 +87,22 @@ def test_route(routes, case, expected):
     got = routes[case]
     want = dict(kv.split("=") for kv in expected.split())
     assert {k: got[k] for k in want} == want, f"{case}: {got}"
+
+
+TX_YARDSTICK = ["C=131072 F=1 n=16 pcm=0x1000",             # PCM below 2^22 samples: the enc_uni form, two blocks per CU
+                "C=131072 F=1 n=32 pcm=0x1000",          # 2^22 samples exactly: the table form, one block per CU
+                "C=65536 F=128 pcm=0x1000",
+                "C=65536 F=128 pcm=0x1000 tab_lds=0",   # the raised LDS limit refused: the enc_uni form at any size
+                "C=65536 F=128 g711=0x1000", "C=4096 F=1 pcm=0x1000", "C=100 F=8 n=164 g711=0x1000"]
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
+def test_tx_yardstick_grid_is_the_entry_grid():
+    """igdsp_internal_tx_copy runs the groups, blocks and threads of the igdsp_tx_packetize launch of the same arguments at 256 CUs: a
+    PCM launch below 2^22 samples takes cus * 2 blocks, the table form cus"""
+    got = route_util.run([f"{e} {c} cus=256" for c in TX_YARDSTICK for e in ("tx", "tx_copy")])
+    for i, c in enumerate(TX_YARDSTICK):
+        entry, yard = got[2 * i], got[2 * i + 1]
+        assert {k: yard[k] for k in ("n_groups", "grid", "threads", "form")} == {k: entry[k] for k in ("n_groups", "grid", "threads", "form")}, c
+    assert (got[0]["form"], got[0]["grid"], got[0]["table"]) == ("pcm", "512", "0")
+    assert (got[2]["form"], got[2]["grid"], got[2]["table"]) == ("pcm_tab", "256", "1")

@@ -16,7 +16,6 @@ Algorithmic bytes per group-frame: 8 m of info + 160 payload bytes when voted + 
 with no decode, scale, clamp, records or state machine.  Kernel times: run this under `rocprofv3 --kernel-trace --stats` in a run
 of its own."""
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -86,10 +85,7 @@ def run_case(ctx, name, reps, warmup):
     rsrc = torch.randint(0, 256, (F_ * G_ * N,), dtype=torch.uint8, device="cuda", generator=g)
     rcodec = torch.full((G_,), 8, dtype=torch.uint8, device="cuda")
     s = torch.cuda.current_stream()
-    L = capi.load()
-    cp = L.igdsp_internal_bss_copy
-    cp.restype = ctypes.c_int
-    cp.argtypes = [ctypes.c_void_p] * 9 + [ctypes.c_uint32, ctypes.c_void_p] + [ctypes.c_uint32] * 5 + [ctypes.c_void_p] * 6
+    cp = capi.internal("igdsp_internal_bss_copy")
 
     def select():
         ctx.bss_select(d_info, d_ptr, d_mem, C_, state, words, C_, G_, F_, N, payload=src, codec=codec, sel=sel, out=out, stats=st,

@@ -14,7 +14,6 @@ Algorithmic bytes = the distinct channels' frames (F x n each) + their codec byt
 The yardstick (igdsp_internal_conf_copy) walks the same items and member lists and reads and writes the same bytes, with no decode,
 scale, clamp or record arithmetic.  Kernel times: run this under `rocprofv3 --kernel-trace --stats` in a run of its own."""
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -71,10 +70,7 @@ def run_case(ctx, name, reps, warmup):
     out = torch.empty((F_ * P_ * N,), dtype=torch.int16, device="cuda")
     st = torch.empty((F_ * P_ * 16,), dtype=torch.uint8, device="cuda")
     s = torch.cuda.current_stream()
-    L = capi.load()
-    cp = L.igdsp_internal_conf_copy
-    cp.restype = ctypes.c_int
-    cp.argtypes = [ctypes.c_void_p] * 8 + [ctypes.c_uint32] * 5 + [ctypes.c_void_p] * 3
+    cp = capi.internal("igdsp_internal_conf_copy")
 
     def mix():
         ctx.conf_mix(gain, d_ptr, d_mem, len(mem), C_, P_, F_, N, out=out, stats=st, payload=src, codec=codec, stream=s.cuda_stream)

@@ -20,7 +20,6 @@ every tick copied as igdsp_depayload would) with no header walk, state machine o
 by call, on the same stream of packets, the same state and ring and the same output buffers (the adaptive one with its igdsp_jb_adapt
 beside them).  Its bar: the fixed entry's median plus the fixed entry's own max - min spread in that run."""
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -146,10 +145,7 @@ def run_case(ctx, name, reps, warmup, adaptive=False):
     inf = torch.empty((T * S * C_ * 8,), dtype=torch.uint8, device="cuda")
     fl = torch.empty((T * C_,), dtype=torch.uint8, device="cuda")
     s = torch.cuda.current_stream()
-    L = capi.load()
-    cp = L.igdsp_internal_jb_copy
-    cp.restype = ctypes.c_int
-    cp.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_uint32] * 6 + [ctypes.c_void_p] * 8
+    cp = capi.internal("igdsp_internal_jb_copy")
     k = [0]
 
     def args():

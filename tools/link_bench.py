@@ -11,7 +11,6 @@ Shapes (65 536 legs, 1 arrival slot per tick, every slot holding a packet, kind 
 Algorithmic bytes per call: 8 T C of records + T C kind bytes + 32 C of state in and out (read twice with a list).  Kernel times: run
 this under `rocprofv3 --kernel-trace --stats` in a run of its own."""
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -61,11 +60,7 @@ def run_case(ctx, name, reps, warmup):
     events = torch.empty(CAP * 16, dtype=torch.uint8, device="cuda")
     count = torch.zeros(2, dtype=torch.int32, device="cuda")
     work = torch.empty(capi.link_work_bytes(C_, T_), dtype=torch.uint8, device="cuda")
-    L = capi.load()
-    cp = L.igdsp_internal_link_copy
-    cp.restype = ctypes.c_int
-    vp, u32 = ctypes.c_void_p, ctypes.c_uint32
-    cp.argtypes = [vp] * 5 + [u32] * 3 + [ctypes.c_uint64] + [u32] * 3 + [vp] * 3 + [u32] + [vp] * 3
+    cp = capi.internal("igdsp_internal_link_copy")
     t0 = [1_000_000]
 
     def link(want_list=True):

@@ -15,7 +15,6 @@ counted).  Decode is igdsp_decode_meter with d_pcm and d_stats on the same paylo
 walks the same rows with every tick PLAIN and no decode, search, synthesis or stats.  Kernel times: run this under
 `rocprofv3 --kernel-trace --stats` in a run of its own."""
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -82,10 +81,7 @@ def run_case(ctx, name, reps, warmup):
     lo = torch.empty(T * C_, dtype=torch.int16, device="cuda")
     st = torch.empty(T * C_ * 16, dtype=torch.uint8, device="cuda")
     s = torch.cuda.current_stream()
-    L = capi.load()
-    cp = L.igdsp_internal_plc_copy
-    cp.restype = ctypes.c_int
-    cp.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_uint32] * 3 + [ctypes.c_void_p] * 5
+    cp = capi.internal("igdsp_internal_plc_copy")
 
     def plc():
         ctx.plc_conceal(fl, state, out, C_, T, N, payload=pl, codec=codec, len_out=lo, stats=st, stream=s.cuda_stream)

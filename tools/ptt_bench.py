@@ -13,7 +13,6 @@ Each channel's ED-137 word is constant over the frames: keyed (PTT type 1 .. 3) 
 group-frame: 8 m of info + 160 payload bytes when held + 320 out + 16 record + 4 sel + 8 tick + 1 ctl.  Kernel times: run this under
 `rocprofv3 --kernel-trace --stats` in a run of its own."""
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -69,10 +68,7 @@ def run_case(ctx, name, reps, warmup):
     sel = torch.empty(F_ * G_, dtype=torch.int32, device="cuda")
     tick = torch.empty(F_ * G_ * 2, dtype=torch.int32, device="cuda")
     ctl = torch.empty(F_ * G_, dtype=torch.uint8, device="cuda")
-    L = capi.load()
-    cp = L.igdsp_internal_ptt_copy
-    cp.restype = ctypes.c_int
-    cp.argtypes = [ctypes.c_void_p] * 9 + [ctypes.c_uint32, ctypes.c_void_p] + [ctypes.c_uint32] * 5 + [ctypes.c_void_p] * 8
+    cp = capi.internal("igdsp_internal_ptt_copy")
 
     def ptt():
         ctx.ptt_arbitrate(d_info, d_ptr, d_mem, C_, pstate, pslots, C_, G_, F_, N, payload=p_pl, codec=codec, sel=sel, tick=tick, ctl_out=ctl,

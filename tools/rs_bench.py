@@ -14,7 +14,6 @@ history write-back behind the kernel), which the yardstick does not run.
 launcher at every call; the frames are cut to match), entry and yardstick in the same run: the wave-count sweep of DESIGN 3.18.
 Kernel times: run this under `rocprofv3 --kernel-trace --stats` in a run of its own."""
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -61,9 +60,7 @@ def run_case(ctx, name, bufs, reps, warmup):
     n_out = N * R if direction == capi.RS_UP else N
     in_bytes = C * F * n_in * (1 if g711 else 2)
     out_bytes, rec_bytes = C * F * n_out * 2, C * F * 16
-    copy = capi.load().igdsp_internal_rs_copy
-    copy.restype = ctypes.c_int
-    copy.argtypes = [ctypes.c_void_p] + [ctypes.c_uint32] * 3 + [ctypes.c_void_p] * 5 + [ctypes.c_uint32] * 5 + [ctypes.c_void_p] * 3
+    copy = capi.internal("igdsp_internal_rs_copy")
     payload, codec, pcm = (d_g711, d_codec, None) if g711 else (None, None, d_in)
     out = d_out if bulk else None
 

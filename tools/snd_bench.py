@@ -15,7 +15,6 @@ Shapes (n = 160 samples, random int16 input):
 Algorithmic bytes = the input + the bulk output + 16 per record, each only where it is read or written (the yardstick: input + bulk).
 Kernel times: run this under `rocprofv3 --kernel-trace --stats` in a run of its own."""
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -55,9 +54,7 @@ def run_case(ctx, name, reps, warmup):
     ioset, (p_in, p_out, p_st), rep = ctx.io_alloc([(nb, capi.IO_INPUT), (nb, capi.IO_BULK), (rb, capi.IO_RECORD)])
     s = torch.cuda.current_stream()
     ctx.gen_uniform(p_in, nb, seed=D_ + K_ + F_, stream=s.cuda_stream)
-    cp = capi.load().igdsp_internal_snd_copy
-    cp.restype = ctypes.c_int
-    cp.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_uint32] * 4 + [ctypes.c_void_p] * 3
+    cp = capi.internal("igdsp_internal_snd_copy")
 
     def copy():
         rc = cp(ctx.h, p_in, D_, K_, F_, N, p_out, None, s.cuda_stream)

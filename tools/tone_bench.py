@@ -13,7 +13,6 @@ Shapes (65 536 ports, n = 160 samples, one plan for all ports, positions uniform
 The figure judged is fill_over_tone, the yardstick's time over the entry's in the same run (target 0.95 at T1).
 Kernel times: run this under `rocprofv3 --kernel-trace --stats` in a run of its own."""
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -61,9 +60,7 @@ def run_case(ctx, name, reps, warmup):
     st["flags"] = capi.TONE_PLAYING
     d_state = torch.from_numpy(st.view(np.uint8).copy()).cuda()
     d_len = torch.zeros(lb, dtype=torch.uint8, device="cuda")
-    fill = capi.load().igdsp_internal_tone_fill
-    fill.restype = ctypes.c_int
-    fill.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_uint32] + [ctypes.c_void_p] * 3 + [ctypes.c_uint32] * 4 + [ctypes.c_void_p] * 4
+    fill = capi.internal("igdsp_internal_tone_fill")
     rows = []
     for mode in modes:
         pcm, stats = (p_pcm if mode != "stats" else None), (p_st if mode != "pcm" else None)

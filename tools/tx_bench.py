@@ -10,7 +10,6 @@ cadence), 65 536 x {1, 2, 8} and 4 096 x {1, 128}.  Prints one JSON line per cas
 --ab: for every all-audio case also the compute-free packet writer (igdsp_internal_tx_copy: the same traversal and packet bytes,
 no decisions, no encoder, no records) on the same buffers, in the same process.  --only N: just the first N cases."""
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -83,10 +82,7 @@ def run_case(ctx, C_, F_, form, mix, reps, warmup):
     us = float(np.median(times))
     ab = None
     if AB and not mix:
-        L = capi.load()
-        fn = L.igdsp_internal_tx_copy
-        fn.restype = ctypes.c_int
-        fn.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_uint32] * 3 + [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]
+        fn = capi.internal("igdsp_internal_tx_copy")
         tcopy = []
         for r in range(warmup + reps):
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
