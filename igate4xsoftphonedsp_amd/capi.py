@@ -87,6 +87,15 @@ RS_ROWS, RS_SUBFRAMES = 0, 1
 RS_TAPS, RS_HIST = 24, 144
 RS_FACTORS = (2, 3, 4, 6)
 RS_STATE = np.dtype([("hist", "<i2", (RS_HIST,)), ("flags", "<u4"), ("frames", "<u4")], align=True)   # igdsp_rs_state, 296 bytes
+# the sound port's delay buffer (igdsp_dbuf_run / igdsp_dbuf_step)
+DBUF_CAP, DBUF_WIN, DBUF_RECALC = 1024, 280, 200
+DBUF_PUT, DBUF_GET = 1, 2
+DBUF_STATE = np.dtype(
+    [("ring", "<i2", (DBUF_CAP,)), ("head", "<u2"), ("len", "<u2"), ("eff", "<u2"), ("level", "<u2"), ("max_level", "<u2"), ("since", "<u2"),
+     ("last_op", "<u2"), ("reserved0", "<u2"), ("underruns", "<u4"), ("shrinks", "<u4"), ("shrunk", "<u4"), ("dropped", "<u4"), ("puts", "<u4"),
+     ("gets", "<u4"), ("reserved", "<u4", (6,))],
+    align=True,
+)                                                                                                # igdsp_dbuf_state, 2112 bytes
 CHAN_PROBE = np.dtype([("run", "<u4"), ("alarms", "<u4")], align=True)
 # the jitter buffer (igdsp_jb_receive / igdsp_jb_report)
 JB_STATE = np.dtype(
@@ -254,6 +263,8 @@ PROTOTYPES = [
     ("igdsp_rs_taps", _int, [_u32, _u32, C.POINTER(_vp), C.POINTER(_u32)]),
     ("igdsp_rs_frame", _int, [_vp, _u32, _u32, _vp, _u32, _vp]),
     ("igdsp_resample", _int, [_vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp]),
+    ("igdsp_dbuf_run", _int, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("igdsp_dbuf_step", _int, [_vp, _u32, _vp, _u32, _u32, _vp, C.POINTER(_u32)]),
     ("igdsp_g726_reorder", _int, [_vp, _vp, _vp, _u64, _int, _vp]),
     ("igdsp_gen_uniform", _int, [_vp, _vp, _u64, _u64, _u64, _vp]),
     ("igdsp_dev_alloc", _int, [_vp, C.POINTER(_vp), C.c_size_t]),
@@ -292,13 +303,18 @@ _PUBLIC = {name: (res, args) for name, res, args in PROTOTYPES}
 INTERNAL = {name: _PUBLIC[twin] for name, twin in INTERNAL_TWIN.items()}
 INTERNAL["igdsp_internal_tx_copy"] = (_int, [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp])
 
+# A yardstick whose name is not of the *_copy / *_fill form: the same derivation, a table of its own; internal() consults both
+INTERNAL_MORE_TWIN = {"igdsp_internal_dbuf_move": "igdsp_dbuf_run"}
+INTERNAL_MORE = {name: _PUBLIC[twin] for name, twin in INTERNAL_MORE_TWIN.items()}
+
 _lib = None
 
 
 def internal(name: str):
-    """The bound function of a yardstick entry of INTERNAL ("igdsp_internal_rs_copy", or short "rs_copy"); it returns the raw code."""
+    """The bound function of a yardstick entry of INTERNAL or INTERNAL_MORE ("igdsp_internal_rs_copy", or short "rs_copy"); it returns
+    the raw code."""
     name = name if name.startswith("igdsp_internal_") else "igdsp_internal_" + name
-    res, args = INTERNAL[name]                      # KeyError == not a yardstick entry
+    res, args = INTERNAL[name] if name in INTERNAL else INTERNAL_MORE[name]   # KeyError == not a yardstick entry
     fn = getattr(load(), name)
     fn.restype, fn.argtypes = res, list(args)
     return fn
@@ -427,6 +443,21 @@ def rs_taps(direction: int, factor: int) -> np.ndarray:
         raise IgdspError(rc, "igdsp_rs_taps")
     t = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int16)), (n.value,)).copy()
     return t.reshape(factor, RS_TAPS) if direction == RS_UP else t
+
+
+def dbuf_step(state, op: int, n: int, max_samples: int, x=None):
+    """igdsp_dbuf_step (host only, no GPU): one step of one channel.  state a DBUF_STATE record updated in place, op DBUF_PUT / DBUF_GET /
+    both / 0, x the frame a PUT appends (int16 [n]).  Returns (the row a GET took or None, the step's flag: JB_PLAYED / JB_LOST / JB_IDLE)."""
+    assert state.dtype == DBUF_STATE and state.flags["C_CONTIGUOUS"] and state.flags["WRITEABLE"]
+    x = None if x is None else np.ascontiguousarray(x, dtype=np.int16)
+    assert x is None or len(x) == n
+    out = np.zeros(n, np.int16) if op & DBUF_GET else None
+    flag = _u32(0)
+    rc = load().igdsp_dbuf_step(state.ctypes.data_as(_vp), op, None if x is None else x.ctypes.data_as(_vp), n, max_samples,
+                                None if out is None else out.ctypes.data_as(_vp), C.byref(flag))
+    if rc != 0:
+        raise IgdspError(rc, "igdsp_dbuf_step")
+    return out, int(flag.value)
 
 
 def rs_frame(state, direction: int, factor: int, x) -> np.ndarray:
@@ -666,6 +697,12 @@ class Context:
         self._ck(self.L.igdsp_resample(self.h, direction, factor, layout, _ptr(payload), _ptr(codec), _ptr(pcm), _ptr(length), _ptr(state), C_, F_, n,
                                        rows_narrow, rows_wide, _ptr(out), _ptr(stats), stream), "igdsp_resample")
 
+    def dbuf_run(self, ops, pcm, state, C_, T_, n, max_samples, out, flags=None, length=None, fill=None, stats=None, stream=None):
+        """igdsp_dbuf_run: ops [T][C] u8 (DBUF_PUT | DBUF_GET), pcm [T][C][n] int16 (rows of PUT steps), state [C] DBUF_STATE (in and out)
+        -> out [T][C][n] int16 (rows of GET steps), flags [T][C] u8, length [T][C] u16, fill [T][C] u16, stats [T][C] FRAME_STATS."""
+        self._ck(self.L.igdsp_dbuf_run(self.h, _ptr(ops), _ptr(pcm), C_, T_, n, max_samples, _ptr(state), _ptr(out), _ptr(flags), _ptr(length),
+                                       _ptr(fill), _ptr(stats), stream), "igdsp_dbuf_run")
+
     def bss_select(self, info, group_ptr, members, n_members, state, words, C_, G_, F_, n=160, payload=None, codec=None, pcm=None,
                    length=None, gain=None, mute=None, vote_frames=0, sel=None, out=None, stats=None, stream=None):
         """igdsp_bss_select: info [F][C] RTP_INFO; at most one of payload [F][C][n] u8 (+ codec [C]) / pcm [F][C][n] int16; state [G]
@@ -903,7 +940,7 @@ class Timer:
 class _ViaLib:
     def __init__(self, lib, entry):
         name = entry if entry.startswith("igdsp_internal_") else "igdsp_internal_" + entry
-        twin = INTERNAL_TWIN[name]
+        twin = INTERNAL_TWIN[name] if name in INTERNAL_TWIN else INTERNAL_MORE_TWIN[name]
         self._lib, self._fn = lib, internal(name)
         self._twins = {twin, "igdsp_snd_split"} if twin == "igdsp_snd_combine" else {twin}
 

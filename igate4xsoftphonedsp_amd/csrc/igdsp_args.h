@@ -413,4 +413,32 @@ inline Verdict resample(uint32_t dir, uint32_t factor, uint32_t layout, P d_payl
     return kRun;
 }
 
+// ---- delay buffer.  The frame and the maximum are checked whether or not there is work.  The buffers' extents are known from the
+// shape, so "no output may overlap" is a test of byte ranges: every output against every input, the state and every other output
+inline bool ranges_overlap(P a, uint64_t a_bytes, P b, uint64_t b_bytes)
+{
+    const uint64_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return a && b && x < y + b_bytes && y < x + a_bytes;
+}
+inline Verdict dbuf_run(P d_ops, P d_in, uint32_t C, uint32_t T, uint32_t n, uint32_t M, P d_state, P d_out, P d_flags_out, P d_len_out, P d_fill,
+                        P d_stats)
+{
+    if (n == 0 || n > IGDSP_MAX_PAYLOAD || M < 2u * n || M > IGDSP_DBUF_CAP) return kInvalid;
+    if (empty(C, T)) return kNothing;
+    if (any_null({d_ops, d_in, d_state, d_out})) return kInvalid;
+    if ((uint64_t)C * T >= 0xFFFFFFE0ull) return reject(IGDSP_ERANGE);
+    if (misaligned(2, {d_in, d_out, d_len_out, d_fill}) || misaligned(4, {d_state}) || misaligned(8, {d_stats})) return kInvalid;
+    const uint64_t steps = (uint64_t)C * T;
+    struct Buf { P p; uint64_t bytes; };
+    const Buf ins[3] = {{d_ops, steps}, {d_in, steps * n * 2u}, {d_state, (uint64_t)C * sizeof(igdsp_dbuf_state)}};
+    const Buf outs[5] = {{d_out, steps * n * 2u}, {d_flags_out, steps}, {d_len_out, steps * 2u}, {d_fill, steps * 2u}, {d_stats, steps * 16u}};
+    for (int i = 0; i < 5; ++i) {
+        for (const Buf &b : ins)
+            if (ranges_overlap(outs[i].p, outs[i].bytes, b.p, b.bytes)) return reject(IGDSP_EINVAL, "an output must not overlap an input or the state");
+        for (int j = 0; j < i; ++j)
+            if (ranges_overlap(outs[i].p, outs[i].bytes, outs[j].p, outs[j].bytes)) return reject(IGDSP_EINVAL, "two outputs must not overlap");
+    }
+    return kRun;
+}
+
 }  // namespace igdsp::args

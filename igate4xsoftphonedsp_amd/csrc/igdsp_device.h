@@ -12,6 +12,7 @@
 #pragma once
 #include "igdsp_internal.h"
 #include "igdsp_pcmrec.h"
+#include "igdsp_pitch.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -417,6 +418,25 @@ __device__ __forceinline__ void wave_lds_fence()
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// The pitch search of igdsp_pitch.h, wave-wide: yb[k] = z[k] ^ 0x8000 (the window, biased for the unsigned SAD) and ys[k] = yb[k + 1]
+// (odd lags read dword pairs from there), both 4-byte aligned in LDS and fenced by the caller.  AMDF over lags 40 .. 120: lag 40 + lane,
+// and 104 + lane for the first 17 lanes; the key is min-reduced over the wave.  Every lane of the wave active; every lane gets p.
+__device__ __forceinline__ uint32_t pitch_search_wave(const uint16_t *yb, const uint16_t *ys, uint32_t lane)
+{
+    constexpr uint32_t kH = IGDSP_PLC_HIST;
+    uint32_t best = 0;                     // max of ~key = ~min of key
+    for (uint32_t li = lane; li <= (uint32_t)(IGDSP_PLC_PMAX - IGDSP_PLC_PMIN); li += 64u) {
+        const uint32_t p = IGDSP_PLC_PMIN + li, base = kH - IGDSP_PLC_SPAN - p;   // 120 - p
+        const uint32_t *ref = reinterpret_cast<const uint32_t *>(yb + (kH - IGDSP_PLC_SPAN));
+        const uint32_t *lag = (base & 1u) ? reinterpret_cast<const uint32_t *>(ys + base - 1u) : reinterpret_cast<const uint32_t *>(yb + base);
+        uint32_t d = 0;
+#pragma unroll 8
+        for (uint32_t i = 0; i < IGDSP_PLC_SPAN / 2u; ++i) d = __builtin_amdgcn_sad_u16(ref[i], lag[i], d);
+        best = max(best, ~pitch_key(d, p));
+    }
+    return (~wave_reduce_dpp(best, OpMax{})) & 127u;
 }
 
 // Silence-probe helper.  Bytes 28 / 38 / 48 of a frame sit in its pieces 1 / 2 / 3

@@ -144,6 +144,12 @@ hipError_t launch_tone(const LaunchCfg &cfg, const igdsp_tone_plan *plans, uint3
 hipError_t launch_rs(const LaunchCfg &cfg, uint32_t dir, uint32_t R, uint32_t layout, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm,
                      const uint16_t *len, igdsp_rs_state *state, uint32_t C, uint32_t F, uint32_t n, uint32_t rows_narrow, uint32_t rows_wide,
                      int16_t *out, igdsp_frame_stats *stats, bool yardstick, hipStream_t s);
+// igdsp_dbuf_run: flags, len_out, fill, stats may each be nullptr.  yardstick: the compute-free form, every step taken as PUT|GET at a
+// fixed fill of n, the rows through the ring as by a launch, no update, search, blend or record arithmetic (records carry only the
+// length); the scalars are written as by a launch
+hipError_t launch_dbuf_run(const LaunchCfg &cfg, const uint8_t *ops, const int16_t *in, uint32_t C, uint32_t T, uint32_t n, uint32_t M,
+                           igdsp_dbuf_state *state, int16_t *out, uint8_t *flags, uint16_t *len_out, uint16_t *fill, igdsp_frame_stats *stats,
+                           bool yardstick, hipStream_t s);
 hipError_t launch_wav_expand(const LaunchCfg &cfg, const uint8_t *payload, uint32_t C, uint32_t F, uint32_t n, uint32_t rate,
                              uint8_t *files, uint64_t file_stride, hipStream_t s);
 hipError_t launch_g726(const LaunchCfg &cfg, const uint8_t *in, uint8_t *out, uint64_t n_bytes, int mode, hipStream_t s);

@@ -13,8 +13,9 @@
 //      history ring lives in LDS: synthetic and faded rows are written there as they are made.  A run start gathers the last 280
 //      output samples from three places: the ring (the rows this walk made, and the state's ring for samples older than the
 //      launch), the input (PLAIN rows: read-only, decoded again) and zeros (IDLE rows).  Nothing this launch wrote to global memory
-//      is read back.  The pitch search runs one lag per lane on biased samples with v_sad_u16, the key (D << 7) | p is min-reduced
-//      over the wave.  At the end of its walk the channel's final ring and state go out.
+//      is read back.  The pitch search (pitch_search_wave, igdsp_device.h) runs one lag per lane on biased samples with v_sad_u16, the
+//      key (D << 7) | p is min-reduced over the wave; the delay buffer (k_dbuf) runs the same search.  At the end of its walk the
+//      channel's final ring and state go out.
 //   D. the final ring of every channel without loss (positions the part overwrote: decoded input or zeros) and every channel's
 //      scalar state.  Each channel's ring is written once per part; the state's ring is read only for a run that starts before the
 //      part has refilled it.
@@ -26,8 +27,7 @@
 namespace igdsp {
 
 static_assert(sizeof(igdsp_plc_state) == 832 && alignof(igdsp_plc_state) == 4, "igdsp_plc_state layout (capi.PLC_STATE mirrors it)");
-static_assert(IGDSP_PLC_HIST == IGDSP_PLC_SPAN + IGDSP_PLC_PMAX && IGDSP_MAX_PAYLOAD < IGDSP_PLC_HIST, "a tick never overlaps itself");
-static_assert(IGDSP_PLC_PMAX - IGDSP_PLC_PMIN + 1 <= 128, "the pitch fits 7 bits of the search key");
+static_assert(IGDSP_MAX_PAYLOAD < IGDSP_PLC_HIST, "a tick never overlaps itself");   // (the window and the key: igdsp_pitch.h)
 
 constexpr uint32_t kPlcH = IGDSP_PLC_HIST;
 enum : uint32_t { kPkPlain = 0, kPkIdle = 1, kPkStart = 2, kPkCont = 3, kPkRecover = 4 };
@@ -73,13 +73,11 @@ __device__ __forceinline__ int32_t plc_x(const PlcArgs &a, uint32_t t, uint32_t 
     const uint64_t o = ((uint64_t)(a.t0 + t) * a.C + c) * a.n + i;
     return a.g711 ? g711_dec(a.g711[o], plc_alaw(a, c)) : (int32_t)a.pcm[o];
 }
-__device__ __forceinline__ int32_t plc_w(uint32_t i, uint32_t q) { return (int32_t)(((i + 1u) << 15) / (q + 1u)); }
 __device__ __forceinline__ int32_t plc_gain(uint32_t m)
 {
     const int32_t d = m > (uint32_t)IGDSP_PLC_FLAT ? (int32_t)min(m - (uint32_t)IGDSP_PLC_FLAT, 1024u) * IGDSP_PLC_STEP : 0;
     return max(0, 32768 - d);
 }
-__device__ __forceinline__ int32_t q15(int32_t acc) { return (acc + 16384) >> 15; }
 
 __device__ __forceinline__ void plc_record(const PlcArgs &a, uint64_t o, uint64_t sumsq, uint32_t peak, uint32_t flags, bool idle)
 {
@@ -210,25 +208,14 @@ __device__ __forceinline__ void plc_walk(const PlcArgs &a, PlcLds &L, uint32_t c
                 if (k > 0u) L.ys[k - 1u] = (uint16_t)(y ^ 0x8000u);
             }
             wave_lds_fence();
-            // AMDF over lags 40 .. 120: lag 40 + lane, and 104 + lane for the first 17 lanes
-            uint32_t best = 0;                     // max of ~key = ~min of key
-            for (uint32_t li = lane; li <= (uint32_t)(IGDSP_PLC_PMAX - IGDSP_PLC_PMIN); li += 64u) {
-                const uint32_t p = IGDSP_PLC_PMIN + li, base = kPlcH - IGDSP_PLC_SPAN - p;   // 120 - p
-                const uint32_t *ref = reinterpret_cast<const uint32_t *>(L.yb + (kPlcH - IGDSP_PLC_SPAN));
-                const uint32_t *lag = (base & 1u) ? reinterpret_cast<const uint32_t *>(L.ys + base - 1u) : reinterpret_cast<const uint32_t *>(L.yb + base);
-                uint32_t d = 0;
-#pragma unroll 8
-                for (uint32_t i = 0; i < IGDSP_PLC_SPAN / 2u; ++i) d = __builtin_amdgcn_sad_u16(ref[i], lag[i], d);
-                best = max(best, ~(d << 7 | p));
-            }
-            const uint32_t p = (~wave_reduce_dpp(best, OpMax{})) & 127u;
+            const uint32_t p = pitch_search_wave(L.yb, L.ys, lane);
             q = p >> 2;
             for (uint32_t i = lane; i < p; i += 64u) {
                 const int32_t y0 = (int16_t)(L.yb[kPlcH - p + i] ^ 0x8000u);
                 int32_t v = y0;
                 if (i >= p - q) {
-                    const int32_t w = plc_w(i - (p - q), q), y1 = (int16_t)(L.yb[kPlcH - 2u * p + i] ^ 0x8000u);
-                    v = q15(y0 * (32768 - w) + y1 * w);
+                    const int32_t w = pitch_w(i - (p - q), q), y1 = (int16_t)(L.yb[kPlcH - 2u * p + i] ^ 0x8000u);
+                    v = pitch_q15(y0 * (32768 - w) + y1 * w);
                 }
                 L.cyc[i] = (int16_t)v;
             }
@@ -245,13 +232,13 @@ __device__ __forceinline__ void plc_walk(const PlcArgs &a, PlcLds &L, uint32_t c
             if (kind == kPkRecover && i >= q) {
                 v = plc_x(a, t, c, i, l);
             } else {
-                const int32_t s = q15((int32_t)L.cyc[(pos + i) % pitch] * plc_gain(missing + i));
+                const int32_t s = pitch_q15((int32_t)L.cyc[(pos + i) % pitch] * plc_gain(missing + i));
                 if (kind == kPkStart && i < q) {
-                    const int32_t w = plc_w(i, q), y = (int16_t)(L.yb[kPlcH - 1u - i] ^ 0x8000u);
-                    v = q15(y * (32768 - w) + s * w);
+                    const int32_t w = pitch_w(i, q), y = (int16_t)(L.yb[kPlcH - 1u - i] ^ 0x8000u);
+                    v = pitch_q15(y * (32768 - w) + s * w);
                 } else if (kind == kPkRecover) {
-                    const int32_t w = plc_w(i, q);
-                    v = q15(s * (32768 - w) + plc_x(a, t, c, i, l) * w);
+                    const int32_t w = pitch_w(i, q);
+                    v = pitch_q15(s * (32768 - w) + plc_x(a, t, c, i, l) * w);
                 } else {
                     v = s;
                 }

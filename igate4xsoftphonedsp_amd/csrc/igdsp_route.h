@@ -1001,6 +1001,36 @@ inline RsRoute rs_route(uint32_t dir, uint32_t R, uint32_t C, uint32_t F, uint32
     return r;
 }
 
+// ---- igdsp_dbuf_run (launch_dbuf_run): k_dbuf<COPY>.  A wave owns one channel for the steps of one part (<= kDbufPart steps) and walks
+// them in order: the scalars in registers, the samples in the channel's ring in global memory (a step touches the row it appends, the
+// row it takes and the 280 samples of a shrink), the shrink's window in the wave's LDS.  A launch of more steps goes out in parts; the
+// state carries between them as between launches.  The grid is one wave per channel, and the kernel is kept small enough for
+// kDbufResident blocks on a CU (8 waves per SIMD: at most 64 VGPRs each, tests/test_dbuf_resources_cpu.py): the walk is a chain of
+// dependent memory round trips, and only other waves hide them.
+//   vector form: n even, d_in and d_out dword aligned: a row moves as dwords while the channel's ring position is even;
+//   general form: everything else, and a channel of the vector form while its ring position is odd: a sample at a time.
+constexpr int kDbufWaves = 4;                             // waves per block, a channel each, independent of each other
+constexpr uint32_t kDbufPart = 128;                       // steps per part
+constexpr uint32_t kDbufResident = 8;                     // blocks per CU k_dbuf's registers and LDS admit
+constexpr uint32_t kDbufLdsBytes = kDbufWaves * 2u * IGDSP_DBUF_WIN * 2u;   // a block's LDS: per wave the window and its shifted copy
+struct DbufRoute {
+    uint32_t vec = 0;                      // the vector form
+    uint32_t grid = 0, threads = 0, lds = 0;
+    uint32_t part_steps = 0, parts = 0;    // the last part takes the rest
+};
+inline DbufRoute dbuf_route(uint32_t C, uint32_t T, uint32_t n, uint32_t M, uintptr_t in, uintptr_t out)
+{
+    DbufRoute r;
+    if ((uint64_t)C * T == 0 || (uint64_t)C * T >= 0xFFFFFFE0ull || n == 0 || n > IGDSP_MAX_PAYLOAD || M < 2u * n || M > IGDSP_DBUF_CAP) return r;
+    r.vec = (n & 1u) == 0u && aligned(in | out, 4) ? 1u : 0u;
+    r.grid = (uint32_t)(((uint64_t)C + kDbufWaves - 1) / kDbufWaves);
+    r.threads = kDbufWaves * 64;
+    r.lds = kDbufLdsBytes;
+    r.part_steps = std::min(T, kDbufPart);
+    r.parts = (T + kDbufPart - 1) / kDbufPart;
+    return r;
+}
+
 // ---- igdsp_tx_flush (launch_tx_staged): a wave owns kTsLegs staged legs (runs) of the flush; lanes 0 .. kTsLegs-1 decide, the
 // whole wave writes the packets.  No dynamic LDS: each wave's records (kTsLegs x IGDSP_STAGE_DEPTH) are static.
 constexpr int kTsWaves = 4;

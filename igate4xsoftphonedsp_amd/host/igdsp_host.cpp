@@ -941,6 +941,50 @@ int igdsp_host_rs_down(void *v, const int16_t *wide, int16_t *narrow)
     return static_cast<Resampler *>(v)->down(wide, narrow);
 }
 
+// ---- a reverse channel's delay buffer, no context needed
+DelayBuf::DelayBuf(uint32_t samples_per_frame, uint32_t max_samples_) : n(samples_per_frame), max_samples(max_samples_)
+{
+    ok = n >= 1 && n <= IGDSP_MAX_PAYLOAD && max_samples >= 2 * n && max_samples <= IGDSP_DBUF_CAP;
+    std::memset(&state, 0, sizeof(state));
+}
+
+int DelayBuf::put(const int16_t *frame)
+{
+    return ok ? igdsp_dbuf_step(&state, IGDSP_DBUF_PUT, frame, n, max_samples, nullptr, nullptr) : IGDSP_EINVAL;
+}
+
+int DelayBuf::get(int16_t *frame)
+{
+    uint32_t flag = 0;
+    const int rc = ok ? igdsp_dbuf_step(&state, IGDSP_DBUF_GET, nullptr, n, max_samples, frame, &flag) : IGDSP_EINVAL;
+    return rc == IGDSP_OK ? (int)flag : rc;
+}
+
+void *igdsp_host_dbuf_new(uint32_t samples_per_frame, uint32_t max_samples)
+{
+    DelayBuf *d = new (std::nothrow) DelayBuf(samples_per_frame, max_samples);
+    if (d && !d->ok) { delete d; d = nullptr; }
+    return d;
+}
+void igdsp_host_dbuf_free(void *v) { delete static_cast<DelayBuf *>(v); }
+int igdsp_host_dbuf_put(void *v, const int16_t *frame)
+{
+    if (!v || !frame) return IGDSP_EINVAL;
+    return static_cast<DelayBuf *>(v)->put(frame);
+}
+int igdsp_host_dbuf_get(void *v, int16_t *frame)
+{
+    if (!v || !frame) return IGDSP_EINVAL;
+    return static_cast<DelayBuf *>(v)->get(frame);
+}
+int igdsp_host_dbuf_fill(void *v) { return v ? (int)static_cast<DelayBuf *>(v)->fill() : IGDSP_EINVAL; }
+int igdsp_host_dbuf_state(void *v, igdsp_dbuf_state *out)
+{
+    if (!v || !out) return IGDSP_EINVAL;
+    *out = static_cast<DelayBuf *>(v)->state;
+    return IGDSP_OK;
+}
+
 // ---- conference receive levels, no context needed
 void *igdsp_host_levels_new(uint32_t n_channels)
 {

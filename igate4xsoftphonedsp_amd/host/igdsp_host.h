@@ -197,7 +197,7 @@ private:
 // The sound-card splitter / combiner, pjmedia_splitcomb as initSlaveSoundCard drives it (roip_ed137.cpp:3314-3435), without a context:
 // K mono rows of n samples <-> one card frame of n x K interleaved samples, and the per-channel VU of either side in plain loops.  A
 // gateway of the reference's size (one card) keeps the step on the CPU with this; igdsp_snd_combine / igdsp_snd_split are the same
-// steps on the device for thousands of cards.  No delay buffers: one call is one frame on one clock.
+// steps on the device for thousands of cards.  It buffers nothing, one call is one frame; the card's other clock is DelayBuf's business.
 class SplitComb {
 public:
     SplitComb(int channels, int samples_per_frame);   // clamped to 1 .. IGDSP_SND_MAX_CHANNELS and 1 .. IGDSP_MAX_PAYLOAD
@@ -247,6 +247,21 @@ public:
     igdsp_rs_state to_bridge, from_bridge;
     int up(const int16_t *narrow, int16_t *wide);      // n samples -> n * factor (igdsp_rs_frame, IGDSP_RS_UP)
     int down(const int16_t *wide, int16_t *narrow);    // n * factor samples -> n (IGDSP_RS_DOWN)
+};
+
+// A reverse channel's delay buffer, as pjmedia_splitcomb_create_rev_channel puts one between the bridge's tick and the card's clock
+// (initSlaveSoundCard, roip_ed137.cpp:3314-3435), without a context: one channel, one direction.  put() is the producer's frame, get() the
+// consumer's: they are called as the two clocks deliver, in any order.  A gateway of the reference's size keeps one per card channel and
+// direction; igdsp_dbuf_run takes the same states for thousands of card channels.
+class DelayBuf {
+public:
+    explicit DelayBuf(uint32_t samples_per_frame = IGDSP_SAMPLES_PER_FRAME, uint32_t max_samples = 6 * IGDSP_SAMPLES_PER_FRAME);
+    uint32_t n, max_samples;
+    bool ok;                                 // n in 1 .. 256 and 2 n <= max_samples <= IGDSP_DBUF_CAP
+    igdsp_dbuf_state state;
+    int put(const int16_t *frame);           // n samples in (igdsp_dbuf_step, IGDSP_DBUF_PUT)
+    int get(int16_t *frame);                 // n samples out; IGDSP_JB_PLAYED, or IGDSP_JB_LOST with a frame of zeros on underrun; negative: an error
+    uint32_t fill() const { return state.len; }   // the delay, samples
 };
 
 class RoIP_ED137 {
@@ -367,6 +382,14 @@ void *igdsp_host_rs_new(uint32_t bridge_rate, uint32_t samples_per_frame);
 void  igdsp_host_rs_free(void *v);
 int   igdsp_host_rs_up(void *v, const int16_t *narrow, int16_t *wide);
 int   igdsp_host_rs_down(void *v, const int16_t *wide, int16_t *narrow);
+// a reverse channel's delay buffer without a context (DelayBuf): NULL from _new for sizes igdsp_dbuf_step rejects; _put one frame in, _get
+// one frame out (returns IGDSP_JB_PLAYED or IGDSP_JB_LOST; IGDSP_EINVAL for a NULL argument); _fill the delay in samples; _state a copy
+void *igdsp_host_dbuf_new(uint32_t samples_per_frame, uint32_t max_samples);
+void  igdsp_host_dbuf_free(void *v);
+int   igdsp_host_dbuf_put(void *v, const int16_t *frame);
+int   igdsp_host_dbuf_get(void *v, int16_t *frame);
+int   igdsp_host_dbuf_fill(void *v);
+int   igdsp_host_dbuf_state(void *v, igdsp_dbuf_state *out);
 // Meter output on the reference's other channel: AudioMeter (audiometer.cpp:11-34) reads ASCII decimal levels from the
 // FIFO /tmp/capturefifo<card>, 32 bytes per read, and emits onValueChanged(int(float(v*100.0/30000.0))).  These write
 // such records, so the reference's own meter consumer can be fed from igdsp_poll().rms.  open() waits up to

@@ -42,7 +42,8 @@ extern "C" {
  *    igdsp_link_work_bytes, igdsp_link_watch); the sound-card splitter / combiner (IGDSP_SND_*, igdsp_snd_combine, igdsp_snd_split,
  *    igdsp_snd_vu_t, igdsp_snd_vu); the tone generator (IGDSP_TONE_*, igdsp_tone_desc, igdsp_tone_seg, igdsp_tone_plan,
  *    igdsp_tone_state, igdsp_tone_plan_build, igdsp_tone_frame, igdsp_tone_generate); the rate converter (IGDSP_RS_*, igdsp_rs_state,
- *    igdsp_resample, igdsp_rs_frame, igdsp_rs_taps). */
+ *    igdsp_resample, igdsp_rs_frame, igdsp_rs_taps); the sound port's delay buffer (IGDSP_DBUF_*, igdsp_dbuf_state, igdsp_dbuf_run,
+ *    igdsp_dbuf_step). */
 #define IGDSP_ABI_VERSION 3
 
 /* ---- error codes (0 == PJ_SUCCESS-style success) ------------------------- */
@@ -1125,7 +1126,8 @@ int igdsp_plc_conceal(igdsp_ctx *ctx, const uint8_t *d_tick_flags,
  *
  * Fidelity.  UNVERIFIED: the interleaving order s * K + k is the standard PCM layout the ALSA card takes; pjmedia's splitcomb.c is not
  * in the reference tree.  DIFFERENT ON PURPOSE: pjmedia's reverse channels carry a delay buffer because the bridge and the card have
- * separate clocks; here one launch is one clock and nothing is buffered.  The reference opens only a player on this card
+ * separate clocks; these two entries buffer nothing, and the delay buffer is a step of its own between them and the bridge
+ * (igdsp_dbuf_run, "Delay buffer" below).  The reference opens only a player on this card
  * (pjmedia_snd_port_create_player; the bidirectional pjmedia_snd_port_create is commented out at :3411-3420), so its capture direction
  * carries silence today although both directions are wired; igdsp_snd_split is the step that wiring implies. */
 #define IGDSP_SND_MAX_CHANNELS 8
@@ -1291,6 +1293,93 @@ int igdsp_resample(igdsp_ctx *ctx, uint32_t direction, uint32_t factor, uint32_t
                    uint32_t rows_narrow, uint32_t rows_wide, int16_t *d_out, igdsp_frame_stats *d_stats /* dense */, void *stream);
 int igdsp_rs_frame(igdsp_rs_state *st, uint32_t direction, uint32_t factor, const int16_t *in, uint32_t n_in, int16_t *out);
 int igdsp_rs_taps(uint32_t direction, uint32_t factor, const int16_t **taps, uint32_t *count);
+
+/* ---- Delay buffer: the sound port's two clocks, between the splitter / combiner and the bridge ------------------------------------------
+ * initSlaveSoundCard (roip_ed137.cpp:3314-3435) creates five pjmedia_splitcomb_create_rev_channel ports, and each of those carries a
+ * delay buffer in both directions: the bridge's tick and the card's crystal are separate clocks, so within one tick of the one side the
+ * other has delivered zero, one or two frames.  igdsp_dbuf_run is that buffer for every card channel of a launch, in either direction:
+ * igdsp_snd_split -> igdsp_dbuf_run -> igdsp_conf_mix (capture) and igdsp_conf_mix -> igdsp_dbuf_run -> igdsp_snd_combine (playback).
+ * Everything is integer.
+ *
+ * STATE.  A channel buffers len samples, oldest first: y[k] = ring[(head + k) % IGDSP_DBUF_CAP], k < len.  n = samples_per_frame
+ * (1..256), M = max_samples (2 n <= M <= IGDSP_DBUF_CAP).  A state is READ as: head %= CAP; if len > M the oldest len - M samples are
+ * skipped (head advanced, len = M, not counted); eff == 0 reads as M >> 1, otherwise min(eff, M); last_op other than IGDSP_DBUF_PUT or
+ * IGDSP_DBUF_GET reads as 0; since reads as min(since, IGDSP_DBUF_RECALC - 1); and it is written back so: all-zero is the reset state and
+ * a garbage state stays in bounds.  The six counters are telemetry and wrap.
+ *
+ * STEPS.  A launch is T = n_steps steps; step t of channel c has op = d_ops[t][c] & 3.  With both bits set the PUT runs first, then
+ * the GET.  Two frames of one side inside one tick of the other are two steps, so any interleaving of the two clocks can be written
+ * down.
+ *   update(op)  (the burst level, learnt per direction switch)
+ *       if last_op == op:  level = min(level + 1, 65535); return
+ *       if last_op != 0:   max_level = max(max_level, level); since += level
+ *       last_op = op; level = 1
+ *       if since >= IGDSP_DBUF_RECALC:
+ *           eff = (3 * eff + min(M, (max_level + 1) * n)) >> 2;  max_level = 0;  since = 0
+ *   PUT, x = d_in[t][c][0 .. n)
+ *       update(PUT); puts += 1
+ *       if (len > n + eff || len + n > M) && len >= IGDSP_DBUF_WIN:  shrink()           (at most one per PUT)
+ *       d = len + n - M;  if d > 0: head = (head + d) % CAP; len -= d; dropped += d       (the oldest samples)
+ *       y[len .. len + n) = x;  len += n
+ *   shrink()  drops one pitch period of the newest audio by overlap-add, with the rules of the concealment (igdsp_plc_conceal):
+ *       z[k] = y[len - 280 + k];  D(p) = sum_{i<160} |z[120 + i] - z[120 + i - p]| for p = IGDSP_PLC_PMIN .. IGDSP_PLC_PMAX;
+ *       p = the smallest D, the smallest p on ties (the key (D << 7) | p);  w(i) = ((i + 1) << 15) / (p + 1);
+ *       b[i] = (z[280 - 2 p + i] * (32768 - w(i)) + z[280 - p + i] * w(i) + 16384) >> 15 for i < p   (>> arithmetic: a floor);
+ *       the newest 2 p samples are replaced by b[0 .. p);  len -= p; shrinks += 1; shrunk += p.
+ *       The blend is convex: no clamp is needed and every product fits int32.
+ *   GET
+ *       update(GET); gets += 1
+ *       if len < n:  out = zeros; head = (head + len) % CAP; len = 0; underruns += 1; flag = IGDSP_JB_LOST
+ *       else:        out = y[0 .. n); head = (head + n) % CAP; len -= n;              flag = IGDSP_JB_PLAYED
+ *
+ * OUTPUTS per step and channel.  d_out[t][c][n] is written on GET steps only (rows of steps without a GET are never written).
+ * d_flags_out[t][c] (optional): PLAYED or LOST as above, IGDSP_JB_IDLE without a GET: when every step has a GET, igdsp_plc_conceal
+ * takes the flags as they are and conceals the underruns.  d_len_out[t][c] (optional): n on GET, else 0, what igdsp_conf_mix's d_len
+ * takes.  d_fill[t][c] (optional): len after the step, the delay in samples; a host reads its drift here.  d_stats[t][c] (optional):
+ * the record over the output row as igdsp_conf_mix writes it (sumsq exact, rms = sqrtf((float)sumsq / n), peak, byte_mean 0,
+ * IGDSP_FLAG_SILENT when peak <= 8; an underrun row is a row of zeros); steps without a GET get the len-0 record (all 0,
+ * IGDSP_FLAG_EMPTY).  Rows of d_in whose step has no PUT are never read.
+ *
+ * CHAINING.  T launches of one step, one launch of T steps and any split in between give the same outputs and the same state: the
+ * same scalars and the same live samples y[0 .. len).  Ring bytes outside the live region are unspecified.
+ *
+ * ARGUMENTS.  samples_per_frame and max_samples out of range: IGDSP_EINVAL, whether or not there is work.  n_channels == 0 or
+ * n_steps == 0: nothing to do, the state is untouched.  d_ops, d_in, d_state and d_out are required.  n_channels * n_steps < 2^32 - 32
+ * (IGDSP_ERANGE).  d_in, d_out, d_len_out, d_fill 2-byte, d_state 4-byte, d_stats 8-byte aligned.  No output may overlap an input, the
+ * state or another output.  Enqueued on `stream`, not synchronised.
+ *
+ * igdsp_dbuf_step (host only, no GPU): one step of one channel by the same rule.  op is IGDSP_DBUF_PUT, IGDSP_DBUF_GET, both or 0
+ * (the state is only read and written back); in is read on PUT, out (n samples) is written on GET only, *flag (optional) as
+ * d_flags_out.  IGDSP_EINVAL for a NULL state, an op above 3, sizes out of range, or a NULL row its op needs.
+ *
+ * Fidelity.  UNVERIFIED: pjmedia's delaybuf.c and wsola.c are not in the reference tree.  PINNED to their structure: the burst level
+ * learnt per direction switch; the effective size smoothed 3 : 1 and re-learnt every IGDSP_DBUF_RECALC half-frames of traffic; a shrink
+ * when the fill exceeds a frame plus the effective size or would exceed the maximum; the oldest samples dropped when that is not
+ * enough; a zero frame and an emptied buffer on underrun.  DIFFERENT ON PURPOSE: a 128 ms cap instead of pjmedia's 400 ms default,
+ * which keeps the state at 2 KiB per channel; one period per PUT, with the concealment's integer pitch search, instead of a windowed
+ * float WSOLA loop; mono PCM only (the split runs before the buffer); an underrun is not expanded: the LOST flag hands the gap to
+ * igdsp_plc_conceal. */
+#define IGDSP_DBUF_CAP     1024   /* ring samples per channel: 128 ms at 8 kHz            */
+#define IGDSP_DBUF_WIN      280   /* the shrink's window = IGDSP_PLC_HIST                 */
+#define IGDSP_DBUF_RECALC   200   /* burst levels summed between two updates of eff       */
+#define IGDSP_DBUF_PUT     0x01   /* d_ops bits */
+#define IGDSP_DBUF_GET     0x02
+typedef struct igdsp_dbuf_state {
+    int16_t  ring[IGDSP_DBUF_CAP];  /* buffered sample k (0 = oldest) is ring[(head + k) % CAP], k < len */
+    uint16_t head, len;             /* the live region                                        */
+    uint16_t eff;                   /* effective size, samples (0 reads as max_samples >> 1)  */
+    uint16_t level, max_level;      /* the current burst, the longest since the last recalc   */
+    uint16_t since;                 /* burst levels summed since the last recalc              */
+    uint16_t last_op, reserved0;    /* 0, IGDSP_DBUF_PUT or IGDSP_DBUF_GET                    */
+    uint32_t underruns, shrinks, shrunk, dropped, puts, gets;   /* telemetry, wrapping       */
+    uint32_t reserved[6];
+} igdsp_dbuf_state;                 /* 2112 bytes; all-zero = reset */
+int igdsp_dbuf_run(igdsp_ctx *ctx, const uint8_t *d_ops /* [T][C] */, const int16_t *d_in /* [T][C][n] */,
+                   uint32_t n_channels, uint32_t n_steps, uint32_t samples_per_frame, uint32_t max_samples,
+                   igdsp_dbuf_state *d_state /* [C], in and out */, int16_t *d_out /* [T][C][n] */, uint8_t *d_flags_out, uint16_t *d_len_out,
+                   uint16_t *d_fill, igdsp_frame_stats *d_stats, void *stream);
+int igdsp_dbuf_step(igdsp_dbuf_state *st, uint32_t op, const int16_t *in, uint32_t samples_per_frame,
+                    uint32_t max_samples, int16_t *out, uint32_t *flag);
 
 /* ---- synthetic input generators (device side; SURVEY 8(d) definitions) ---------
  * D-uniform: byte k of global byte index g is
