@@ -96,6 +96,12 @@ DBUF_STATE = np.dtype(
      ("gets", "<u4"), ("reserved", "<u4", (6,))],
     align=True,
 )                                                                                                # igdsp_dbuf_state, 2112 bytes
+# the spectrum graph (igdsp_spectrum / igdsp_spec_frame)
+SPEC_N, SPEC_BINS, SPEC_FLOOR_DB = 1024, 512, -70.0
+SPEC_HOP, SPEC_LIVE = 1, 1
+SPEC_STATE = np.dtype([("hist", "<i2", (SPEC_N,)), ("avg", "<f4", (SPEC_BINS,)), ("since", "<u4"), ("hops", "<u4"), ("flags", "<u4"),
+                       ("reserved", "<u4")], align=True)                                          # igdsp_spec_state, 4112 bytes
+SPEC_REC = np.dtype([("peak_bin", "<u2"), ("flags", "<u2"), ("peak_db", "<f4")], align=True)     # igdsp_spec_rec, 8 bytes
 CHAN_PROBE = np.dtype([("run", "<u4"), ("alarms", "<u4")], align=True)
 # the jitter buffer (igdsp_jb_receive / igdsp_jb_report)
 JB_STATE = np.dtype(
@@ -157,6 +163,11 @@ class Window(C.Structure):
     """igdsp_window: the ED-137 gated window of igdsp_window_update / igdsp_decode_meter_window."""
     _fields_ = [("gate_mode", C.c_uint32), ("probe_alarm", C.c_uint32), ("d_hold", C.c_void_p), ("d_gate", C.c_void_p),
                 ("d_probe", C.c_void_p), ("d_work", C.c_void_p)]
+
+
+class SpecCfg(C.Structure):
+    """igdsp_spec_cfg: a spectrum every hop_frames frames, the average's gain alpha"""
+    _fields_ = [("hop_frames", C.c_uint32), ("alpha", C.c_float)]
 
 
 class ChanProbe(C.Structure):
@@ -265,6 +276,9 @@ PROTOTYPES = [
     ("igdsp_resample", _int, [_vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp]),
     ("igdsp_dbuf_run", _int, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("igdsp_dbuf_step", _int, [_vp, _u32, _vp, _u32, _u32, _vp, C.POINTER(_u32)]),
+    ("igdsp_spectrum", _int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("igdsp_spec_frame", _int, [_vp, _vp, _u32, _vp, _vp, _vp]),
+    ("igdsp_spec_tables", _int, [C.POINTER(_vp), C.POINTER(_vp)]),
     ("igdsp_g726_reorder", _int, [_vp, _vp, _vp, _u64, _int, _vp]),
     ("igdsp_gen_uniform", _int, [_vp, _vp, _u64, _u64, _u64, _vp]),
     ("igdsp_dev_alloc", _int, [_vp, C.POINTER(_vp), C.c_size_t]),
@@ -304,7 +318,7 @@ INTERNAL = {name: _PUBLIC[twin] for name, twin in INTERNAL_TWIN.items()}
 INTERNAL["igdsp_internal_tx_copy"] = (_int, [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp])
 
 # A yardstick whose name is not of the *_copy / *_fill form: the same derivation, a table of its own; internal() consults both
-INTERNAL_MORE_TWIN = {"igdsp_internal_dbuf_move": "igdsp_dbuf_run"}
+INTERNAL_MORE_TWIN = {"igdsp_internal_dbuf_move": "igdsp_dbuf_run", "igdsp_internal_spec_move": "igdsp_spectrum"}
 INTERNAL_MORE = {name: _PUBLIC[twin] for name, twin in INTERNAL_MORE_TWIN.items()}
 
 _lib = None
@@ -458,6 +472,40 @@ def dbuf_step(state, op: int, n: int, max_samples: int, x=None):
     if rc != 0:
         raise IgdspError(rc, "igdsp_dbuf_step")
     return out, int(flag.value)
+
+
+def _spec_cfg(cfg):
+    """a SpecCfg from one, a (hop_frames, alpha) pair or None (the defaults: 1, 0.25)"""
+    if cfg is None or isinstance(cfg, SpecCfg):
+        return cfg
+    return SpecCfg(int(cfg[0]), float(cfg[1]))
+
+
+def spec_frame(state, row, cfg=None, want_raw=True):
+    """igdsp_spec_frame (host only, no GPU): one frame of one channel.  state a SPEC_STATE record updated in place, row the frame's PCM
+    (int16 [n]), cfg a SpecCfg, a (hop_frames, alpha) pair or None.  Returns (the frame's SPEC_REC record, the raw spectrum float32 [512]
+    or None when the frame did not hop or want_raw is off)."""
+    assert state.dtype == SPEC_STATE and state.flags["C_CONTIGUOUS"] and state.flags["WRITEABLE"]
+    row = np.ascontiguousarray(row, dtype=np.int16)
+    c = _spec_cfg(cfg)
+    rec = np.zeros((), SPEC_REC)
+    raw = np.zeros(SPEC_BINS, np.float32) if want_raw else None
+    rc = load().igdsp_spec_frame(state.ctypes.data_as(_vp), row.ctypes.data_as(_vp), len(row), None if c is None else C.cast(C.pointer(c), _vp),
+                                 rec.ctypes.data_as(_vp), None if raw is None else raw.ctypes.data_as(_vp))
+    if rc != 0:
+        raise IgdspError(rc, "igdsp_spec_frame")
+    return rec, (raw if want_raw and rec["flags"] & SPEC_HOP else None)
+
+
+def spec_tables():
+    """igdsp_spec_tables (host only, no GPU): the committed window (float32 [1024]) and twiddle factors (float32 [1024][2]: cos, -sin)."""
+    w, t = _vp(), _vp()
+    rc = load().igdsp_spec_tables(C.byref(w), C.byref(t))
+    if rc != 0:
+        raise IgdspError(rc, "igdsp_spec_tables")
+    win = np.ctypeslib.as_array(C.cast(w, C.POINTER(C.c_float)), (SPEC_N,)).copy()
+    tw = np.ctypeslib.as_array(C.cast(t, C.POINTER(C.c_float)), (2 * SPEC_N,)).copy()
+    return win, tw.reshape(SPEC_N, 2)
 
 
 def rs_frame(state, direction: int, factor: int, x) -> np.ndarray:
@@ -702,6 +750,13 @@ class Context:
         -> out [T][C][n] int16 (rows of GET steps), flags [T][C] u8, length [T][C] u16, fill [T][C] u16, stats [T][C] FRAME_STATS."""
         self._ck(self.L.igdsp_dbuf_run(self.h, _ptr(ops), _ptr(pcm), C_, T_, n, max_samples, _ptr(state), _ptr(out), _ptr(flags), _ptr(length),
                                        _ptr(fill), _ptr(stats), stream), "igdsp_dbuf_run")
+
+    def spectrum(self, state, C_, F_, n, g711=None, codec=None, pcm=None, cfg=None, rec=None, avg=None, raw=None, stream=None):
+        """igdsp_spectrum: exactly one of g711 [F][C][n] u8 (+ codec [C]) / pcm [F][C][n] int16; state [C] SPEC_STATE (in and out); cfg a
+        SpecCfg, a (hop_frames, alpha) pair or None (1, 0.25) -> rec [F][C] SPEC_REC, avg [C][512] f32, raw [C][512] f32 (each optional)."""
+        c = _spec_cfg(cfg)
+        self._ck(self.L.igdsp_spectrum(self.h, _ptr(g711), _ptr(codec), _ptr(pcm), C_, F_, n, None if c is None else C.cast(C.pointer(c), _vp),
+                                       _ptr(state), _ptr(rec), _ptr(avg), _ptr(raw), stream), "igdsp_spectrum")
 
     def bss_select(self, info, group_ptr, members, n_members, state, words, C_, G_, F_, n=160, payload=None, codec=None, pcm=None,
                    length=None, gain=None, mute=None, vote_frames=0, sel=None, out=None, stats=None, stream=None):

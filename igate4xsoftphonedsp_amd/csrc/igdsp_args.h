@@ -441,4 +441,33 @@ inline Verdict dbuf_run(P d_ops, P d_in, uint32_t C, uint32_t T, uint32_t n, uin
     return kRun;
 }
 
+// ---- spectrum.  The frame and the cfg (NULL = the defaults) are checked whether or not there is work.  The state is read and written:
+// like the outputs it may overlap neither an input nor an output
+constexpr bool spec_cfg_ok(const igdsp_spec_cfg *cfg)
+{
+    return !cfg || (cfg->hop_frames >= 1u && cfg->alpha > 0.0f && cfg->alpha <= 1.0f);        // (a NaN alpha fails)
+}
+inline Verdict spec_run(P d_g711, P d_codec, P d_pcm, uint32_t C, uint32_t F, uint32_t n, const igdsp_spec_cfg *cfg, P d_state, P d_rec, P d_avg,
+                        P d_raw)
+{
+    if (n == 0 || n > IGDSP_MAX_PAYLOAD || !spec_cfg_ok(cfg)) return kInvalid;
+    if (empty(C, F)) return kNothing;
+    if (!exactly_one(d_g711, d_pcm) || (d_g711 && !d_codec) || !d_state) return kInvalid;
+    if ((uint64_t)C * F >= 0xFFFFFFE0ull) return reject(IGDSP_ERANGE);
+    if (misaligned(2, {d_pcm}) || misaligned(4, {d_state, d_avg, d_raw}) || misaligned(8, {d_rec})) return kInvalid;
+    const uint64_t frames = (uint64_t)C * F;
+    struct Buf { P p; uint64_t bytes; };
+    const Buf ins[3] = {{d_g711, frames * n}, {d_g711 ? d_codec : nullptr, C}, {d_pcm, frames * n * 2u}};
+    const Buf outs[4] = {{d_state, (uint64_t)C * sizeof(igdsp_spec_state)}, {d_rec, frames * sizeof(igdsp_spec_rec)},
+                         {d_avg, (uint64_t)C * IGDSP_SPEC_BINS * 4u}, {d_raw, (uint64_t)C * IGDSP_SPEC_BINS * 4u}};
+    for (int i = 0; i < 4; ++i) {
+        for (const Buf &b : ins)
+            if (ranges_overlap(outs[i].p, outs[i].bytes, b.p, b.bytes)) return reject(IGDSP_EINVAL, "the state and the outputs must not overlap an input");
+        for (int j = 0; j < i; ++j)
+            if (ranges_overlap(outs[i].p, outs[i].bytes, outs[j].p, outs[j].bytes))
+                return reject(IGDSP_EINVAL, "the state and the outputs must not overlap each other");
+    }
+    return kRun;
+}
+
 }  // namespace igdsp::args

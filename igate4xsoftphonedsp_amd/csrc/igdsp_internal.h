@@ -150,6 +150,12 @@ hipError_t launch_rs(const LaunchCfg &cfg, uint32_t dir, uint32_t R, uint32_t la
 hipError_t launch_dbuf_run(const LaunchCfg &cfg, const uint8_t *ops, const int16_t *in, uint32_t C, uint32_t T, uint32_t n, uint32_t M,
                            igdsp_dbuf_state *state, int16_t *out, uint8_t *flags, uint16_t *len_out, uint16_t *fill, igdsp_frame_stats *stats,
                            bool yardstick, hipStream_t s);
+// igdsp_spectrum: exactly one of g711 (with codec) and pcm; rec, avg, raw may each be nullptr.  yardstick: the compute-free form, the same
+// rows into the ring, the same ring loads, tile exchanges and stores at a hop, no window, butterfly, twiddle, split, log or average (a
+// record carries only IGDSP_SPEC_HOP; the averaged array is stored as it was read)
+hipError_t launch_spectrum(const LaunchCfg &cfg, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm, uint32_t C, uint32_t F, uint32_t n,
+                           uint32_t hop_frames, float alpha, igdsp_spec_state *state, igdsp_spec_rec *rec, float *avg, float *raw, bool yardstick,
+                           hipStream_t s);
 hipError_t launch_wav_expand(const LaunchCfg &cfg, const uint8_t *payload, uint32_t C, uint32_t F, uint32_t n, uint32_t rate,
                              uint8_t *files, uint64_t file_stride, hipStream_t s);
 hipError_t launch_g726(const LaunchCfg &cfg, const uint8_t *in, uint8_t *out, uint64_t n_bytes, int mode, hipStream_t s);

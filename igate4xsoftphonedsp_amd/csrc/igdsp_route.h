@@ -1031,6 +1031,33 @@ inline DbufRoute dbuf_route(uint32_t C, uint32_t T, uint32_t n, uint32_t M, uint
     return r;
 }
 
+// ---- igdsp_spectrum (launch_spectrum): k_spec<COPY>.  A wave owns one channel for all the launch's frames, because the averaged array
+// is sequential in time: the 1 024 samples of history as a ring in the wave's LDS, the averaged array in registers (8 bins per lane),
+// the next frame's row load in flight during the transform.  A hop packs the windowed history as 512 complex points, 8 per lane, and
+// runs three radix-8 passes in registers with two exchanges through the wave's LDS tile (8 rows of 64 points, padded to kSpecTileRow
+// so that both the row-wise stores and the strided loads of an exchange spread over the banks), then the split pass to the 512 bins
+// with the partner bins fetched from the mirror lane.  The window and the twiddle factors a lane needs are the same for every hop:
+// they live in registers, which is why the kernel is sized for kSpecResident blocks per CU (16 waves, up to 128 VGPRs each) and not
+// for more: a lane's eight butterflies are independent, so the transform hides its own latencies.  Waves of a block are independent
+// of each other.  No parts: the frame loop is the wave's own.
+constexpr int kSpecWaves = 4;                             // waves per block, a channel each
+constexpr uint32_t kSpecResident = 4;                     // blocks per CU k_spec's registers and LDS admit
+constexpr uint32_t kSpecTileRow = 72;                     // complex points per tile row: 64 and 8 of padding
+constexpr uint32_t kSpecTile = 8u * kSpecTileRow;         // complex points of a wave's tile
+constexpr uint32_t kSpecLdsBytes = kSpecWaves * (IGDSP_SPEC_N * 2u + kSpecTile * 8u);   // a block's LDS: per wave the ring and the tile
+struct SpecRoute {
+    uint32_t grid = 0, threads = 0, lds = 0;
+};
+inline SpecRoute spec_route(uint32_t C, uint32_t F, uint32_t n)
+{
+    SpecRoute r;
+    if ((uint64_t)C * F == 0 || (uint64_t)C * F >= 0xFFFFFFE0ull || n == 0 || n > IGDSP_MAX_PAYLOAD) return r;
+    r.grid = (uint32_t)(((uint64_t)C + kSpecWaves - 1) / kSpecWaves);
+    r.threads = kSpecWaves * 64;
+    r.lds = kSpecLdsBytes;
+    return r;
+}
+
 // ---- igdsp_tx_flush (launch_tx_staged): a wave owns kTsLegs staged legs (runs) of the flush; lanes 0 .. kTsLegs-1 decide, the
 // whole wave writes the packets.  No dynamic LDS: each wave's records (kTsLegs x IGDSP_STAGE_DEPTH) are static.
 constexpr int kTsWaves = 4;

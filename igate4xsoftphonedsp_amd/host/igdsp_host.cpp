@@ -985,6 +985,57 @@ int igdsp_host_dbuf_state(void *v, igdsp_dbuf_state *out)
     return IGDSP_OK;
 }
 
+// ---- the spectrum graph, no context needed
+SpectrumGraph::SpectrumGraph(uint32_t samples_per_frame, uint32_t hop_frames, float alpha) : n(samples_per_frame), fftSize(IGDSP_SPEC_N)
+{
+    cfg.hop_frames = hop_frames;
+    cfg.alpha = alpha;
+    ok = n >= 1 && n <= IGDSP_MAX_PAYLOAD && hop_frames >= 1 && alpha > 0.0f && alpha <= 1.0f;
+    initSpectrumGraph();
+}
+
+void SpectrumGraph::initSpectrumGraph()
+{
+    d_fftAvg = (float)(1.0 - 1.0e-2 * 75);
+    spectClear();
+}
+
+void SpectrumGraph::spectClear()
+{
+    std::memset(&state, 0, sizeof(state));
+    std::memset(&last, 0, sizeof(last));
+    for (int k = 0; k < IGDSP_SPEC_BINS; ++k) d_realFftData[k] = d_iirFftData[k] = IGDSP_SPEC_FLOOR_DB;
+}
+
+int SpectrumGraph::feed(const int16_t *frame)
+{
+    if (!ok || !frame) return IGDSP_EINVAL;
+    igdsp_spec_rec rec;
+    const int rc = igdsp_spec_frame(&state, frame, n, &cfg, &rec, d_realFftData);
+    if (rc != IGDSP_OK) return rc;
+    if (!(rec.flags & IGDSP_SPEC_HOP)) return 0;
+    std::memcpy(d_iirFftData, state.avg, sizeof(d_iirFftData));
+    last = rec;
+    return 1;
+}
+
+void *igdsp_host_spect_new(uint32_t samples_per_frame, uint32_t hop_frames, float alpha)
+{
+    SpectrumGraph *g = new (std::nothrow) SpectrumGraph(samples_per_frame, hop_frames, alpha);
+    if (g && !g->ok) { delete g; g = nullptr; }
+    return g;
+}
+void igdsp_host_spect_free(void *v) { delete static_cast<SpectrumGraph *>(v); }
+int igdsp_host_spect_feed(void *v, const int16_t *frame)
+{
+    if (!v || !frame) return IGDSP_EINVAL;
+    return static_cast<SpectrumGraph *>(v)->feed(frame);
+}
+void igdsp_host_spect_clear(void *v) { if (v) static_cast<SpectrumGraph *>(v)->spectClear(); }
+const float *igdsp_host_spect_real(void *v) { return v ? static_cast<SpectrumGraph *>(v)->d_realFftData : nullptr; }
+const float *igdsp_host_spect_iir(void *v) { return v ? static_cast<SpectrumGraph *>(v)->d_iirFftData : nullptr; }
+float igdsp_host_spect_fft_avg(void *v) { return v ? static_cast<SpectrumGraph *>(v)->d_fftAvg : 0.0f; }
+
 // ---- conference receive levels, no context needed
 void *igdsp_host_levels_new(uint32_t n_channels)
 {

@@ -264,6 +264,28 @@ public:
     uint32_t fill() const { return state.len; }   // the delay, samples
 };
 
+// The spectrum graph the reference declares (roip_ed137.h:510-522: fftSize, d_realFftData, d_iirFftData, d_fftAvg, spectValueChanged,
+// spectClear) and initialises (initSpectrumGraph, roip_ed137.cpp:6350-6365) without ever computing a transform, without a context: one
+// channel through igdsp_spec_frame.  d_fftAvg keeps the reference's value 1.0 - 1.0e-2 * 75; the average's gain is 1 - d_fftAvg = 0.25
+// unless the constructor is given another.  A gateway of the reference's size keeps one per displayed leg; igdsp_spectrum takes the same
+// states for thousands of channels.
+class SpectrumGraph {
+public:
+    explicit SpectrumGraph(uint32_t samples_per_frame = IGDSP_SAMPLES_PER_FRAME, uint32_t hop_frames = 1, float alpha = 0.25f);
+    uint32_t n;
+    igdsp_spec_cfg cfg;
+    bool ok;                                 // n in 1 .. 256, hop_frames >= 1, alpha in (0, 1]
+    int fftSize;                             // IGDSP_SPEC_N
+    float d_fftAvg;                          // 1.0 - 1.0e-2 * 75, as the reference sets it
+    float d_realFftData[IGDSP_SPEC_BINS];    // the last raw spectrum, dBFS
+    float d_iirFftData[IGDSP_SPEC_BINS];     // the averaged spectrum, dBFS
+    igdsp_spec_state state;
+    igdsp_spec_rec last;                     // the record of the last frame that computed a spectrum
+    void initSpectrumGraph();                // both arrays -70 dBFS, d_fftAvg, the state reset
+    void spectClear();                       // the state reset: history silent, both arrays -70 dBFS
+    int feed(const int16_t *frame);          // n samples in; 1 when the frame computed a spectrum (the reference's spectValueChanged), 0 when not; negative: an error
+};
+
 class RoIP_ED137 {
 public:
     // Unlike the reference singleton (roip_ed137.cpp:192) the instance owns an igdsp context; device < 0
@@ -390,6 +412,16 @@ int   igdsp_host_dbuf_put(void *v, const int16_t *frame);
 int   igdsp_host_dbuf_get(void *v, int16_t *frame);
 int   igdsp_host_dbuf_fill(void *v);
 int   igdsp_host_dbuf_state(void *v, igdsp_dbuf_state *out);
+// the spectrum graph without a context (SpectrumGraph): NULL from _new for sizes igdsp_spec_frame rejects; _feed one frame in (1: it
+// computed a spectrum, 0: not, IGDSP_EINVAL for a NULL argument); _real / _iir the two arrays of 512 floats, owned by the handle; _clear
+// is spectClear; _fft_avg is d_fftAvg
+void *igdsp_host_spect_new(uint32_t samples_per_frame, uint32_t hop_frames, float alpha);
+void  igdsp_host_spect_free(void *v);
+int   igdsp_host_spect_feed(void *v, const int16_t *frame);
+void  igdsp_host_spect_clear(void *v);
+const float *igdsp_host_spect_real(void *v);
+const float *igdsp_host_spect_iir(void *v);
+float igdsp_host_spect_fft_avg(void *v);
 // Meter output on the reference's other channel: AudioMeter (audiometer.cpp:11-34) reads ASCII decimal levels from the
 // FIFO /tmp/capturefifo<card>, 32 bytes per read, and emits onValueChanged(int(float(v*100.0/30000.0))).  These write
 // such records, so the reference's own meter consumer can be fed from igdsp_poll().rms.  open() waits up to

@@ -43,7 +43,8 @@ extern "C" {
  *    igdsp_snd_vu_t, igdsp_snd_vu); the tone generator (IGDSP_TONE_*, igdsp_tone_desc, igdsp_tone_seg, igdsp_tone_plan,
  *    igdsp_tone_state, igdsp_tone_plan_build, igdsp_tone_frame, igdsp_tone_generate); the rate converter (IGDSP_RS_*, igdsp_rs_state,
  *    igdsp_resample, igdsp_rs_frame, igdsp_rs_taps); the sound port's delay buffer (IGDSP_DBUF_*, igdsp_dbuf_state, igdsp_dbuf_run,
- *    igdsp_dbuf_step). */
+ *    igdsp_dbuf_step); the spectrum graph (IGDSP_SPEC_*, igdsp_spec_state, igdsp_spec_cfg, igdsp_spec_rec, igdsp_spectrum,
+ *    igdsp_spec_frame, igdsp_spec_tables). */
 #define IGDSP_ABI_VERSION 3
 
 /* ---- error codes (0 == PJ_SUCCESS-style success) ------------------------- */
@@ -1380,6 +1381,82 @@ int igdsp_dbuf_run(igdsp_ctx *ctx, const uint8_t *d_ops /* [T][C] */, const int1
                    uint16_t *d_fill, igdsp_frame_stats *d_stats, void *stream);
 int igdsp_dbuf_step(igdsp_dbuf_state *st, uint32_t op, const int16_t *in, uint32_t samples_per_frame,
                     uint32_t max_samples, int16_t *out, uint32_t *flag);
+
+/* ---- Spectrum: the spectrum graph's 1 024-point transform, per channel and hop ------------------------------------------------------------
+ * The reference declares a spectrum graph and never computes one: DEFAULT_FFT_SIZE 1024 (roip_ed137.h:118), fftSize, d_realFftData,
+ * d_iirFftData, signalInput[1024], d_fftAvg, spectValueChanged(int), spectClear() (roip_ed137.h:510-522); initSpectrumGraph()
+ * (roip_ed137.cpp:6350-6365) fills both arrays with -70 dBFS and sets d_fftAvg = 1.0 - 1.0e-2 * 75; the fftw calls of the teardown
+ * (roip_ed137.cpp:1705-1710) are commented out.  igdsp_spectrum is that pipeline for every channel of a launch: 1 024 points, a raw
+ * dBFS array, and an array averaged in the dB domain that starts at -70 with gain 0.25.  It takes the rows igdsp_plc_conceal leaves
+ * (or a port's rows ahead of igdsp_conf_mix), G.711 codes or PCM.  All arithmetic is fp32.
+ *
+ * STATE.  igdsp_spec_state is opaque to callers: the last 1 024 samples (oldest first), the averaged array, the frames since the last
+ * hop, a hop count and a flag that says the averaged array is live.  All-zero is the reset state: its history is silence and its
+ * averaged array reads as IGDSP_SPEC_FLOOR_DB in every bin.  A state is READ as: since >= hop_frames reads as hop_frames - 1; only
+ * bit IGDSP_SPEC_LIVE of flags counts; and it is written back so (flags = IGDSP_SPEC_LIVE, the averaged array materialised), so a
+ * garbage state stays in bounds.  hops is telemetry and wraps.
+ *
+ * PER FRAME f of channel c, n = samples_per_frame (1..256), cfg = {hop_frames >= 1, alpha in (0, 1]} (NULL: {1, 0.25f}):
+ *   1. the row's n samples are decoded (d_g711[f][c][n] with d_codec[c]: IGDSP_PT_PCMA is A-law, anything else mu-law; or
+ *      d_pcm[f][c][n]) and appended to the history, the oldest n samples leave;  since += 1
+ *   2. if since == hop_frames, a hop:  since = 0;  x[0 .. 1023] = the history, oldest first
+ *        y[i]   = (float)x[i] * w[i],  w the periodic Hann window 0.5 - 0.5 cos(2 pi i / 1024)
+ *        X[k]   = sum_i y[i] e^(-2 pi i k i / 1024),  k = 0 .. IGDSP_SPEC_BINS - 1   (bins 0 .. 511: the Nyquist bin is dropped)
+ *        P[k]   = (re^2 + im^2) * 2^-46        (a full-scale sine on a bin centre: |X| = 32768 * 512 / 2 = 2^23, 0 dBFS)
+ *        raw[k] = 10 log10f(P[k] + 1e-20f)
+ *        avg[k] += alpha * (raw[k] - avg[k]);  hops += 1
+ * The window and the twiddle factors are committed constants (csrc/igdsp_spec_tab.h, igdsp_spec_tables); no sinf / cosf runs.  The
+ * transform's order of operations is the library's own (three radix-8 passes over the samples packed as 512 complex points, then a
+ * split pass): results agree with a float64 evaluation of the formulas within 0.05 dB on every bin within 60 dB of the frame's total
+ * power, not bit for bit with another FFT.  On the device a channel's results are bit for bit the same whatever n_channels, its
+ * position, and the way the frames are split over launches.
+ *
+ * OUTPUTS, each optional (NULL: skipped).  d_rec[f][c]: peak_db / peak_bin = the maximum of raw over the 512 bins (the lowest bin
+ * on a tie) and flags = IGDSP_SPEC_HOP when the frame computed a spectrum; a frame without a hop writes an all-zero record.
+ * d_avg[c][512]: the averaged array after the launch's last frame.  d_raw[c][512]: the last raw spectrum of the launch, written only
+ * for channels that hopped in this launch.
+ *
+ * ARGUMENTS.  samples_per_frame and cfg out of range: IGDSP_EINVAL, whether or not there is work.  n_channels == 0 or n_frames == 0:
+ * nothing to do.  Exactly one of d_g711 (with d_codec) and d_pcm; d_state is required.  n_channels * n_frames < 2^32 - 32
+ * (IGDSP_ERANGE).  d_pcm 2-byte, d_state, d_avg, d_raw 4-byte, d_rec 8-byte aligned.  The state and the outputs may overlap neither
+ * an input nor each other.  Enqueued on `stream`, not synchronised.
+ *
+ * igdsp_spec_frame (host only, no GPU): one frame of one channel by the same rule, row = n PCM samples; rec (optional) as d_rec,
+ * raw (optional, 512 floats) is written on a hop only.  IGDSP_EINVAL for a NULL state or row, n or cfg out of range.
+ * igdsp_spec_tables (host only): the window (1 024 floats) and the twiddle factors t[k] = (cos(2 pi k / 1024), -sin(2 pi k / 1024)),
+ * k = 0 .. 1023, as 2 048 floats; either pointer may be NULL.
+ *
+ * Fidelity.  PINNED to the reference's declarations: 1 024 points, -70 dBFS initial arrays, the gain 0.25 (= 1 - d_fftAvg).
+ * UNVERIFIED: the reference computes no spectrum, so window, scaling and the dB-domain average follow the receiver whose constants
+ * it copied (a Hann window, dBFS of a full-scale sine, avg += gain * (raw - avg)).  DIFFERENT ON PURPOSE: the rows' own rate only,
+ * full rows only (feed concealed PCM), one FFT size. */
+#define IGDSP_SPEC_N        1024    /* points = samples of history                              */
+#define IGDSP_SPEC_BINS      512    /* bins 0 .. 511; the Nyquist bin is dropped                */
+#define IGDSP_SPEC_FLOOR_DB (-70.0f) /* what a reset state's averaged array reads as            */
+#define IGDSP_SPEC_HOP    0x0001    /* igdsp_spec_rec.flags: this frame computed a spectrum     */
+#define IGDSP_SPEC_LIVE   0x0001    /* igdsp_spec_state.flags: the averaged array is live       */
+typedef struct igdsp_spec_state {
+    int16_t  hist[IGDSP_SPEC_N];    /* the last 1 024 samples, oldest first                     */
+    float    avg[IGDSP_SPEC_BINS];  /* the averaged array, dBFS (valid with IGDSP_SPEC_LIVE)    */
+    uint32_t since;                 /* frames since the last hop                                */
+    uint32_t hops;                  /* telemetry, wrapping                                      */
+    uint32_t flags, reserved;
+} igdsp_spec_state;                 /* 4112 bytes; all-zero = reset */
+typedef struct igdsp_spec_cfg {
+    uint32_t hop_frames;            /* >= 1: a spectrum every hop_frames frames                 */
+    float    alpha;                 /* (0, 1]: the average's gain                               */
+} igdsp_spec_cfg;
+typedef struct igdsp_spec_rec {
+    uint16_t peak_bin, flags;
+    float    peak_db;
+} igdsp_spec_rec;                   /* 8 bytes */
+int igdsp_spectrum(igdsp_ctx *ctx, const uint8_t *d_g711 /* [F][C][n] */, const uint8_t *d_codec /* [C] */, const int16_t *d_pcm /* [F][C][n] */,
+                   uint32_t n_channels, uint32_t n_frames, uint32_t samples_per_frame, const igdsp_spec_cfg *cfg,
+                   igdsp_spec_state *d_state /* [C], in and out */, igdsp_spec_rec *d_rec /* [F][C] */, float *d_avg /* [C][512] */,
+                   float *d_raw /* [C][512] */, void *stream);
+int igdsp_spec_frame(igdsp_spec_state *st, const int16_t *row, uint32_t samples_per_frame, const igdsp_spec_cfg *cfg,
+                     igdsp_spec_rec *rec, float *raw);
+int igdsp_spec_tables(const float **window, const float **twiddle);
 
 /* ---- synthetic input generators (device side; SURVEY 8(d) definitions) ---------
  * D-uniform: byte k of global byte index g is
