@@ -102,6 +102,17 @@ SPEC_HOP, SPEC_LIVE = 1, 1
 SPEC_STATE = np.dtype([("hist", "<i2", (SPEC_N,)), ("avg", "<f4", (SPEC_BINS,)), ("since", "<u4"), ("hops", "<u4"), ("flags", "<u4"),
                        ("reserved", "<u4")], align=True)                                          # igdsp_spec_state, 4112 bytes
 SPEC_REC = np.dtype([("peak_bin", "<u2"), ("flags", "<u2"), ("peak_db", "<f4")], align=True)     # igdsp_spec_rec, 8 bytes
+# the tone detector (igdsp_tone_detect / igdsp_tdet_frame)
+TDET_MAX_FREQ, TDET_HIST = 16, 128
+TDET_ON0, TDET_OFF0, TDET_ON1, TDET_OFF1, TDET_EVENT_DEFAULT = 1, 2, 4, 8, 15
+TDET_THR = np.dtype([("min_amp", "<u2"), ("rel_q8", "<u2"), ("fwd_q8", "<u2"), ("rev_q8", "<u2"), ("frac_q8", "<u2"), ("min_on", "u1"),
+                     ("min_off", "u1")], align=True)                                               # igdsp_tdet_thr, 12 bytes
+TDET_PLAN = np.dtype([("clock_rate", "<u4"), ("n_lo", "u1"), ("n_hi", "u1"), ("reserved", "u1", (2,)), ("thr", TDET_THR),
+                      ("step", "<u4", (TDET_MAX_FREQ,))], align=True)                              # igdsp_tdet_plan, 84 bytes
+TDET_STATE = np.dtype([("hist", "<i2", (TDET_HIST,)), ("cur", "u1"), ("cand", "u1"), ("run", "u1"), ("off", "u1"), ("len", "<u2"),
+                       ("reserved", "<u2")], align=True)                                           # igdsp_tdet_state, 264 bytes
+TDET_REC = np.dtype([("hit", "u1", (2,)), ("cur", "u1"), ("flags", "u1"), ("len", "<u2"), ("code", "u1"), ("reserved", "u1")], align=True)
+TDET_EVENT = np.dtype([("channel", "<u4"), ("frame", "<u4"), ("rec", TDET_REC)], align=True)     # igdsp_tdet_event, 16 bytes
 CHAN_PROBE = np.dtype([("run", "<u4"), ("alarms", "<u4")], align=True)
 # the jitter buffer (igdsp_jb_receive / igdsp_jb_report)
 JB_STATE = np.dtype(
@@ -279,6 +290,13 @@ PROTOTYPES = [
     ("igdsp_spectrum", _int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("igdsp_spec_frame", _int, [_vp, _vp, _u32, _vp, _vp, _vp]),
     ("igdsp_spec_tables", _int, [C.POINTER(_vp), C.POINTER(_vp)]),
+    ("igdsp_tdet_plan_build", _int, [_u32, _vp, _u32, _u32, _vp, _vp]),
+    ("igdsp_tdet_plan_dtmf", _int, [_u32, _vp]),
+    ("igdsp_tdet_digit", _int, [_u32]),
+    ("igdsp_tdet_table", _int, [_vp, _u32, _vp]),
+    ("igdsp_tdet_frame", _int, [_vp, _vp, _vp, _u32, _vp]),
+    ("igdsp_tdet_work_bytes", C.c_size_t, [_u32, _u32, _int]),
+    ("igdsp_tone_detect", _int, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _u32, _vp, _vp, _vp]),
     ("igdsp_g726_reorder", _int, [_vp, _vp, _vp, _u64, _int, _vp]),
     ("igdsp_gen_uniform", _int, [_vp, _vp, _u64, _u64, _u64, _vp]),
     ("igdsp_dev_alloc", _int, [_vp, C.POINTER(_vp), C.c_size_t]),
@@ -318,7 +336,8 @@ INTERNAL = {name: _PUBLIC[twin] for name, twin in INTERNAL_TWIN.items()}
 INTERNAL["igdsp_internal_tx_copy"] = (_int, [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp])
 
 # A yardstick whose name is not of the *_copy / *_fill form: the same derivation, a table of its own; internal() consults both
-INTERNAL_MORE_TWIN = {"igdsp_internal_dbuf_move": "igdsp_dbuf_run", "igdsp_internal_spec_move": "igdsp_spectrum"}
+INTERNAL_MORE_TWIN = {"igdsp_internal_dbuf_move": "igdsp_dbuf_run", "igdsp_internal_spec_move": "igdsp_spectrum",
+                      "igdsp_internal_tdet_move": "igdsp_tone_detect"}
 INTERNAL_MORE = {name: _PUBLIC[twin] for name, twin in INTERNAL_MORE_TWIN.items()}
 
 _lib = None
@@ -495,6 +514,62 @@ def spec_frame(state, row, cfg=None, want_raw=True):
     if rc != 0:
         raise IgdspError(rc, "igdsp_spec_frame")
     return rec, (raw if want_raw and rec["flags"] & SPEC_HOP else None)
+
+
+def tdet_plan_build(freq_lo, freq_hi=(), clock_rate: int = 8000, thr=None) -> np.ndarray:
+    """igdsp_tdet_plan_build (host only, no GPU): the low group's and the high group's frequencies in Hz, thr a TDET_THR record or None
+    (the defaults); returns one TDET_PLAN record."""
+    f = np.asarray(list(freq_lo) + list(freq_hi), "<u2")
+    out = np.zeros((), TDET_PLAN)
+    t = None if thr is None else np.asarray(thr, TDET_THR)
+    rc = load().igdsp_tdet_plan_build(clock_rate, f.ctypes.data_as(_vp), len(freq_lo), len(freq_hi), None if t is None else t.ctypes.data_as(_vp),
+                                      out.ctypes.data_as(_vp))
+    if rc != 0:
+        raise IgdspError(rc, "igdsp_tdet_plan_build")
+    return out
+
+
+def tdet_plan_dtmf(clock_rate: int = 8000) -> np.ndarray:
+    """igdsp_tdet_plan_dtmf (host only, no GPU): the 4 + 4 DTMF plan with the default thresholds."""
+    out = np.zeros((), TDET_PLAN)
+    rc = load().igdsp_tdet_plan_dtmf(clock_rate, out.ctypes.data_as(_vp))
+    if rc != 0:
+        raise IgdspError(rc, "igdsp_tdet_plan_dtmf")
+    return out
+
+
+def tdet_digit(code: int) -> str:
+    """igdsp_tdet_digit: the DTMF plan's character of a code, "" for any other code."""
+    v = int(load().igdsp_tdet_digit(int(code)))
+    return chr(v) if v else ""
+
+
+def tdet_table(plan, n: int) -> np.ndarray:
+    """igdsp_tdet_table (host only, no GPU): int16 [n_lo + n_hi][2][n], the cosine then the sine column of every frequency."""
+    assert plan.dtype == TDET_PLAN
+    nf = min(int(plan["n_lo"]), 8) + min(int(plan["n_hi"]), 8)
+    out = np.zeros((nf, 2, n), "<i2")
+    rc = load().igdsp_tdet_table(plan.ctypes.data_as(_vp), n, out.ctypes.data_as(_vp))
+    if rc != 0:
+        raise IgdspError(rc, "igdsp_tdet_table")
+    return out
+
+
+def tdet_frame(plan, state, row):
+    """igdsp_tdet_frame (host only, no GPU): one frame of one channel.  plan a TDET_PLAN record, state a TDET_STATE record updated in
+    place, row the frame's PCM (int16 [n]).  Returns the frame's TDET_REC record."""
+    assert plan.dtype == TDET_PLAN and state.dtype == TDET_STATE and state.flags["C_CONTIGUOUS"] and state.flags["WRITEABLE"]
+    row = np.ascontiguousarray(row, dtype=np.int16)
+    rec = np.zeros((), TDET_REC)
+    rc = load().igdsp_tdet_frame(plan.ctypes.data_as(_vp), state.ctypes.data_as(_vp), row.ctypes.data_as(_vp), len(row), rec.ctypes.data_as(_vp))
+    if rc != 0:
+        raise IgdspError(rc, "igdsp_tdet_frame")
+    return rec
+
+
+def tdet_work_bytes(n_channels: int, n_frames: int, with_rec: bool) -> int:
+    """igdsp_tdet_work_bytes (host only, no GPU): bytes of igdsp_tone_detect's d_work for a launch of this shape."""
+    return int(load().igdsp_tdet_work_bytes(n_channels, n_frames, 1 if with_rec else 0))
 
 
 def spec_tables():
@@ -757,6 +832,14 @@ class Context:
         c = _spec_cfg(cfg)
         self._ck(self.L.igdsp_spectrum(self.h, _ptr(g711), _ptr(codec), _ptr(pcm), C_, F_, n, None if c is None else C.cast(C.pointer(c), _vp),
                                        _ptr(state), _ptr(rec), _ptr(avg), _ptr(raw), stream), "igdsp_spectrum")
+
+    def tone_detect(self, plans, state, C_, F_, n, g711=None, codec=None, pcm=None, n_plans=1, plan_of=None, event_mask=0, rec=None, events=None,
+                    event_cap=0, event_count=None, work=None, stream=None):
+        """igdsp_tone_detect: exactly one of g711 [F][C][n] u8 (+ codec [C]) / pcm [F][C][n] int16; plans [n_plans] TDET_PLAN, plan_of [C]
+        u16 or None (plan 0); state [C] TDET_STATE (in and out) -> rec [F][C] TDET_REC, events [event_cap] TDET_EVENT with event_count [2]
+        u32 and work (tdet_work_bytes), each optional."""
+        self._ck(self.L.igdsp_tone_detect(self.h, _ptr(g711), _ptr(codec), _ptr(pcm), _ptr(plans), n_plans, _ptr(plan_of), C_, F_, n, event_mask,
+                                          _ptr(state), _ptr(rec), _ptr(events), event_cap, _ptr(event_count), _ptr(work), stream), "igdsp_tone_detect")
 
     def bss_select(self, info, group_ptr, members, n_members, state, words, C_, G_, F_, n=160, payload=None, codec=None, pcm=None,
                    length=None, gain=None, mute=None, vote_frames=0, sel=None, out=None, stats=None, stream=None):

@@ -470,4 +470,35 @@ inline Verdict spec_run(P d_g711, P d_codec, P d_pcm, uint32_t C, uint32_t F, ui
     return kRun;
 }
 
+// ---- tone detector.  The frame length is checked whether or not there is work.  Nothing to do with a list still writes the counts, so
+// d_event_count's own rules apply before the shape's
+inline Verdict tdet_run(P d_g711, P d_codec, P d_pcm, P d_plans, uint32_t n_plans, P d_plan_of, uint32_t C, uint32_t F, uint32_t n, P d_state,
+                        P d_rec, P d_events, uint32_t event_cap, P d_event_count, P d_work)
+{
+    if (n < 2u || n > IGDSP_MAX_PAYLOAD || (n & 1u)) return kInvalid;
+    if (misaligned(4, {d_event_count}) || misaligned(16, {d_work}) || (d_event_count && !d_work)) return kInvalid;
+    if (d_event_count && event_cap != 0u && !d_events) return kInvalid;
+    if (empty(C, F)) return d_event_count ? kRun : kNothing;              // the counts are written as 0
+    if (!exactly_one(d_g711, d_pcm) || (d_g711 && !d_codec) || !d_state || !d_plans || n_plans == 0u) return kInvalid;
+    if ((uint64_t)C * F >= 0xFFFFFFE0ull) return reject(IGDSP_ERANGE);
+    // the kernel reads a row two samples at a time (n is even, so every row starts as the buffer does) and stores an event as 16 bytes
+    if (misaligned(2, {d_g711, d_plan_of}) || misaligned(4, {d_pcm, d_plans, d_state}) || misaligned(8, {d_rec}) || misaligned(16, {d_events})) return kInvalid;
+    const uint64_t frames = (uint64_t)C * F;
+    const bool list = d_event_count != nullptr;
+    struct Buf { P p; uint64_t bytes; };
+    const Buf ins[5] = {{d_g711, frames * n}, {d_g711 ? d_codec : nullptr, C}, {d_pcm, frames * n * 2u},
+                        {d_plans, (uint64_t)n_plans * sizeof(igdsp_tdet_plan)}, {d_plan_of, (uint64_t)C * 2u}};
+    const Buf outs[5] = {{d_state, (uint64_t)C * sizeof(igdsp_tdet_state)}, {d_rec, frames * sizeof(igdsp_tdet_rec)},
+                         {list ? d_events : nullptr, (uint64_t)event_cap * sizeof(igdsp_tdet_event)}, {d_event_count, 8u},
+                         {list ? d_work : nullptr, tdet_work_bytes(C, F, d_rec != nullptr)}};
+    for (int i = 0; i < 5; ++i) {
+        for (const Buf &b : ins)
+            if (ranges_overlap(outs[i].p, outs[i].bytes, b.p, b.bytes)) return reject(IGDSP_EINVAL, "the state and the outputs must not overlap an input");
+        for (int j = 0; j < i; ++j)
+            if (ranges_overlap(outs[i].p, outs[i].bytes, outs[j].p, outs[j].bytes))
+                return reject(IGDSP_EINVAL, "the state and the outputs must not overlap each other");
+    }
+    return kRun;
+}
+
 }  // namespace igdsp::args

@@ -156,6 +156,18 @@ hipError_t launch_dbuf_run(const LaunchCfg &cfg, const uint8_t *ops, const int16
 hipError_t launch_spectrum(const LaunchCfg &cfg, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm, uint32_t C, uint32_t F, uint32_t n,
                            uint32_t hop_frames, float alpha, igdsp_spec_state *state, igdsp_spec_rec *rec, float *avg, float *raw, bool yardstick,
                            hipStream_t s);
+// the link stage's scan (igdsp_k_link.hip), which igdsp_tone_detect's list launches as well: counts[0 .. N) behind the 16-byte head of
+// `head` -> exclusive offsets in place; first: start at 0, else at head[0]; last: event_count = {total, min(total, cap)}.  One block of
+// kLinkScanThreads
+__global__ void k_link_scan(uint32_t *head, uint64_t N, uint32_t first, uint32_t last, uint32_t cap, uint32_t *event_count);
+// igdsp_tone_detect: exactly one of g711 (with codec) and pcm; plan_of, rec, events may each be nullptr; event_count nullptr = no list
+// (work unused), else work is igdsp_tdet_work_bytes bytes, 16-byte aligned; event_mask 0 = IGDSP_TDET_EVENT_DEFAULT.  C * F == 0 with a
+// list: only the two counts are written (0).  yardstick: the compute-free form, the same rows into the same buffers, the same records,
+// state and list passes, no table, dot product, decision or debounce (records are all-zero, the debounce fields stay as they were)
+hipError_t launch_tone_detect(const LaunchCfg &cfg, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm, const igdsp_tdet_plan *plans,
+                              uint32_t n_plans, const uint16_t *plan_of, uint32_t C, uint32_t F, uint32_t n, uint32_t event_mask,
+                              igdsp_tdet_state *state, igdsp_tdet_rec *rec, igdsp_tdet_event *events, uint32_t event_cap, uint32_t *event_count,
+                              void *work, bool yardstick, hipStream_t s);
 hipError_t launch_wav_expand(const LaunchCfg &cfg, const uint8_t *payload, uint32_t C, uint32_t F, uint32_t n, uint32_t rate,
                              uint8_t *files, uint64_t file_stride, hipStream_t s);
 hipError_t launch_g726(const LaunchCfg &cfg, const uint8_t *in, uint8_t *out, uint64_t n_bytes, int mode, hipStream_t s);

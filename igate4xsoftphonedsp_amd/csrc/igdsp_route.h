@@ -1058,6 +1058,48 @@ inline SpecRoute spec_route(uint32_t C, uint32_t F, uint32_t n)
     return r;
 }
 
+// ---- igdsp_tone_detect (launch_tone_detect): k_tdet<COPY, E0> (+ k_tdet_list<WRITE> and the link stage's k_link_scan for a list).
+// A DPP row of 16 lanes serves one channel for all the launch's frames (the debounce is sequential in time): lanes 0..7 are the low
+// group's bins, lanes 8..15 the high group's, so one three-step butterfly over eight lanes finds both groups' maxima.  A wave is four
+// channels, a block kTdetWaves waves.  The block's LDS holds one plan's reference table (16 bytes per two sample pairs and lane: the
+// cosine and sine values), and per channel 128 + 256 values v: the history and the frame, which the 16 lanes read as broadcasts.  The
+// block walks the distinct plans of its channels one after the other (one pass when they share a plan).  E0: how evaluation 0's window
+// is aligned (n % 8 == 0: 8-byte reads, n % 4 == 0: dwords, else halves).  Registers: the route is written for kTdetResident blocks per CU (80 VGPRs).
+// The list: the records are dense (in d_rec, or in d_work when there is none); k_tdet_list counts the event lanes per (frame, wave of 64
+// channels), k_link_scan turns the counts into offsets and writes the two totals, k_tdet_list<true> stores the events.
+constexpr int kTdetWaves = 8;                             // waves per block
+constexpr uint32_t kTdetChans = kTdetWaves * 4u;          // channels per block
+constexpr uint32_t kTdetResident = 3;                     // blocks per CU: 3 x 40 KiB of LDS, 6 waves per SIMD
+constexpr uint32_t kTdetBuf = 128u + 256u;                // values per channel in LDS
+constexpr uint32_t kTdetLdsBytes = 128u * 16u * 8u + kTdetChans * kTdetBuf * 2u + kTdetChans * 4u;   // table, buffers, the channels' plans
+constexpr int kTdetListWaves = 4;
+struct TdetRoute {
+    uint32_t grid = 0, threads = 0, lds = 0;
+    uint32_t e0 = 0;                       // k_tdet<, E0>: how evaluation 0's window is aligned in LDS (0: n % 8 == 0, 1: n % 4 == 0, 2: else)
+    uint32_t waves = 0;                    // waves of 64 channels: the counts' row
+    uint32_t list_grid = 0;                // k_tdet_list, both passes (0: no list)
+    uint64_t counts_bytes = 0;             // d_work: head + counts, rounded to 16
+    uint64_t work_bytes = 0;               // d_work in all: + the records when d_rec is NULL
+};
+inline uint64_t tdet_counts_bytes(uint32_t C, uint32_t F) { return kLinkWorkHead + (((uint64_t)F * link_waves(C) * 4u + 15u) & ~15ull); }
+inline uint64_t tdet_work_bytes(uint32_t C, uint32_t F, bool with_rec) { return tdet_counts_bytes(C, F) + (with_rec ? 0u : (uint64_t)C * F * 8u); }
+inline TdetRoute tdet_route(uint32_t C, uint32_t F, uint32_t n, bool list, bool with_rec)
+{
+    TdetRoute r;
+    if ((uint64_t)C * F == 0 || (uint64_t)C * F >= 0xFFFFFFE0ull || n < 2u || n > IGDSP_MAX_PAYLOAD || (n & 1u)) return r;
+    r.grid = (uint32_t)(((uint64_t)C + kTdetChans - 1u) / kTdetChans);
+    r.threads = kTdetWaves * 64;
+    r.lds = kTdetLdsBytes;
+    r.e0 = n % 8u == 0u ? 0u : (n % 4u == 0u ? 1u : 2u);
+    r.waves = link_waves(C);
+    if (list) {
+        r.list_grid = (uint32_t)(((uint64_t)F * r.waves + kTdetListWaves - 1u) / kTdetListWaves);
+        r.counts_bytes = tdet_counts_bytes(C, F);
+        r.work_bytes = tdet_work_bytes(C, F, with_rec);
+    }
+    return r;
+}
+
 // ---- igdsp_tx_flush (launch_tx_staged): a wave owns kTsLegs staged legs (runs) of the flush; lanes 0 .. kTsLegs-1 decide, the
 // whole wave writes the packets.  No dynamic LDS: each wave's records (kTsLegs x IGDSP_STAGE_DEPTH) are static.
 constexpr int kTsWaves = 4;

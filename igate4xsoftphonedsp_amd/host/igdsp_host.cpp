@@ -1036,6 +1036,51 @@ const float *igdsp_host_spect_real(void *v) { return v ? static_cast<SpectrumGra
 const float *igdsp_host_spect_iir(void *v) { return v ? static_cast<SpectrumGraph *>(v)->d_iirFftData : nullptr; }
 float igdsp_host_spect_fft_avg(void *v) { return v ? static_cast<SpectrumGraph *>(v)->d_fftAvg : 0.0f; }
 
+// ---- in-band DTMF on one leg, no context needed
+DtmfReceiver::DtmfReceiver(uint32_t samples_per_frame, uint32_t clock_rate) : n(samples_per_frame)
+{
+    ok = igdsp_tdet_plan_dtmf(clock_rate, &plan) == IGDSP_OK && n >= 2 && n <= IGDSP_MAX_PAYLOAD && (n & 1u) == 0;
+    newCall();
+}
+
+void DtmfReceiver::newCall()
+{
+    std::memset(&state, 0, sizeof(state));
+    std::memset(&last, 0, sizeof(last));
+    std::memset(dialled, 0, sizeof(dialled));
+    count = 0;
+}
+
+int DtmfReceiver::feed(const int16_t *frame)
+{
+    if (!ok || !frame) return IGDSP_EINVAL;
+    const int rc = igdsp_tdet_frame(&plan, &state, frame, n, &last);
+    if (rc != IGDSP_OK) return rc;
+    if (!(last.flags & (IGDSP_TDET_ON0 | IGDSP_TDET_ON1))) return 0;
+    const int ch = igdsp_tdet_digit(state.cur ? state.cur : last.code);    // the digit that is up (an ON is the frame's last event unless it also ended)
+    if (ch) {
+        if (count == sizeof(dialled) - 1) { std::memmove(dialled, dialled + 1, count - 1); --count; }
+        dialled[count++] = (char)ch;
+        dialled[count] = 0;
+    }
+    return ch;
+}
+
+void *igdsp_host_dtmf_new(uint32_t samples_per_frame, uint32_t clock_rate)
+{
+    DtmfReceiver *r = new (std::nothrow) DtmfReceiver(samples_per_frame, clock_rate);
+    if (r && !r->ok) { delete r; r = nullptr; }
+    return r;
+}
+void igdsp_host_dtmf_free(void *v) { delete static_cast<DtmfReceiver *>(v); }
+int igdsp_host_dtmf_feed(void *v, const int16_t *frame)
+{
+    if (!v || !frame) return IGDSP_EINVAL;
+    return static_cast<DtmfReceiver *>(v)->feed(frame);
+}
+const char *igdsp_host_dtmf_digits(void *v) { return v ? static_cast<DtmfReceiver *>(v)->digits() : nullptr; }
+void igdsp_host_dtmf_new_call(void *v) { if (v) static_cast<DtmfReceiver *>(v)->newCall(); }
+
 // ---- conference receive levels, no context needed
 void *igdsp_host_levels_new(uint32_t n_channels)
 {

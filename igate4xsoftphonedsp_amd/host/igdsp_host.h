@@ -286,6 +286,26 @@ public:
     int feed(const int16_t *frame);          // n samples in; 1 when the frame computed a spectrum (the reference's spectValueChanged), 0 when not; negative: an error
 };
 
+// In-band DTMF on one leg, without a context: one channel through igdsp_tdet_frame with the DTMF plan.  pjsua reports digits through
+// on_dtmf_digit only when the far end sends telephone-event packets; this hears the digits inside the audio.  feed() returns the digit
+// a frame's ON raised (its character), 0 when none; digits() is the string dialled so far in this call.  A gateway of the reference's
+// size keeps one per SIP leg; igdsp_tone_detect takes the same states for thousands of channels.
+class DtmfReceiver {
+public:
+    explicit DtmfReceiver(uint32_t samples_per_frame = IGDSP_SAMPLES_PER_FRAME, uint32_t clock_rate = IGDSP_CLOCK_RATE);
+    uint32_t n;
+    bool ok;                                 // n even in 2 .. 256 and a clock rate igdsp_tdet_plan_dtmf takes
+    igdsp_tdet_plan plan;
+    igdsp_tdet_state state;
+    igdsp_tdet_rec last;                     // the record of the last frame fed
+    int feed(const int16_t *frame);          // n samples in; the digit's character when the frame raised ON, 0 when not; negative: an error
+    const char *digits() const { return dialled; }   // the digits of this call, oldest first (the last 63 of them)
+    void newCall();                          // the state reset, the string emptied
+private:
+    char dialled[64];
+    uint32_t count;
+};
+
 class RoIP_ED137 {
 public:
     // Unlike the reference singleton (roip_ed137.cpp:192) the instance owns an igdsp context; device < 0
@@ -412,6 +432,14 @@ int   igdsp_host_dbuf_put(void *v, const int16_t *frame);
 int   igdsp_host_dbuf_get(void *v, int16_t *frame);
 int   igdsp_host_dbuf_fill(void *v);
 int   igdsp_host_dbuf_state(void *v, igdsp_dbuf_state *out);
+// in-band DTMF on one leg without a context (DtmfReceiver): NULL from _new for a frame length or clock rate igdsp_tdet_frame /
+// igdsp_tdet_plan_dtmf reject; _feed one frame in (the digit's character when the frame raised ON, 0 when not, IGDSP_EINVAL for a NULL
+// argument); _digits the string dialled in this call, owned by the handle; _new_call resets the state and empties the string
+void *igdsp_host_dtmf_new(uint32_t samples_per_frame, uint32_t clock_rate);
+void  igdsp_host_dtmf_free(void *v);
+int   igdsp_host_dtmf_feed(void *v, const int16_t *frame);
+const char *igdsp_host_dtmf_digits(void *v);
+void  igdsp_host_dtmf_new_call(void *v);
 // the spectrum graph without a context (SpectrumGraph): NULL from _new for sizes igdsp_spec_frame rejects; _feed one frame in (1: it
 // computed a spectrum, 0: not, IGDSP_EINVAL for a NULL argument); _real / _iir the two arrays of 512 floats, owned by the handle; _clear
 // is spectClear; _fft_avg is d_fftAvg

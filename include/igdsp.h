@@ -1458,6 +1458,122 @@ int igdsp_spec_frame(igdsp_spec_state *st, const int16_t *row, uint32_t samples_
                      igdsp_spec_rec *rec, float *raw);
 int igdsp_spec_tables(const float **window, const float **twiddle);
 
+/* ---- Tone detector: in-band DTMF and single tones, per channel and frame ---------------------------------------------------------------
+ * A gateway between SIP telephone legs (isSipCall) and analogue radios gets its signalling in the audio: digits dialled through a
+ * G.711 leg, the 440 + 480 Hz ring tone of igdsp_tone_generate, a SELCAL or answer tone on a radio channel.  igdsp_tone_detect hears
+ * them in the rows igdsp_plc_conceal, igdsp_snd_split or igdsp_tone_generate leave (G.711 codes with d_codec, or PCM, [F][C][n]).
+ * Everything is integer; no libm runs at run time.
+ *
+ * PLAN (igdsp_tdet_plan_build, host only).  clock_rate as the generator's; n_lo = 1..8 frequencies of the low group, n_hi = 0..8 of
+ * the high group, freq[0 .. n_lo) the low group, freq[n_lo .. n_lo + n_hi) the high group, each in 1..clock_rate / 2 - 1 and stored as
+ * the generator's 32-bit phase step ((f << 32) + clock_rate / 2) / clock_rate; steps past n_lo + n_hi are 0.  thr (NULL: the defaults)
+ * = {min_amp 8..32767 [400], rel_q8 [1024], fwd_q8 [673, 4.2 dB], rev_q8 [1615, 8 dB], frac_q8 [150], min_on 1..255 [3],
+ * min_off 1..255 [2]}, the q8 values 1..65535.  Anything else: IGDSP_EINVAL, nothing written.  n_hi == 0 is a single-group plan: one
+ * tone out of n_lo, code = index + 1, no twist test; otherwise code = 1 + lo_index * n_hi + hi_index.  igdsp_tdet_plan_dtmf fills the
+ * 4 + 4 DTMF plan (697 770 852 941 / 1209 1336 1477 1633 Hz) with the defaults; igdsp_tdet_digit(code) is the character of its code
+ * ("123A456B789C*0#D"[code - 1], 0 for any other code).
+ *
+ * TABLE.  With the generator's T[1024] and osc(ph) = T[i] + (((T[(i + 1) & 1023] - T[i]) * fr) >> 16), i = ph >> 22, fr = (ph >> 6)
+ * & 0xFFFF: for window index i = 0..n - 1 and frequency k, ph = (uint32_t)(i * step_k),
+ *   ws[k][i] = osc(ph) / 16,  wc[k][i] = osc(ph + 0x40000000) / 16     C division, toward zero: both lie in [-2047, 2047]
+ * (the cosine is the sine a quarter turn ahead).  The phase restarts at 0 in every window.  igdsp_tdet_table (host only) writes
+ * wc then ws of frequency k at out[(2 k) * n] and out[(2 k + 1) * n], k < n_lo + n_hi.
+ *
+ * EVALUATION.  n = samples_per_frame even, 2..256 (odd: IGDSP_EINVAL).  Two evaluations per frame over windows of n samples:
+ * e = 0 over the state's last n / 2 samples followed by the frame's first n / 2, e = 1 over the frame.  x = the window's samples
+ * (G.711 decoded as igdsp_spectrum does: IGDSP_PT_PCMA is A-law, anything else mu-law),
+ *   v[i] = x[i] >> 3  (arithmetic),  I_k = sum v[i] wc[k][i],  Q_k = sum v[i] ws[k][i],  P_k = I_k^2 + Q_k^2,  E = sum v[i]^2.
+ * |v| <= 4096, |w| <= 2047, n <= 256: |I_k|, |Q_k| <= 4096 * 2047 * 256 = 2 146 435 072 < 2^31, so both fit int32; P_k < 2^63 and
+ * E <= 2^32 are uint64.
+ *
+ * HIT.  Per group the strongest bin by P, the lowest index on a tie: lo (and hi).  S = P >> 16 (part of the rule: it keeps every
+ * product below 2^64).  The hit code is the plan's code when ALL of these hold, else 0:
+ *   every chosen P >= ((min_amp >> 3) * 2047 * (n / 2))^2;
+ *   S_chosen * 256 >= rel_q8 * S_other for every other bin of its group;
+ *   two groups only:  S_hi * 256 <= fwd_q8 * S_lo  and  S_lo * 256 <= rev_q8 * S_hi;
+ *   (S_lo + S_hi) * 256 >= frac_q8 * ((E * (n / 2) * 2047^2) >> 16)      (S_hi = 0 in a single-group plan).
+ *
+ * DEBOUNCE.  Per channel cur, cand, run, off (bytes) and len (16 bits).  Per evaluation with hit code h, in this order:
+ *   1. cur != 0:  len = min(len + 1, 65535);  h == cur: off = 0;  else off = min(off + 1, 255)
+ *   2. candidate: h != 0 && h == cand: run = min(run + 1, 255);  else cand = h, run = h ? 1 : 0.   (h == cur != 0: cand = 0, run = 0)
+ *   3. cur != 0 && off >= min_off:  OFF;  len = len > off ? len - off : 0  (the digit's length in evaluations, the trailing misses
+ *      taken off);  cur = 0;  off = 0
+ *   4. cur == 0 && cand != 0 && run >= min_on:  ON;  cur = cand;  len = run;  off = 0;  cand = 0;  run = 0
+ * So the evaluation that ends a digit already counts as a candidate for the next one, and len keeps an ended digit's length until the
+ * next ON.
+ *
+ * STATE.  igdsp_tdet_state: the last 128 values v (the samples >> 3, oldest first) and the debounce fields.  All-zero is the reset state.  Any bytes
+ * are a valid state (nothing indexes by them); reserved is written back 0.  F frames in one launch, F launches of one frame and any
+ * split in between give the same bytes; a channel's results are the same at any channel count and position.
+ *
+ * OUTPUTS, each optional.  d_rec[f][c] (igdsp_tdet_rec): the two evaluations' hit codes, cur and len after the frame, flags =
+ * IGDSP_TDET_ON0 / _OFF0 / _ON1 / _OFF1, code = the digit the frame's last ON or OFF is about (0: none).  The event list has
+ * igdsp_link_watch's contract: (f, c) is an event iff flags & event_mask (0 = IGDSP_TDET_EVENT_DEFAULT), order frame-major then
+ * ascending channel, d_event_count[0] = the number of events, [1] = min(that, event_cap) = the number stored, nothing is written past
+ * d_events[event_cap); d_events may be NULL iff event_cap == 0; d_event_count NULL: no list.  A list needs d_work of
+ * igdsp_tdet_work_bytes(n_channels, n_frames, d_rec != NULL) bytes, 16-byte aligned, one per stream that launches.
+ * d_plan_of[C] (optional, NULL: plan 0) with n_plans >= 1 as the generator has; a channel whose plan index is >= n_plans detects
+ * nothing: all-zero records, no event, its state untouched.  Four consecutive channels (4 k .. 4 k + 3) are worked on together, once
+ * per distinct plan among them: channels interleaved over four plans cost up to four times channels sorted by plan.
+ *
+ * ARGUMENTS.  An odd or out-of-range samples_per_frame: IGDSP_EINVAL, whether or not there is work.  n_channels == 0 or n_frames == 0:
+ * nothing to do, the counts are written as 0.  Exactly one of d_g711 (with d_codec) and d_pcm; d_plans and d_state required.
+ * n_channels * n_frames < 2^32 - 32 (IGDSP_ERANGE).  d_g711, d_plan_of 2-byte, d_pcm, d_plans, d_state, d_event_count 4-byte, d_rec
+ * 8-byte, d_events, d_work 16-byte aligned (the rows are read two samples, the events stored 16 bytes at a time).  The state and the outputs may overlap neither an input nor each other.  Enqueued on `stream`, not
+ * synchronised.
+ *
+ * igdsp_tdet_frame (host only, no GPU): one frame of one channel by the same rule, row = n PCM samples; rec optional.
+ *
+ * Fidelity.  This is the library's own rule.  UNVERIFIED against ITU-T Q.24 and against any other detector; what is promised is what
+ * the tests show (tests/test_tdet_cpu.py: the 16 digits, twist, frequency offset, talk-off, noise, duration). */
+#define IGDSP_TDET_MAX_FREQ 16      /* frequencies per plan, both groups                        */
+#define IGDSP_TDET_HIST     128     /* samples of history in the state                          */
+#define IGDSP_TDET_ON0   0x01       /* igdsp_tdet_rec.flags: ON raised by evaluation 0          */
+#define IGDSP_TDET_OFF0  0x02
+#define IGDSP_TDET_ON1   0x04
+#define IGDSP_TDET_OFF1  0x08
+#define IGDSP_TDET_EVENT_DEFAULT 0x0F
+typedef struct igdsp_tdet_thr {
+    uint16_t min_amp, rel_q8, fwd_q8, rev_q8, frac_q8;
+    uint8_t  min_on, min_off;
+} igdsp_tdet_thr;                   /* 12 bytes */
+typedef struct igdsp_tdet_plan {
+    uint32_t clock_rate;
+    uint8_t  n_lo, n_hi, reserved[2];
+    igdsp_tdet_thr thr;
+    uint32_t step[IGDSP_TDET_MAX_FREQ];
+} igdsp_tdet_plan;                  /* 84 bytes */
+typedef struct igdsp_tdet_state {
+    int16_t  hist[IGDSP_TDET_HIST]; /* the last 128 samples >> 3, oldest first                  */
+    uint8_t  cur, cand, run, off;
+    uint16_t len, reserved;
+} igdsp_tdet_state;                 /* 264 bytes; all-zero = reset */
+typedef struct igdsp_tdet_rec {
+    uint8_t  hit[2];                /* the raw hit code of evaluations 0 and 1                  */
+    uint8_t  cur;                   /* after the frame                                          */
+    uint8_t  flags;                 /* IGDSP_TDET_ON0 | _OFF0 | _ON1 | _OFF1                    */
+    uint16_t len;                   /* the running length after the frame, saturating           */
+    uint8_t  code;                  /* the digit of the frame's last ON or OFF                  */
+    uint8_t  reserved;              /* 0 */
+} igdsp_tdet_rec;                   /* 8 bytes */
+typedef struct igdsp_tdet_event {
+    uint32_t channel;
+    uint32_t frame;                 /* f within this launch                                     */
+    igdsp_tdet_rec rec;             /* d_rec[f][c]                                              */
+} igdsp_tdet_event;                 /* 16 bytes */
+int igdsp_tdet_plan_build(uint32_t clock_rate, const uint16_t *freq, uint32_t n_lo, uint32_t n_hi, const igdsp_tdet_thr *thr,
+                          igdsp_tdet_plan *out);
+int igdsp_tdet_plan_dtmf(uint32_t clock_rate, igdsp_tdet_plan *out);
+int igdsp_tdet_digit(uint32_t code);
+int igdsp_tdet_table(const igdsp_tdet_plan *plan, uint32_t samples_per_frame, int16_t *out /* [2 (n_lo + n_hi)][n] */);
+int igdsp_tdet_frame(const igdsp_tdet_plan *plan, igdsp_tdet_state *st, const int16_t *row, uint32_t samples_per_frame, igdsp_tdet_rec *rec);
+size_t igdsp_tdet_work_bytes(uint32_t n_channels, uint32_t n_frames, int with_rec);
+int igdsp_tone_detect(igdsp_ctx *ctx, const uint8_t *d_g711 /* [F][C][n] */, const uint8_t *d_codec /* [C] */, const int16_t *d_pcm /* [F][C][n] */,
+                      const igdsp_tdet_plan *d_plans, uint32_t n_plans, const uint16_t *d_plan_of /* [C], NULL: plan 0 */,
+                      uint32_t n_channels, uint32_t n_frames, uint32_t samples_per_frame, uint32_t event_mask,
+                      igdsp_tdet_state *d_state /* [C], in and out */, igdsp_tdet_rec *d_rec /* [F][C] */,
+                      igdsp_tdet_event *d_events, uint32_t event_cap, uint32_t *d_event_count, void *d_work, void *stream);
+
 /* ---- synthetic input generators (device side; SURVEY 8(d) definitions) ---------
  * D-uniform: byte k of global byte index g is
  *   (splitmix64(seed + (g>>3)) >> (8*(g&7))) & 0xFF,  g = first_byte + k
