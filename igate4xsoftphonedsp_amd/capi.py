@@ -113,6 +113,16 @@ TDET_STATE = np.dtype([("hist", "<i2", (TDET_HIST,)), ("cur", "u1"), ("cand", "u
                        ("reserved", "<u2")], align=True)                                           # igdsp_tdet_state, 264 bytes
 TDET_REC = np.dtype([("hit", "u1", (2,)), ("cur", "u1"), ("flags", "u1"), ("len", "<u2"), ("code", "u1"), ("reserved", "u1")], align=True)
 TDET_EVENT = np.dtype([("channel", "<u4"), ("frame", "<u4"), ("rec", TDET_REC)], align=True)     # igdsp_tdet_event, 16 bytes
+# the echo canceller (igdsp_echo_cancel / igdsp_ec_frame)
+EC_MAX_TAIL, EC_BLOCK, EC_TAG = 256, 8, 0xEC010000
+EC_RUN, EC_FREEZE, EC_BYPASS, EC_RESET = 0, 1, 2, 3
+EC_ADAPTED, EC_DOUBLETALK, EC_FAR_ACTIVE, EC_W_SATURATED, EC_BYPASSED = 1, 2, 4, 8, 16
+EC_CFG = np.dtype([("tail", "<u2"), ("mu_shift", "u1"), ("reserved", "u1"), ("pmin", "<u4"), ("hang", "<u2"), ("dmin", "<u2")],
+                  align=True)                                                                      # igdsp_ec_cfg, 12 bytes
+EC_STATE = np.dtype([("w", "<i4", (EC_MAX_TAIL,)), ("hist", "<i2", (EC_MAX_TAIL,)), ("hang", "<u4"), ("flags", "<u4"), ("tag", "<u4"),
+                     ("reserved", "<u4")], align=True)                                             # igdsp_ec_state, 1552 bytes
+EC_REC = np.dtype([("near_e", "<u4"), ("out_e", "<u4"), ("flags", "u1"), ("n_adapt", "u1"), ("n_dt", "u1"), ("reserved", "u1"),
+                   ("wmax", "<u2"), ("reserved2", "<u2")], align=True)                             # igdsp_ec_rec, 16 bytes
 CHAN_PROBE = np.dtype([("run", "<u4"), ("alarms", "<u4")], align=True)
 # the jitter buffer (igdsp_jb_receive / igdsp_jb_report)
 JB_STATE = np.dtype(
@@ -297,6 +307,9 @@ PROTOTYPES = [
     ("igdsp_tdet_frame", _int, [_vp, _vp, _vp, _u32, _vp]),
     ("igdsp_tdet_work_bytes", C.c_size_t, [_u32, _u32, _int]),
     ("igdsp_tone_detect", _int, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _u32, _vp, _vp, _vp]),
+    ("igdsp_ec_cfg_default", None, [_u32, _vp]),
+    ("igdsp_ec_frame", _int, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp]),
+    ("igdsp_echo_cancel", _int, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
     ("igdsp_g726_reorder", _int, [_vp, _vp, _vp, _u64, _int, _vp]),
     ("igdsp_gen_uniform", _int, [_vp, _vp, _u64, _u64, _u64, _vp]),
     ("igdsp_dev_alloc", _int, [_vp, C.POINTER(_vp), C.c_size_t]),
@@ -337,7 +350,7 @@ INTERNAL["igdsp_internal_tx_copy"] = (_int, [_vp, _vp, _vp, _u32, _u32, _u32, _v
 
 # A yardstick whose name is not of the *_copy / *_fill form: the same derivation, a table of its own; internal() consults both
 INTERNAL_MORE_TWIN = {"igdsp_internal_dbuf_move": "igdsp_dbuf_run", "igdsp_internal_spec_move": "igdsp_spectrum",
-                      "igdsp_internal_tdet_move": "igdsp_tone_detect"}
+                      "igdsp_internal_tdet_move": "igdsp_tone_detect", "igdsp_internal_ec_move": "igdsp_echo_cancel"}
 INTERNAL_MORE = {name: _PUBLIC[twin] for name, twin in INTERNAL_MORE_TWIN.items()}
 
 _lib = None
@@ -565,6 +578,31 @@ def tdet_frame(plan, state, row):
     if rc != 0:
         raise IgdspError(rc, "igdsp_tdet_frame")
     return rec
+
+
+def ec_cfg_default(tail: int = 128) -> np.ndarray:
+    """igdsp_ec_cfg_default (host only, no GPU): one EC_CFG record, the defaults at this tail."""
+    out = np.zeros((), EC_CFG)
+    load().igdsp_ec_cfg_default(int(tail), out.ctypes.data_as(_vp))
+    return out
+
+
+def ec_frame(cfg, state, near, far=None, ctl: int = EC_RUN):
+    """igdsp_ec_frame (host only, no GPU): one frame of one channel.  cfg an EC_CFG record or None (the defaults at tail 128), state an
+    EC_STATE record updated in place, near and far the frame's PCM (int16 [n]; far None: no far end).  Returns (out int16 [n], the
+    frame's EC_REC record)."""
+    assert state.dtype == EC_STATE and state.flags["C_CONTIGUOUS"] and state.flags["WRITEABLE"]
+    near = np.ascontiguousarray(near, np.int16)
+    far = None if far is None else np.ascontiguousarray(far, np.int16)
+    assert far is None or len(far) == len(near)
+    c = None if cfg is None else np.ascontiguousarray(cfg, EC_CFG)
+    out = np.zeros(len(near), np.int16)
+    rec = np.zeros((), EC_REC)
+    rc = load().igdsp_ec_frame(None if c is None else c.ctypes.data_as(_vp), state.ctypes.data_as(_vp), near.ctypes.data_as(_vp),
+                               None if far is None else far.ctypes.data_as(_vp), len(near), int(ctl), out.ctypes.data_as(_vp), rec.ctypes.data_as(_vp))
+    if rc != 0:
+        raise IgdspError(rc, "igdsp_ec_frame")
+    return out, rec
 
 
 def tdet_work_bytes(n_channels: int, n_frames: int, with_rec: bool) -> int:
@@ -840,6 +878,16 @@ class Context:
         u32 and work (tdet_work_bytes), each optional."""
         self._ck(self.L.igdsp_tone_detect(self.h, _ptr(g711), _ptr(codec), _ptr(pcm), _ptr(plans), n_plans, _ptr(plan_of), C_, F_, n, event_mask,
                                           _ptr(state), _ptr(rec), _ptr(events), event_cap, _ptr(event_count), _ptr(work), stream), "igdsp_tone_detect")
+
+    def echo_cancel(self, far, n_far_rows, state, C_, F_, n, g711=None, codec=None, pcm=None, far_of=None, ctl=None, cfg=None, out=None, rec=None,
+                    stats=None, stream=None):
+        """igdsp_echo_cancel: exactly one of g711 [F][C][n] u8 (+ codec [C]) / pcm [F][C][n] int16 (the near end); far [F][n_far_rows][n]
+        int16, far_of [C] u32 or None (row c), ctl [C] u8 or None (EC_RUN); cfg an EC_CFG record (host memory) or None (the defaults at
+        tail 128); state [C] EC_STATE (in and out) -> out [F][C][n] int16, rec [F][C] EC_REC, stats [F][C] FRAME_STATS, each optional."""
+        c = None if cfg is None else np.ascontiguousarray(cfg, EC_CFG)
+        self._ck(self.L.igdsp_echo_cancel(self.h, _ptr(g711), _ptr(codec), _ptr(pcm), _ptr(far), n_far_rows, _ptr(far_of), _ptr(ctl),
+                                          None if c is None else c.ctypes.data_as(_vp), C_, F_, n, _ptr(state), _ptr(out), _ptr(rec), _ptr(stats),
+                                          stream), "igdsp_echo_cancel")
 
     def bss_select(self, info, group_ptr, members, n_members, state, words, C_, G_, F_, n=160, payload=None, codec=None, pcm=None,
                    length=None, gain=None, mute=None, vote_frames=0, sel=None, out=None, stats=None, stream=None):

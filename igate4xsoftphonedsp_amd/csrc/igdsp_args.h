@@ -501,4 +501,32 @@ inline Verdict tdet_run(P d_g711, P d_codec, P d_pcm, P d_plans, uint32_t n_plan
     return kRun;
 }
 
+// ---- echo canceller.  The frame length and the cfg (NULL = the defaults) are checked whether or not there is work
+constexpr bool ec_cfg_ok(const igdsp_ec_cfg *cfg) { return !cfg || ((cfg->tail == 128u || cfg->tail == 256u) && cfg->mu_shift <= 6u); }
+inline Verdict ec_run(P d_near_g711, P d_codec, P d_near_pcm, P d_far_pcm, uint32_t n_far, P d_far_of, P d_ctl, const igdsp_ec_cfg *cfg, uint32_t C,
+                      uint32_t F, uint32_t n, P d_state, P d_out, P d_rec, P d_stats)
+{
+    if (n < 2u || n > IGDSP_MAX_PAYLOAD || (n & 1u) || !ec_cfg_ok(cfg)) return kInvalid;
+    if (empty(C, F)) return kNothing;
+    if (!exactly_one(d_near_g711, d_near_pcm) || (d_near_g711 && !d_codec) || !d_state || (n_far != 0u && !d_far_pcm)) return kInvalid;
+    if ((uint64_t)C * F >= 0xFFFFFFE0ull || (uint64_t)n_far * F >= 0xFFFFFFE0ull) return reject(IGDSP_ERANGE);
+    // rows are read and stored two samples at a time (n is even, so every row starts as its buffer does), weights and records as 16 bytes
+    if (misaligned(2, {d_near_g711}) || misaligned(4, {d_near_pcm, d_far_pcm, d_far_of, d_out}) || misaligned(8, {d_stats}) ||
+        misaligned(16, {d_state, d_rec})) return kInvalid;
+    const uint64_t frames = (uint64_t)C * F;
+    struct Buf { P p; uint64_t bytes; };
+    const Buf ins[6] = {{d_near_g711, frames * n}, {d_near_g711 ? d_codec : nullptr, C}, {d_near_pcm, frames * n * 2u},
+                        {d_far_pcm, (uint64_t)n_far * F * n * 2u}, {d_far_of, (uint64_t)C * 4u}, {d_ctl, C}};
+    const Buf outs[4] = {{d_state, (uint64_t)C * sizeof(igdsp_ec_state)}, {d_out, frames * n * 2u}, {d_rec, frames * sizeof(igdsp_ec_rec)},
+                         {d_stats, frames * sizeof(igdsp_frame_stats)}};
+    for (int i = 0; i < 4; ++i) {
+        for (const Buf &b : ins)
+            if (ranges_overlap(outs[i].p, outs[i].bytes, b.p, b.bytes)) return reject(IGDSP_EINVAL, "the state and the outputs must not overlap an input");
+        for (int j = 0; j < i; ++j)
+            if (ranges_overlap(outs[i].p, outs[i].bytes, outs[j].p, outs[j].bytes))
+                return reject(IGDSP_EINVAL, "the state and the outputs must not overlap each other");
+    }
+    return kRun;
+}
+
 }  // namespace igdsp::args

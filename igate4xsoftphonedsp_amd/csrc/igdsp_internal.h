@@ -168,6 +168,12 @@ hipError_t launch_tone_detect(const LaunchCfg &cfg, const uint8_t *g711, const u
                               uint32_t n_plans, const uint16_t *plan_of, uint32_t C, uint32_t F, uint32_t n, uint32_t event_mask,
                               igdsp_tdet_state *state, igdsp_tdet_rec *rec, igdsp_tdet_event *events, uint32_t event_cap, uint32_t *event_count,
                               void *work, bool yardstick, hipStream_t s);
+// igdsp_echo_cancel: exactly one of near_g711 (with codec) and near_pcm; far_of, ctl, out, rec, stats may each be nullptr; cfg checked
+// by the C ABI.  yardstick: the compute-free form, the same row loads, history moves, state and row stores, no dot product, reduction or
+// update (out = the near row, the weights as they were, the history as by a launch; records carry the energies and BYPASSED)
+hipError_t launch_echo_cancel(const LaunchCfg &cfg, const uint8_t *near_g711, const uint8_t *codec, const int16_t *near_pcm, const int16_t *far_pcm,
+                              uint32_t n_far, const uint32_t *far_of, const uint8_t *ctl, const igdsp_ec_cfg &ec, uint32_t C, uint32_t F, uint32_t n,
+                              igdsp_ec_state *state, int16_t *out, igdsp_ec_rec *rec, igdsp_frame_stats *stats, bool yardstick, hipStream_t s);
 hipError_t launch_wav_expand(const LaunchCfg &cfg, const uint8_t *payload, uint32_t C, uint32_t F, uint32_t n, uint32_t rate,
                              uint8_t *files, uint64_t file_stride, hipStream_t s);
 hipError_t launch_g726(const LaunchCfg &cfg, const uint8_t *in, uint8_t *out, uint64_t n_bytes, int mode, hipStream_t s);

@@ -1100,6 +1100,36 @@ inline TdetRoute tdet_route(uint32_t C, uint32_t F, uint32_t n, bool list, bool 
     return r;
 }
 
+// ---- igdsp_echo_cancel (launch_echo_cancel): k_ec<NEAR_G711, L, COPY>.  A DPP row of 16 lanes owns a channel for the whole launch (the
+// adaptation is sequential in time): a lane keeps L / 16 consecutive weights in registers; a wave is four channels, a block kEcWaves
+// waves.  LDS per channel: kEcPad values, the shifted far history of L values and the frame of up to 256 behind it, kEcPad values
+// (a block's window is read anchored at the block's END, so a short last block reads below the frame and the lowest lane below the
+// history), and the near row behind kEcPad values; the output overwrites the near row in place.  Registers: the route is written for
+// kEcResident blocks per CU (3 waves per SIMD, 168 VGPRs).
+constexpr int kEcWaves = 4;                               // waves per block
+constexpr uint32_t kEcChans = kEcWaves * 4u;              // channels per block
+constexpr uint32_t kEcResident = 3;                       // blocks per CU
+constexpr uint32_t kEcPad = 8;
+constexpr uint32_t kEcXBuf = kEcPad + 256u + 256u + kEcPad;   // values per channel: pad, history, frame, pad
+constexpr uint32_t kEcNBuf = kEcPad + 256u;                   // values per channel: pad, near row
+constexpr uint32_t kEcLdsBytes = kEcChans * (kEcXBuf + kEcNBuf) * 2u;
+struct EcRoute {
+    uint32_t grid = 0, threads = 0, lds = 0;
+    uint32_t tail = 0;                     // k_ec<, L, >
+    uint32_t blocks = 0;                   // blocks of 8 (the last may be shorter) per frame
+};
+inline EcRoute ec_route(uint32_t C, uint32_t F, uint32_t n, uint32_t tail)
+{
+    EcRoute r;
+    if ((uint64_t)C * F == 0 || (uint64_t)C * F >= 0xFFFFFFE0ull || n < 2u || n > IGDSP_MAX_PAYLOAD || (n & 1u) || (tail != 128u && tail != 256u)) return r;
+    r.grid = (uint32_t)(((uint64_t)C + kEcChans - 1u) / kEcChans);
+    r.threads = kEcWaves * 64;
+    r.lds = kEcLdsBytes;
+    r.tail = tail;
+    r.blocks = (n + 7u) / 8u;
+    return r;
+}
+
 // ---- igdsp_tx_flush (launch_tx_staged): a wave owns kTsLegs staged legs (runs) of the flush; lanes 0 .. kTsLegs-1 decide, the
 // whole wave writes the packets.  No dynamic LDS: each wave's records (kTsLegs x IGDSP_STAGE_DEPTH) are static.
 constexpr int kTsWaves = 4;

@@ -1081,6 +1081,53 @@ int igdsp_host_dtmf_feed(void *v, const int16_t *frame)
 const char *igdsp_host_dtmf_digits(void *v) { return v ? static_cast<DtmfReceiver *>(v)->digits() : nullptr; }
 void igdsp_host_dtmf_new_call(void *v) { if (v) static_cast<DtmfReceiver *>(v)->newCall(); }
 
+// ---- the sound port's echo canceller on one leg, no context needed
+EchoCanceller::EchoCanceller(uint32_t samples_per_frame, uint32_t tail) : n(samples_per_frame)
+{
+    igdsp_ec_cfg_default(tail, &cfg);
+    ok = (tail == 128 || tail == 256) && n >= 2 && n <= IGDSP_MAX_PAYLOAD && (n & 1u) == 0;
+    reset();
+}
+
+void EchoCanceller::reset()
+{
+    std::memset(&state, 0, sizeof(state));
+    std::memset(&last, 0, sizeof(last));
+}
+
+int EchoCanceller::cancel(const int16_t *near_frame, const int16_t *far_frame, int16_t *out, uint32_t ctl)
+{
+    if (!ok || !near_frame || !out) return IGDSP_EINVAL;
+    return igdsp_ec_frame(&cfg, &state, near_frame, far_frame, n, ctl, out, &last);
+}
+
+float EchoCanceller::erleDb() const
+{
+    if (!last.near_e || !last.out_e) return 0.0f;
+    return 10.0f * std::log10((float)last.near_e / (float)last.out_e);
+}
+
+void *igdsp_host_ec_new(uint32_t samples_per_frame, uint32_t tail)
+{
+    EchoCanceller *e = new (std::nothrow) EchoCanceller(samples_per_frame, tail);
+    if (e && !e->ok) { delete e; e = nullptr; }
+    return e;
+}
+void igdsp_host_ec_free(void *v) { delete static_cast<EchoCanceller *>(v); }
+int igdsp_host_ec_cancel(void *v, const int16_t *near_frame, const int16_t *far_frame, int16_t *out, uint32_t ctl)
+{
+    if (!v) return IGDSP_EINVAL;
+    return static_cast<EchoCanceller *>(v)->cancel(near_frame, far_frame, out, ctl);
+}
+int igdsp_host_ec_rec(void *v, igdsp_ec_rec *out)
+{
+    if (!v || !out) return IGDSP_EINVAL;
+    *out = static_cast<EchoCanceller *>(v)->last;
+    return IGDSP_OK;
+}
+float igdsp_host_ec_erle_db(void *v) { return v ? static_cast<EchoCanceller *>(v)->erleDb() : 0.0f; }
+void igdsp_host_ec_reset(void *v) { if (v) static_cast<EchoCanceller *>(v)->reset(); }
+
 // ---- conference receive levels, no context needed
 void *igdsp_host_levels_new(uint32_t n_channels)
 {

@@ -306,6 +306,24 @@ private:
     uint32_t count;
 };
 
+// The sound port's echo canceller on one leg, without a context: one channel through igdsp_ec_frame.  pjmedia creates one on the
+// pjmedia_snd_port when media_cfg.ec_tail_len is not 0; the reference sets it to 0 and mutes a group's receivers during transmit
+// instead.  cancel() takes the frame the card captured (near) and the frame that was played (far) and returns what is left; the
+// record of the frame tells the echo return loss enhancement and whether the filter adapted.  A gateway of the reference's size keeps
+// one per sound-card channel; igdsp_echo_cancel takes the same states for thousands of channels.
+class EchoCanceller {
+public:
+    explicit EchoCanceller(uint32_t samples_per_frame = IGDSP_SAMPLES_PER_FRAME, uint32_t tail = 128);
+    uint32_t n;
+    bool ok;                                 // n even in 2 .. 256 and a tail of 128 or 256
+    igdsp_ec_cfg cfg;                        // the defaults at this tail; a caller may change mu_shift, pmin, hang, dmin
+    igdsp_ec_state state;
+    igdsp_ec_rec last;                       // the record of the last frame
+    int cancel(const int16_t *near_frame, const int16_t *far_frame, int16_t *out, uint32_t ctl = IGDSP_EC_RUN);   // far NULL: nothing was played
+    float erleDb() const;                    // of the last frame: 10 log10(near_e / out_e), 0 when either is 0
+    void reset();                            // the filter, the history and the hold forgotten
+};
+
 class RoIP_ED137 {
 public:
     // Unlike the reference singleton (roip_ed137.cpp:192) the instance owns an igdsp context; device < 0
@@ -440,6 +458,15 @@ void  igdsp_host_dtmf_free(void *v);
 int   igdsp_host_dtmf_feed(void *v, const int16_t *frame);
 const char *igdsp_host_dtmf_digits(void *v);
 void  igdsp_host_dtmf_new_call(void *v);
+// the echo canceller on one leg without a context (EchoCanceller): NULL from _new for a frame length or tail igdsp_ec_frame rejects;
+// _cancel one frame (far NULL: nothing was played; IGDSP_EINVAL for a NULL handle, near or out); _rec a copy of the last frame's record;
+// _erle_db of the last frame; _reset forgets the filter
+void *igdsp_host_ec_new(uint32_t samples_per_frame, uint32_t tail);
+void  igdsp_host_ec_free(void *v);
+int   igdsp_host_ec_cancel(void *v, const int16_t *near_frame, const int16_t *far_frame, int16_t *out, uint32_t ctl);
+int   igdsp_host_ec_rec(void *v, igdsp_ec_rec *out);
+float igdsp_host_ec_erle_db(void *v);
+void  igdsp_host_ec_reset(void *v);
 // the spectrum graph without a context (SpectrumGraph): NULL from _new for sizes igdsp_spec_frame rejects; _feed one frame in (1: it
 // computed a spectrum, 0: not, IGDSP_EINVAL for a NULL argument); _real / _iir the two arrays of 512 floats, owned by the handle; _clear
 // is spectClear; _fft_avg is d_fftAvg

@@ -44,7 +44,8 @@ extern "C" {
  *    igdsp_tone_state, igdsp_tone_plan_build, igdsp_tone_frame, igdsp_tone_generate); the rate converter (IGDSP_RS_*, igdsp_rs_state,
  *    igdsp_resample, igdsp_rs_frame, igdsp_rs_taps); the sound port's delay buffer (IGDSP_DBUF_*, igdsp_dbuf_state, igdsp_dbuf_run,
  *    igdsp_dbuf_step); the spectrum graph (IGDSP_SPEC_*, igdsp_spec_state, igdsp_spec_cfg, igdsp_spec_rec, igdsp_spectrum,
- *    igdsp_spec_frame, igdsp_spec_tables). */
+ *    igdsp_spec_frame, igdsp_spec_tables); the tone detector (IGDSP_TDET_*, igdsp_tdet_*, igdsp_tone_detect); the echo canceller
+ *    (IGDSP_EC_*, igdsp_ec_cfg, igdsp_ec_state, igdsp_ec_rec, igdsp_ec_cfg_default, igdsp_ec_frame, igdsp_echo_cancel). */
 #define IGDSP_ABI_VERSION 3
 
 /* ---- error codes (0 == PJ_SUCCESS-style success) ------------------------- */
@@ -1573,6 +1574,96 @@ int igdsp_tone_detect(igdsp_ctx *ctx, const uint8_t *d_g711 /* [F][C][n] */, con
                       uint32_t n_channels, uint32_t n_frames, uint32_t samples_per_frame, uint32_t event_mask,
                       igdsp_tdet_state *d_state /* [C], in and out */, igdsp_tdet_rec *d_rec /* [F][C] */,
                       igdsp_tdet_event *d_events, uint32_t event_cap, uint32_t *d_event_count, void *d_work, void *stream);
+
+/* ---- Echo canceller: the sound port's echo canceller, per channel, as an adaptive FIR filter ---------------------------------------------
+ * pjmedia hangs an echo canceller on the pjmedia_snd_port the reference opens and the reference switches it off (ec_tail_len = 0); it
+ * then closes every receiver of a group while a transmitter of the group is keyed (groupMute).  igdsp_echo_cancel takes the far end (what
+ * the channel's transmitter sends: a PCM row as igdsp_conf_mix writes it per port) out of the near end (what the channel's receiver
+ * hears: G.711 codes with d_codec, or PCM, [F][C][n]), so that a receiver stays open, metered and voted on during transmit.
+ * Everything is integer; every sum is exact, so no result depends on the order of summation.
+ *
+ * RULE.  A block-normalised LMS filter with blocks of B = 8 samples and a tail of L = cfg->tail = 128 or 256 taps (one value per
+ * launch).  xs = far >> 2 (arithmetic) stands behind the state's history of the last L values xs.  A frame of n samples (even, 2..256)
+ * is cut into blocks of 8 from its start; the last block is shorter when n % 8 != 0.  Per block of b samples at positions j:
+ *   1. wh[k] = w[k] >> 18                                         (14 bits, Q13; the weights from before the block serve all of it)
+ *   2. acc_j = sum over k < L of wh[k] * xs[j - k];  yhat_j = clamp16((acc_j + 1024) >> 11);  out_j = e_j = clamp16(near_j - yhat_j)
+ *   3. P = sum of xs^2 over the L most recent values at the block's end
+ *   4. xmax = 4 * max |xs| over the last L + b values;  dmax = max |near_j| over the block
+ *   5. if 2 * dmax > xmax and dmax >= cfg->dmin:  hang = cfg->hang;   else if hang > 0:  hang = hang - 1
+ *   6. only if hang == 0 and P >= cfg->pmin and the channel is not frozen:   es_j = e_j / 4 (C division, toward zero),
+ *        g[k] = sum over j of es_j * xs[j - k],   q = the bit length of P,   sh = 31 - cfg->mu_shift - q,
+ *        w[k] = sat32(w[k] + (sh >= 0 ? g[k] << sh : g[k] >> -sh))          (in 64 bits; the right shift arithmetic)
+ * |wh| <= 2^13 and |xs| <= 2^13: a product is at most 2^26, 16 of them fit 32 bits, a whole tail (2^34) needs 64.  |es| <= 2^13 likewise.
+ * igdsp_ec_cfg_default(tail, out) fills {tail, mu_shift 2, pmin 65536, hang 80 blocks, dmin 256}.
+ *
+ * STATE.  igdsp_ec_state, one per channel, read at the start of a launch and written back at its end.  tag = IGDSP_EC_TAG | L names the
+ * layout and the tail the state was run with: a state with any other tag (all-zero included) starts as the RESET state, w, hist, hang
+ * and flags 0.  Under the right tag any bytes are a valid state: hist is read clamped to -8192..8191, nothing indexes by a field.  At
+ * L = 128 the upper halves of w and hist are written 0.  flags keeps IGDSP_EC_W_SATURATED since the last reset.  F frames in one launch,
+ * F launches of one frame and any split in between give the same bytes; a channel's results are the same at any channel count and position.
+ *
+ * FAR END AND CONTROL.  d_far_pcm is [F][n_far_rows][n]; channel c reads row d_far_of[c] (NULL: row c), so the receivers of a group
+ * share their transmitter's row.  An index >= n_far_rows means no far end: the channel runs as IGDSP_EC_BYPASS over a far row of zeros.
+ * d_ctl[c] (NULL: IGDSP_EC_RUN; a value above 3 counts as RUN) holds for the launch:
+ *   IGDSP_EC_RUN;   IGDSP_EC_FREEZE: filter and detect, never adapt;   IGDSP_EC_BYPASS: out = near, no filter, no detector (hang
+ *   stays), the history still advances;   IGDSP_EC_RESET: the state becomes the RESET state before the launch's first frame, then RUN.
+ *
+ * OUTPUTS, each optional.  d_out[f][c][n] = e.  d_rec[f][c] (igdsp_ec_rec): near_e = (sum near^2) >> 8 and out_e = (sum out^2) >> 8 (the
+ * echo return loss enhancement of a frame is 10 log10(near_e / out_e)), flags = IGDSP_EC_ADAPTED (a block adapted), _DOUBLETALK (a
+ * block ended with hang > 0), _FAR_ACTIVE (a block had P >= pmin), _W_SATURATED (a weight was clipped in this frame), _BYPASSED;
+ * n_adapt and n_dt the counts of such blocks; wmax = max |w[k] >> 18| after the frame.  d_stats[f][c]: the PCM record of out, as
+ * igdsp_conf_mix writes it.  With d_out NULL the stage runs for state and records only.
+ *
+ * ARGUMENTS.  samples_per_frame odd or outside 2..256, cfg->tail not 128 or 256, cfg->mu_shift > 6: IGDSP_EINVAL, whether or not there
+ * is work (cfg NULL: the defaults at tail 128).  n_channels == 0 or n_frames == 0: nothing to do.  Exactly one of d_near_g711 (with
+ * d_codec) and d_near_pcm; d_far_pcm (unless n_far_rows == 0) and d_state required.  n_channels * n_frames and n_far_rows * n_frames
+ * < 2^32 - 32 (IGDSP_ERANGE).  d_near_g711 2-byte, d_near_pcm, d_far_pcm, d_far_of, d_out 4-byte, d_stats 8-byte, d_state, d_rec
+ * 16-byte aligned (rows are read and stored two samples, weights and records 16 bytes at a time).  The state and the outputs may
+ * overlap neither an input nor each other.  Enqueued on `stream`, not synchronised.
+ *
+ * igdsp_ec_frame (host only, no GPU): one frame of one channel by the same rule; near is PCM, far NULL = no far end, out and rec
+ * optional.  IGDSP_EINVAL for what the entry rejects.
+ *
+ * Fidelity.  This is the library's own rule.  UNVERIFIED against ITU-T G.168, against speex, WebRTC and any other canceller; what is
+ * promised is what the tests show (tests/test_ec_cpu.py: integer against float64, single talk, double talk, the controls). */
+#define IGDSP_EC_MAX_TAIL 256
+#define IGDSP_EC_BLOCK    8
+#define IGDSP_EC_TAG      0xEC010000u /* | L: igdsp_ec_state.tag                                 */
+#define IGDSP_EC_RUN      0           /* d_ctl                                                    */
+#define IGDSP_EC_FREEZE   1
+#define IGDSP_EC_BYPASS   2
+#define IGDSP_EC_RESET    3
+#define IGDSP_EC_ADAPTED     0x01     /* igdsp_ec_rec.flags                                       */
+#define IGDSP_EC_DOUBLETALK  0x02
+#define IGDSP_EC_FAR_ACTIVE  0x04
+#define IGDSP_EC_W_SATURATED 0x08     /* igdsp_ec_state.flags as well                             */
+#define IGDSP_EC_BYPASSED    0x10
+typedef struct igdsp_ec_cfg {
+    uint16_t tail;                  /* L: 128 or 256                                            */
+    uint8_t  mu_shift;              /* 0..6: the step is 2^-mu_shift                            */
+    uint8_t  reserved;
+    uint32_t pmin;                  /* adapt only when P >= pmin                                */
+    uint16_t hang;                  /* blocks without adaptation after the detector fires       */
+    uint16_t dmin;                  /* the detector fires only when dmax >= dmin                */
+} igdsp_ec_cfg;                     /* 12 bytes */
+typedef struct igdsp_ec_state {
+    int32_t  w[IGDSP_EC_MAX_TAIL];    /* Q31: w / 2^31 is the tap                                 */
+    int16_t  hist[IGDSP_EC_MAX_TAIL]; /* the last L values far >> 2, oldest first, in hist[0 .. L) */
+    uint32_t hang, flags, tag, reserved;
+} igdsp_ec_state;                   /* 1552 bytes */
+typedef struct igdsp_ec_rec {
+    uint32_t near_e, out_e;         /* (sum of squares) >> 8                                    */
+    uint8_t  flags, n_adapt, n_dt, reserved;
+    uint16_t wmax, reserved2;
+} igdsp_ec_rec;                     /* 16 bytes */
+void igdsp_ec_cfg_default(uint32_t tail, igdsp_ec_cfg *out);
+int igdsp_ec_frame(const igdsp_ec_cfg *cfg, igdsp_ec_state *st, const int16_t *near_pcm, const int16_t *far_pcm, uint32_t samples_per_frame,
+                   uint32_t ctl, int16_t *out, igdsp_ec_rec *rec);
+int igdsp_echo_cancel(igdsp_ctx *ctx, const uint8_t *d_near_g711 /* [F][C][n] */, const uint8_t *d_codec /* [C] */,
+                      const int16_t *d_near_pcm /* [F][C][n] */, const int16_t *d_far_pcm /* [F][P][n] */, uint32_t n_far_rows,
+                      const uint32_t *d_far_of /* [C], NULL: row c */, const uint8_t *d_ctl /* [C], NULL: RUN */, const igdsp_ec_cfg *cfg,
+                      uint32_t n_channels, uint32_t n_frames, uint32_t samples_per_frame, igdsp_ec_state *d_state /* [C], in and out */,
+                      int16_t *d_out /* [F][C][n] */, igdsp_ec_rec *d_rec /* [F][C] */, igdsp_frame_stats *d_stats /* [F][C] */, void *stream);
 
 /* ---- synthetic input generators (device side; SURVEY 8(d) definitions) ---------
  * D-uniform: byte k of global byte index g is
