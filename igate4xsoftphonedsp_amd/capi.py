@@ -123,6 +123,16 @@ EC_STATE = np.dtype([("w", "<i4", (EC_MAX_TAIL,)), ("hist", "<i2", (EC_MAX_TAIL,
                      ("reserved", "<u4")], align=True)                                             # igdsp_ec_state, 1552 bytes
 EC_REC = np.dtype([("near_e", "<u4"), ("out_e", "<u4"), ("flags", "u1"), ("n_adapt", "u1"), ("n_dt", "u1"), ("reserved", "u1"),
                    ("wmax", "<u2"), ("reserved2", "<u2")], align=True)                             # igdsp_ec_rec, 16 bytes
+# the level control (igdsp_agc_run / igdsp_agc_frame)
+AGC_BLOCK, AGC_UNITY, AGC_CAP, AGC_TAG = 8, 4096, 65535, 0xA6C10001
+AGC_RUN, AGC_FREEZE, AGC_BYPASS, AGC_RESET = 0, 1, 2, 3
+AGC_ACTIVE, AGC_LIMITED, AGC_AT_MAX, AGC_AT_MIN, AGC_ATTACKED, AGC_FROZEN, AGC_BYPASSED = 1, 2, 4, 8, 16, 32, 64
+AGC_CFG = np.dtype([("target", "<u2"), ("ceil", "<u2"), ("gate", "<u2"), ("gmin", "<u2"), ("gmax", "<u2"), ("att", "u1"), ("rel", "u1"), ("up", "u1"),
+                    ("down", "u1"), ("lrel", "u1"), ("reserved", "u1")], align=True)               # igdsp_agc_cfg, 16 bytes
+AGC_STATE = np.dtype([("tag", "<u4"), ("env", "<u2"), ("gain", "<u2"), ("cap", "<u2"), ("flags", "<u2"), ("reserved", "<u4")],
+                     align=True)                                                                   # igdsp_agc_state, 16 bytes
+AGC_REC = np.dtype([("gain", "<u2"), ("tmin", "<u2"), ("in_peak", "<u2"), ("out_peak", "<u2"), ("env", "<u2"), ("flags", "u1"), ("n_limited", "u1"),
+                    ("reserved", "<u4")], align=True)                                              # igdsp_agc_rec, 16 bytes
 CHAN_PROBE = np.dtype([("run", "<u4"), ("alarms", "<u4")], align=True)
 # the jitter buffer (igdsp_jb_receive / igdsp_jb_report)
 JB_STATE = np.dtype(
@@ -310,6 +320,9 @@ PROTOTYPES = [
     ("igdsp_ec_cfg_default", None, [_u32, _vp]),
     ("igdsp_ec_frame", _int, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp]),
     ("igdsp_echo_cancel", _int, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
+    ("igdsp_agc_cfg_default", None, [_vp]),
+    ("igdsp_agc_frame", _int, [_vp, _vp, _vp, _u32, _u32, _vp, _vp]),
+    ("igdsp_agc_run", _int, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
     ("igdsp_g726_reorder", _int, [_vp, _vp, _vp, _u64, _int, _vp]),
     ("igdsp_gen_uniform", _int, [_vp, _vp, _u64, _u64, _u64, _vp]),
     ("igdsp_dev_alloc", _int, [_vp, C.POINTER(_vp), C.c_size_t]),
@@ -350,7 +363,8 @@ INTERNAL["igdsp_internal_tx_copy"] = (_int, [_vp, _vp, _vp, _u32, _u32, _u32, _v
 
 # A yardstick whose name is not of the *_copy / *_fill form: the same derivation, a table of its own; internal() consults both
 INTERNAL_MORE_TWIN = {"igdsp_internal_dbuf_move": "igdsp_dbuf_run", "igdsp_internal_spec_move": "igdsp_spectrum",
-                      "igdsp_internal_tdet_move": "igdsp_tone_detect", "igdsp_internal_ec_move": "igdsp_echo_cancel"}
+                      "igdsp_internal_tdet_move": "igdsp_tone_detect", "igdsp_internal_ec_move": "igdsp_echo_cancel",
+                      "igdsp_internal_agc_move": "igdsp_agc_run"}
 INTERNAL_MORE = {name: _PUBLIC[twin] for name, twin in INTERNAL_MORE_TWIN.items()}
 
 _lib = None
@@ -602,6 +616,28 @@ def ec_frame(cfg, state, near, far=None, ctl: int = EC_RUN):
                                None if far is None else far.ctypes.data_as(_vp), len(near), int(ctl), out.ctypes.data_as(_vp), rec.ctypes.data_as(_vp))
     if rc != 0:
         raise IgdspError(rc, "igdsp_ec_frame")
+    return out, rec
+
+
+def agc_cfg_default() -> np.ndarray:
+    """igdsp_agc_cfg_default (host only, no GPU): one AGC_CFG record, the defaults."""
+    out = np.zeros((), AGC_CFG)
+    load().igdsp_agc_cfg_default(out.ctypes.data_as(_vp))
+    return out
+
+
+def agc_frame(cfg, state, pcm, ctl: int = AGC_RUN):
+    """igdsp_agc_frame (host only, no GPU): one frame of one channel.  cfg an AGC_CFG record or None (the defaults), state an AGC_STATE
+    record updated in place, pcm the frame (int16 [n]).  Returns (out int16 [n], the frame's AGC_REC record)."""
+    assert state.dtype == AGC_STATE and state.flags["C_CONTIGUOUS"] and state.flags["WRITEABLE"]
+    pcm = np.ascontiguousarray(pcm, np.int16)
+    c = None if cfg is None else np.ascontiguousarray(cfg, AGC_CFG)
+    out = np.zeros(len(pcm), np.int16)
+    rec = np.zeros((), AGC_REC)
+    rc = load().igdsp_agc_frame(None if c is None else c.ctypes.data_as(_vp), state.ctypes.data_as(_vp), pcm.ctypes.data_as(_vp), len(pcm), int(ctl),
+                                out.ctypes.data_as(_vp), rec.ctypes.data_as(_vp))
+    if rc != 0:
+        raise IgdspError(rc, "igdsp_agc_frame")
     return out, rec
 
 
@@ -888,6 +924,14 @@ class Context:
         self._ck(self.L.igdsp_echo_cancel(self.h, _ptr(g711), _ptr(codec), _ptr(pcm), _ptr(far), n_far_rows, _ptr(far_of), _ptr(ctl),
                                           None if c is None else c.ctypes.data_as(_vp), C_, F_, n, _ptr(state), _ptr(out), _ptr(rec), _ptr(stats),
                                           stream), "igdsp_echo_cancel")
+
+    def agc_run(self, state, C_, F_, n, g711=None, codec=None, pcm=None, ctl=None, cfg=None, out=None, rec=None, stats=None, stream=None):
+        """igdsp_agc_run: exactly one of g711 [F][C][n] u8 (+ codec [C]) / pcm [F][C][n] int16; ctl [C] u8 or None (AGC_RUN); cfg an
+        AGC_CFG record (host memory) or None (the defaults); state [C] AGC_STATE (in and out) -> out [F][C][n] int16, rec [F][C] AGC_REC,
+        stats [F][C] FRAME_STATS, each optional, at least one."""
+        c = None if cfg is None else np.ascontiguousarray(cfg, AGC_CFG)
+        self._ck(self.L.igdsp_agc_run(self.h, _ptr(g711), _ptr(codec), _ptr(pcm), _ptr(ctl), None if c is None else c.ctypes.data_as(_vp), C_, F_, n,
+                                      _ptr(state), _ptr(out), _ptr(rec), _ptr(stats), stream), "igdsp_agc_run")
 
     def bss_select(self, info, group_ptr, members, n_members, state, words, C_, G_, F_, n=160, payload=None, codec=None, pcm=None,
                    length=None, gain=None, mute=None, vote_frames=0, sel=None, out=None, stats=None, stream=None):

@@ -11,6 +11,7 @@
 #include <initializer_list>
 
 #include "igdsp.h"
+#include "igdsp_agc.h"
 #include "igdsp_route.h"
 
 namespace igdsp::args {
@@ -518,6 +519,31 @@ inline Verdict ec_run(P d_near_g711, P d_codec, P d_near_pcm, P d_far_pcm, uint3
     const Buf ins[6] = {{d_near_g711, frames * n}, {d_near_g711 ? d_codec : nullptr, C}, {d_near_pcm, frames * n * 2u},
                         {d_far_pcm, (uint64_t)n_far * F * n * 2u}, {d_far_of, (uint64_t)C * 4u}, {d_ctl, C}};
     const Buf outs[4] = {{d_state, (uint64_t)C * sizeof(igdsp_ec_state)}, {d_out, frames * n * 2u}, {d_rec, frames * sizeof(igdsp_ec_rec)},
+                         {d_stats, frames * sizeof(igdsp_frame_stats)}};
+    for (int i = 0; i < 4; ++i) {
+        for (const Buf &b : ins)
+            if (ranges_overlap(outs[i].p, outs[i].bytes, b.p, b.bytes)) return reject(IGDSP_EINVAL, "the state and the outputs must not overlap an input");
+        for (int j = 0; j < i; ++j)
+            if (ranges_overlap(outs[i].p, outs[i].bytes, outs[j].p, outs[j].bytes))
+                return reject(IGDSP_EINVAL, "the state and the outputs must not overlap each other");
+    }
+    return kRun;
+}
+
+// ---- level control.  The frame length and the cfg (NULL = the defaults) are checked whether or not there is work
+inline Verdict agc_run(P d_g711, P d_codec, P d_pcm, P d_ctl, const igdsp_agc_cfg *cfg, uint32_t C, uint32_t F, uint32_t n, P d_state, P d_out,
+                       P d_rec, P d_stats)
+{
+    if (!agc_n_ok(n) || !agc_cfg_ok(cfg)) return kInvalid;
+    if (empty(C, F)) return kNothing;
+    if (!exactly_one(d_g711, d_pcm) || (d_g711 && !d_codec) || !d_state || !(d_out || d_rec || d_stats)) return kInvalid;
+    if ((uint64_t)C * F >= 0xFFFFFFE0ull) return reject(IGDSP_ERANGE);
+    // a block of 8 samples is one load (8 bytes of codes, 16 of PCM) and one 16-byte store; the state and a record are 16 bytes
+    if (misaligned(8, {d_g711, d_stats}) || misaligned(16, {d_pcm, d_state, d_out, d_rec})) return kInvalid;
+    const uint64_t frames = (uint64_t)C * F;
+    struct Buf { P p; uint64_t bytes; };
+    const Buf ins[4] = {{d_g711, frames * n}, {d_g711 ? d_codec : nullptr, C}, {d_pcm, frames * n * 2u}, {d_ctl, C}};
+    const Buf outs[4] = {{d_state, (uint64_t)C * sizeof(igdsp_agc_state)}, {d_out, frames * n * 2u}, {d_rec, frames * sizeof(igdsp_agc_rec)},
                          {d_stats, frames * sizeof(igdsp_frame_stats)}};
     for (int i = 0; i < 4; ++i) {
         for (const Buf &b : ins)

@@ -174,6 +174,12 @@ hipError_t launch_tone_detect(const LaunchCfg &cfg, const uint8_t *g711, const u
 hipError_t launch_echo_cancel(const LaunchCfg &cfg, const uint8_t *near_g711, const uint8_t *codec, const int16_t *near_pcm, const int16_t *far_pcm,
                               uint32_t n_far, const uint32_t *far_of, const uint8_t *ctl, const igdsp_ec_cfg &ec, uint32_t C, uint32_t F, uint32_t n,
                               igdsp_ec_state *state, int16_t *out, igdsp_ec_rec *rec, igdsp_frame_stats *stats, bool yardstick, hipStream_t s);
+// igdsp_agc_run: exactly one of g711 (with codec) and pcm; ctl, out, rec, stats may each be nullptr; cfg checked by the C ABI.
+// yardstick: the compute-free form, the same row loads, state load and store, row, record and PCM-record stores, no peak, division,
+// recurrence or gain (out = the row, the state as read, tagged; records carry the state's gain and env, tmin 4096 and BYPASSED)
+hipError_t launch_agc(const LaunchCfg &cfg, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm, const uint8_t *ctl, const igdsp_agc_cfg &agc,
+                      uint32_t C, uint32_t F, uint32_t n, igdsp_agc_state *state, int16_t *out, igdsp_agc_rec *rec, igdsp_frame_stats *stats,
+                      bool yardstick, hipStream_t s);
 hipError_t launch_wav_expand(const LaunchCfg &cfg, const uint8_t *payload, uint32_t C, uint32_t F, uint32_t n, uint32_t rate,
                              uint8_t *files, uint64_t file_stride, hipStream_t s);
 hipError_t launch_g726(const LaunchCfg &cfg, const uint8_t *in, uint8_t *out, uint64_t n_bytes, int mode, hipStream_t s);

@@ -1130,6 +1130,32 @@ inline EcRoute ec_route(uint32_t C, uint32_t F, uint32_t n, uint32_t tail)
     return r;
 }
 
+// ---- igdsp_agc_run (launch_agc): k_agc<IN_G711, COPY>.  Half a wave, 32 lanes, owns a channel for the whole launch (the gain and the
+// limiter's cap run through time): lane b owns block b of 8 samples, one load and one store per frame, and knot b + 1; a frame of n
+// samples keeps n / 8 of the 32 lanes busy.  A wave is two channels, a block kAgcWaves waves.  No LDS: the lanes talk by DPP and
+// ds_bpermute.  Registers: the route is written for kAgcResident blocks per CU (8 waves per SIMD, 64 VGPRs).
+constexpr int kAgcWaves = 4;                              // waves per block
+constexpr uint32_t kAgcLanes = 32;                        // lanes per channel
+constexpr uint32_t kAgcChans = kAgcWaves * 2u;            // channels per block
+constexpr uint32_t kAgcResident = 8;                      // blocks per CU
+struct AgcRoute {
+    uint32_t grid = 0, threads = 0, lds = 0;
+    bool g711 = false, copy = false;       // k_agc<IN_G711, COPY>
+    uint32_t blocks = 0;                   // blocks of 8 per frame = busy lanes per channel
+};
+inline AgcRoute agc_route(uint32_t C, uint32_t F, uint32_t n, bool g711, bool yardstick)
+{
+    AgcRoute r;
+    if ((uint64_t)C * F == 0 || (uint64_t)C * F >= 0xFFFFFFE0ull || n < 8u || n > IGDSP_MAX_PAYLOAD || (n & 7u)) return r;
+    r.grid = (uint32_t)(((uint64_t)C + kAgcChans - 1u) / kAgcChans);
+    r.threads = kAgcWaves * 64;
+    r.lds = 0;
+    r.g711 = g711;
+    r.copy = yardstick;
+    r.blocks = n / 8u;
+    return r;
+}
+
 // ---- igdsp_tx_flush (launch_tx_staged): a wave owns kTsLegs staged legs (runs) of the flush; lanes 0 .. kTsLegs-1 decide, the
 // whole wave writes the packets.  No dynamic LDS: each wave's records (kTsLegs x IGDSP_STAGE_DEPTH) are static.
 constexpr int kTsWaves = 4;

@@ -1128,6 +1128,53 @@ int igdsp_host_ec_rec(void *v, igdsp_ec_rec *out)
 float igdsp_host_ec_erle_db(void *v) { return v ? static_cast<EchoCanceller *>(v)->erleDb() : 0.0f; }
 void igdsp_host_ec_reset(void *v) { if (v) static_cast<EchoCanceller *>(v)->reset(); }
 
+// ---- the level control on one leg, no context needed
+LevelControl::LevelControl(uint32_t samples_per_frame) : n(samples_per_frame)
+{
+    igdsp_agc_cfg_default(&cfg);
+    ok = n >= 8 && n <= IGDSP_MAX_PAYLOAD && (n & 7u) == 0;
+    reset();
+}
+
+void LevelControl::reset()
+{
+    std::memset(&state, 0, sizeof(state));
+    std::memset(&last, 0, sizeof(last));
+}
+
+int LevelControl::process(const int16_t *frame, int16_t *out, uint32_t ctl)
+{
+    if (!ok || !frame || !out) return IGDSP_EINVAL;
+    return igdsp_agc_frame(&cfg, &state, frame, n, ctl, out, &last);
+}
+
+float LevelControl::gainDb() const
+{
+    if (!last.gain) return 0.0f;
+    return 20.0f * std::log10((float)last.gain / (float)IGDSP_AGC_UNITY);
+}
+
+void *igdsp_host_agc_new(uint32_t samples_per_frame)
+{
+    LevelControl *e = new (std::nothrow) LevelControl(samples_per_frame);
+    if (e && !e->ok) { delete e; e = nullptr; }
+    return e;
+}
+void igdsp_host_agc_free(void *v) { delete static_cast<LevelControl *>(v); }
+int igdsp_host_agc_process(void *v, const int16_t *frame, int16_t *out, uint32_t ctl)
+{
+    if (!v) return IGDSP_EINVAL;
+    return static_cast<LevelControl *>(v)->process(frame, out, ctl);
+}
+int igdsp_host_agc_rec(void *v, igdsp_agc_rec *out)
+{
+    if (!v || !out) return IGDSP_EINVAL;
+    *out = static_cast<LevelControl *>(v)->last;
+    return IGDSP_OK;
+}
+float igdsp_host_agc_gain_db(void *v) { return v ? static_cast<LevelControl *>(v)->gainDb() : 0.0f; }
+void igdsp_host_agc_reset(void *v) { if (v) static_cast<LevelControl *>(v)->reset(); }
+
 // ---- conference receive levels, no context needed
 void *igdsp_host_levels_new(uint32_t n_channels)
 {

@@ -324,6 +324,22 @@ public:
     void reset();                            // the filter, the history and the hold forgotten
 };
 
+// The level control on one leg, without a context: one channel through igdsp_agc_frame.  Neither pjmedia nor the reference holds one (the
+// only gain there is SLOT_VOLUME); process() brings a frame to the target level and keeps every sample under the ceiling, the record of
+// the frame tells the gain and whether the limiter worked.  igdsp_agc_run takes the same states for thousands of channels.
+class LevelControl {
+public:
+    explicit LevelControl(uint32_t samples_per_frame = IGDSP_SAMPLES_PER_FRAME);
+    uint32_t n;
+    bool ok;                                 // n a multiple of 8 in 8 .. 256
+    igdsp_agc_cfg cfg;                       // the defaults; a caller may change any field (an invalid cfg: process() gives IGDSP_EINVAL)
+    igdsp_agc_state state;
+    igdsp_agc_rec last;                      // the record of the last frame
+    int process(const int16_t *frame, int16_t *out, uint32_t ctl = IGDSP_AGC_RUN);
+    float gainDb() const;                    // of the last frame: 20 log10(gain / 4096)
+    void reset();                            // envelope, gain and cap forgotten
+};
+
 class RoIP_ED137 {
 public:
     // Unlike the reference singleton (roip_ed137.cpp:192) the instance owns an igdsp context; device < 0
@@ -467,6 +483,15 @@ int   igdsp_host_ec_cancel(void *v, const int16_t *near_frame, const int16_t *fa
 int   igdsp_host_ec_rec(void *v, igdsp_ec_rec *out);
 float igdsp_host_ec_erle_db(void *v);
 void  igdsp_host_ec_reset(void *v);
+// the level control on one leg without a context (LevelControl): NULL from _new for a frame length igdsp_agc_frame rejects; _process
+// one frame (IGDSP_EINVAL for a NULL handle, frame or out); _rec a copy of the last frame's record; _gain_db of the last frame;
+// _reset forgets envelope, gain and cap
+void *igdsp_host_agc_new(uint32_t samples_per_frame);
+void  igdsp_host_agc_free(void *v);
+int   igdsp_host_agc_process(void *v, const int16_t *frame, int16_t *out, uint32_t ctl);
+int   igdsp_host_agc_rec(void *v, igdsp_agc_rec *out);
+float igdsp_host_agc_gain_db(void *v);
+void  igdsp_host_agc_reset(void *v);
 // the spectrum graph without a context (SpectrumGraph): NULL from _new for sizes igdsp_spec_frame rejects; _feed one frame in (1: it
 // computed a spectrum, 0: not, IGDSP_EINVAL for a NULL argument); _real / _iir the two arrays of 512 floats, owned by the handle; _clear
 // is spectClear; _fft_avg is d_fftAvg

@@ -45,7 +45,8 @@ extern "C" {
  *    igdsp_resample, igdsp_rs_frame, igdsp_rs_taps); the sound port's delay buffer (IGDSP_DBUF_*, igdsp_dbuf_state, igdsp_dbuf_run,
  *    igdsp_dbuf_step); the spectrum graph (IGDSP_SPEC_*, igdsp_spec_state, igdsp_spec_cfg, igdsp_spec_rec, igdsp_spectrum,
  *    igdsp_spec_frame, igdsp_spec_tables); the tone detector (IGDSP_TDET_*, igdsp_tdet_*, igdsp_tone_detect); the echo canceller
- *    (IGDSP_EC_*, igdsp_ec_cfg, igdsp_ec_state, igdsp_ec_rec, igdsp_ec_cfg_default, igdsp_ec_frame, igdsp_echo_cancel). */
+ *    (IGDSP_EC_*, igdsp_ec_cfg, igdsp_ec_state, igdsp_ec_rec, igdsp_ec_cfg_default, igdsp_ec_frame, igdsp_echo_cancel); the level control
+ *    (IGDSP_AGC_*, igdsp_agc_cfg, igdsp_agc_state, igdsp_agc_rec, igdsp_agc_cfg_default, igdsp_agc_frame, igdsp_agc_run). */
 #define IGDSP_ABI_VERSION 3
 
 /* ---- error codes (0 == PJ_SUCCESS-style success) ------------------------- */
@@ -604,7 +605,8 @@ int igdsp_tx_counts(igdsp_ctx *ctx, int32_t call_id, uint32_t *refused, uint32_t
  * int16), and pjsua's float level -> adj mapping is (int)((level - 1) * 128) with adj = 128 + that (igdsp_conf_level_q7).  Both are
  * UNVERIFIED here: pjmedia is a third-party dependency of the reference and is not in this tree.  pjmedia's adaptive normalisation
  * of a sum of several transmitters is deliberately NOT restated: the mix saturates instead; the two agree whenever at most one
- * member of a port contributes (the PTT arbitration's usual state: one call unmuted, the others at level 0). */
+ * member of a port contributes (the PTT arbitration's usual state: one call unmuted, the others at level 0).  A port row that must
+ * not clip goes through igdsp_agc_run ("Level control" below) behind the mix. */
 #define IGDSP_FLAG_SATURATED 0x10  /* igdsp_conf_mix: a per-member or the final int16 clamp fired in this port-frame */
 /* Q7 receive level of a float slot volume: 128 + (int)((level - 1.0f) * 128.0f) in float arithmetic, as pjsua converts it
  * (0.0 -> 0, 0.1f -> 13, 0.5 -> 64, 1.0 -> 128, 2.0 -> 256).  IGDSP_EINVAL for NaN, a negative result (an adjustment below -128)
@@ -1664,6 +1666,103 @@ int igdsp_echo_cancel(igdsp_ctx *ctx, const uint8_t *d_near_g711 /* [F][C][n] */
                       const uint32_t *d_far_of /* [C], NULL: row c */, const uint8_t *d_ctl /* [C], NULL: RUN */, const igdsp_ec_cfg *cfg,
                       uint32_t n_channels, uint32_t n_frames, uint32_t samples_per_frame, igdsp_ec_state *d_state /* [C], in and out */,
                       int16_t *d_out /* [F][C][n] */, igdsp_ec_rec *d_rec /* [F][C] */, igdsp_frame_stats *d_stats /* [F][C] */, void *stream);
+
+/* ---- Level control: per channel an automatic gain control with a peak limiter ------------------------------------------------------------
+ * Neither pjmedia nor the reference holds one: the only gain there is the static SLOT_VOLUME (igdsp_conf_level_q7).  igdsp_agc_run brings
+ * a row (G.711 codes with d_codec, or PCM, [F][C][n]) to a target peak level with a slow gain and keeps every output sample under a
+ * ceiling with a fast limiter whose gain ramp starts one block ahead of a loud block, at no added delay.  It stands between
+ * igdsp_plc_conceal / igdsp_bss_select and igdsp_conf_mix (the mix takes d_out as d_pcm), and between a port row of igdsp_conf_mix and
+ * igdsp_tx_packetize.  Everything is integer.  This is the library's own rule, UNVERIFIED against ITU-T G.169.
+ *
+ * RULE.  A frame is n samples, n a multiple of 8 in 8..256: B = n / 8 blocks of 8 and B + 1 knots, knot k at sample 8 k (knot B is knot 0
+ * of the next frame).  Gains are Q12 in 16 bits, 4096 is unity, CAP = 65535.  "/" is C division, toward zero.  G, env, cap: the state.
+ *   1. p_b = max |x| over block b (32768 for -32768);  pk = max p_b.
+ *   2. The slow gain.  The frame is ACTIVE when pk >= gate.  Not active, or frozen: Gn = G, env stays.  Active:
+ *        env == 0: env = pk;   pk > env: env += (pk - env + (1 << att) - 1) >> att;   else env -= (env - pk) >> rel
+ *        Gt = clamp((target << 12) / env, gmin, gmax);  d = Gt - G
+ *        d >= 0: Gn = G + ((d + (1 << up) - 1) >> up);   else Gn = G - ((-d + (1 << down) - 1) >> down)
+ *      The slow gain at knot k: A_k = G + ((Gn - G) * k) / B.
+ *   3. The limiter's cap.  r_b = CAP when p_b == 0, else min(CAP, (ceil << 12) / p_b);  m_k = min(r_(k-1), r_k), a term outside
+ *      0..B-1 counting as CAP;  c_0 = min(m_0, cap) (no release step across the frame boundary: it is one instant);
+ *      c_k = min(m_k, min(CAP, c_(k-1) + max(1, c_(k-1) >> lrel))) for k >= 1;  cap' = c_B.
+ *   4. T_k = min(A_k, c_k);  sample j = 8 b + i takes t_j = T_b + ((T_(b+1) - T_b) * i) / 8;  out_j = (x_j * t_j + 2048) >> 12
+ *      (arithmetic shift).
+ *   5. G' = Gn.
+ * In block b both knots are <= r_b, and t_j lies between them, so |x_j| * t_j <= ceil << 12 < 2^27: the product fits 32 bits, and
+ * |out_j| <= ceil on every sample: no clamp exists (csrc/igdsp_agc.h proves both).  A loud onset is met by a ramp that starts one
+ * block (1 ms at 8 kHz) before the loud block; an onset in a frame's FIRST block has no block before it, the gain steps down at the
+ * frame boundary, and the record carries IGDSP_AGC_ATTACKED.
+ *
+ * CONFIGURATION.  igdsp_agc_cfg holds for the launch; NULL: the defaults of igdsp_agc_cfg_default: target 8192, ceil 23170 (-3 dBFS),
+ * gate 256, gmin 1024, gmax 32768, att 1, rel 5, up 5, down 2, lrel 6.  Valid: 1 <= gate; 1 <= target <= ceil <= 32767;
+ * 1 <= gmin <= 4096 <= gmax <= 65535; att, rel, up, down <= 15; 1 <= lrel <= 15.
+ *
+ * STATE.  igdsp_agc_state, one per channel, read at the start of a launch and written at its end.  A tag other than IGDSP_AGC_TAG
+ * (all-zero included) means the RESET state: env 0, gain 4096, cap CAP.  Under the right tag any bytes are a valid state: gain is read
+ * clamped to [gmin, gmax], nothing indexes by a field.  flags is written as the last frame's record flags, reserved as 0.  F frames
+ * in one launch, F launches of one frame and any split in between write the same bytes; a channel's results are the same at any
+ * channel count and position.
+ *
+ * CONTROL.  d_ctl[c] (NULL: IGDSP_AGC_RUN; a value above 3 counts as RUN) holds for the launch:
+ *   IGDSP_AGC_RUN;   IGDSP_AGC_FREEZE: step 2 is skipped (Gn = G, env stays), the limiter runs;   IGDSP_AGC_BYPASS: out = x, the
+ *   state's bytes are not touched;   IGDSP_AGC_RESET: the state becomes the RESET state before the first frame, then RUN.
+ *
+ * OUTPUTS, each optional, at least one required.  d_out[f][c][n].  d_rec[f][c] (igdsp_agc_rec): gain = Gn, tmin = min T_k, in_peak =
+ * pk, out_peak = max |out|, env after the frame, n_limited = the knots with c_k < A_k, flags = IGDSP_AGC_ACTIVE (pk >= gate),
+ * _LIMITED (n_limited > 0), _AT_MAX / _AT_MIN ((target << 12) / env lay above gmax / below gmin), _ATTACKED (m_0 < cap), _FROZEN,
+ * _BYPASSED (then gain = G and env as read, tmin 4096, out_peak = in_peak, nothing else).  d_stats[f][c]: the PCM record of out, as
+ * igdsp_conf_mix writes it.  With d_out NULL the stage runs for state and records only.
+ *
+ * ARGUMENTS.  samples_per_frame not a multiple of 8 in 8..256, an invalid cfg: IGDSP_EINVAL, whether or not there is work.
+ * n_channels == 0 or n_frames == 0: nothing to do.  Exactly one of d_g711 (with d_codec) and d_pcm; d_state and one of d_out, d_rec,
+ * d_stats required.  n_channels * n_frames < 2^32 - 32 (IGDSP_ERANGE).  d_g711 8-byte, d_pcm, d_out, d_state, d_rec 16-byte, d_stats
+ * 8-byte aligned (a block of 8 samples is one load and one store; state and record are 16 bytes: tighter than igdsp_echo_cancel's rows).
+ * The state and the outputs may overlap neither an input nor each other.  Enqueued on `stream`, not synchronised.
+ *
+ * igdsp_agc_frame (host only, no GPU): one frame of one channel from PCM by the same rule; out and rec optional.  IGDSP_EINVAL for
+ * what the entry rejects. */
+#define IGDSP_AGC_BLOCK   8
+#define IGDSP_AGC_UNITY   4096
+#define IGDSP_AGC_CAP     65535
+#define IGDSP_AGC_TAG     0xA6C10001u /* igdsp_agc_state.tag                                      */
+#define IGDSP_AGC_RUN     0           /* d_ctl                                                    */
+#define IGDSP_AGC_FREEZE  1
+#define IGDSP_AGC_BYPASS  2
+#define IGDSP_AGC_RESET   3
+#define IGDSP_AGC_ACTIVE   0x01       /* igdsp_agc_rec.flags                                      */
+#define IGDSP_AGC_LIMITED  0x02
+#define IGDSP_AGC_AT_MAX   0x04
+#define IGDSP_AGC_AT_MIN   0x08
+#define IGDSP_AGC_ATTACKED 0x10
+#define IGDSP_AGC_FROZEN   0x20
+#define IGDSP_AGC_BYPASSED 0x40
+typedef struct igdsp_agc_cfg {
+    uint16_t target;                /* the peak level the slow gain aims at                      */
+    uint16_t ceil;                  /* no output sample exceeds it                               */
+    uint16_t gate;                  /* a frame with pk below it moves neither env nor gain       */
+    uint16_t gmin, gmax;            /* Q12 bounds of the slow gain                               */
+    uint8_t  att, rel;              /* env: shifts of the rise and the fall                      */
+    uint8_t  up, down;              /* gain: shifts of the rise and the fall per frame           */
+    uint8_t  lrel;                  /* the limiter's release: cap += max(1, cap >> lrel) a block */
+    uint8_t  reserved;
+} igdsp_agc_cfg;                    /* 16 bytes */
+typedef struct igdsp_agc_state {
+    uint32_t tag;
+    uint16_t env, gain, cap, flags;
+    uint32_t reserved;
+} igdsp_agc_state;                  /* 16 bytes */
+typedef struct igdsp_agc_rec {
+    uint16_t gain, tmin, in_peak, out_peak, env;
+    uint8_t  flags, n_limited;
+    uint32_t reserved;
+} igdsp_agc_rec;                    /* 16 bytes */
+void igdsp_agc_cfg_default(igdsp_agc_cfg *out);
+int igdsp_agc_frame(const igdsp_agc_cfg *cfg, igdsp_agc_state *st, const int16_t *pcm, uint32_t samples_per_frame, uint32_t ctl,
+                    int16_t *out, igdsp_agc_rec *rec);
+int igdsp_agc_run(igdsp_ctx *ctx, const uint8_t *d_g711 /* [F][C][n] */, const uint8_t *d_codec /* [C] */,
+                  const int16_t *d_pcm /* [F][C][n] */, const uint8_t *d_ctl /* [C], NULL: RUN */, const igdsp_agc_cfg *cfg,
+                  uint32_t n_channels, uint32_t n_frames, uint32_t samples_per_frame, igdsp_agc_state *d_state /* [C], in and out */,
+                  int16_t *d_out /* [F][C][n] */, igdsp_agc_rec *d_rec /* [F][C] */, igdsp_frame_stats *d_stats /* [F][C] */, void *stream);
 
 /* ---- synthetic input generators (device side; SURVEY 8(d) definitions) ---------
  * D-uniform: byte k of global byte index g is
