@@ -133,6 +133,23 @@ AGC_STATE = np.dtype([("tag", "<u4"), ("env", "<u2"), ("gain", "<u2"), ("cap", "
                      align=True)                                                                   # igdsp_agc_state, 16 bytes
 AGC_REC = np.dtype([("gain", "<u2"), ("tmin", "<u2"), ("in_peak", "<u2"), ("out_peak", "<u2"), ("env", "<u2"), ("flags", "u1"), ("n_limited", "u1"),
                     ("reserved", "<u4")], align=True)                                              # igdsp_agc_rec, 16 bytes
+# voice activity, DTX and the comfort-noise payload (igdsp_vad_run / igdsp_vad_frame)
+VAD_ORDER, VAD_KMAX, VAD_TAG = 10, 32508, 0x7AD10001
+VAD_RUN, VAD_FREEZE, VAD_BYPASS, VAD_RESET = 0, 1, 2, 3
+VAD_NONE, VAD_VOICE, VAD_SID = 0, 1, 2
+VAD_F_RAW, VAD_F_VOICE, VAD_F_ONSET, VAD_F_OFFSET, VAD_F_SID, VAD_F_QUIET, VAD_F_FROZEN, VAD_F_BYPASSED = 1, 2, 4, 8, 16, 32, 64, 128
+VAD_EVENT_DEFAULT = 0x0C
+VAD_CFG = np.dtype([("thr_abs", "<u4"), ("nf_min", "<u4"), ("nf_max", "<u4"), ("sid_every", "<u2"), ("ratio_on_q4", "u1"), ("ratio_off_q4", "u1"),
+                    ("dn", "u1"), ("up", "u1"), ("up_v", "u1"), ("asm_shift", "u1"), ("burst", "u1"), ("hang_long", "u1"), ("hang_short", "u1"),
+                    ("order", "u1"), ("dtx", "u1"), ("sid_delta", "u1"), ("sid_gap", "u1"), ("vox_on", "u1"), ("vox_off", "u1"),
+                    ("reserved", "u1", (3,))], align=True)                                         # igdsp_vad_cfg, 32 bytes
+VAD_STATE = np.dtype([("tag", "<u4"), ("nf", "<u4"), ("A", "<i8", (11,)), ("since_sid", "<u2"), ("run", "<u2"), ("hang", "u1"), ("voice", "u1"),
+                      ("avalid", "u1"), ("last_level", "u1"), ("sid_sent", "u1"), ("flags", "u1"), ("reserved", "u1", (22,))],
+                     align=True)                                                                   # igdsp_vad_state, 128 bytes
+VAD_REC = np.dtype([("ms", "<u4"), ("nf", "<u4"), ("run", "<u2"), ("flags", "u1"), ("kind", "u1"), ("level", "u1"), ("hang", "u1"), ("sid_len", "u1"),
+                    ("reserved", "u1")], align=True)                                               # igdsp_vad_rec, 16 bytes
+VAD_EVENT = np.dtype([("channel", "<u4"), ("frame", "<u4"), ("ms", "<u4"), ("run", "<u2"), ("flags", "u1"), ("level", "u1")],
+                     align=True)                                                                   # igdsp_vad_event, 16 bytes
 CHAN_PROBE = np.dtype([("run", "<u4"), ("alarms", "<u4")], align=True)
 # the jitter buffer (igdsp_jb_receive / igdsp_jb_report)
 JB_STATE = np.dtype(
@@ -323,6 +340,12 @@ PROTOTYPES = [
     ("igdsp_agc_cfg_default", None, [_vp]),
     ("igdsp_agc_frame", _int, [_vp, _vp, _vp, _u32, _u32, _vp, _vp]),
     ("igdsp_agc_run", _int, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
+    ("igdsp_vad_cfg_default", None, [_vp]),
+    ("igdsp_vad_table", _int, [_vp]),
+    ("igdsp_vad_frame", _int, [_vp, _vp, _vp, _u32, _u32, _vp, _vp]),
+    ("igdsp_sid_decode", _int, [_vp, _u32, _vp, _vp]),
+    ("igdsp_vad_work_bytes", C.c_size_t, [_u32, _u32, _int]),
+    ("igdsp_vad_run", _int, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp]),
     ("igdsp_g726_reorder", _int, [_vp, _vp, _vp, _u64, _int, _vp]),
     ("igdsp_gen_uniform", _int, [_vp, _vp, _u64, _u64, _u64, _vp]),
     ("igdsp_dev_alloc", _int, [_vp, C.POINTER(_vp), C.c_size_t]),
@@ -364,7 +387,7 @@ INTERNAL["igdsp_internal_tx_copy"] = (_int, [_vp, _vp, _vp, _u32, _u32, _u32, _v
 # A yardstick whose name is not of the *_copy / *_fill form: the same derivation, a table of its own; internal() consults both
 INTERNAL_MORE_TWIN = {"igdsp_internal_dbuf_move": "igdsp_dbuf_run", "igdsp_internal_spec_move": "igdsp_spectrum",
                       "igdsp_internal_tdet_move": "igdsp_tone_detect", "igdsp_internal_ec_move": "igdsp_echo_cancel",
-                      "igdsp_internal_agc_move": "igdsp_agc_run"}
+                      "igdsp_internal_agc_move": "igdsp_agc_run", "igdsp_internal_vad_move": "igdsp_vad_run"}
 INTERNAL_MORE = {name: _PUBLIC[twin] for name, twin in INTERNAL_MORE_TWIN.items()}
 
 _lib = None
@@ -639,6 +662,51 @@ def agc_frame(cfg, state, pcm, ctl: int = AGC_RUN):
     if rc != 0:
         raise IgdspError(rc, "igdsp_agc_frame")
     return out, rec
+
+
+def vad_cfg_default() -> np.ndarray:
+    """igdsp_vad_cfg_default (host only, no GPU): one VAD_CFG record, the defaults."""
+    out = np.zeros((), VAD_CFG)
+    load().igdsp_vad_cfg_default(out.ctypes.data_as(_vp))
+    return out
+
+
+def vad_table() -> np.ndarray:
+    """igdsp_vad_table (host only, no GPU): the 128 values of T8 as uint64."""
+    out = np.zeros(128, "<u8")
+    rc = load().igdsp_vad_table(out.ctypes.data_as(_vp))
+    if rc != 0:
+        raise IgdspError(rc, "igdsp_vad_table")
+    return out
+
+
+def vad_frame(cfg, state, pcm, ctl: int = VAD_RUN):
+    """igdsp_vad_frame (host only, no GPU): one frame of one channel.  cfg a VAD_CFG record or None (the defaults), state a VAD_STATE
+    record updated in place, pcm the frame (int16 [n]).  Returns (kind, the frame's VAD_REC record, the payload's 16 bytes)."""
+    assert state.dtype == VAD_STATE and state.flags["C_CONTIGUOUS"] and state.flags["WRITEABLE"]
+    pcm = np.ascontiguousarray(pcm, np.int16)
+    c = None if cfg is None else np.ascontiguousarray(cfg, VAD_CFG)
+    rec, sid = np.zeros((), VAD_REC), np.zeros(16, np.uint8)
+    rc = load().igdsp_vad_frame(None if c is None else c.ctypes.data_as(_vp), state.ctypes.data_as(_vp), pcm.ctypes.data_as(_vp), len(pcm), int(ctl),
+                                rec.ctypes.data_as(_vp), sid.ctypes.data_as(_vp))
+    if rc < 0:
+        raise IgdspError(rc, "igdsp_vad_frame")
+    return rc, rec, sid
+
+
+def sid_decode(payload):
+    """igdsp_sid_decode (host only, no GPU): (level in -dBov, the ten Q15 reflection coefficients) of an RFC 3389 payload."""
+    p = np.ascontiguousarray(payload, np.uint8)
+    lvl, k = np.zeros(1, np.uint8), np.zeros(10, np.int16)
+    rc = load().igdsp_sid_decode(p.ctypes.data_as(_vp), len(p), lvl.ctypes.data_as(_vp), k.ctypes.data_as(_vp))
+    if rc != 0:
+        raise IgdspError(rc, "igdsp_sid_decode")
+    return int(lvl[0]), k
+
+
+def vad_work_bytes(n_channels: int, n_frames: int, with_rec: bool) -> int:
+    """igdsp_vad_work_bytes (host only, no GPU): bytes of igdsp_vad_run's d_work for a launch of this shape."""
+    return int(load().igdsp_vad_work_bytes(n_channels, n_frames, 1 if with_rec else 0))
 
 
 def tdet_work_bytes(n_channels: int, n_frames: int, with_rec: bool) -> int:
@@ -932,6 +1000,16 @@ class Context:
         c = None if cfg is None else np.ascontiguousarray(cfg, AGC_CFG)
         self._ck(self.L.igdsp_agc_run(self.h, _ptr(g711), _ptr(codec), _ptr(pcm), _ptr(ctl), None if c is None else c.ctypes.data_as(_vp), C_, F_, n,
                                       _ptr(state), _ptr(out), _ptr(rec), _ptr(stats), stream), "igdsp_agc_run")
+
+    def vad_run(self, state, C_, F_, n, g711=None, codec=None, pcm=None, ctl=None, cfg=None, event_mask=0, kind=None, rec=None, sid=None, txctl=None,
+                events=None, event_cap=0, event_count=None, work=None, stream=None):
+        """igdsp_vad_run: exactly one of g711 [F][C][n] u8 (+ codec [C]) / pcm [F][C][n] int16; ctl [C] u8 or None (VAD_RUN); cfg a VAD_CFG
+        record (host memory) or None (the defaults); state [C] VAD_STATE (in and out) -> kind [F][C] u8, rec [F][C] VAD_REC, sid [F][C][16]
+        u8, txctl [F][C] u8, events [event_cap] VAD_EVENT with event_count [2] u32 and work (vad_work_bytes), each optional, at least one."""
+        c = None if cfg is None else np.ascontiguousarray(cfg, VAD_CFG)
+        self._ck(self.L.igdsp_vad_run(self.h, _ptr(g711), _ptr(codec), _ptr(pcm), _ptr(ctl), None if c is None else c.ctypes.data_as(_vp), C_, F_, n,
+                                      event_mask, _ptr(state), _ptr(kind), _ptr(rec), _ptr(sid), _ptr(txctl), _ptr(events), event_cap,
+                                      _ptr(event_count), _ptr(work), stream), "igdsp_vad_run")
 
     def bss_select(self, info, group_ptr, members, n_members, state, words, C_, G_, F_, n=160, payload=None, codec=None, pcm=None,
                    length=None, gain=None, mute=None, vote_frames=0, sel=None, out=None, stats=None, stream=None):

@@ -13,6 +13,7 @@
 #include "igdsp.h"
 #include "igdsp_agc.h"
 #include "igdsp_route.h"
+#include "igdsp_vad.h"
 
 namespace igdsp::args {
 
@@ -546,6 +547,37 @@ inline Verdict agc_run(P d_g711, P d_codec, P d_pcm, P d_ctl, const igdsp_agc_cf
     const Buf outs[4] = {{d_state, (uint64_t)C * sizeof(igdsp_agc_state)}, {d_out, frames * n * 2u}, {d_rec, frames * sizeof(igdsp_agc_rec)},
                          {d_stats, frames * sizeof(igdsp_frame_stats)}};
     for (int i = 0; i < 4; ++i) {
+        for (const Buf &b : ins)
+            if (ranges_overlap(outs[i].p, outs[i].bytes, b.p, b.bytes)) return reject(IGDSP_EINVAL, "the state and the outputs must not overlap an input");
+        for (int j = 0; j < i; ++j)
+            if (ranges_overlap(outs[i].p, outs[i].bytes, outs[j].p, outs[j].bytes))
+                return reject(IGDSP_EINVAL, "the state and the outputs must not overlap each other");
+    }
+    return kRun;
+}
+
+// ---- voice activity.  The frame length and the cfg (NULL = the defaults) are checked whether or not there is work.  Nothing to do with
+// a list still writes the counts, so d_event_count's own rules apply before the shape's
+inline Verdict vad_run(P d_g711, P d_codec, P d_pcm, P d_ctl, const igdsp_vad_cfg *cfg, uint32_t C, uint32_t F, uint32_t n, P d_state, P d_kind,
+                       P d_rec, P d_sid, P d_txctl, P d_events, uint32_t event_cap, P d_event_count, P d_work)
+{
+    if (!vad_n_ok(n) || !vad_cfg_ok(cfg)) return kInvalid;
+    if (misaligned(4, {d_event_count}) || misaligned(16, {d_work}) || (d_event_count && !d_work)) return kInvalid;
+    if (d_event_count && event_cap != 0u && !d_events) return kInvalid;
+    if (empty(C, F)) return d_event_count ? kRun : kNothing;              // the counts are written as 0
+    if (!exactly_one(d_g711, d_pcm) || (d_g711 && !d_codec) || !d_state || !(d_kind || d_rec || d_sid || d_txctl || d_event_count)) return kInvalid;
+    if ((uint64_t)C * F >= 0xFFFFFFE0ull) return reject(IGDSP_ERANGE);
+    // a piece of 8 samples is one load (8 bytes of codes, 16 of PCM); the state is read as dwords and 8-byte sums, a record, a payload
+    // and an event are one 16-byte store each
+    if (misaligned(8, {d_g711}) || misaligned(16, {d_pcm, d_state, d_rec, d_sid, d_events})) return kInvalid;
+    const uint64_t frames = (uint64_t)C * F;
+    const bool list = d_event_count != nullptr;
+    struct Buf { P p; uint64_t bytes; };
+    const Buf ins[4] = {{d_g711, frames * n}, {d_g711 ? d_codec : nullptr, C}, {d_pcm, frames * n * 2u}, {d_ctl, C}};
+    const Buf outs[8] = {{d_state, (uint64_t)C * sizeof(igdsp_vad_state)}, {d_kind, frames}, {d_rec, frames * sizeof(igdsp_vad_rec)}, {d_sid, frames * 16u},
+                         {d_txctl, frames}, {list ? d_events : nullptr, (uint64_t)event_cap * sizeof(igdsp_vad_event)}, {d_event_count, 8u},
+                         {list ? d_work : nullptr, vad_work_bytes(C, F, d_rec != nullptr)}};
+    for (int i = 0; i < 8; ++i) {
         for (const Buf &b : ins)
             if (ranges_overlap(outs[i].p, outs[i].bytes, b.p, b.bytes)) return reject(IGDSP_EINVAL, "the state and the outputs must not overlap an input");
         for (int j = 0; j < i; ++j)

@@ -180,6 +180,16 @@ hipError_t launch_echo_cancel(const LaunchCfg &cfg, const uint8_t *near_g711, co
 hipError_t launch_agc(const LaunchCfg &cfg, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm, const uint8_t *ctl, const igdsp_agc_cfg &agc,
                       uint32_t C, uint32_t F, uint32_t n, igdsp_agc_state *state, int16_t *out, igdsp_agc_rec *rec, igdsp_frame_stats *stats,
                       bool yardstick, hipStream_t s);
+// igdsp_vad_run: exactly one of g711 (with codec) and pcm; ctl, kind, rec, sid, txctl, events may each be nullptr; cfg checked by the C
+// ABI; event_count nullptr = no list (work unused), else work is igdsp_vad_work_bytes bytes, 16-byte aligned; event_mask 0 =
+// IGDSP_VAD_EVENT_DEFAULT.  C * F == 0 with a list: only the two counts are written (0).  yardstick: the compute-free form, the same row
+// loads, decode, LDS stores, state load and store, output stores and list passes, no lag sum, level, decision, model or recursion: it
+// stores the bytes igdsp_vad_run stores with every channel at IGDSP_VAD_BYPASS except ms = 0 and level = 127 in the records, and the
+// state, which a bypass leaves alone, as it was read (nf and A clamped; another tag: the RESET state) with the tag, flags
+// IGDSP_VAD_F_BYPASSED and reserved 0
+hipError_t launch_vad(const LaunchCfg &cfg, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm, const uint8_t *ctl, const igdsp_vad_cfg &vad,
+                      uint32_t C, uint32_t F, uint32_t n, uint32_t event_mask, igdsp_vad_state *state, uint8_t *kind, igdsp_vad_rec *rec, uint8_t *sid,
+                      uint8_t *txctl, igdsp_vad_event *events, uint32_t event_cap, uint32_t *event_count, void *work, bool yardstick, hipStream_t s);
 hipError_t launch_wav_expand(const LaunchCfg &cfg, const uint8_t *payload, uint32_t C, uint32_t F, uint32_t n, uint32_t rate,
                              uint8_t *files, uint64_t file_stride, hipStream_t s);
 hipError_t launch_g726(const LaunchCfg &cfg, const uint8_t *in, uint8_t *out, uint64_t n_bytes, int mode, hipStream_t s);

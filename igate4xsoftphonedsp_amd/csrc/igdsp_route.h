@@ -1156,6 +1156,52 @@ inline AgcRoute agc_route(uint32_t C, uint32_t F, uint32_t n, bool g711, bool ya
     return r;
 }
 
+// ---- igdsp_vad_run (launch_vad): k_vad<IN_G711, COPY> (+ k_vad_list<WRITE> and the link stage's k_link_scan for a list).  A DPP row of
+// 16 lanes owns a channel for the whole launch (the floor, the hangover and the noise model run through time): lane p and lane p + 16's
+// turn load a piece of 8 samples each (one 8-byte load of codes or one 16-byte load of PCM), the row goes to LDS as v = x >> 2 between
+// zeros and once more one sample ahead (for the odd lags), and lane k sums lag k over the whole row (the transposed shape: 11 of 16 lanes
+// busy, no reduction) and keeps A[k].  A wave is four channels, a block kVadWaves waves.  LDS: the level table times n, per channel the
+// row twice and the rare path's arrays (A, R, a, the payload).  Registers: the route is written for kVadResident blocks per CU (6 waves per SIMD, 80 VGPRs: at 64 the
+// PCM form spills).
+// The list: the records are dense (in d_rec, or in d_work when there is none), counted and stored as igdsp_tone_detect's.
+constexpr int kVadWaves = 4;                              // waves per block
+constexpr uint32_t kVadLanes = 16;                        // lanes per channel
+constexpr uint32_t kVadChans = kVadWaves * 4u;            // channels per block
+constexpr uint32_t kVadResident = 6;                      // blocks per CU
+constexpr uint32_t kVadPad = 16;                          // zeros in front of the row: the highest lane's lag is 15
+constexpr uint32_t kVadBuf = kVadPad + 256u + 8u;         // values per channel in LDS: zeros, the row, zeros (the second copy's last pair ends in one)
+constexpr uint32_t kVadLdsBytes = 128u * 8u + kVadChans * (kVadBuf * 2u + 256u * 2u + 3u * 12u * 8u + 16u);   // table; row, its second copy, A, R, a, payload
+constexpr int kVadListWaves = 4;
+struct VadRoute {
+    uint32_t grid = 0, threads = 0, lds = 0;
+    bool g711 = false, copy = false;       // k_vad<IN_G711, COPY>
+    uint32_t pieces = 0;                   // pieces of 8 samples per row: lanes p and p + 16 of the 16 take them in two turns
+    uint32_t waves = 0;                    // waves of 64 channels: the counts' row
+    uint32_t list_grid = 0;                // k_vad_list, both passes (0: no list)
+    uint64_t counts_bytes = 0;             // d_work: head + counts, rounded to 16
+    uint64_t work_bytes = 0;               // d_work in all: + the records when d_rec is NULL
+};
+inline uint64_t vad_counts_bytes(uint32_t C, uint32_t F) { return kLinkWorkHead + (((uint64_t)F * link_waves(C) * 4u + 15u) & ~15ull); }
+inline uint64_t vad_work_bytes(uint32_t C, uint32_t F, bool with_rec) { return vad_counts_bytes(C, F) + (with_rec ? 0u : (uint64_t)C * F * 16u); }
+inline VadRoute vad_route(uint32_t C, uint32_t F, uint32_t n, bool g711, bool yardstick, bool list, bool with_rec)
+{
+    VadRoute r;
+    if ((uint64_t)C * F == 0 || (uint64_t)C * F >= 0xFFFFFFE0ull || n < 16u || n > IGDSP_MAX_PAYLOAD || (n & 7u)) return r;
+    r.grid = (uint32_t)(((uint64_t)C + kVadChans - 1u) / kVadChans);
+    r.threads = kVadWaves * 64;
+    r.lds = kVadLdsBytes;
+    r.g711 = g711;
+    r.copy = yardstick;
+    r.pieces = n / 8u;
+    r.waves = link_waves(C);
+    if (list) {
+        r.list_grid = (uint32_t)(((uint64_t)F * r.waves + kVadListWaves - 1u) / kVadListWaves);
+        r.counts_bytes = vad_counts_bytes(C, F);
+        r.work_bytes = vad_work_bytes(C, F, with_rec);
+    }
+    return r;
+}
+
 // ---- igdsp_tx_flush (launch_tx_staged): a wave owns kTsLegs staged legs (runs) of the flush; lanes 0 .. kTsLegs-1 decide, the
 // whole wave writes the packets.  No dynamic LDS: each wave's records (kTsLegs x IGDSP_STAGE_DEPTH) are static.
 constexpr int kTsWaves = 4;

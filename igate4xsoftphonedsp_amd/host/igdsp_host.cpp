@@ -1175,6 +1175,59 @@ int igdsp_host_agc_rec(void *v, igdsp_agc_rec *out)
 float igdsp_host_agc_gain_db(void *v) { return v ? static_cast<LevelControl *>(v)->gainDb() : 0.0f; }
 void igdsp_host_agc_reset(void *v) { if (v) static_cast<LevelControl *>(v)->reset(); }
 
+// ---- the silence detector on one leg, no context needed
+VoiceDetector::VoiceDetector(uint32_t samples_per_frame) : n(samples_per_frame)
+{
+    igdsp_vad_cfg_default(&cfg);
+    ok = n >= 16 && n <= IGDSP_MAX_PAYLOAD && (n & 7u) == 0;
+    reset();
+}
+
+void VoiceDetector::reset()
+{
+    std::memset(&state, 0, sizeof(state));
+    std::memset(&last, 0, sizeof(last));
+    std::memset(sid, 0, sizeof(sid));
+}
+
+int VoiceDetector::process(const int16_t *frame, uint32_t ctl)
+{
+    if (!ok || !frame) return IGDSP_EINVAL;
+    return igdsp_vad_frame(&cfg, &state, frame, n, ctl, &last, sid);
+}
+
+void *igdsp_host_vad_new(uint32_t samples_per_frame)
+{
+    VoiceDetector *e = new (std::nothrow) VoiceDetector(samples_per_frame);
+    if (e && !e->ok) { delete e; e = nullptr; }
+    return e;
+}
+void igdsp_host_vad_free(void *v) { delete static_cast<VoiceDetector *>(v); }
+int igdsp_host_vad_process(void *v, const int16_t *frame, uint32_t ctl)
+{
+    if (!v) return IGDSP_EINVAL;
+    return static_cast<VoiceDetector *>(v)->process(frame, ctl);
+}
+int igdsp_host_vad_rec(void *v, igdsp_vad_rec *out)
+{
+    if (!v || !out) return IGDSP_EINVAL;
+    *out = static_cast<VoiceDetector *>(v)->last;
+    return IGDSP_OK;
+}
+int igdsp_host_vad_sid(void *v, uint8_t out[16])
+{
+    if (!v || !out) return IGDSP_EINVAL;
+    std::memcpy(out, static_cast<VoiceDetector *>(v)->sid, 16);
+    return (int)static_cast<VoiceDetector *>(v)->sidLen();
+}
+int igdsp_host_vad_cfg(void *v, const igdsp_vad_cfg *cfg)
+{
+    if (!v || !cfg) return IGDSP_EINVAL;
+    static_cast<VoiceDetector *>(v)->cfg = *cfg;
+    return IGDSP_OK;
+}
+void igdsp_host_vad_reset(void *v) { if (v) static_cast<VoiceDetector *>(v)->reset(); }
+
 // ---- conference receive levels, no context needed
 void *igdsp_host_levels_new(uint32_t n_channels)
 {

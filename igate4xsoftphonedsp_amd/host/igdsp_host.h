@@ -340,6 +340,27 @@ public:
     void reset();                            // envelope, gain and cap forgotten
 };
 
+// The stream's silence detector on one leg, without a context: one channel through igdsp_vad_frame.  pjmedia's stream holds one and the
+// reference switches it off (media_cfg.no_vad = 1); process() tells per frame whether to send it (IGDSP_VAD_VOICE), to send the
+// comfort-noise payload instead (IGDSP_VAD_SID: sid, sidLen bytes, RTP payload type 13) or nothing (IGDSP_VAD_NONE), and the record
+// carries the talkspurt's edges.  igdsp_vad_run takes the same states for thousands of channels.  UNVERIFIED against RFC 3389.
+class VoiceDetector {
+public:
+    explicit VoiceDetector(uint32_t samples_per_frame = IGDSP_SAMPLES_PER_FRAME);
+    uint32_t n;
+    bool ok;                                 // n a multiple of 8 in 16 .. 256
+    igdsp_vad_cfg cfg;                       // the defaults; a caller may change any field (an invalid cfg: process() gives IGDSP_EINVAL)
+    igdsp_vad_state state;
+    igdsp_vad_rec last;                      // the record of the last frame
+    uint8_t sid[16];                         // the last frame's payload (zeros unless it was a SID frame)
+    int process(const int16_t *frame, uint32_t ctl = IGDSP_VAD_RUN);   // the frame's kind, or IGDSP_EINVAL
+    uint32_t sidLen() const { return last.sid_len; }
+    bool onset() const { return (last.flags & IGDSP_VAD_F_ONSET) != 0; }      // the RTP marker bit belongs on this frame
+    bool offset() const { return (last.flags & IGDSP_VAD_F_OFFSET) != 0; }
+    bool voice() const { return (last.flags & IGDSP_VAD_F_VOICE) != 0; }
+    void reset();                            // the floor, the hangover and the noise model forgotten
+};
+
 class RoIP_ED137 {
 public:
     // Unlike the reference singleton (roip_ed137.cpp:192) the instance owns an igdsp context; device < 0
@@ -492,6 +513,16 @@ int   igdsp_host_agc_process(void *v, const int16_t *frame, int16_t *out, uint32
 int   igdsp_host_agc_rec(void *v, igdsp_agc_rec *out);
 float igdsp_host_agc_gain_db(void *v);
 void  igdsp_host_agc_reset(void *v);
+// the silence detector on one leg without a context (VoiceDetector): NULL from _new for a frame length igdsp_vad_frame rejects;
+// _process one frame: its kind (IGDSP_EINVAL for a NULL handle or frame); _rec a copy of the last frame's record; _sid its payload's 16
+// bytes, returns the length; _cfg replaces the cfg (IGDSP_EINVAL for NULL); _reset forgets the state
+void *igdsp_host_vad_new(uint32_t samples_per_frame);
+void  igdsp_host_vad_free(void *v);
+int   igdsp_host_vad_process(void *v, const int16_t *frame, uint32_t ctl);
+int   igdsp_host_vad_rec(void *v, igdsp_vad_rec *out);
+int   igdsp_host_vad_sid(void *v, uint8_t out[16]);
+int   igdsp_host_vad_cfg(void *v, const igdsp_vad_cfg *cfg);
+void  igdsp_host_vad_reset(void *v);
 // the spectrum graph without a context (SpectrumGraph): NULL from _new for sizes igdsp_spec_frame rejects; _feed one frame in (1: it
 // computed a spectrum, 0: not, IGDSP_EINVAL for a NULL argument); _real / _iir the two arrays of 512 floats, owned by the handle; _clear
 // is spectClear; _fft_avg is d_fftAvg

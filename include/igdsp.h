@@ -46,7 +46,9 @@ extern "C" {
  *    igdsp_dbuf_step); the spectrum graph (IGDSP_SPEC_*, igdsp_spec_state, igdsp_spec_cfg, igdsp_spec_rec, igdsp_spectrum,
  *    igdsp_spec_frame, igdsp_spec_tables); the tone detector (IGDSP_TDET_*, igdsp_tdet_*, igdsp_tone_detect); the echo canceller
  *    (IGDSP_EC_*, igdsp_ec_cfg, igdsp_ec_state, igdsp_ec_rec, igdsp_ec_cfg_default, igdsp_ec_frame, igdsp_echo_cancel); the level control
- *    (IGDSP_AGC_*, igdsp_agc_cfg, igdsp_agc_state, igdsp_agc_rec, igdsp_agc_cfg_default, igdsp_agc_frame, igdsp_agc_run). */
+ *    (IGDSP_AGC_*, igdsp_agc_cfg, igdsp_agc_state, igdsp_agc_rec, igdsp_agc_cfg_default, igdsp_agc_frame, igdsp_agc_run); voice
+ *    activity, DTX and the RFC 3389 comfort-noise payload (IGDSP_VAD_*, igdsp_vad_cfg, igdsp_vad_state, igdsp_vad_rec, igdsp_vad_event,
+ *    igdsp_vad_cfg_default, igdsp_vad_table, igdsp_vad_frame, igdsp_sid_decode, igdsp_vad_work_bytes, igdsp_vad_run). */
 #define IGDSP_ABI_VERSION 3
 
 /* ---- error codes (0 == PJ_SUCCESS-style success) ------------------------- */
@@ -1763,6 +1765,140 @@ int igdsp_agc_run(igdsp_ctx *ctx, const uint8_t *d_g711 /* [F][C][n] */, const u
                   const int16_t *d_pcm /* [F][C][n] */, const uint8_t *d_ctl /* [C], NULL: RUN */, const igdsp_agc_cfg *cfg,
                   uint32_t n_channels, uint32_t n_frames, uint32_t samples_per_frame, igdsp_agc_state *d_state /* [C], in and out */,
                   int16_t *d_out /* [F][C][n] */, igdsp_agc_rec *d_rec /* [F][C] */, igdsp_frame_stats *d_stats /* [F][C] */, void *stream);
+
+/* ---- Voice activity: the stream's silence detector, DTX and the RFC 3389 comfort-noise payload, per channel and frame ----------------------
+ * pjmedia's stream holds a silence detector and the reference switches it off (media_cfg.no_vad = 1, next to ec_tail_len = 0).
+ * igdsp_vad_run is that detector for a batch, on the send side in front of igdsp_tx_packetize: it follows igdsp_conf_mix or
+ * igdsp_agc_run (their d_out as d_pcm) or sits on a leg's G.711 rows.  It gives a leg without a PTT line its control byte (VOX), tells
+ * a SIP leg which frames to send, which to replace by one PT 13 comfort-noise packet and which to skip (DTX), and lists the talkspurt
+ * edges.  Everything is integer: the same bits on the host and the device, at any channel count and position and for any split of
+ * the frames over launches.  The rule is the library's own; the payload's scale and sign convention are RFC 3389 section 3.2 as
+ * recalled.  UNVERIFIED against RFC 3389 and G.711 Appendix II.
+ *
+ * RULE.  A frame is n samples, n a multiple of 8 in 16..256.  M = 10.  "/" is C division, ">>" on a signed value an arithmetic shift.
+ *   0. v_j = x_j >> 2 (G.711 decoded as igdsp_spectrum does; decoded mu-law values are multiples of 4, A-law of 8: nothing is lost.
+ *      PCM loses two bits).
+ *   1. r[k] = sum over j = k .. n - 1 of v_j * v_(j-k), k = 0..M, exact in 64 bits (r[0] < 2^34), no history across frames.
+ *      E = r[0], ms = E / n.
+ *   2. The decision.  nf == 0 (the floor is unset): nf = clamp(ms, nf_min, nf_max) first.  ratio = VOICE ? ratio_off_q4 : ratio_on_q4;
+ *      raw = ms >= thr_abs && ms * 16 > nf * ratio.
+ *   3. The floor (skipped under FREEZE).  QUIET = ms < nf_min: the floor stays (digital silence does not teach it).  Else ms <= nf:
+ *      nf -= (nf - ms) >> dn;  else nf = min(ms, nf + max(1, nf >> (raw ? up_v : up))).  Then nf = clamp(nf, nf_min, nf_max).
+ *   4. The hangover.  raw: run = min(run + 1, 65535); hang = run >= burst ? hang_long : max(hang, hang_short); VOICE.  Not raw: run = 0;
+ *      hang > 0: hang -= 1 and VOICE stays as it was;  else not VOICE.  ONSET: VOICE after not-VOICE; OFFSET: the first not-VOICE
+ *      frame after VOICE.  raw, QUIET, VOICE, ONSET and OFFSET are the record's flags IGDSP_VAD_F_RAW, _F_QUIET, _F_VOICE, _F_ONSET and
+ *      _F_OFFSET; the kind IGDSP_VAD_VOICE of step 6 is a value of its own.
+ *   5. The noise model (skipped under FREEZE).  On every frame that is not raw (hangover and QUIET frames included):
+ *      avalid == 0: A[k] = r[k], avalid = 1;  else A[k] += (r[k] - A[k]) >> asm_shift.
+ *   6. DTX.  cfg.dtx == 0: kind = VOICE on every frame, no SID (the flags still carry the decision).  Else a VOICE frame has kind =
+ *      VOICE; on a non-VOICE frame lvl = level(A[0]) and a SID is due when it is the OFFSET frame, or no SID has been sent since RESET,
+ *      or sid_every > 0 && since_sid >= sid_every, or |lvl - last_level| >= sid_delta && since_sid >= sid_gap.  Due: kind = SID,
+ *      since_sid = 0, last_level = lvl, sid_sent = 1.  Else kind = NONE, since_sid = min(since_sid + 1, 65535).
+ *   7. The SID payload, 1 + order bytes (order 0..10).  Byte 0 = lvl.  level(e) = 127 for e <= 0, else the least d in 0..126 with
+ *      (e << 8) >= n * T8[d], 127 if there is none;  T8[d] = floor(2^34 * 10^(-d / 10) + 1/2) (igdsp_vad_table): lvl = ceil(-dBov), a
+ *      full-scale square wave reads 0.  Bytes 1..order: N_i = 127 + sign(k_i) * ((|k_i| + 129) / 258), k_i in Q15 from this
+ *      recursion on A:  A[0] <= 0: every k = 0.  R0 = A[0] + (A[0] >> 10) + 1;  sh = bitlen(R0) - 30;  R[k] = clamp(A[k], -A[0], A[0])
+ *      >> sh (<< -sh when sh < 0), R[0] from R0;  a[] Q15 in 64 bits;  err = R[0].  For i = 1..order:
+ *        acc = (R[i] << 15) + sum over 1 <= j < i of a[j] * R[i-j];  k_i = clamp(-acc / err, -32508, 32508);
+ *        a'[j] = a[j] + ((k_i * a[i-j] + 16384) >> 15) for j < i, a'[i] = k_i;  err -= (((k_i * k_i) >> 15) * err) >> 15;
+ *        err <= 0: stop, the remaining k are 0.
+ *      k_i = a_i^(i) of the predictor A(z) = 1 + sum a_j z^-j: positively correlated noise has k_1 < 0.  igdsp_sid_decode is the
+ *      inverse map: level = byte 0, k_i = 258 * (N_i - 127), N_i = 255 read as 254; bytes past 1 + 10 are ignored; k past the payload 0.
+ *
+ * CONFIGURATION.  igdsp_vad_cfg holds for the launch; NULL: the defaults of igdsp_vad_cfg_default.  Levels are in the v domain (ms of
+ * v): thr_abs 212 (about -55 dBov), nf_min 8 (just above both G.711 digital silences: 0, and A-law's +8, ms 4), nf_max 1 << 20,
+ * ratio_on_q4 80 (about 7 dB), ratio_off_q4 40 (about 4 dB), dn 2, up 5, up_v 7, burst 5, hang_long 10, hang_short 2, order 10,
+ * asm_shift 2, dtx 1, sid_every 0, sid_delta 2, sid_gap 2, vox_on 0x81, vox_off 0x80.  Valid: 1 <= nf_min <= nf_max <= 1 << 24;
+ * 16 <= ratio_off_q4 <= ratio_on_q4; dn, up, up_v, asm_shift <= 15; order <= 10; hang_short <= hang_long.
+ *
+ * STATE.  igdsp_vad_state, 128 bytes, one per channel, read at the start of a launch and written at its end.  A tag other than
+ * IGDSP_VAD_TAG (all-zero included) means the RESET state: everything 0.  Under the right tag any bytes are a valid state: nf is read
+ * clamped to [nf_min, nf_max] (0 stays 0: unset), A[k] clamped to +-2^40, voice, avalid and sid_sent by their bit 0; nothing indexes by
+ * a field.  flags is written as the last frame's record flags, reserved as 0.
+ *
+ * CONTROL.  d_ctl[c] (NULL: IGDSP_VAD_RUN; a value above 3 counts as RUN) holds for the launch: IGDSP_VAD_FREEZE skips steps 3 and 5
+ * (the decision still runs; an unset floor is still set);  IGDSP_VAD_BYPASS: kind = VOICE, vox_on, flags = IGDSP_VAD_F_BYPASSED, ms and
+ * level of the frame, nf, run and hang as read, no SID, the state's bytes untouched;  IGDSP_VAD_RESET: the state becomes the RESET
+ * state before the first frame, then RUN.
+ *
+ * OUTPUTS, each optional; one of d_kind, d_rec, d_sid, d_txctl or the event list is required.  d_kind[f][c]: IGDSP_VAD_NONE / _VOICE /
+ * _SID.  d_rec[f][c] (igdsp_vad_rec): ms, nf after the frame, run, flags (IGDSP_VAD_F_RAW, _F_VOICE, _F_ONSET, _F_OFFSET, _F_SID,
+ * _F_QUIET, _F_FROZEN, _F_BYPASSED), kind (IGDSP_VAD_NONE / _VOICE / _SID), level = this frame's own level(E), hang, sid_len.  d_sid[f][c][16]: always written as one 16-byte store,
+ * the payload in the first sid_len bytes, zeros behind.  d_txctl[f][c]: vox_on on frames whose flags carry IGDSP_VAD_F_VOICE (or _F_BYPASSED), vox_off otherwise:
+ * igdsp_tx_packetize takes it as d_ctl.  The event list has igdsp_link_watch's contract: (f, c) is an event iff flags & event_mask
+ * (0 = IGDSP_VAD_EVENT_DEFAULT = IGDSP_VAD_F_ONSET | IGDSP_VAD_F_OFFSET), order frame-major then ascending channel, d_event_count[0] = the number of events,
+ * [1] = min(that, event_cap) = the number stored, nothing is written past d_events[event_cap); d_events may be NULL iff event_cap ==
+ * 0; d_event_count NULL: no list.  A list needs d_work of igdsp_vad_work_bytes(n_channels, n_frames, d_rec != NULL) bytes.
+ *
+ * ARGUMENTS.  samples_per_frame not a multiple of 8 in 16..256, an invalid cfg: IGDSP_EINVAL, whether or not there is work.
+ * n_channels == 0 or n_frames == 0: nothing to do, the counts of a list are written as 0.  Exactly one of d_g711 (with d_codec) and
+ * d_pcm; d_state required.  n_channels * n_frames < 2^32 - 32 (IGDSP_ERANGE).  d_g711 8-byte, d_event_count 4-byte, d_pcm, d_state,
+ * d_rec, d_sid, d_events, d_work 16-byte aligned.  The state and the outputs may overlap neither an input nor each other.  Enqueued
+ * on `stream`, not synchronised.
+ *
+ * igdsp_vad_frame (host only, no GPU): one frame of one channel from PCM by the same rule; rec and sid optional; returns the kind
+ * (>= 0) or IGDSP_EINVAL for what the entry rejects.  igdsp_vad_table: the 128 values of T8. */
+#define IGDSP_VAD_ORDER   10
+#define IGDSP_VAD_KMAX    32508       /* 126 * 258: the largest |k| the payload carries               */
+#define IGDSP_VAD_TAG     0x7AD10001u /* igdsp_vad_state.tag                                      */
+#define IGDSP_VAD_RUN     0           /* d_ctl                                                    */
+#define IGDSP_VAD_FREEZE  1
+#define IGDSP_VAD_BYPASS  2
+#define IGDSP_VAD_RESET   3
+#define IGDSP_VAD_NONE    0           /* d_kind, igdsp_vad_rec.kind                               */
+#define IGDSP_VAD_VOICE   1
+#define IGDSP_VAD_SID     2
+#define IGDSP_VAD_F_RAW      0x01     /* igdsp_vad_rec.flags                                      */
+#define IGDSP_VAD_F_VOICE    0x02
+#define IGDSP_VAD_F_ONSET    0x04
+#define IGDSP_VAD_F_OFFSET   0x08
+#define IGDSP_VAD_F_SID      0x10
+#define IGDSP_VAD_F_QUIET    0x20
+#define IGDSP_VAD_F_FROZEN   0x40
+#define IGDSP_VAD_F_BYPASSED 0x80
+#define IGDSP_VAD_EVENT_DEFAULT 0x0C
+typedef struct igdsp_vad_cfg {
+    uint32_t thr_abs;               /* ms below it is never raw                                  */
+    uint32_t nf_min, nf_max;        /* the floor's bounds                                        */
+    uint16_t sid_every;             /* frames between scheduled SIDs, 0: none                    */
+    uint8_t  ratio_on_q4, ratio_off_q4;
+    uint8_t  dn, up, up_v, asm_shift;
+    uint8_t  burst, hang_long, hang_short, order;
+    uint8_t  dtx, sid_delta, sid_gap, vox_on;
+    uint8_t  vox_off, reserved[3];
+} igdsp_vad_cfg;                    /* 32 bytes */
+typedef struct igdsp_vad_state {
+    uint32_t tag;
+    uint32_t nf;                    /* 0: unset                                                  */
+    int64_t  A[IGDSP_VAD_ORDER + 1];/* the noise model's autocorrelation                         */
+    uint16_t since_sid, run;
+    uint8_t  hang, voice, avalid, last_level;
+    uint8_t  sid_sent, flags, reserved[22];
+} igdsp_vad_state;                  /* 128 bytes */
+typedef struct igdsp_vad_rec {
+    uint32_t ms, nf;
+    uint16_t run;
+    uint8_t  flags, kind, level, hang, sid_len, reserved;
+} igdsp_vad_rec;                    /* 16 bytes */
+typedef struct igdsp_vad_event {
+    uint32_t channel;
+    uint32_t frame;                 /* f within this launch                                      */
+    uint32_t ms;
+    uint16_t run;
+    uint8_t  flags, level;
+} igdsp_vad_event;                  /* 16 bytes */
+void igdsp_vad_cfg_default(igdsp_vad_cfg *out);
+int igdsp_vad_table(uint64_t out[128]);
+int igdsp_vad_frame(const igdsp_vad_cfg *cfg, igdsp_vad_state *st, const int16_t *pcm, uint32_t samples_per_frame, uint32_t ctl,
+                    igdsp_vad_rec *rec, uint8_t sid[16]);
+int igdsp_sid_decode(const uint8_t *payload, uint32_t len, uint8_t *level_dbov, int16_t k_q15[10]);
+size_t igdsp_vad_work_bytes(uint32_t n_channels, uint32_t n_frames, int with_rec);
+int igdsp_vad_run(igdsp_ctx *ctx, const uint8_t *d_g711 /* [F][C][n] */, const uint8_t *d_codec /* [C] */,
+                  const int16_t *d_pcm /* [F][C][n] */, const uint8_t *d_ctl /* [C], NULL: RUN */, const igdsp_vad_cfg *cfg,
+                  uint32_t n_channels, uint32_t n_frames, uint32_t samples_per_frame, uint32_t event_mask,
+                  igdsp_vad_state *d_state /* [C], in and out */, uint8_t *d_kind /* [F][C] */, igdsp_vad_rec *d_rec /* [F][C] */,
+                  uint8_t *d_sid /* [F][C][16] */, uint8_t *d_txctl /* [F][C] */, igdsp_vad_event *d_events, uint32_t event_cap,
+                  uint32_t *d_event_count, void *d_work, void *stream);
 
 /* ---- synthetic input generators (device side; SURVEY 8(d) definitions) ---------
  * D-uniform: byte k of global byte index g is
