@@ -150,6 +150,15 @@ VAD_REC = np.dtype([("ms", "<u4"), ("nf", "<u4"), ("run", "<u2"), ("flags", "u1"
                     ("reserved", "u1")], align=True)                                               # igdsp_vad_rec, 16 bytes
 VAD_EVENT = np.dtype([("channel", "<u4"), ("frame", "<u4"), ("ms", "<u4"), ("run", "<u2"), ("flags", "u1"), ("level", "u1")],
                      align=True)                                                                   # igdsp_vad_event, 16 bytes
+# comfort noise from RFC 3389 SIDs (igdsp_cng_run / igdsp_cng_frame)
+CNG_TAG, CNG_GMAX = 0xC4610001, 3632640
+CNG_RUN, CNG_FREEZE, CNG_BYPASS, CNG_RESET = 0, 1, 2, 3
+CNG_F_GENERATED, CNG_F_SID, CNG_F_NO_MODEL, CNG_F_VOICE, CNG_F_CLIPPED, CNG_F_SID_EMPTY, CNG_F_FROZEN, CNG_F_BYPASSED = 1, 2, 4, 8, 16, 32, 64, 128
+CNG_STATE = np.dtype([("tag", "<u4"), ("seed", "<u4"), ("ctr", "<u4"), ("g", "<u4"), ("g_tgt", "<u4"), ("b", "<i4", (10,)), ("kq", "<i2", (10,)),
+                      ("since_sid", "<u2"), ("level", "u1"), ("order", "u1"), ("have", "u1"), ("flags", "u1"), ("reserved", "u1", (10,))],
+                     align=True)                                                                   # igdsp_cng_state, 96 bytes
+CNG_REC = np.dtype([("g", "<u4"), ("g_tgt", "<u4"), ("since_sid", "<u2"), ("flags", "u1"), ("level", "u1"), ("order", "u1"), ("reserved", "u1", (3,))],
+                   align=True)                                                                     # igdsp_cng_rec, 16 bytes
 CHAN_PROBE = np.dtype([("run", "<u4"), ("alarms", "<u4")], align=True)
 # the jitter buffer (igdsp_jb_receive / igdsp_jb_report)
 JB_STATE = np.dtype(
@@ -346,6 +355,10 @@ PROTOTYPES = [
     ("igdsp_sid_decode", _int, [_vp, _u32, _vp, _vp]),
     ("igdsp_vad_work_bytes", C.c_size_t, [_u32, _u32, _int]),
     ("igdsp_vad_run", _int, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp]),
+    ("igdsp_cng_table", _int, [_vp]),
+    ("igdsp_cng_gain", _int, [_vp, _u32, _vp]),
+    ("igdsp_cng_frame", _int, [_vp, _u32, _vp, _u32, _vp, _u32, _u32, _u32, _vp, _vp]),
+    ("igdsp_cng_run", _int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("igdsp_g726_reorder", _int, [_vp, _vp, _vp, _u64, _int, _vp]),
     ("igdsp_gen_uniform", _int, [_vp, _vp, _u64, _u64, _u64, _vp]),
     ("igdsp_dev_alloc", _int, [_vp, C.POINTER(_vp), C.c_size_t]),
@@ -387,7 +400,8 @@ INTERNAL["igdsp_internal_tx_copy"] = (_int, [_vp, _vp, _vp, _u32, _u32, _u32, _v
 # A yardstick whose name is not of the *_copy / *_fill form: the same derivation, a table of its own; internal() consults both
 INTERNAL_MORE_TWIN = {"igdsp_internal_dbuf_move": "igdsp_dbuf_run", "igdsp_internal_spec_move": "igdsp_spectrum",
                       "igdsp_internal_tdet_move": "igdsp_tone_detect", "igdsp_internal_ec_move": "igdsp_echo_cancel",
-                      "igdsp_internal_agc_move": "igdsp_agc_run", "igdsp_internal_vad_move": "igdsp_vad_run"}
+                      "igdsp_internal_agc_move": "igdsp_agc_run", "igdsp_internal_vad_move": "igdsp_vad_run",
+                      "igdsp_internal_cng_move": "igdsp_cng_run"}
 INTERNAL_MORE = {name: _PUBLIC[twin] for name, twin in INTERNAL_MORE_TWIN.items()}
 
 _lib = None
@@ -704,6 +718,40 @@ def sid_decode(payload):
     return int(lvl[0]), k
 
 
+def cng_table() -> np.ndarray:
+    """igdsp_cng_table (host only, no GPU): the 128 values of G as uint32."""
+    out = np.zeros(128, np.uint32)
+    rc = load().igdsp_cng_table(out.ctypes.data_as(_vp))
+    if rc != 0:
+        raise IgdspError(rc, "igdsp_cng_table")
+    return out
+
+
+def cng_gain(payload) -> int:
+    """igdsp_cng_gain (host only, no GPU): g_tgt of an RFC 3389 payload of 1..16 bytes."""
+    p = np.ascontiguousarray(payload, np.uint8)
+    out = C.c_uint32(0)
+    rc = load().igdsp_cng_gain(p.ctypes.data_as(_vp), len(p), C.byref(out))
+    if rc != 0:
+        raise IgdspError(rc, "igdsp_cng_gain")
+    return int(out.value)
+
+
+def cng_frame(state, kind: int, n: int, sid=None, sid_len: int = 11, voice=None, ctl: int = CNG_RUN, seed: int = 0):
+    """igdsp_cng_frame (host only, no GPU): one frame of one channel.  state a CNG_STATE record updated in place, sid the payload
+    (uint8, up to 16 bytes) or None, voice the leg's row (int16 [n]) or None.  Returns (out int16 [n], len_out, the frame's CNG_REC)."""
+    assert state.dtype == CNG_STATE and state.flags["C_CONTIGUOUS"] and state.flags["WRITEABLE"]
+    p = None if sid is None else np.ascontiguousarray(sid, np.uint8)
+    v = None if voice is None else np.ascontiguousarray(voice, np.int16)
+    assert v is None or len(v) == n
+    out, rec = np.zeros(n, np.int16), np.zeros((), CNG_REC)
+    rc = load().igdsp_cng_frame(state.ctypes.data_as(_vp), int(kind), None if p is None else p.ctypes.data_as(_vp), int(sid_len),
+                                None if v is None else v.ctypes.data_as(_vp), n, int(ctl), int(seed), out.ctypes.data_as(_vp), rec.ctypes.data_as(_vp))
+    if rc < 0:
+        raise IgdspError(rc, "igdsp_cng_frame")
+    return out, rc, rec
+
+
 def vad_work_bytes(n_channels: int, n_frames: int, with_rec: bool) -> int:
     """igdsp_vad_work_bytes (host only, no GPU): bytes of igdsp_vad_run's d_work for a launch of this shape."""
     return int(load().igdsp_vad_work_bytes(n_channels, n_frames, 1 if with_rec else 0))
@@ -1010,6 +1058,14 @@ class Context:
         self._ck(self.L.igdsp_vad_run(self.h, _ptr(g711), _ptr(codec), _ptr(pcm), _ptr(ctl), None if c is None else c.ctypes.data_as(_vp), C_, F_, n,
                                       event_mask, _ptr(state), _ptr(kind), _ptr(rec), _ptr(sid), _ptr(txctl), _ptr(events), event_cap,
                                       _ptr(event_count), _ptr(work), stream), "igdsp_vad_run")
+
+    def cng_run(self, kind, sid, state, out, C_, F_, n, sid_len=None, g711=None, codec=None, pcm=None, ctl=None, seed=None, len_out=None, rec=None,
+                stats=None, stream=None):
+        """igdsp_cng_run: kind [F][C] u8 and sid [F][C][16] u8 as igdsp_vad_run writes them, sid_len [F][C] u8 or None (11); at most one of
+        g711 [F][C][n] u8 (+ codec [C]) / pcm [F][C][n] int16; ctl [C] u8 or None (CNG_RUN); seed [C] u32 or None; state [C] CNG_STATE (in and
+        out) -> out [F][C][n] int16, len_out [F][C] u16, rec [F][C] CNG_REC, stats [F][C] FRAME_STATS (the last three optional)."""
+        self._ck(self.L.igdsp_cng_run(self.h, _ptr(kind), _ptr(sid), _ptr(sid_len), _ptr(g711), _ptr(codec), _ptr(pcm), _ptr(ctl), _ptr(seed), C_, F_, n,
+                                      _ptr(state), _ptr(out), _ptr(len_out), _ptr(rec), _ptr(stats), stream), "igdsp_cng_run")
 
     def bss_select(self, info, group_ptr, members, n_members, state, words, C_, G_, F_, n=160, payload=None, codec=None, pcm=None,
                    length=None, gain=None, mute=None, vote_frames=0, sel=None, out=None, stats=None, stream=None):

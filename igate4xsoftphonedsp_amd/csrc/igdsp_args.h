@@ -12,6 +12,7 @@
 
 #include "igdsp.h"
 #include "igdsp_agc.h"
+#include "igdsp_cng.h"
 #include "igdsp_route.h"
 #include "igdsp_vad.h"
 
@@ -578,6 +579,33 @@ inline Verdict vad_run(P d_g711, P d_codec, P d_pcm, P d_ctl, const igdsp_vad_cf
                          {d_txctl, frames}, {list ? d_events : nullptr, (uint64_t)event_cap * sizeof(igdsp_vad_event)}, {d_event_count, 8u},
                          {list ? d_work : nullptr, vad_work_bytes(C, F, d_rec != nullptr)}};
     for (int i = 0; i < 8; ++i) {
+        for (const Buf &b : ins)
+            if (ranges_overlap(outs[i].p, outs[i].bytes, b.p, b.bytes)) return reject(IGDSP_EINVAL, "the state and the outputs must not overlap an input");
+        for (int j = 0; j < i; ++j)
+            if (ranges_overlap(outs[i].p, outs[i].bytes, outs[j].p, outs[j].bytes))
+                return reject(IGDSP_EINVAL, "the state and the outputs must not overlap each other");
+    }
+    return kRun;
+}
+
+// ---- comfort noise.  The frame length is checked whether or not there is work
+inline Verdict cng_run(P d_kind, P d_sid, P d_sid_len, P d_g711, P d_codec, P d_pcm, P d_ctl, P d_seed, uint32_t C, uint32_t F, uint32_t n, P d_state,
+                       P d_out, P d_len_out, P d_rec, P d_stats)
+{
+    if (!cng_n_ok(n)) return kInvalid;
+    if (empty(C, F)) return kNothing;
+    if (any_null({d_kind, d_sid, d_state, d_out}) || !at_most_one(d_g711, d_pcm) || (d_g711 && !d_codec)) return kInvalid;
+    if ((uint64_t)C * F >= 0xFFFFFFE0ull) return reject(IGDSP_ERANGE);
+    // a piece of 8 samples is one load (8 bytes of codes, 16 of PCM) and one 16-byte store; the state goes as six 16-byte pieces, a
+    // payload, a record and a stats record as one
+    if (misaligned(8, {d_g711}) || misaligned(16, {d_sid, d_pcm, d_state, d_out, d_rec, d_stats})) return kInvalid;
+    const uint64_t frames = (uint64_t)C * F;
+    struct Buf { P p; uint64_t bytes; };
+    const Buf ins[8] = {{d_kind, frames}, {d_sid, frames * 16u}, {d_sid_len, frames}, {d_g711, frames * n}, {d_g711 ? d_codec : nullptr, C},
+                        {d_pcm, frames * n * 2u}, {d_ctl, C}, {d_seed, (uint64_t)C * 4u}};
+    const Buf outs[5] = {{d_state, (uint64_t)C * sizeof(igdsp_cng_state)}, {d_out, frames * n * 2u}, {d_len_out, frames * 2u},
+                         {d_rec, frames * sizeof(igdsp_cng_rec)}, {d_stats, frames * sizeof(igdsp_frame_stats)}};
+    for (int i = 0; i < 5; ++i) {
         for (const Buf &b : ins)
             if (ranges_overlap(outs[i].p, outs[i].bytes, b.p, b.bytes)) return reject(IGDSP_EINVAL, "the state and the outputs must not overlap an input");
         for (int j = 0; j < i; ++j)

@@ -190,6 +190,14 @@ hipError_t launch_agc(const LaunchCfg &cfg, const uint8_t *g711, const uint8_t *
 hipError_t launch_vad(const LaunchCfg &cfg, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm, const uint8_t *ctl, const igdsp_vad_cfg &vad,
                       uint32_t C, uint32_t F, uint32_t n, uint32_t event_mask, igdsp_vad_state *state, uint8_t *kind, igdsp_vad_rec *rec, uint8_t *sid,
                       uint8_t *txctl, igdsp_vad_event *events, uint32_t event_cap, uint32_t *event_count, void *work, bool yardstick, hipStream_t s);
+// igdsp_cng_run: kind, sid, state, out required; at most one of g711 (with codec) and pcm; sid_len (nullptr: 11), ctl, seed, len_out, rec,
+// stats may each be nullptr.  yardstick: the compute-free form, the same kind, length and voice-row loads, decode, tile stores and reads,
+// state load and store and output stores, no excitation, lattice, gain step or SID step: it stores the bytes igdsp_cng_run stores with
+// every channel at IGDSP_CNG_BYPASS, and the state, which a bypass leaves alone, as it was read (b, kq, g, g_tgt clamped, have its bit
+// 0; another tag: the RESET state with d_seed's seed) with the tag, flags as read and reserved 0; ctl and the payloads are not read
+hipError_t launch_cng(const LaunchCfg &cfg, const uint8_t *kind, const uint8_t *sid, const uint8_t *sid_len, const uint8_t *g711, const uint8_t *codec,
+                      const int16_t *pcm, const uint8_t *ctl, const uint32_t *seed, uint32_t C, uint32_t F, uint32_t n, igdsp_cng_state *state,
+                      int16_t *out, uint16_t *len_out, igdsp_cng_rec *rec, igdsp_frame_stats *stats, bool yardstick, hipStream_t s);
 hipError_t launch_wav_expand(const LaunchCfg &cfg, const uint8_t *payload, uint32_t C, uint32_t F, uint32_t n, uint32_t rate,
                              uint8_t *files, uint64_t file_stride, hipStream_t s);
 hipError_t launch_g726(const LaunchCfg &cfg, const uint8_t *in, uint8_t *out, uint64_t n_bytes, int mode, hipStream_t s);

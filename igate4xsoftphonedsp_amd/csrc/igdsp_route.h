@@ -1202,6 +1202,44 @@ inline VadRoute vad_route(uint32_t C, uint32_t F, uint32_t n, bool g711, bool ya
     return r;
 }
 
+// ---- igdsp_cng_run (launch_cng): k_cng<IN, COPY>.  A lane owns a channel for the whole launch (the lattice is serial in the sample: the
+// parallelism is across channels); a block is one wave and kCngChans channels.  LDS: the frame's kCngChans rows as a tile, a row
+// n / 2 + 1 dwords apart (odd: the lanes' dword stores of one sample pair fall into different banks), and a byte per row that says
+// who fills it.  The wave fills the voice rows and stores the whole tile piece by piece (16 bytes of a row, pieces of a tile are
+// consecutive in memory); item i of a pass is row i / P, piece i % P, the division done by the multiplier `inv` (exact below 2^11
+// items for P <= 32).  Registers and LDS: the route is written for kCngResident blocks per CU, one wave per SIMD at 65 536 channels
+// (128 VGPRs; 33 088 bytes of LDS at n = 256).
+constexpr uint32_t kCngChans = 64;                        // channels per block: the lanes of its one wave
+constexpr uint32_t kCngResident = 4;                      // blocks per CU
+constexpr uint32_t kCngVgprs = 128;
+constexpr int kCngNone = 0, kCngG711 = 1, kCngPcm = 2;    // k_cng<IN, >: the voice input
+constexpr uint32_t cng_row_dwords(uint32_t n) { return n / 2u + 1u; }
+constexpr uint32_t cng_lds_bytes(uint32_t n) { return kCngChans * cng_row_dwords(n) * 4u + kCngChans; }
+constexpr uint32_t cng_inv(uint32_t pieces) { return (1u << 20) / pieces + 1u; }
+static_assert(kCngResident * cng_lds_bytes(256) <= 160u * 1024u, "the resident blocks' tiles fit a CU's LDS");
+struct CngRoute {
+    uint32_t grid = 0, threads = 0, lds = 0;
+    int in = kCngNone;                     // k_cng<IN, COPY>
+    bool copy = false;
+    uint32_t pieces = 0;                   // pieces of 8 samples per row
+    uint32_t passes = 0;                   // turns of the wave per tile pass: ceil(kCngChans * pieces / 64)
+    uint32_t inv = 0;                      // item / pieces == (item * inv) >> 20
+};
+inline CngRoute cng_route(uint32_t C, uint32_t F, uint32_t n, bool g711, bool pcm, bool yardstick)
+{
+    CngRoute r;
+    if ((uint64_t)C * F == 0 || (uint64_t)C * F >= 0xFFFFFFE0ull || n < 16u || n > IGDSP_MAX_PAYLOAD || (n & 7u)) return r;
+    r.grid = (uint32_t)(((uint64_t)C + kCngChans - 1u) / kCngChans);
+    r.threads = 64;
+    r.lds = cng_lds_bytes(n);
+    r.in = g711 ? kCngG711 : (pcm ? kCngPcm : kCngNone);
+    r.copy = yardstick;
+    r.pieces = n / 8u;
+    r.passes = (kCngChans * r.pieces + 63u) / 64u;
+    r.inv = cng_inv(r.pieces);
+    return r;
+}
+
 // ---- igdsp_tx_flush (launch_tx_staged): a wave owns kTsLegs staged legs (runs) of the flush; lanes 0 .. kTsLegs-1 decide, the
 // whole wave writes the packets.  No dynamic LDS: each wave's records (kTsLegs x IGDSP_STAGE_DEPTH) are static.
 constexpr int kTsWaves = 4;

@@ -1228,6 +1228,45 @@ int igdsp_host_vad_cfg(void *v, const igdsp_vad_cfg *cfg)
 }
 void igdsp_host_vad_reset(void *v) { if (v) static_cast<VoiceDetector *>(v)->reset(); }
 
+// ---- comfort noise on one leg, no context needed
+ComfortNoise::ComfortNoise(uint32_t samples_per_frame, uint32_t seed_) : n(samples_per_frame), seed(seed_)
+{
+    ok = n >= 16 && n <= IGDSP_MAX_PAYLOAD && (n & 7u) == 0;
+    reset();
+}
+
+void ComfortNoise::reset()
+{
+    std::memset(&state, 0, sizeof(state));                   // no tag: the RESET state, which takes the seed
+    std::memset(&last, 0, sizeof(last));
+}
+
+int ComfortNoise::process(uint32_t kind, const uint8_t *sid, uint32_t sid_len, const int16_t *voice, int16_t *out, uint32_t ctl)
+{
+    if (!ok || !out) return IGDSP_EINVAL;
+    return igdsp_cng_frame(&state, kind, sid, sid_len, voice, n, ctl, seed, out, &last);
+}
+
+void *igdsp_host_cng_new(uint32_t samples_per_frame, uint32_t seed)
+{
+    ComfortNoise *e = new (std::nothrow) ComfortNoise(samples_per_frame, seed);
+    if (e && !e->ok) { delete e; e = nullptr; }
+    return e;
+}
+void igdsp_host_cng_free(void *v) { delete static_cast<ComfortNoise *>(v); }
+int igdsp_host_cng_process(void *v, uint32_t kind, const uint8_t *sid, uint32_t sid_len, const int16_t *voice, int16_t *out, uint32_t ctl)
+{
+    if (!v) return IGDSP_EINVAL;
+    return static_cast<ComfortNoise *>(v)->process(kind, sid, sid_len, voice, out, ctl);
+}
+int igdsp_host_cng_rec(void *v, igdsp_cng_rec *out)
+{
+    if (!v || !out) return IGDSP_EINVAL;
+    *out = static_cast<ComfortNoise *>(v)->last;
+    return IGDSP_OK;
+}
+void igdsp_host_cng_reset(void *v) { if (v) static_cast<ComfortNoise *>(v)->reset(); }
+
 // ---- conference receive levels, no context needed
 void *igdsp_host_levels_new(uint32_t n_channels)
 {

@@ -361,6 +361,24 @@ public:
     void reset();                            // the floor, the hangover and the noise model forgotten
 };
 
+// Comfort noise on one leg, without a context: one channel through igdsp_cng_frame, the receive side of VoiceDetector's DTX.  A PT 13
+// packet's payload goes in as a SID frame, the ticks without a packet as IGDSP_VAD_NONE, a decoded voice frame as IGDSP_VAD_VOICE;
+// process() writes the row the bridge plays and returns its length (n, or 0 for a row that does not exist: no model yet, or a voice
+// frame without a row).  igdsp_cng_run takes the same states for thousands of channels.  UNVERIFIED against RFC 3389.
+class ComfortNoise {
+public:
+    explicit ComfortNoise(uint32_t samples_per_frame = IGDSP_SAMPLES_PER_FRAME, uint32_t seed = 0);
+    uint32_t n;
+    bool ok;                                 // n a multiple of 8 in 16 .. 256
+    uint32_t seed;                           // the excitation's seed, for example the leg's SSRC; taken at construction and reset()
+    igdsp_cng_state state;
+    igdsp_cng_rec last;                      // the record of the last frame
+    int process(uint32_t kind, const uint8_t *sid, uint32_t sid_len, const int16_t *voice, int16_t *out, uint32_t ctl = IGDSP_CNG_RUN);
+    bool generated() const { return (last.flags & IGDSP_CNG_F_GENERATED) != 0; }
+    bool hasModel() const { return state.have != 0; }
+    void reset();                            // model, gain and the lattice's delays forgotten
+};
+
 class RoIP_ED137 {
 public:
     // Unlike the reference singleton (roip_ed137.cpp:192) the instance owns an igdsp context; device < 0
@@ -523,6 +541,14 @@ int   igdsp_host_vad_rec(void *v, igdsp_vad_rec *out);
 int   igdsp_host_vad_sid(void *v, uint8_t out[16]);
 int   igdsp_host_vad_cfg(void *v, const igdsp_vad_cfg *cfg);
 void  igdsp_host_vad_reset(void *v);
+// comfort noise on one leg without a context (ComfortNoise): NULL from _new for a frame length igdsp_cng_frame rejects; _process one
+// frame: the row's length (IGDSP_EINVAL for a NULL handle or out, or a SID without its payload); _rec a copy of the last frame's
+// record; _reset forgets the state
+void *igdsp_host_cng_new(uint32_t samples_per_frame, uint32_t seed);
+void  igdsp_host_cng_free(void *v);
+int   igdsp_host_cng_process(void *v, uint32_t kind, const uint8_t *sid, uint32_t sid_len, const int16_t *voice, int16_t *out, uint32_t ctl);
+int   igdsp_host_cng_rec(void *v, igdsp_cng_rec *out);
+void  igdsp_host_cng_reset(void *v);
 // the spectrum graph without a context (SpectrumGraph): NULL from _new for sizes igdsp_spec_frame rejects; _feed one frame in (1: it
 // computed a spectrum, 0: not, IGDSP_EINVAL for a NULL argument); _real / _iir the two arrays of 512 floats, owned by the handle; _clear
 // is spectClear; _fft_avg is d_fftAvg

@@ -48,7 +48,8 @@ extern "C" {
  *    (IGDSP_EC_*, igdsp_ec_cfg, igdsp_ec_state, igdsp_ec_rec, igdsp_ec_cfg_default, igdsp_ec_frame, igdsp_echo_cancel); the level control
  *    (IGDSP_AGC_*, igdsp_agc_cfg, igdsp_agc_state, igdsp_agc_rec, igdsp_agc_cfg_default, igdsp_agc_frame, igdsp_agc_run); voice
  *    activity, DTX and the RFC 3389 comfort-noise payload (IGDSP_VAD_*, igdsp_vad_cfg, igdsp_vad_state, igdsp_vad_rec, igdsp_vad_event,
- *    igdsp_vad_cfg_default, igdsp_vad_table, igdsp_vad_frame, igdsp_sid_decode, igdsp_vad_work_bytes, igdsp_vad_run). */
+ *    igdsp_vad_cfg_default, igdsp_vad_table, igdsp_vad_frame, igdsp_sid_decode, igdsp_vad_work_bytes, igdsp_vad_run); comfort noise from
+ *    RFC 3389 SIDs (IGDSP_CNG_*, igdsp_cng_state, igdsp_cng_rec, igdsp_cng_table, igdsp_cng_gain, igdsp_cng_frame, igdsp_cng_run). */
 #define IGDSP_ABI_VERSION 3
 
 /* ---- error codes (0 == PJ_SUCCESS-style success) ------------------------- */
@@ -1899,6 +1900,101 @@ int igdsp_vad_run(igdsp_ctx *ctx, const uint8_t *d_g711 /* [F][C][n] */, const u
                   igdsp_vad_state *d_state /* [C], in and out */, uint8_t *d_kind /* [F][C] */, igdsp_vad_rec *d_rec /* [F][C] */,
                   uint8_t *d_sid /* [F][C][16] */, uint8_t *d_txctl /* [F][C] */, igdsp_vad_event *d_events, uint32_t event_cap,
                   uint32_t *d_event_count, void *d_work, void *stream);
+
+/* ---- Comfort noise: RFC 3389 SID payloads back into audio, per channel and frame ---------------------------------------------------------
+ * The receive side of igdsp_vad_run's DTX.  A leg under DTX reaches the bridge as one PT 13 packet now and then and nothing in
+ * between; igdsp_cng_run turns the frame's kind (as igdsp_vad_run writes d_kind) and, on SID frames, the payload into a row for
+ * igdsp_conf_mix / igdsp_bss_select: VOICE frames pass the leg's row through, SID and NONE frames get synthetic noise at the payload's
+ * level and spectral shape.  Everything is integer: the same bits on the host and the device, at any channel count and position and
+ * for any split of the frames over launches.  The rule is the library's own.  UNVERIFIED against RFC 3389 and G.711 Appendix II.
+ *
+ * RULE.  A frame is n samples, n a multiple of 8 in 16..256.  ">>" on a signed value is an arithmetic shift, "/" C division,
+ * clamp(v) = min(131071, max(-131071, v)).
+ *   Tables and helpers.  G[d] = isqrt(T8[d]), d = 0..127 (igdsp_cng_table; T8 is igdsp_vad_table's, isqrt the floor integer square
+ *   root): the rms of a -d dBov signal in Q2, G[0] = 131072, 0 from d = 106 on.  mix(x) on uint32: x ^= x >> 16; x *= 0x7feb352d;
+ *   x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16.  hs = mix(seed).  For the stream's sample index q (mod 2^32): r = mix(q ^ hs), e(q) =
+ *   the sum of the four bytes of r, minus 510: -510..510, variance 65535 / 3 (sd 147.80).  Legs differ by their seed (d_seed, for
+ *   example the SSRC); nothing depends on the channel's index.
+ *   Per frame, unless the channel is under BYPASS:
+ *   1. A SID is taken when kind == IGDSP_VAD_SID, the channel is not under FREEZE and len = min(sid_len, 11) > 0.  A SID frame of
+ *      length 0 counts as NONE (IGDSP_CNG_F_SID_EMPTY).  Any kind other than SID or NONE is VOICE.
+ *   2. A taken SID sets the model: (level, k[10]) = igdsp_sid_decode(payload, len); kq[i] = k[i] / 2 (Q14, |kq| <= 16383, 0 past the
+ *      payload); order = len - 1; p = 1 << 30, then for all ten k: p = (p * ((1 << 30) - k * k)) >> 30 in 64 bits; sp = isqrt(p);
+ *      g_tgt = (G[min(level, 127)] * sp * 7095) >> 23 (7095 is about 2^20 / 147.80; g_tgt is Q12, at most 3 632 640).  No model was
+ *      held: g = g_tgt, have = 1.  since_sid = 0.  A frame that takes no SID: since_sid = min(since_sid + 1, 65535).
+ *   3. A VOICE frame: out = the voice row (d_g711 decoded as igdsp_decode_meter decodes, or d_pcm), len_out = n; with neither input
+ *      zeros and len_out = 0.  The lattice's state is left alone.
+ *   4. A SID or NONE frame with have == 0: zeros, len_out = 0, IGDSP_CNG_F_NO_MODEL.
+ *   5. A SID or NONE frame with a model: d = g_tgt - g; g += d - d / 2 (the gain halves its distance per frame and arrives exactly).
+ *      For j = 0..n-1:  f = clamp((e(ctr + j) * g + 2048) >> 12);  for i = 10 down to 1:  f = clamp(f - ((kq_i * b[i-1] + 8192) >>
+ *      14)) and, if i < 10, b[i] = clamp(b[i-1] + ((kq_i * f + 8192) >> 14)) with the old b[i-1];  then b[0] = f and out[j] =
+ *      min(32767, max(-32768, (f + 2) >> 2)).  kq_i is the state's kq[i-1].  All ten stages always run: a stage with kq = 0 is a plain
+ *      delay, so a shorter payload leaves no stale state.  Every product fits 32 bits.  len_out = n.
+ *   6. ctr += n (mod 2^32) on every frame of any kind.
+ *   The sign convention is the voice detector's: k_i = a_i^(i) of A(z) = 1 + sum a_j z^-j, the synthesis is 1 / A(z); positively
+ *   correlated noise has k_1 < 0 and comes out low-pass.
+ *
+ * CONTROL.  d_ctl[c] (NULL: IGDSP_CNG_RUN; a value above 3 counts as RUN) holds for the launch.  IGDSP_CNG_FREEZE: SIDs are not taken,
+ * model and gain's target stay, noise goes on (IGDSP_CNG_F_FROZEN).  IGDSP_CNG_BYPASS: out = the voice row on VOICE frames (len_out = n),
+ * zeros (len_out = 0) otherwise; the state's bytes are untouched, the record carries the state as read and only the flag
+ * IGDSP_CNG_F_BYPASSED.  IGDSP_CNG_RESET: the state becomes the RESET state before the first frame, then RUN.
+ *
+ * STATE.  igdsp_cng_state, 96 bytes, one per channel, read at the start of a launch and written at its end.  A tag other than
+ * IGDSP_CNG_TAG (all-zero included) means the RESET state: everything 0 and seed = d_seed ? d_seed[c] : 0.  d_seed is read only then
+ * and on IGDSP_CNG_RESET.  Under the right tag any bytes are a valid state: b is read clamped to +-131071, kq to +-16383, g and g_tgt
+ * to at most 3 632 640, have by its bit 0; nothing indexes by a field.  flags is written as the last frame's record flags, reserved
+ * as 0.
+ *
+ * OUTPUTS.  d_out[f][c][n] is required, the others optional.  d_len_out[f][c]: n, or 0 on the zero rows of steps 3 and 4 and of a
+ * bypass.  d_rec[f][c] (igdsp_cng_rec): g, g_tgt and since_sid after the frame, the flags, the model's level byte and order.
+ * d_stats[f][c]: the PCM record of igdsp_conf_mix over out; rows with len 0 get the len-0 record (IGDSP_FLAG_EMPTY).  (d_out,
+ * d_len_out) feed igdsp_conf_mix and igdsp_bss_select through d_pcm / d_len unchanged.
+ *
+ * ARGUMENTS.  samples_per_frame not a multiple of 8 in 16..256: IGDSP_EINVAL, whether or not there is work.  n_channels == 0 or
+ * n_frames == 0: nothing to do.  d_kind, d_sid, d_state and d_out are required; d_sid_len NULL: every payload has 11 bytes; at most
+ * one of d_g711 (with d_codec) and d_pcm.  n_channels * n_frames < 2^32 - 32 (IGDSP_ERANGE).  d_g711 8-byte, d_sid, d_pcm, d_state,
+ * d_out, d_rec, d_stats 16-byte aligned.  The state and the outputs may overlap neither an input nor each other.  Enqueued on
+ * `stream`, not synchronised.
+ *
+ * Host only, no GPU: igdsp_cng_frame is one frame of one channel by the same rule (sid may be NULL unless a SID is taken; voice may be
+ * NULL; rec optional; seed is d_seed[c]); it returns len_out (>= 0) or IGDSP_EINVAL.  igdsp_cng_gain is step 2's g_tgt of a payload of
+ * 1..16 bytes (bytes past 11 are ignored).  igdsp_cng_table: the 128 values of G. */
+#define IGDSP_CNG_TAG     0xC4610001u /* igdsp_cng_state.tag                                      */
+#define IGDSP_CNG_GMAX    3632640u    /* the largest g and g_tgt                                  */
+#define IGDSP_CNG_RUN     0           /* d_ctl                                                    */
+#define IGDSP_CNG_FREEZE  1
+#define IGDSP_CNG_BYPASS  2
+#define IGDSP_CNG_RESET   3
+#define IGDSP_CNG_F_GENERATED 0x01    /* igdsp_cng_rec.flags: the row is synthetic noise          */
+#define IGDSP_CNG_F_SID       0x02    /* a SID was taken on this frame                            */
+#define IGDSP_CNG_F_NO_MODEL  0x04    /* a silent frame before any model was held                 */
+#define IGDSP_CNG_F_VOICE     0x08    /* the frame was passed through as voice                    */
+#define IGDSP_CNG_F_CLIPPED   0x10    /* a generated row holds a sample of magnitude >= 32767     */
+#define IGDSP_CNG_F_SID_EMPTY 0x20    /* a SID frame of length 0, counted as NONE                 */
+#define IGDSP_CNG_F_FROZEN    0x40
+#define IGDSP_CNG_F_BYPASSED  0x80
+typedef struct igdsp_cng_state {
+    uint32_t tag, seed, ctr, g, g_tgt;
+    int32_t  b[10];                 /* the lattice's delays                                      */
+    int16_t  kq[10];                /* the model's reflection coefficients, Q14                  */
+    uint16_t since_sid;
+    uint8_t  level, order, have, flags, reserved[10];
+} igdsp_cng_state;                  /* 96 bytes */
+typedef struct igdsp_cng_rec {
+    uint32_t g, g_tgt;
+    uint16_t since_sid;
+    uint8_t  flags, level, order, reserved[3];
+} igdsp_cng_rec;                    /* 16 bytes */
+int igdsp_cng_table(uint32_t out[128]);
+int igdsp_cng_gain(const uint8_t *payload, uint32_t len, uint32_t *g_tgt);
+int igdsp_cng_frame(igdsp_cng_state *st, uint32_t kind, const uint8_t *sid, uint32_t sid_len, const int16_t *voice /* may be NULL */,
+                    uint32_t samples_per_frame, uint32_t ctl, uint32_t seed, int16_t *out, igdsp_cng_rec *rec);
+int igdsp_cng_run(igdsp_ctx *ctx, const uint8_t *d_kind /* [F][C] */, const uint8_t *d_sid /* [F][C][16] */,
+                  const uint8_t *d_sid_len /* [F][C], NULL: 11 */, const uint8_t *d_g711 /* [F][C][n] */, const uint8_t *d_codec /* [C] */,
+                  const int16_t *d_pcm /* [F][C][n] */, const uint8_t *d_ctl /* [C], NULL: RUN */, const uint32_t *d_seed /* [C] */,
+                  uint32_t n_channels, uint32_t n_frames, uint32_t samples_per_frame, igdsp_cng_state *d_state /* [C], in and out */,
+                  int16_t *d_out /* [F][C][n] */, uint16_t *d_len_out /* [F][C] */, igdsp_cng_rec *d_rec /* [F][C] */,
+                  igdsp_frame_stats *d_stats /* [F][C] */, void *stream);
 
 /* ---- synthetic input generators (device side; SURVEY 8(d) definitions) ---------
  * D-uniform: byte k of global byte index g is

@@ -45,6 +45,18 @@ def _resources_of(path):
         r["file"] = os.path.basename(path).split("-")[0]
     return out
 
+def loop_valu_count(path, mangled, marker):
+    """Vector ALU instructions (lines that begin with v_) in the basic-block run of kernel `mangled` in the .s file `path` that holds the
+    instruction `marker`: from the last label in front of the marker to the first branch behind it, the body of a loop that was not split"""
+    text = open(path).read().split("\n")
+    start = next(i for i, line in enumerate(text) if line.startswith(mangled + ":"))
+    end = next(i for i in range(start, len(text)) if "s_endpgm" in text[i])
+    at = next(i for i in range(start, end) if text[i].strip().startswith(marker))
+    top = max(i for i in range(start, at) if re.match(r"\.LBB\d+_\d+:", text[i]))
+    bottom = next(i for i in range(at, end) if text[i].strip().startswith("s_cbranch"))
+    return sum(1 for line in text[top + 1:bottom] if line.strip().startswith("v_"))
+
+
 if __name__ == "__main__":
     for r in resources():
         if len(sys.argv) < 2 or sys.argv[1] in r["demangled"]:
