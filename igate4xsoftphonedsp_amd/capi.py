@@ -159,6 +159,19 @@ CNG_STATE = np.dtype([("tag", "<u4"), ("seed", "<u4"), ("ctr", "<u4"), ("g", "<u
                      align=True)                                                                   # igdsp_cng_state, 96 bytes
 CNG_REC = np.dtype([("g", "<u4"), ("g_tgt", "<u4"), ("since_sid", "<u2"), ("flags", "u1"), ("level", "u1"), ("order", "u1"), ("reserved", "u1", (3,))],
                    align=True)                                                                     # igdsp_cng_rec, 16 bytes
+# the filter: per channel a chain of second-order sections (igdsp_filt_run / igdsp_filt_frame)
+FILT_TAG, FILT_MAX_SECTIONS, FILT_UNITY = 0xF1170001, 4, 8192
+FILT_RUN, FILT_BYPASS, FILT_RESET = 0, 1, 2
+FILT_CLIPPED, FILT_NO_PLAN, FILT_BAD_PLAN, FILT_BYPASSED, FILT_WAS_RESET = 1, 2, 4, 8, 16
+FILT_LOWPASS, FILT_HIGHPASS, FILT_BANDPASS, FILT_NOTCH, FILT_PEAK, FILT_LOWSHELF, FILT_HIGHSHELF, FILT_LP1, FILT_HP1 = range(9)
+FILT_VOICE_BAND, FILT_CTCSS_HP, FILT_DEEMPH, FILT_PREEMPH, FILT_DC_BLOCK = range(5)
+FILT_SECTION = np.dtype([("b0", "<i2"), ("b1", "<i2"), ("b2", "<i2"), ("a1", "<i2"), ("a2", "<i2")])      # igdsp_filt_section, 10 bytes
+FILT_PLAN = np.dtype([("n_sections", "<u2"), ("reserved", "<u2"), ("clock_rate", "<u4"), ("s", FILT_SECTION, (4,))])   # igdsp_filt_plan, 48 bytes
+FILT_HIST = np.dtype([("x1", "<i2"), ("x2", "<i2"), ("y1", "<i2"), ("y2", "<i2"), ("e", "<u2")])         # igdsp_filt_hist, 10 bytes
+FILT_STATE = np.dtype([("tag", "<u4"), ("s", FILT_HIST, (4,)), ("flags", "<u2"), ("reserved", "<u2")])    # igdsp_filt_state, 48 bytes
+FILT_REC = np.dtype([("in_peak", "<u2"), ("out_peak", "<u2"), ("n_clipped", "<u2"), ("plan", "<u2"), ("flags", "u1"), ("n_sections", "u1"),
+                     ("reserved", "u1", (6,))])                                                    # igdsp_filt_rec, 16 bytes
+assert FILT_PLAN.itemsize == 48 and FILT_STATE.itemsize == 48 and FILT_REC.itemsize == 16
 CHAN_PROBE = np.dtype([("run", "<u4"), ("alarms", "<u4")], align=True)
 # the jitter buffer (igdsp_jb_receive / igdsp_jb_report)
 JB_STATE = np.dtype(
@@ -359,6 +372,11 @@ PROTOTYPES = [
     ("igdsp_cng_gain", _int, [_vp, _u32, _vp]),
     ("igdsp_cng_frame", _int, [_vp, _u32, _vp, _u32, _vp, _u32, _u32, _u32, _vp, _vp]),
     ("igdsp_cng_run", _int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("igdsp_filt_frame", _int, [_vp, _vp, _vp, _u32, _u32, _vp, _vp]),
+    ("igdsp_filt_plan_check", _int, [_vp]),
+    ("igdsp_filt_design", _int, [_u32, _u32, C.c_double, C.c_double, C.c_double, _vp]),
+    ("igdsp_filt_plan_preset", _int, [_u32, _u32, _vp]),
+    ("igdsp_filt_run", _int, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
     ("igdsp_g726_reorder", _int, [_vp, _vp, _vp, _u64, _int, _vp]),
     ("igdsp_gen_uniform", _int, [_vp, _vp, _u64, _u64, _u64, _vp]),
     ("igdsp_dev_alloc", _int, [_vp, C.POINTER(_vp), C.c_size_t]),
@@ -401,7 +419,7 @@ INTERNAL["igdsp_internal_tx_copy"] = (_int, [_vp, _vp, _vp, _u32, _u32, _u32, _v
 INTERNAL_MORE_TWIN = {"igdsp_internal_dbuf_move": "igdsp_dbuf_run", "igdsp_internal_spec_move": "igdsp_spectrum",
                       "igdsp_internal_tdet_move": "igdsp_tone_detect", "igdsp_internal_ec_move": "igdsp_echo_cancel",
                       "igdsp_internal_agc_move": "igdsp_agc_run", "igdsp_internal_vad_move": "igdsp_vad_run",
-                      "igdsp_internal_cng_move": "igdsp_cng_run"}
+                      "igdsp_internal_cng_move": "igdsp_cng_run", "igdsp_internal_filt_move": "igdsp_filt_run"}
 INTERNAL_MORE = {name: _PUBLIC[twin] for name, twin in INTERNAL_MORE_TWIN.items()}
 
 _lib = None
@@ -752,6 +770,44 @@ def cng_frame(state, kind: int, n: int, sid=None, sid_len: int = 11, voice=None,
     return out, rc, rec
 
 
+def filt_frame(plan, state, pcm, ctl: int = FILT_RUN):
+    """igdsp_filt_frame (host only, no GPU): one frame of one channel.  plan a FILT_PLAN record or None (a channel without a plan),
+    state a FILT_STATE record updated in place, pcm the frame (int16 [n]).  Returns (out int16 [n], the frame's FILT_REC)."""
+    assert state.dtype == FILT_STATE and state.flags["C_CONTIGUOUS"] and state.flags["WRITEABLE"]
+    pcm = np.ascontiguousarray(pcm, np.int16)
+    p = None if plan is None else np.ascontiguousarray(plan, FILT_PLAN)
+    out, rec = np.zeros(len(pcm), np.int16), np.zeros((), FILT_REC)
+    rc = load().igdsp_filt_frame(None if p is None else p.ctypes.data_as(_vp), state.ctypes.data_as(_vp), pcm.ctypes.data_as(_vp), len(pcm), int(ctl),
+                                 out.ctypes.data_as(_vp), rec.ctypes.data_as(_vp))
+    if rc != 0:
+        raise IgdspError(rc, "igdsp_filt_frame")
+    return out, rec
+
+
+def filt_plan_check(plan) -> int:
+    """igdsp_filt_plan_check (host only, no GPU): 0, or IGDSP_EINVAL for a plan the kernel would flag.  Returns the raw code."""
+    p = np.ascontiguousarray(plan, FILT_PLAN)
+    return int(load().igdsp_filt_plan_check(p.ctypes.data_as(_vp)))
+
+
+def filt_design(kind: int, clock_rate: int, f0_hz: float, q: float = 0.7071067811865476, gain_db: float = 0.0) -> np.ndarray:
+    """igdsp_filt_design (host only, no GPU): the section {b0, b1, b2, a1, a2} in Q13 as int16 [5]."""
+    out = np.zeros(5, np.int16)
+    rc = load().igdsp_filt_design(int(kind), int(clock_rate), float(f0_hz), float(q), float(gain_db), out.ctypes.data_as(_vp))
+    if rc != 0:
+        raise IgdspError(rc, "igdsp_filt_design")
+    return out
+
+
+def filt_plan_preset(preset: int, clock_rate: int) -> np.ndarray:
+    """igdsp_filt_plan_preset (host only, no GPU): the preset's FILT_PLAN record."""
+    plan = np.zeros((), FILT_PLAN)
+    rc = load().igdsp_filt_plan_preset(int(preset), int(clock_rate), plan.ctypes.data_as(_vp))
+    if rc != 0:
+        raise IgdspError(rc, "igdsp_filt_plan_preset")
+    return plan
+
+
 def vad_work_bytes(n_channels: int, n_frames: int, with_rec: bool) -> int:
     """igdsp_vad_work_bytes (host only, no GPU): bytes of igdsp_vad_run's d_work for a launch of this shape."""
     return int(load().igdsp_vad_work_bytes(n_channels, n_frames, 1 if with_rec else 0))
@@ -1066,6 +1122,14 @@ class Context:
         out) -> out [F][C][n] int16, len_out [F][C] u16, rec [F][C] CNG_REC, stats [F][C] FRAME_STATS (the last three optional)."""
         self._ck(self.L.igdsp_cng_run(self.h, _ptr(kind), _ptr(sid), _ptr(sid_len), _ptr(g711), _ptr(codec), _ptr(pcm), _ptr(ctl), _ptr(seed), C_, F_, n,
                                       _ptr(state), _ptr(out), _ptr(len_out), _ptr(rec), _ptr(stats), stream), "igdsp_cng_run")
+
+    def filt_run(self, plans, n_plans, state, C_, F_, n, g711=None, codec=None, pcm=None, ctl=None, plan_of=None, max_sections=0, out=None, rec=None,
+                 stats=None, stream=None):
+        """igdsp_filt_run: exactly one of g711 [F][C][n] u8 (+ codec [C]) / pcm [F][C][n] int16; plans [n_plans] FILT_PLAN (device memory),
+        plan_of [C] u16 or None (plan 0), ctl [C] u8 or None (FILT_RUN); max_sections the largest n_sections among the plans (0: 4); state
+        [C] FILT_STATE (in and out) -> out [F][C][n] int16, rec [F][C] FILT_REC, stats [F][C] FRAME_STATS, each optional, at least one."""
+        self._ck(self.L.igdsp_filt_run(self.h, _ptr(g711), _ptr(codec), _ptr(pcm), _ptr(ctl), _ptr(plans), n_plans, _ptr(plan_of), max_sections, C_, F_, n,
+                                       _ptr(state), _ptr(out), _ptr(rec), _ptr(stats), stream), "igdsp_filt_run")
 
     def bss_select(self, info, group_ptr, members, n_members, state, words, C_, G_, F_, n=160, payload=None, codec=None, pcm=None,
                    length=None, gain=None, mute=None, vote_frames=0, sel=None, out=None, stats=None, stream=None):

@@ -198,6 +198,14 @@ hipError_t launch_vad(const LaunchCfg &cfg, const uint8_t *g711, const uint8_t *
 hipError_t launch_cng(const LaunchCfg &cfg, const uint8_t *kind, const uint8_t *sid, const uint8_t *sid_len, const uint8_t *g711, const uint8_t *codec,
                       const int16_t *pcm, const uint8_t *ctl, const uint32_t *seed, uint32_t C, uint32_t F, uint32_t n, igdsp_cng_state *state,
                       int16_t *out, uint16_t *len_out, igdsp_cng_rec *rec, igdsp_frame_stats *stats, bool yardstick, hipStream_t s);
+// igdsp_filt_run: exactly one of g711 (with codec) and pcm; plans (n_plans >= 1) and state required; ctl, plan_of, out, rec, stats may
+// each be nullptr; max_sections 0..4.  yardstick: the compute-free form, the same row loads, decode, tile stores, reads and writes,
+// state load and store and output stores, and the peak fold of a bypassed row; no section runs.  It stores the bytes igdsp_filt_run
+// stores with every channel at IGDSP_FILT_BYPASS, and the state, which a bypass leaves alone, as it was read (e masked; another tag:
+// zero histories) with the tag, flags as read and reserved 0; ctl is not read, of a plan only its first dword
+hipError_t launch_filt(const LaunchCfg &cfg, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm, const uint8_t *ctl, const igdsp_filt_plan *plans,
+                       uint32_t n_plans, const uint16_t *plan_of, uint32_t max_sections, uint32_t C, uint32_t F, uint32_t n, igdsp_filt_state *state,
+                       int16_t *out, igdsp_filt_rec *rec, igdsp_frame_stats *stats, bool yardstick, hipStream_t s);
 hipError_t launch_wav_expand(const LaunchCfg &cfg, const uint8_t *payload, uint32_t C, uint32_t F, uint32_t n, uint32_t rate,
                              uint8_t *files, uint64_t file_stride, hipStream_t s);
 hipError_t launch_g726(const LaunchCfg &cfg, const uint8_t *in, uint8_t *out, uint64_t n_bytes, int mode, hipStream_t s);

@@ -1240,6 +1240,51 @@ inline CngRoute cng_route(uint32_t C, uint32_t F, uint32_t n, bool g711, bool pc
     return r;
 }
 
+// ---- igdsp_filt_run (launch_filt): k_filt<IN, S, COPY>.  A lane owns a channel for the whole launch (the recurrence is serial in the
+// sample: the parallelism is across channels); a block is one wave and kFiltChans channels.  S = 1, 2 or 4 sections run per sample: the
+// entry's max_sections rounded up (a channel with fewer runs identity sections, so the lanes of a wave do not diverge); the yardstick
+// runs none and is built once per input form (S = 1).  LDS: the frame's kFiltChans rows as a tile, filtered in place, a row n / 2 + 1
+// dwords apart (odd: the lanes' dword accesses of one sample pair fall into different banks), and a byte per row for its law.  The wave
+// fills the tile and stores it piece by piece (16 bytes of a row; pieces of a tile are consecutive in memory); item i of a pass is
+// row i / P, piece i % P, the division done by the multiplier `inv` as in cng_route.  The NEXT frame's pieces are loaded into
+// registers before the sample loop and written to the tile behind the store pass: the first kFiltAhead turns of 16 bytes (PCM) or 8
+// (codes) per lane, 64 or 32 VGPRs; a row's turns past those (n > 128) are loaded behind the store pass.  Registers and LDS: the route is written for kFiltResident blocks per CU, one wave per SIMD at
+// 65 536 channels and never more than two (kFiltVgprs = 256 of a SIMD's 512; 33 088 bytes of LDS at n = 256).
+constexpr uint32_t kFiltChans = 64;                       // channels per block: the lanes of its one wave
+constexpr uint32_t kFiltResident = 4;                     // blocks per CU
+constexpr uint32_t kFiltVgprs = 256;
+constexpr uint32_t kFiltMaxPieces = IGDSP_MAX_PAYLOAD / 8;   // pieces of 8 samples per row = turns of the wave per tile pass
+constexpr uint32_t kFiltAhead = 16;                       // turns of the next frame held in registers through the sample loop
+static_assert(2u * kFiltAhead == kFiltMaxPieces, "the early and the late turns cover a row");
+constexpr int kFiltG711 = 1, kFiltPcm = 2;                // k_filt<IN, , >
+constexpr uint32_t filt_row_dwords(uint32_t n) { return n / 2u + 1u; }
+constexpr uint32_t filt_lds_bytes(uint32_t n) { return kFiltChans * filt_row_dwords(n) * 4u + kFiltChans; }
+constexpr uint32_t filt_inv(uint32_t pieces) { return (1u << 20) / pieces + 1u; }
+static_assert(kFiltResident * filt_lds_bytes(256) <= 160u * 1024u && 2u * kFiltVgprs <= 512u, "the resident blocks' tiles fit a CU's LDS, two waves a SIMD's registers");
+struct FiltRoute {
+    uint32_t grid = 0, threads = 0, lds = 0;
+    int in = 0, sections = 0;              // k_filt<IN, S, COPY>
+    bool copy = false;
+    uint32_t pieces = 0;                   // pieces of 8 samples per row = turns of the wave per tile pass
+    uint32_t inv = 0;                      // item / pieces == (item * inv) >> 20
+    uint32_t max_sections = 0;             // what a plan may hold and still run: 1..4
+};
+inline FiltRoute filt_route(uint32_t C, uint32_t F, uint32_t n, bool g711, uint32_t max_sections, bool yardstick)
+{
+    FiltRoute r;
+    if ((uint64_t)C * F == 0 || (uint64_t)C * F >= 0xFFFFFFE0ull || n < 8u || n > IGDSP_MAX_PAYLOAD || (n & 7u) || max_sections > 4u) return r;
+    r.grid = (uint32_t)(((uint64_t)C + kFiltChans - 1u) / kFiltChans);
+    r.threads = 64;
+    r.lds = filt_lds_bytes(n);
+    r.in = g711 ? kFiltG711 : kFiltPcm;
+    r.max_sections = max_sections == 0u ? 4u : max_sections;
+    r.sections = yardstick ? 1 : (r.max_sections <= 2u ? (int)r.max_sections : 4);
+    r.copy = yardstick;
+    r.pieces = n / 8u;
+    r.inv = filt_inv(r.pieces);
+    return r;
+}
+
 // ---- igdsp_tx_flush (launch_tx_staged): a wave owns kTsLegs staged legs (runs) of the flush; lanes 0 .. kTsLegs-1 decide, the
 // whole wave writes the packets.  No dynamic LDS: each wave's records (kTsLegs x IGDSP_STAGE_DEPTH) are static.
 constexpr int kTsWaves = 4;

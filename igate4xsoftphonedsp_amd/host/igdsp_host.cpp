@@ -1267,6 +1267,67 @@ int igdsp_host_cng_rec(void *v, igdsp_cng_rec *out)
 }
 void igdsp_host_cng_reset(void *v) { if (v) static_cast<ComfortNoise *>(v)->reset(); }
 
+// ---- a filter on one leg, no context needed
+LegFilter::LegFilter(uint32_t samples_per_frame) : n(samples_per_frame), planned(false)
+{
+    ok = n >= 8 && n <= IGDSP_MAX_PAYLOAD && (n & 7u) == 0;
+    std::memset(&plan, 0, sizeof(plan));
+    reset();
+}
+
+void LegFilter::reset()
+{
+    std::memset(&state, 0, sizeof(state));                   // no tag: all-zero histories
+    std::memset(&last, 0, sizeof(last));
+}
+
+int LegFilter::setPlan(const igdsp_filt_plan *p)
+{
+    if (!p || igdsp_filt_plan_check(p) != IGDSP_OK) return IGDSP_EINVAL;
+    plan = *p;
+    planned = true;
+    reset();
+    return IGDSP_OK;
+}
+
+int LegFilter::setPreset(uint32_t preset, uint32_t clock_rate)
+{
+    igdsp_filt_plan p;
+    if (igdsp_filt_plan_preset(preset, clock_rate, &p) != IGDSP_OK) return IGDSP_EINVAL;
+    return setPlan(&p);
+}
+
+int LegFilter::process(const int16_t *pcm, int16_t *out, uint32_t ctl)
+{
+    if (!ok || !pcm || !out) return IGDSP_EINVAL;
+    return igdsp_filt_frame(planned ? &plan : nullptr, &state, pcm, n, ctl, out, &last);
+}
+
+void *igdsp_host_filt_new(uint32_t samples_per_frame)
+{
+    LegFilter *e = new (std::nothrow) LegFilter(samples_per_frame);
+    if (e && !e->ok) { delete e; e = nullptr; }
+    return e;
+}
+void igdsp_host_filt_free(void *v) { delete static_cast<LegFilter *>(v); }
+int igdsp_host_filt_plan(void *v, const igdsp_filt_plan *plan) { return v ? static_cast<LegFilter *>(v)->setPlan(plan) : IGDSP_EINVAL; }
+int igdsp_host_filt_preset(void *v, uint32_t preset, uint32_t clock_rate)
+{
+    return v ? static_cast<LegFilter *>(v)->setPreset(preset, clock_rate) : IGDSP_EINVAL;
+}
+int igdsp_host_filt_process(void *v, const int16_t *pcm, int16_t *out, uint32_t ctl)
+{
+    if (!v) return IGDSP_EINVAL;
+    return static_cast<LegFilter *>(v)->process(pcm, out, ctl);
+}
+int igdsp_host_filt_rec(void *v, igdsp_filt_rec *out)
+{
+    if (!v || !out) return IGDSP_EINVAL;
+    *out = static_cast<LegFilter *>(v)->last;
+    return IGDSP_OK;
+}
+void igdsp_host_filt_reset(void *v) { if (v) static_cast<LegFilter *>(v)->reset(); }
+
 // ---- conference receive levels, no context needed
 void *igdsp_host_levels_new(uint32_t n_channels)
 {

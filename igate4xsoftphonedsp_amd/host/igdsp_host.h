@@ -379,6 +379,26 @@ public:
     void reset();                            // model, gain and the lattice's delays forgotten
 };
 
+// A filter on one leg, without a context: one channel through igdsp_filt_frame with one plan and one state: a high pass under a radio's
+// sub-audible tone, a de- or pre-emphasis, a band limit, a notch.  setPlan() / setPreset() take a new plan and forget the histories (the
+// state carries no plan identity).  igdsp_filt_run takes the same states for thousands of channels.  The rule is the library's own,
+// UNVERIFIED against any other filter implementation.
+class LegFilter {
+public:
+    explicit LegFilter(uint32_t samples_per_frame = IGDSP_SAMPLES_PER_FRAME);
+    uint32_t n;
+    bool ok;                                 // n a multiple of 8 in 8 .. 256
+    bool planned;                            // a plan was taken: without one process() passes the row through (IGDSP_FILT_NO_PLAN)
+    igdsp_filt_plan plan;
+    igdsp_filt_state state;
+    igdsp_filt_rec last;                     // the record of the last frame
+    int setPlan(const igdsp_filt_plan *p);   // IGDSP_EINVAL (and the old plan stays) for a plan igdsp_filt_plan_check rejects
+    int setPreset(uint32_t preset, uint32_t clock_rate);
+    int process(const int16_t *pcm, int16_t *out, uint32_t ctl = IGDSP_FILT_RUN);
+    bool clipped() const { return (last.flags & IGDSP_FILT_CLIPPED) != 0; }
+    void reset();                            // the histories forgotten, the plan stays
+};
+
 class RoIP_ED137 {
 public:
     // Unlike the reference singleton (roip_ed137.cpp:192) the instance owns an igdsp context; device < 0
@@ -549,6 +569,16 @@ void  igdsp_host_cng_free(void *v);
 int   igdsp_host_cng_process(void *v, uint32_t kind, const uint8_t *sid, uint32_t sid_len, const int16_t *voice, int16_t *out, uint32_t ctl);
 int   igdsp_host_cng_rec(void *v, igdsp_cng_rec *out);
 void  igdsp_host_cng_reset(void *v);
+// a filter on one leg without a context (LegFilter): NULL from _new for a frame length igdsp_filt_frame rejects; _plan / _preset take a
+// plan (IGDSP_EINVAL for one igdsp_filt_plan_check / igdsp_filt_plan_preset rejects) and forget the histories; _process one frame
+// (IGDSP_EINVAL for a NULL argument); _rec a copy of the last frame's record; _reset forgets the histories
+void *igdsp_host_filt_new(uint32_t samples_per_frame);
+void  igdsp_host_filt_free(void *v);
+int   igdsp_host_filt_plan(void *v, const igdsp_filt_plan *plan);
+int   igdsp_host_filt_preset(void *v, uint32_t preset, uint32_t clock_rate);
+int   igdsp_host_filt_process(void *v, const int16_t *pcm, int16_t *out, uint32_t ctl);
+int   igdsp_host_filt_rec(void *v, igdsp_filt_rec *out);
+void  igdsp_host_filt_reset(void *v);
 // the spectrum graph without a context (SpectrumGraph): NULL from _new for sizes igdsp_spec_frame rejects; _feed one frame in (1: it
 // computed a spectrum, 0: not, IGDSP_EINVAL for a NULL argument); _real / _iir the two arrays of 512 floats, owned by the handle; _clear
 // is spectClear; _fft_avg is d_fftAvg

@@ -49,7 +49,9 @@ extern "C" {
  *    (IGDSP_AGC_*, igdsp_agc_cfg, igdsp_agc_state, igdsp_agc_rec, igdsp_agc_cfg_default, igdsp_agc_frame, igdsp_agc_run); voice
  *    activity, DTX and the RFC 3389 comfort-noise payload (IGDSP_VAD_*, igdsp_vad_cfg, igdsp_vad_state, igdsp_vad_rec, igdsp_vad_event,
  *    igdsp_vad_cfg_default, igdsp_vad_table, igdsp_vad_frame, igdsp_sid_decode, igdsp_vad_work_bytes, igdsp_vad_run); comfort noise from
- *    RFC 3389 SIDs (IGDSP_CNG_*, igdsp_cng_state, igdsp_cng_rec, igdsp_cng_table, igdsp_cng_gain, igdsp_cng_frame, igdsp_cng_run). */
+ *    RFC 3389 SIDs (IGDSP_CNG_*, igdsp_cng_state, igdsp_cng_rec, igdsp_cng_table, igdsp_cng_gain, igdsp_cng_frame, igdsp_cng_run); the
+ *    filter (IGDSP_FILT_*, igdsp_filt_plan, igdsp_filt_state, igdsp_filt_rec, igdsp_filt_frame, igdsp_filt_plan_check,
+ *    igdsp_filt_design, igdsp_filt_plan_preset, igdsp_filt_run). */
 #define IGDSP_ABI_VERSION 3
 
 /* ---- error codes (0 == PJ_SUCCESS-style success) ------------------------- */
@@ -1995,6 +1997,128 @@ int igdsp_cng_run(igdsp_ctx *ctx, const uint8_t *d_kind /* [F][C] */, const uint
                   uint32_t n_channels, uint32_t n_frames, uint32_t samples_per_frame, igdsp_cng_state *d_state /* [C], in and out */,
                   int16_t *d_out /* [F][C][n] */, uint16_t *d_len_out /* [F][C] */, igdsp_cng_rec *d_rec /* [F][C] */,
                   igdsp_frame_stats *d_stats /* [F][C] */, void *stream);
+
+/* ---- Filter: per channel a chain of up to four second-order IIR sections ------------------------------------------------------------------
+ * Neither pjmedia nor the reference holds a linear filter: the reference's only per-slot control is the static SLOT_VOLUME, its sidetone
+ * levels are further static gains.  igdsp_filt_run runs a row (G.711 codes with d_codec, or PCM, [F][C][n]) through the channel's plan:
+ * a high pass under a radio's sub-audible tone, a de- or pre-emphasis, a band limit, a notch, a DC block.  It stands after
+ * igdsp_plc_conceal / igdsp_cng_run / igdsp_bss_select and before igdsp_agc_run, on a port row before igdsp_tx_packetize, on
+ * igdsp_snd_split's rows before igdsp_vad_run, and behind igdsp_tone_detect for a notch.  Everything is integer.
+ * The rule is the library's own, UNVERIFIED against any other filter implementation.
+ *
+ * RULE.  A section is five Q13 coefficients in int16, b0 b1 b2 a1 a2 (8192 is 1.0, a0 is 1).  A plan is 1..4 sections and the clock
+ * rate it was designed for (informational: it plays no part in the arithmetic).  A section is VALID when
+ * |b0| + |b1| + |b2| + |a1| + |a2| <= 65535.  Per channel and section the state is x1, x2, y1, y2 (int16) and e (0..8191).  Each sample
+ * goes through the sections 0 .. S-1 in order, v the section's input:
+ *        acc = b0*v + b1*x1 + b2*x2 - a1*y1 - a2*y2 + e          (int32, exact)
+ *        y = acc >> 13 (arithmetic);  e = acc & 8191
+ *        y > 32767: y = 32767, e = 0, clipped += 1;   y < -32768: y = -32768, e = 0, clipped += 1
+ *        x2 = x1; x1 = v; y2 = y1; y1 = y;   v = y
+ * e is first-order error feedback: the 13 bits the shift drops go into the next sample, which holds a 300 Hz pole pair in place with
+ * 16-bit states and lets the output of a stable section decay to exact zero on zero input.  Every |state| <= 32768, so with a valid
+ * section |acc| and every partial sum of it stay <= 65535 * 32768 + 8191 < 2^31 (csrc/igdsp_filt.h proves it): nothing needs 64 bits.
+ * The identity section {8192, 0, 0, 0, 0} returns its input bit for bit and leaves e as it was.
+ *
+ * PLANS.  d_plans[n_plans] lives in device memory and may hold any bytes; d_plan_of[c] (NULL: plan 0) picks the channel's.
+ * n_sections is read as min(n_sections, 4).  A channel whose index is >= n_plans, or whose plan has n_sections 0: out = x, the state's
+ * bytes are not touched, IGDSP_FILT_NO_PLAN.  An invalid section is not run (IGDSP_FILT_BAD_PLAN).  A section that is not run -
+ * invalid, or at or past n_sections - passes its input on and leaves its history as read.  max_sections is the caller's word for
+ * the largest n_sections among the launch's plans (1..4; 0 counts as 4): it picks the kernel, one written for 1, 2 or 4 sections.  A
+ * plan with more sections than that is not run at all: out = x, the state untouched, IGDSP_FILT_NO_PLAN | IGDSP_FILT_BAD_PLAN.
+ *
+ * STATE.  igdsp_filt_state, 48 bytes, one per channel, read at the start of a launch and written at its end.  A tag other than
+ * IGDSP_FILT_TAG (all-zero included) means all-zero histories.  Under the right tag any bytes are a valid state: e is read & 8191,
+ * nothing indexes by a field.  flags is written as the last frame's record flags, reserved as 0.  F frames in one launch, F launches
+ * of one frame and any split in between write the same bytes; a channel's results are the same at any channel count and position.
+ * The state carries no plan identity: a caller that changes a channel's plan sends IGDSP_FILT_RESET.
+ *
+ * CONTROL.  d_ctl[c] (NULL: IGDSP_FILT_RUN; a value above 2 counts as RUN) holds for the launch:
+ *   IGDSP_FILT_RUN;   IGDSP_FILT_BYPASS: out = x, the state's bytes are not touched, the record carries IGDSP_FILT_BYPASSED alone;
+ *   IGDSP_FILT_RESET: the histories are zeroed before the first frame, then RUN (a channel without a plan stays untouched).
+ *
+ * OUTPUTS, each optional, at least one required.  d_out[f][c][n].  d_rec[f][c] (igdsp_filt_rec): in_peak = max |x| (32768 for
+ * -32768), out_peak = max |out|, n_clipped = the frame's clipped count summed over the sections (saturating at 65535), plan =
+ * the channel's plan index, n_sections = min(n_sections, 4) of its plan (0 without one), flags = IGDSP_FILT_CLIPPED (n_clipped > 0),
+ * _NO_PLAN, _BAD_PLAN, _BYPASSED, _WAS_RESET (the launch's first frame, when the histories were zeroed by RESET or by another tag).
+ * d_stats[f][c]: the PCM record of out, as igdsp_conf_mix writes it.  With d_out NULL the stage runs for state and records only.
+ * Rows at a bridge rate above 8 kHz go as the sub-frames igdsp_resample writes: the state chains across frames.
+ *
+ * ARGUMENTS.  samples_per_frame not a multiple of 8 in 8..256, max_sections > 4: IGDSP_EINVAL, whether or not there is work.
+ * n_channels == 0 or n_frames == 0: nothing to do.  Exactly one of d_g711 (with d_codec) and d_pcm; d_plans with n_plans >= 1, d_state
+ * and one of d_out, d_rec, d_stats required.  n_channels * n_frames < 2^32 - 32 (IGDSP_ERANGE).  d_g711 8-byte, d_pcm, d_out,
+ * d_state, d_rec, d_stats 16-byte, d_plans 4-byte, d_plan_of 2-byte aligned.  The state and the outputs may overlap neither an input
+ * nor each other.  Enqueued on `stream`, not synchronised.
+ *
+ * Host only, no GPU.  igdsp_filt_frame: one frame of one channel from PCM by the same rule (plan NULL: a channel without a plan; out
+ * and rec optional; rec.plan is 0).  igdsp_filt_plan_check: IGDSP_EINVAL for a plan the kernel would flag (n_sections 0 or above 4,
+ * an invalid section).  igdsp_filt_design: one section of the RBJ cookbook, computed in double and rounded to the nearest Q13:
+ * LOWPASS, HIGHPASS, BANDPASS (0 dB peak), NOTCH, PEAK, LOWSHELF, HIGHSHELF (q sets alpha = sin(w0) / (2 q); gain_db is read by the
+ * last three), and the first-order LP1 / HP1 (bilinear, b2 = a2 = 0; q and gain_db are not read).  It needs 0 < f0_hz < clock_rate / 2
+ * and q > 0, and returns IGDSP_EINVAL, writing nothing, when a coefficient leaves int16, when the section is invalid or when the
+ * QUANTISED poles are not strictly inside the unit circle (|a2| < 8192 and |a1| < 8192 + a2).  igdsp_filt_plan_preset, clock rates
+ * 8000..48000, IGDSP_EINVAL when a corner is at or above half the clock rate:
+ *   VOICE_BAND: Butterworth HIGHPASS 300 Hz then LOWPASS 3400 Hz, q = 1/sqrt(2) each;
+ *   CTCSS_HP:   fourth-order Butterworth HIGHPASS 300 Hz as two sections, q = 1/(2 cos(pi/8)) and 1/(2 cos(3 pi/8));
+ *   PREEMPH:    6 dB/octave up from 300 Hz, levelling at 3400 Hz: g (1 - a z^-1) / (1 - p z^-1) with a = exp(-2 pi 300 / clock_rate) and
+ *               p = exp(-2 pi 3400 / clock_rate) (the corners matched in z, not warped), g for unity gain at 1 kHz;
+ *   DEEMPH:     its inverse, 6 dB/octave down from 300 Hz: g' (1 - p z^-1) / (1 - a z^-1), unity gain at 1 kHz;
+ *   DC_BLOCK:   HP1 at 20 Hz. */
+#define IGDSP_FILT_TAG      0xF1170001u /* igdsp_filt_state.tag                                   */
+#define IGDSP_FILT_MAX_SECTIONS 4
+#define IGDSP_FILT_UNITY    8192
+#define IGDSP_FILT_RUN      0           /* d_ctl                                                    */
+#define IGDSP_FILT_BYPASS   1
+#define IGDSP_FILT_RESET    2
+#define IGDSP_FILT_CLIPPED   0x01       /* igdsp_filt_rec.flags                                     */
+#define IGDSP_FILT_NO_PLAN   0x02
+#define IGDSP_FILT_BAD_PLAN  0x04
+#define IGDSP_FILT_BYPASSED  0x08
+#define IGDSP_FILT_WAS_RESET 0x10
+#define IGDSP_FILT_LOWPASS   0          /* igdsp_filt_design's kind                                 */
+#define IGDSP_FILT_HIGHPASS  1
+#define IGDSP_FILT_BANDPASS  2
+#define IGDSP_FILT_NOTCH     3
+#define IGDSP_FILT_PEAK      4
+#define IGDSP_FILT_LOWSHELF  5
+#define IGDSP_FILT_HIGHSHELF 6
+#define IGDSP_FILT_LP1       7
+#define IGDSP_FILT_HP1       8
+#define IGDSP_FILT_VOICE_BAND 0         /* igdsp_filt_plan_preset's preset                          */
+#define IGDSP_FILT_CTCSS_HP   1
+#define IGDSP_FILT_DEEMPH     2
+#define IGDSP_FILT_PREEMPH    3
+#define IGDSP_FILT_DC_BLOCK   4
+typedef struct igdsp_filt_section {
+    int16_t b0, b1, b2, a1, a2;     /* Q13                                                       */
+} igdsp_filt_section;               /* 10 bytes */
+typedef struct igdsp_filt_plan {
+    uint16_t n_sections, reserved;
+    uint32_t clock_rate;            /* informational                                             */
+    igdsp_filt_section s[4];
+} igdsp_filt_plan;                  /* 48 bytes */
+typedef struct igdsp_filt_hist {
+    int16_t  x1, x2, y1, y2;
+    uint16_t e;                     /* the error feedback, 0..8191                               */
+} igdsp_filt_hist;                  /* 10 bytes */
+typedef struct igdsp_filt_state {
+    uint32_t tag;
+    igdsp_filt_hist s[4];
+    uint16_t flags, reserved;
+} igdsp_filt_state;                 /* 48 bytes */
+typedef struct igdsp_filt_rec {
+    uint16_t in_peak, out_peak, n_clipped, plan;
+    uint8_t  flags, n_sections, reserved[6];
+} igdsp_filt_rec;                   /* 16 bytes */
+int igdsp_filt_frame(const igdsp_filt_plan *plan, igdsp_filt_state *st, const int16_t *pcm, uint32_t samples_per_frame, uint32_t ctl,
+                     int16_t *out, igdsp_filt_rec *rec);
+int igdsp_filt_plan_check(const igdsp_filt_plan *plan);
+int igdsp_filt_design(uint32_t kind, uint32_t clock_rate, double f0_hz, double q, double gain_db, int16_t *out /* [5] */);
+int igdsp_filt_plan_preset(uint32_t preset, uint32_t clock_rate, igdsp_filt_plan *plan);
+int igdsp_filt_run(igdsp_ctx *ctx, const uint8_t *d_g711 /* [F][C][n] */, const uint8_t *d_codec /* [C] */,
+                   const int16_t *d_pcm /* [F][C][n] */, const uint8_t *d_ctl /* [C], NULL: RUN */, const igdsp_filt_plan *d_plans,
+                   uint32_t n_plans, const uint16_t *d_plan_of /* [C], NULL: plan 0 */, uint32_t max_sections, uint32_t n_channels,
+                   uint32_t n_frames, uint32_t samples_per_frame, igdsp_filt_state *d_state /* [C], in and out */,
+                   int16_t *d_out /* [F][C][n] */, igdsp_filt_rec *d_rec /* [F][C] */, igdsp_frame_stats *d_stats /* [F][C] */, void *stream);
 
 /* ---- synthetic input generators (device side; SURVEY 8(d) definitions) ---------
  * D-uniform: byte k of global byte index g is

@@ -57,6 +57,18 @@ def loop_valu_count(path, mangled, marker):
     return sum(1 for line in text[top + 1:bottom] if line.strip().startswith("v_"))
 
 
+def loop_count(path, mangled, marker):
+    """How often the instruction `marker` itself stands in that same basic-block run: that the run is the whole loop (k_filt: five
+    v_mad_i32_i24 a section and sample, two samples a turn)"""
+    text = open(path).read().split("\n")
+    start = next(i for i, line in enumerate(text) if line.startswith(mangled + ":"))
+    end = next(i for i in range(start, len(text)) if "s_endpgm" in text[i])
+    at = next(i for i in range(start, end) if text[i].strip().startswith(marker))
+    top = max(i for i in range(start, at) if re.match(r"\.LBB\d+_\d+:", text[i]))
+    bottom = next(i for i in range(at, end) if text[i].strip().startswith("s_cbranch"))
+    return sum(1 for line in text[top + 1:bottom] if line.strip().startswith(marker))
+
+
 if __name__ == "__main__":
     for r in resources():
         if len(sys.argv) < 2 or sys.argv[1] in r["demangled"]:
