@@ -172,6 +172,17 @@ FILT_STATE = np.dtype([("tag", "<u4"), ("s", FILT_HIST, (4,)), ("flags", "<u2"),
 FILT_REC = np.dtype([("in_peak", "<u2"), ("out_peak", "<u2"), ("n_clipped", "<u2"), ("plan", "<u2"), ("flags", "u1"), ("n_sections", "u1"),
                      ("reserved", "u1", (6,))])                                                    # igdsp_filt_rec, 16 bytes
 assert FILT_PLAN.itemsize == 48 and FILT_STATE.itemsize == 48 and FILT_REC.itemsize == 16
+# noise suppression: per channel a spectral gain under and between speech (igdsp_ns_run / igdsp_ns_frame)
+NS_TAG, NS_HOP, NS_BANDS, NS_UNITY = 0x4E530001, 80, 32, 32768
+NS_RUN, NS_FREEZE, NS_BYPASS, NS_RESET = 0, 1, 2, 3
+NS_LEARNING, NS_SUPPRESSING, NS_CLIPPED, NS_FROZEN, NS_BYPASSED, NS_WAS_RESET = 1, 2, 4, 8, 16, 32
+NS_CFG = np.dtype([("floor_q15", "<u4"), ("over_q4", "<u2"), ("init_hops", "<u2"), ("track_shift", "<u2"), ("rise_shift", "<u2"), ("reserved", "<u4")],
+                  align=True)                                                                      # igdsp_ns_cfg, 16 bytes
+NS_STATE = np.dtype([("tag", "<u4"), ("hops", "<u2"), ("flags", "<u2"), ("reserved", "<u4", (2,)), ("prev", "<i2", (80,)), ("ola", "<i4", (80,)),
+                     ("S", "<u8", (32,)), ("N", "<u8", (32,)), ("Gt", "<u2", (32,))], align=True)  # igdsp_ns_state, 1 072 bytes
+NS_REC = np.dtype([("in_energy", "<u4"), ("out_energy", "<u4"), ("min_gain_q15", "<u2"), ("n_clipped", "<u2"), ("noise_idx", "u1"), ("flags", "u1"),
+                   ("reserved", "u1", (2,))], align=True)                                          # igdsp_ns_rec, 16 bytes
+assert NS_CFG.itemsize == 16 and NS_STATE.itemsize == 1072 and NS_REC.itemsize == 16
 CHAN_PROBE = np.dtype([("run", "<u4"), ("alarms", "<u4")], align=True)
 # the jitter buffer (igdsp_jb_receive / igdsp_jb_report)
 JB_STATE = np.dtype(
@@ -377,6 +388,10 @@ PROTOTYPES = [
     ("igdsp_filt_design", _int, [_u32, _u32, C.c_double, C.c_double, C.c_double, _vp]),
     ("igdsp_filt_plan_preset", _int, [_u32, _u32, _vp]),
     ("igdsp_filt_run", _int, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
+    ("igdsp_ns_cfg_default", None, [_vp]),
+    ("igdsp_ns_tables", _int, [C.POINTER(_vp), C.POINTER(_vp)]),
+    ("igdsp_ns_frame", _int, [_vp, _vp, _vp, _u32, _u32, _vp, _vp]),
+    ("igdsp_ns_run", _int, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
     ("igdsp_g726_reorder", _int, [_vp, _vp, _vp, _u64, _int, _vp]),
     ("igdsp_gen_uniform", _int, [_vp, _vp, _u64, _u64, _u64, _vp]),
     ("igdsp_dev_alloc", _int, [_vp, C.POINTER(_vp), C.c_size_t]),
@@ -419,7 +434,8 @@ INTERNAL["igdsp_internal_tx_copy"] = (_int, [_vp, _vp, _vp, _u32, _u32, _u32, _v
 INTERNAL_MORE_TWIN = {"igdsp_internal_dbuf_move": "igdsp_dbuf_run", "igdsp_internal_spec_move": "igdsp_spectrum",
                       "igdsp_internal_tdet_move": "igdsp_tone_detect", "igdsp_internal_ec_move": "igdsp_echo_cancel",
                       "igdsp_internal_agc_move": "igdsp_agc_run", "igdsp_internal_vad_move": "igdsp_vad_run",
-                      "igdsp_internal_cng_move": "igdsp_cng_run", "igdsp_internal_filt_move": "igdsp_filt_run"}
+                      "igdsp_internal_cng_move": "igdsp_cng_run", "igdsp_internal_filt_move": "igdsp_filt_run",
+                      "igdsp_internal_ns_move": "igdsp_ns_run"}
 INTERNAL_MORE = {name: _PUBLIC[twin] for name, twin in INTERNAL_MORE_TWIN.items()}
 
 _lib = None
@@ -808,6 +824,40 @@ def filt_plan_preset(preset: int, clock_rate: int) -> np.ndarray:
     return plan
 
 
+def ns_cfg_default() -> np.ndarray:
+    """igdsp_ns_cfg_default (host only, no GPU): one NS_CFG record, the defaults."""
+    out = np.zeros((), NS_CFG)
+    load().igdsp_ns_cfg_default(out.ctypes.data_as(_vp))
+    return out
+
+
+def ns_tables():
+    """igdsp_ns_tables (host only, no GPU): the committed window (int16 [160]) and twiddle factors (int32 [128][2]: cos, sin in Q30)."""
+    w, t = _vp(), _vp()
+    rc = load().igdsp_ns_tables(C.byref(w), C.byref(t))
+    if rc != 0:
+        raise IgdspError(rc, "igdsp_ns_tables")
+    win = np.ctypeslib.as_array(C.cast(w, C.POINTER(C.c_int16)), (2 * NS_HOP,)).copy()
+    tw = np.ctypeslib.as_array(C.cast(t, C.POINTER(C.c_int32)), (256,)).copy()
+    return win, tw.reshape(128, 2)
+
+
+def ns_frame(cfg, state, pcm, ctl: int = NS_RUN, raw: bool = False):
+    """igdsp_ns_frame (host only, no GPU): one frame of one channel.  cfg an NS_CFG record, state an NS_STATE record updated in place,
+    pcm the frame (int16 [80, 160, 240 or 320]).  Returns (out int16 [n], the frame's NS_REC record); raw: the return code alone."""
+    assert state.dtype == NS_STATE and state.flags["C_CONTIGUOUS"] and state.flags["WRITEABLE"]
+    pcm = np.ascontiguousarray(pcm, np.int16)
+    c = np.ascontiguousarray(cfg, NS_CFG)
+    out, rec = np.zeros(len(pcm), np.int16), np.zeros((), NS_REC)
+    rc = load().igdsp_ns_frame(c.ctypes.data_as(_vp), state.ctypes.data_as(_vp), pcm.ctypes.data_as(_vp), len(pcm), int(ctl), out.ctypes.data_as(_vp),
+                               rec.ctypes.data_as(_vp))
+    if raw:
+        return int(rc)
+    if rc != 0:
+        raise IgdspError(rc, "igdsp_ns_frame")
+    return out, rec
+
+
 def vad_work_bytes(n_channels: int, n_frames: int, with_rec: bool) -> int:
     """igdsp_vad_work_bytes (host only, no GPU): bytes of igdsp_vad_run's d_work for a launch of this shape."""
     return int(load().igdsp_vad_work_bytes(n_channels, n_frames, 1 if with_rec else 0))
@@ -1130,6 +1180,14 @@ class Context:
         [C] FILT_STATE (in and out) -> out [F][C][n] int16, rec [F][C] FILT_REC, stats [F][C] FRAME_STATS, each optional, at least one."""
         self._ck(self.L.igdsp_filt_run(self.h, _ptr(g711), _ptr(codec), _ptr(pcm), _ptr(ctl), _ptr(plans), n_plans, _ptr(plan_of), max_sections, C_, F_, n,
                                        _ptr(state), _ptr(out), _ptr(rec), _ptr(stats), stream), "igdsp_filt_run")
+
+    def ns_run(self, state, C_, F_, n, g711=None, codec=None, pcm=None, ctl=None, cfg=None, out=None, rec=None, stats=None, stream=None):
+        """igdsp_ns_run: exactly one of g711 [F][C][n] u8 (+ codec [C]) / pcm [F][C][n] int16 at 8 kHz, n 80, 160, 240 or 320; ctl [C] u8 or
+        None (NS_RUN); cfg an NS_CFG record (host memory) or None (ns_cfg_default()); state [C] NS_STATE (in and out) -> out [F][C][n] int16
+        (the input delayed by 80 samples), rec [F][C] NS_REC, stats [F][C] FRAME_STATS, each optional, at least one."""
+        c = np.ascontiguousarray(ns_cfg_default() if cfg is None else cfg, NS_CFG)
+        self._ck(self.L.igdsp_ns_run(self.h, _ptr(g711), _ptr(codec), _ptr(pcm), _ptr(ctl), c.ctypes.data_as(_vp), C_, F_, n, _ptr(state), _ptr(out),
+                                     _ptr(rec), _ptr(stats), stream), "igdsp_ns_run")
 
     def bss_select(self, info, group_ptr, members, n_members, state, words, C_, G_, F_, n=160, payload=None, codec=None, pcm=None,
                    length=None, gain=None, mute=None, vote_frames=0, sel=None, out=None, stats=None, stream=None):

@@ -14,6 +14,7 @@
 #include "igdsp_agc.h"
 #include "igdsp_cng.h"
 #include "igdsp_filt.h"
+#include "igdsp_ns.h"
 #include "igdsp_route.h"
 #include "igdsp_vad.h"
 
@@ -633,6 +634,32 @@ inline Verdict filt_run(P d_g711, P d_codec, P d_pcm, P d_ctl, P d_plans, uint32
     const Buf ins[6] = {{d_g711, frames * n}, {d_g711 ? d_codec : nullptr, C}, {d_pcm, frames * n * 2u}, {d_ctl, C},
                         {d_plans, (uint64_t)n_plans * sizeof(igdsp_filt_plan)}, {d_plan_of, (uint64_t)C * 2u}};
     const Buf outs[4] = {{d_state, (uint64_t)C * sizeof(igdsp_filt_state)}, {d_out, frames * n * 2u}, {d_rec, frames * sizeof(igdsp_filt_rec)},
+                         {d_stats, frames * sizeof(igdsp_frame_stats)}};
+    for (int i = 0; i < 4; ++i) {
+        for (const Buf &b : ins)
+            if (ranges_overlap(outs[i].p, outs[i].bytes, b.p, b.bytes)) return reject(IGDSP_EINVAL, "the state and the outputs must not overlap an input");
+        for (int j = 0; j < i; ++j)
+            if (ranges_overlap(outs[i].p, outs[i].bytes, outs[j].p, outs[j].bytes))
+                return reject(IGDSP_EINVAL, "the state and the outputs must not overlap each other");
+    }
+    return kRun;
+}
+
+// ---- noise suppression.  The frame length and cfg are checked whether or not there is work
+inline Verdict ns_run(P d_g711, P d_codec, P d_pcm, P d_ctl, const igdsp_ns_cfg *cfg, uint32_t C, uint32_t F, uint32_t n, P d_state, P d_out, P d_rec,
+                      P d_stats)
+{
+    if (!ns_n_ok(n) || !cfg || !ns_cfg_ok(*cfg)) return kInvalid;
+    if (empty(C, F)) return kNothing;
+    if (!exactly_one(d_g711, d_pcm) || (d_g711 && !d_codec) || !d_state || !(d_out || d_rec || d_stats)) return kInvalid;
+    if ((uint64_t)C * F >= 0xFFFFFFE0ull) return reject(IGDSP_ERANGE);
+    // a piece of 8 samples is one load (8 bytes of codes, 16 of PCM) and one 16-byte store; the state goes as 67 16-byte pieces, a
+    // record and a PCM record as one
+    if (misaligned(8, {d_g711}) || misaligned(16, {d_pcm, d_state, d_out, d_rec, d_stats})) return kInvalid;
+    const uint64_t frames = (uint64_t)C * F;
+    struct Buf { P p; uint64_t bytes; };
+    const Buf ins[4] = {{d_g711, frames * n}, {d_g711 ? d_codec : nullptr, C}, {d_pcm, frames * n * 2u}, {d_ctl, C}};
+    const Buf outs[4] = {{d_state, (uint64_t)C * sizeof(igdsp_ns_state)}, {d_out, frames * n * 2u}, {d_rec, frames * sizeof(igdsp_ns_rec)},
                          {d_stats, frames * sizeof(igdsp_frame_stats)}};
     for (int i = 0; i < 4; ++i) {
         for (const Buf &b : ins)

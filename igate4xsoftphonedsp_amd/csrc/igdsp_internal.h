@@ -206,6 +206,13 @@ hipError_t launch_cng(const LaunchCfg &cfg, const uint8_t *kind, const uint8_t *
 hipError_t launch_filt(const LaunchCfg &cfg, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm, const uint8_t *ctl, const igdsp_filt_plan *plans,
                        uint32_t n_plans, const uint16_t *plan_of, uint32_t max_sections, uint32_t C, uint32_t F, uint32_t n, igdsp_filt_state *state,
                        int16_t *out, igdsp_filt_rec *rec, igdsp_frame_stats *stats, bool yardstick, hipStream_t s);
+// igdsp_ns_run: exactly one of g711 (with codec) and pcm; state required; ctl, out, rec, stats may each be nullptr; cfg checked by the
+// caller.  yardstick: the compute-free form, the same row loads, decode, row stores into LDS, state load and store, the hop's pass of
+// ns_hop_bypass over the row, the energy and PCM-record folds, output stores; no transform, no band runs.  It stores the bytes
+// igdsp_ns_run stores with every channel at IGDSP_NS_BYPASS; ctl is not read
+hipError_t launch_ns(const LaunchCfg &cfg, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm, const uint8_t *ctl, const igdsp_ns_cfg &ns,
+                     uint32_t C, uint32_t F, uint32_t n, igdsp_ns_state *state, int16_t *out, igdsp_ns_rec *rec, igdsp_frame_stats *stats, bool yardstick,
+                     hipStream_t s);
 hipError_t launch_wav_expand(const LaunchCfg &cfg, const uint8_t *payload, uint32_t C, uint32_t F, uint32_t n, uint32_t rate,
                              uint8_t *files, uint64_t file_stride, hipStream_t s);
 hipError_t launch_g726(const LaunchCfg &cfg, const uint8_t *in, uint8_t *out, uint64_t n_bytes, int mode, hipStream_t s);

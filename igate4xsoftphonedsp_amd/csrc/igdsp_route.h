@@ -1285,6 +1285,45 @@ inline FiltRoute filt_route(uint32_t C, uint32_t F, uint32_t n, bool g711, uint3
     return r;
 }
 
+// ---- igdsp_ns_run (launch_ns): k_ns<IN, COPY>.  kNsLanes = 16 lanes own a channel for the whole launch (the state is sequential in
+// time); a block is one wave and kNsChans = 4 channels.  Per channel in LDS: the state (1 072 bytes, loaded once, stored once), the
+// transform's 128 complex points with the band gains and the lanes' partial sums behind them (NsWork, igdsp_ns.h), and the frame's row
+// (up to 320 samples, worked in place).  The phases of a hop (igdsp_ns.h) are divided over the 16 lanes: a pass of the transform is
+// four butterflies a lane, the bands two a lane; between phases stands a same-wave LDS fence, never a barrier.  A row is n / 8 pieces of
+// 8 samples (16 bytes of PCM, 8 of codes): lane l of the channel takes pieces l, l + 16, l + 32 (kNsTurns = 3 turns cover 40 pieces),
+// loads the NEXT frame's before the hops and stores the output's as 16-byte pieces behind them.  Registers and LDS: the route is
+// written for kNsResident = 8 blocks per CU, two waves per SIMD (kNsVgprs = 256 of a SIMD's 512 each; 13 568 bytes of LDS a block at n = 320).
+constexpr uint32_t kNsLanes = 16;                         // lanes per channel: a DPP row
+constexpr uint32_t kNsChans = 4;                          // channels per block: the rows of its one wave
+constexpr uint32_t kNsResident = 8;                       // blocks per CU
+constexpr uint32_t kNsVgprs = 256;
+constexpr uint32_t kNsTurns = 3;                          // pieces per lane and row
+constexpr uint32_t kNsMaxN = 320;
+constexpr int kNsG711 = 1, kNsPcm = 2;                    // k_ns<IN, >
+constexpr uint32_t kNsStateBytes = 1072, kNsWorkBytes = 1680;   // sizeof(igdsp_ns_state), sizeof(NsWork): static_asserted in igdsp_k_ns.hip
+constexpr uint32_t ns_chan_bytes(uint32_t n) { return kNsStateBytes + kNsWorkBytes + ((n * 2u + 15u) & ~15u); }
+constexpr uint32_t ns_lds_bytes(uint32_t n) { return kNsChans * ns_chan_bytes(n); }
+static_assert(kNsLanes * kNsChans == 64 && kNsTurns * kNsLanes * 8u >= kNsMaxN && kNsResident * ns_lds_bytes(kNsMaxN) <= 160u * 1024u &&
+              (kNsResident / 4u) * kNsVgprs <= 512u && ns_chan_bytes(80) % 16u == 0u, "a wave of channels; the turns cover a row; the resident blocks fit a CU");
+struct NsRoute {
+    uint32_t grid = 0, threads = 0, lds = 0;
+    int in = 0;                            // k_ns<IN, COPY>
+    bool copy = false;
+    uint32_t pieces = 0;                   // pieces of 8 samples per row
+};
+inline NsRoute ns_route(uint32_t C, uint32_t F, uint32_t n, bool g711, bool yardstick)
+{
+    NsRoute r;
+    if ((uint64_t)C * F == 0 || (uint64_t)C * F >= 0xFFFFFFE0ull || n == 0u || n > kNsMaxN || n % 80u) return r;
+    r.grid = (uint32_t)(((uint64_t)C + kNsChans - 1u) / kNsChans);
+    r.threads = 64;
+    r.lds = ns_lds_bytes(n);
+    r.in = g711 ? kNsG711 : kNsPcm;
+    r.copy = yardstick;
+    r.pieces = n / 8u;
+    return r;
+}
+
 // ---- igdsp_tx_flush (launch_tx_staged): a wave owns kTsLegs staged legs (runs) of the flush; lanes 0 .. kTsLegs-1 decide, the
 // whole wave writes the packets.  No dynamic LDS: each wave's records (kTsLegs x IGDSP_STAGE_DEPTH) are static.
 constexpr int kTsWaves = 4;

@@ -1328,6 +1328,64 @@ int igdsp_host_filt_rec(void *v, igdsp_filt_rec *out)
 }
 void igdsp_host_filt_reset(void *v) { if (v) static_cast<LegFilter *>(v)->reset(); }
 
+// ---- a noise suppressor on one leg, no context needed
+LegDenoiser::LegDenoiser(uint32_t samples_per_frame) : n(samples_per_frame), ctl(IGDSP_NS_RUN)
+{
+    ok = n == 80 || n == 160 || n == 240 || n == 320;
+    igdsp_ns_cfg_default(&cfg);
+    reset();
+}
+
+void LegDenoiser::reset()
+{
+    std::memset(&state, 0, sizeof(state));                   // no tag: a fresh state
+    std::memset(&last, 0, sizeof(last));
+}
+
+int LegDenoiser::setConfig(const igdsp_ns_cfg *c)
+{
+    if (!c) return IGDSP_EINVAL;
+    igdsp_ns_state probe;
+    int16_t zero[80] = {0};
+    std::memset(&probe, 0, sizeof(probe));
+    if (igdsp_ns_frame(c, &probe, zero, 80, IGDSP_NS_RUN, nullptr, nullptr) != IGDSP_OK) return IGDSP_EINVAL;   // the library's range check
+    cfg = *c;
+    return IGDSP_OK;
+}
+
+int LegDenoiser::process(const int16_t *pcm, int16_t *out)
+{
+    if (!ok || !pcm || !out) return IGDSP_EINVAL;
+    return igdsp_ns_frame(&cfg, &state, pcm, n, ctl, out, &last);
+}
+
+void *igdsp_host_ns_new(uint32_t samples_per_frame)
+{
+    LegDenoiser *e = new (std::nothrow) LegDenoiser(samples_per_frame);
+    if (e && !e->ok) { delete e; e = nullptr; }
+    return e;
+}
+void igdsp_host_ns_free(void *v) { delete static_cast<LegDenoiser *>(v); }
+int igdsp_host_ns_config(void *v, const igdsp_ns_cfg *cfg) { return v ? static_cast<LegDenoiser *>(v)->setConfig(cfg) : IGDSP_EINVAL; }
+int igdsp_host_ns_control(void *v, uint32_t ctl)
+{
+    if (!v || ctl > IGDSP_NS_BYPASS) return IGDSP_EINVAL;
+    static_cast<LegDenoiser *>(v)->ctl = ctl;
+    return IGDSP_OK;
+}
+int igdsp_host_ns_process(void *v, const int16_t *pcm, int16_t *out)
+{
+    if (!v) return IGDSP_EINVAL;
+    return static_cast<LegDenoiser *>(v)->process(pcm, out);
+}
+int igdsp_host_ns_rec(void *v, igdsp_ns_rec *out)
+{
+    if (!v || !out) return IGDSP_EINVAL;
+    *out = static_cast<LegDenoiser *>(v)->last;
+    return IGDSP_OK;
+}
+void igdsp_host_ns_reset(void *v) { if (v) static_cast<LegDenoiser *>(v)->reset(); }
+
 // ---- conference receive levels, no context needed
 void *igdsp_host_levels_new(uint32_t n_channels)
 {

@@ -399,6 +399,27 @@ public:
     void reset();                            // the histories forgotten, the plan stays
 };
 
+// A noise suppressor on one leg, without a context: one channel through igdsp_ns_frame with one cfg and one state: a receiver's hiss
+// lowered under and between transmissions.  The output is the input delayed by 80 samples (10 ms).  freeze(true) holds the noise
+// estimate while a tone port or DTMF plays on the leg; bypass(true) passes the input through the same delay.  igdsp_ns_run takes the
+// same states for thousands of channels.  The rule is the library's own, UNVERIFIED against speex, WebRTC and ITU-T G.160.
+class LegDenoiser {
+public:
+    explicit LegDenoiser(uint32_t samples_per_frame = IGDSP_SAMPLES_PER_FRAME);
+    uint32_t n;
+    bool ok;                                 // n is 80, 160, 240 or 320
+    igdsp_ns_cfg cfg;
+    igdsp_ns_state state;
+    igdsp_ns_rec last;                       // the record of the last frame
+    uint32_t ctl;                            // IGDSP_NS_RUN, _FREEZE or _BYPASS: what process() passes
+    int setConfig(const igdsp_ns_cfg *c);    // IGDSP_EINVAL (and the old cfg stays) for one out of range; the state stays
+    void freeze(bool on) { ctl = on ? (uint32_t)IGDSP_NS_FREEZE : (uint32_t)IGDSP_NS_RUN; }
+    void bypass(bool on) { ctl = on ? (uint32_t)IGDSP_NS_BYPASS : (uint32_t)IGDSP_NS_RUN; }
+    int process(const int16_t *pcm, int16_t *out);
+    bool suppressing() const { return (last.flags & IGDSP_NS_SUPPRESSING) != 0; }
+    void reset();                            // the estimate, the gains and the overlap forgotten, the cfg stays
+};
+
 class RoIP_ED137 {
 public:
     // Unlike the reference singleton (roip_ed137.cpp:192) the instance owns an igdsp context; device < 0
@@ -579,6 +600,16 @@ int   igdsp_host_filt_preset(void *v, uint32_t preset, uint32_t clock_rate);
 int   igdsp_host_filt_process(void *v, const int16_t *pcm, int16_t *out, uint32_t ctl);
 int   igdsp_host_filt_rec(void *v, igdsp_filt_rec *out);
 void  igdsp_host_filt_reset(void *v);
+// a noise suppressor on one leg without a context (LegDenoiser): NULL from _new for a frame length igdsp_ns_frame rejects; _config
+// takes a cfg (IGDSP_EINVAL for one out of range); _control sets what _process passes as ctl (IGDSP_NS_RUN, _FREEZE, _BYPASS; anything
+// else IGDSP_EINVAL); _process one frame (IGDSP_EINVAL for a NULL argument); _rec a copy of the last frame's record; _reset forgets
+void *igdsp_host_ns_new(uint32_t samples_per_frame);
+void  igdsp_host_ns_free(void *v);
+int   igdsp_host_ns_config(void *v, const igdsp_ns_cfg *cfg);
+int   igdsp_host_ns_control(void *v, uint32_t ctl);
+int   igdsp_host_ns_process(void *v, const int16_t *pcm, int16_t *out);
+int   igdsp_host_ns_rec(void *v, igdsp_ns_rec *out);
+void  igdsp_host_ns_reset(void *v);
 // the spectrum graph without a context (SpectrumGraph): NULL from _new for sizes igdsp_spec_frame rejects; _feed one frame in (1: it
 // computed a spectrum, 0: not, IGDSP_EINVAL for a NULL argument); _real / _iir the two arrays of 512 floats, owned by the handle; _clear
 // is spectClear; _fft_avg is d_fftAvg

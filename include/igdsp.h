@@ -2120,6 +2120,108 @@ int igdsp_filt_run(igdsp_ctx *ctx, const uint8_t *d_g711 /* [F][C][n] */, const 
                    uint32_t n_frames, uint32_t samples_per_frame, igdsp_filt_state *d_state /* [C], in and out */,
                    int16_t *d_out /* [F][C][n] */, igdsp_filt_rec *d_rec /* [F][C] */, igdsp_frame_stats *d_stats /* [F][C] */, void *stream);
 
+/* ---- Noise suppression: per channel a spectral gain under and between speech ------------------------------------------------------------
+ * What pjmedia's sound port switches on with PJMEDIA_ECHO_USE_NOISE_SUPPRESSOR (speex's preprocessor, `denoise`) and the reference
+ * leaves out: stationary noise (a receiver's hiss) is lowered by up to `floor_q15` under and between transmissions.  Stands behind
+ * igdsp_plc_conceal / igdsp_cng_run / igdsp_bss_select / igdsp_filt_run and before igdsp_agc_run and igdsp_conf_mix; on igdsp_snd_split's
+ * rows before igdsp_vad_run and igdsp_echo_cancel's near end.  The rule is the library's own, UNVERIFIED against speex, WebRTC and
+ * ITU-T G.160.  All integer: the host (igdsp_ns_frame) and the device (igdsp_ns_run) give the same bits, and a channel's bits depend on
+ * nothing but its own samples, state, cfg and ctl: the same at any channel count and position, from G.711 or its decoded PCM, and for
+ * any split of the frames over launches.
+ * THE OUTPUT IS THE INPUT DELAYED BY EXACTLY 80 SAMPLES (10 ms), under every control value.
+ *
+ * 8 kHz rows only (a bridge at a higher rate runs the stage on the narrow side of igdsp_resample).  samples_per_frame is 80, 160, 240
+ * or 320: a frame is 1 to 4 hops of 80 samples.  Per hop (csrc/igdsp_ns.h has every rounding step; tests/ns_model.py restates it):
+ *   1. window: x[0..159] = the previous hop's samples (state.prev), then this hop's; w[i] = round(32768 sin(pi (i + 0.5) / 160))
+ *      (igdsp_ns_tables); xw[i] = (x[i] w[i] + 128) >> 8 (Q7, |xw| < 2^22).
+ *   2. forward transform: xw zero-padded to 256 points; 128 packed complex points z[k] = xw[2k] + i xw[2k+1] through seven radix-2
+ *      passes, decimation in frequency, spans 128 down to 2: a' = a + b (exact), b' = ((a - b) t + 2^29) >> 30 with t = W^pos of the
+ *      span, conjugate for the forward direction; then a split pass over the pairs (k, 128 - k): with A = Z[k], B = conj(Z[128 - k]),
+ *      E = A + B, O = A - B and (c, s) = (cos, sin)(2 pi k / 256): X[k] = (E 2^30 + (-s - i c) O + 2^30) >> 31; X[0] = Re Z[0] + Im Z[0],
+ *      X[128] = Re Z[0] - Im Z[0].  Bins 0..128, unscaled, int32 pairs in Q7.  The twiddle factors are Q30 (igdsp_ns_tables); every
+ *      product with one is formed in 64 bits, a butterfly's sum is kept in 64 bits and each component rounded once.  ">>" is arithmetic.
+ *   3. bands: 32 bands of four bins, band b = bins 4b+1 .. 4b+4; E[b] = (sum of re^2 + im^2, exact in 64 bits) >> 14.
+ *   4. S[b] = E[b] on the state's hop 0, else S[b] += (E[b] - S[b]) >> 2.
+ *   5. unless frozen: hops < init_hops: N += (S - N) >> 2; else S < 4 N: N += (S - N) >> track_shift; else N += (N >> rise_shift) + 1.
+ *   6. d = S - ((over_q4 N) >> 4); d <= 0 or S == 0: G = 0; else t = max(0, bitlen(S) - 16), G = min(32768, ((d >> t) << 15) /
+ *      max(1, S >> t)) (one exact unsigned 32-bit division); G = max(G, floor_q15).
+ *   7. Gs[b] = (G[b-1] + 2 G[b] + G[b+1] + 2) >> 2, the edge bands repeated.
+ *   8. Gs[b] >= Gt[b]: Gt[b] = Gs[b]; else Gt[b] += (Gs[b] - Gt[b]) >> 1 (Gt in the state; fresh: 32768).
+ *   9. bin 0 takes Gt[0], bins 4b+1..4b+4 take Gt[b]: Y = (X Gt + 16384) >> 15 per component.
+ *  10. inverse transform with the 1/256 inside: the split pass backwards, Z[k] = (E 2^30 + (-s + i c) O + 2^30) >> 31 from A = Y[k],
+ *      B = conj(Y[128 - k]), Z[0] = ((Y[0] + Y[128] + 1) >> 1, (Y[0] - Y[128] + 1) >> 1); then seven radix-2 passes, decimation in time,
+ *      spans 2 up to 128, each halving: a' = (a 2^30 + b t + 2^30) >> 31, b' = (a 2^30 - b t + 2^30) >> 31;
+ *      y[i], i = 0..159, Q7, the padded tail dropped; yw[i] = (y[i] w[i] + 16384) >> 15; for i < 80: out[i] = (ola[i] + yw[i] + 64) >> 7
+ *      saturated to int16 (each saturation counts as clipped); then ola[i] = yw[i + 80]; then hops += 1 (saturating at 65535).
+ * Defaults (igdsp_ns_cfg_default): floor_q15 5827 (-15 dB), over_q4 24, init_hops 16, track_shift 4, rise_shift 9.  Ranges, anything
+ * else IGDSP_EINVAL: floor_q15 1..32768, over_q4 16..64, init_hops 1..255, track_shift 1..8, rise_shift 4..12.
+ * LIMIT: a steady tone present from hop 0 is learnt as noise and lands at the floor; one that starts later is kept (the third branch
+ * of step 5 moves N by under 1 dB in 3 s).  A caller sets IGDSP_NS_FREEZE while a tone port or DTMF plays on the leg.
+ *
+ * STATE, 1 072 bytes: another tag (all-zero included) is a fresh state: hops 0, prev, ola, S, N zero, Gt 32768.  Under the tag any
+ * bytes are valid: S and N are read masked to 56 bits, Gt clamped to 32768, nothing indexes by a field.
+ * CONTROL d_ctl[c] (NULL or a value above 3: RUN), held for the launch: RUN; FREEZE (S, N and hops held; the gains still computed, from
+ * the S the hop would have had against the held N, smoothed into Gt and applied); BYPASS (out = the input through the same 80-sample delay, bit for bit; prev is
+ * kept and ola holds what unity gains would leave, so that a switch between RUN and BYPASS does not click; S, N, Gt, hops untouched;
+ * the record carries BYPASSED alone among the flags); RESET (fresh state, then RUN; WAS_RESET on the launch's first frame, as after
+ * another tag).
+ * RECORD, 16 bytes per frame: in_energy / out_energy = (sum of squares of the frame's input / output) >> 8; min_gain_q15 = the least
+ * Gt over the frame's hops and bands (32768 under BYPASS); noise_idx = bitlen(sum of N) after the frame; n_clipped; flags LEARNING (a
+ * hop ran with hops < init_hops), SUPPRESSING (min_gain_q15 < 32768), CLIPPED, FROZEN, BYPASSED, WAS_RESET.
+ * d_stats[f][c]: the PCM record of out, as igdsp_conf_mix writes it.  With d_out NULL the stage runs for state and records only.
+ *
+ * ARGUMENTS.  samples_per_frame not 80, 160, 240 or 320, cfg NULL or out of range: IGDSP_EINVAL, whether or not there is work.
+ * n_channels == 0 or n_frames == 0: nothing to do.  Exactly one of d_g711 (with d_codec) and d_pcm; d_state and one of d_out, d_rec,
+ * d_stats required.  n_channels * n_frames < 2^32 - 32 (IGDSP_ERANGE).  d_g711 8-byte, d_pcm, d_out, d_state, d_rec, d_stats 16-byte
+ * aligned.  The state and the outputs may overlap neither an input nor each other.  cfg is host memory, copied.  Enqueued on `stream`,
+ * not synchronised.
+ * Host only, no GPU: igdsp_ns_cfg_default; igdsp_ns_tables (the window's 160 int16 and the 128 twiddle pairs, either may be NULL);
+ * igdsp_ns_frame: one frame of one channel from PCM by the same rule (out and rec optional). */
+#define IGDSP_NS_TAG        0x4E530001u /* igdsp_ns_state.tag                                      */
+#define IGDSP_NS_HOP        80
+#define IGDSP_NS_BANDS      32
+#define IGDSP_NS_UNITY      32768
+#define IGDSP_NS_RUN        0           /* d_ctl                                                    */
+#define IGDSP_NS_FREEZE     1
+#define IGDSP_NS_BYPASS     2
+#define IGDSP_NS_RESET      3
+#define IGDSP_NS_LEARNING    0x01       /* igdsp_ns_rec.flags                                       */
+#define IGDSP_NS_SUPPRESSING 0x02
+#define IGDSP_NS_CLIPPED     0x04
+#define IGDSP_NS_FROZEN      0x08
+#define IGDSP_NS_BYPASSED    0x10
+#define IGDSP_NS_WAS_RESET   0x20
+typedef struct igdsp_ns_cfg {
+    uint32_t floor_q15;             /* the least gain, Q15: 1..32768                             */
+    uint16_t over_q4;               /* the noise estimate's weight in the gain, Q4: 16..64       */
+    uint16_t init_hops;             /* hops that learn the floor at the start of a leg: 1..255   */
+    uint16_t track_shift;           /* 1..8                                                      */
+    uint16_t rise_shift;            /* 4..12                                                     */
+    uint32_t reserved;
+} igdsp_ns_cfg;                     /* 16 bytes */
+typedef struct igdsp_ns_state {
+    uint32_t tag;
+    uint16_t hops, flags;           /* hops saturates at 65535; flags: the last frame's record flags */
+    uint32_t reserved[2];
+    int16_t  prev[80];              /* the previous hop's input                                  */
+    int32_t  ola[80];               /* the synthesis overlap, Q7                                 */
+    uint64_t S[32], N[32];          /* smoothed band energy, noise estimate                      */
+    uint16_t Gt[32];                /* the band gains, Q15                                       */
+} igdsp_ns_state;                   /* 1 072 bytes */
+typedef struct igdsp_ns_rec {
+    uint32_t in_energy, out_energy;
+    uint16_t min_gain_q15, n_clipped;
+    uint8_t  noise_idx, flags, reserved[2];
+} igdsp_ns_rec;                     /* 16 bytes */
+void igdsp_ns_cfg_default(igdsp_ns_cfg *out);
+int  igdsp_ns_tables(const int16_t **window /* [160] */, const int32_t **twiddle /* [128][2] */);
+int  igdsp_ns_frame(const igdsp_ns_cfg *cfg, igdsp_ns_state *st, const int16_t *pcm, uint32_t samples_per_frame, uint32_t ctl,
+                    int16_t *out, igdsp_ns_rec *rec);
+int  igdsp_ns_run(igdsp_ctx *ctx, const uint8_t *d_g711 /* [F][C][n] */, const uint8_t *d_codec /* [C] */, const int16_t *d_pcm /* [F][C][n] */,
+                  const uint8_t *d_ctl /* [C], NULL: RUN */, const igdsp_ns_cfg *cfg /* host, copied */, uint32_t n_channels, uint32_t n_frames,
+                  uint32_t samples_per_frame, igdsp_ns_state *d_state /* [C], in and out */, int16_t *d_out /* [F][C][n] */,
+                  igdsp_ns_rec *d_rec /* [F][C] */, igdsp_frame_stats *d_stats /* [F][C] */, void *stream);
+
 /* ---- synthetic input generators (device side; SURVEY 8(d) definitions) ---------
  * D-uniform: byte k of global byte index g is
  *   (splitmix64(seed + (g>>3)) >> (8*(g&7))) & 0xFF,  g = first_byte + k

@@ -69,6 +69,28 @@ def loop_count(path, mangled, marker):
     return sum(1 for line in text[top + 1:bottom] if line.strip().startswith(marker))
 
 
+def block_counts(path, mangled):
+    """Every basic block of kernel `mangled` in the .s file `path`, in order: its label, whether the compiler marks it as (part of) a
+    loop, its vector ALU instructions (lines that begin with v_), its LDS instructions (ds_) and how often each v_ mnemonic stands in
+    it (k_ns: the block of one forward and of one inverse butterfly is the one with four v_mad_i64_i32, two LDS reads and two writes)"""
+    text = open(path).read().split("\n")
+    start = next(i for i, line in enumerate(text) if line.startswith(mangled + ":"))
+    end = next(i for i in range(start, len(text)) if "s_endpgm" in text[i])
+    blocks = [{"label": "entry", "loop": False, "valu": 0, "lds": 0, "names": {}}]
+    for line in text[start + 1:end]:
+        m = re.match(r"(\.LBB\d+_\d+):(.*)", line)
+        if m:
+            blocks.append({"label": m.group(1), "loop": "Loop" in m.group(2), "valu": 0, "lds": 0, "names": {}})
+            continue
+        word = line.strip().split(" ")[0]
+        if word.startswith("v_"):
+            blocks[-1]["valu"] += 1
+            blocks[-1]["names"][word] = blocks[-1]["names"].get(word, 0) + 1
+        elif word.startswith("ds_"):
+            blocks[-1]["lds"] += 1
+    return blocks
+
+
 if __name__ == "__main__":
     for r in resources():
         if len(sys.argv) < 2 or sys.argv[1] in r["demangled"]:
