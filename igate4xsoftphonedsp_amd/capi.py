@@ -183,6 +183,15 @@ NS_STATE = np.dtype([("tag", "<u4"), ("hops", "<u2"), ("flags", "<u2"), ("reserv
 NS_REC = np.dtype([("in_energy", "<u4"), ("out_energy", "<u4"), ("min_gain_q15", "<u2"), ("n_clipped", "<u2"), ("noise_idx", "u1"), ("flags", "u1"),
                    ("reserved", "u1", (2,))], align=True)                                          # igdsp_ns_rec, 16 bytes
 assert NS_CFG.itemsize == 16 and NS_STATE.itemsize == 1072 and NS_REC.itemsize == 16
+# SRTP (RFC 3711, AES_CM_128_HMAC_SHA1_80 / _32): per leg and direction (igdsp_srtp_protect / igdsp_srtp_unprotect / igdsp_srtp_*_packet)
+SRTP_TAG, SRTP_MAX_PACKET = 0x53525000, 2048
+SRTP_RUN, SRTP_BYPASS, SRTP_RESET = 0, 1, 2
+SRTP_NO_KEY, SRTP_OK, SRTP_AUTH_FAIL, SRTP_REPLAY, SRTP_OLD, SRTP_MALFORMED, SRTP_EMPTY, SRTP_ROLLED, SRTP_BYPASSED = 0, 1, 2, 4, 8, 16, 32, 64, 128
+SRTP_STATE = np.dtype([("tag", "<u4"), ("roc", "<u4"), ("s_l", "<u2"), ("have_s_l", "<u2"), ("reserved", "<u4"), ("window", "<u8"), ("n_ok", "<u4"),
+                       ("n_auth_fail", "<u4"), ("n_replay", "<u4"), ("n_malformed", "<u4"), ("rk", "<u4", (44,)), ("ks", "u1", (16,)), ("mid_i", "<u4", (5,)),
+                       ("mid_o", "<u4", (5,)), ("reserved2", "<u4", (4,))], align=True)            # igdsp_srtp_state, 288 bytes
+SRTP_REC = np.dtype([("roc_used", "<u4"), ("size_out", "<u2"), ("flags", "u1"), ("reserved", "u1")], align=True)   # igdsp_srtp_rec, 8 bytes
+assert SRTP_STATE.itemsize == 288 and SRTP_REC.itemsize == 8
 CHAN_PROBE = np.dtype([("run", "<u4"), ("alarms", "<u4")], align=True)
 # the jitter buffer (igdsp_jb_receive / igdsp_jb_report)
 JB_STATE = np.dtype(
@@ -392,6 +401,11 @@ PROTOTYPES = [
     ("igdsp_ns_tables", _int, [C.POINTER(_vp), C.POINTER(_vp)]),
     ("igdsp_ns_frame", _int, [_vp, _vp, _vp, _u32, _u32, _vp, _vp]),
     ("igdsp_ns_run", _int, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
+    ("igdsp_srtp_derive", _int, [_vp, _u32, _u32, _vp]),
+    ("igdsp_srtp_protect_packet", _int, [_vp, _u32, _vp, _u32, _vp, _u32, C.POINTER(_u32), _vp]),
+    ("igdsp_srtp_unprotect_packet", _int, [_vp, _u32, _vp, _u32, _vp, _u32, C.POINTER(_u32), _vp]),
+    ("igdsp_srtp_protect", _int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _u32, _vp, _vp, _vp]),
+    ("igdsp_srtp_unprotect", _int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _u32, _vp, _vp, _vp]),
     ("igdsp_g726_reorder", _int, [_vp, _vp, _vp, _u64, _int, _vp]),
     ("igdsp_gen_uniform", _int, [_vp, _vp, _u64, _u64, _u64, _vp]),
     ("igdsp_dev_alloc", _int, [_vp, C.POINTER(_vp), C.c_size_t]),
@@ -435,7 +449,7 @@ INTERNAL_MORE_TWIN = {"igdsp_internal_dbuf_move": "igdsp_dbuf_run", "igdsp_inter
                       "igdsp_internal_tdet_move": "igdsp_tone_detect", "igdsp_internal_ec_move": "igdsp_echo_cancel",
                       "igdsp_internal_agc_move": "igdsp_agc_run", "igdsp_internal_vad_move": "igdsp_vad_run",
                       "igdsp_internal_cng_move": "igdsp_cng_run", "igdsp_internal_filt_move": "igdsp_filt_run",
-                      "igdsp_internal_ns_move": "igdsp_ns_run"}
+                      "igdsp_internal_ns_move": "igdsp_ns_run", "igdsp_internal_srtp_move": "igdsp_srtp_protect"}
 INTERNAL_MORE = {name: _PUBLIC[twin] for name, twin in INTERNAL_MORE_TWIN.items()}
 
 _lib = None
@@ -824,6 +838,40 @@ def filt_plan_preset(preset: int, clock_rate: int) -> np.ndarray:
     return plan
 
 
+def srtp_derive(key_salt, tag_len: int = 10, roc0: int = 0, raw: bool = False):
+    """igdsp_srtp_derive (host only, no GPU): the 30 bytes of master key and salt -> one SRTP_STATE record (RFC 3711 4.3.1, labels 0, 1, 2;
+    the key schedule of k_e, k_s, the two HMAC-SHA1 midstates of k_a); tag_len 4 or 10.  raw: the return code alone."""
+    ks = np.frombuffer(bytes(key_salt), np.uint8).copy()
+    assert ks.size == 30
+    out = np.zeros((), SRTP_STATE)
+    rc = load().igdsp_srtp_derive(ks.ctypes.data_as(_vp), int(tag_len), int(roc0) & 0xFFFFFFFF, out.ctypes.data_as(_vp))
+    if raw:
+        return int(rc)
+    if rc != 0:
+        raise IgdspError(rc, "igdsp_srtp_derive")
+    return out
+
+
+def srtp_packet(state, packet, unprotect: bool = False, ctl: int = SRTP_RUN, capacity: int = SRTP_MAX_PACKET, in_place: bool = False, fill: int = 0xA5):
+    """igdsp_srtp_protect_packet / igdsp_srtp_unprotect_packet (host only, no GPU): one packet of one leg.  state an SRTP_STATE record
+    updated in place, packet bytes.  Returns (the output buffer of `capacity` bytes, prefilled with `fill`, as a uint8 array, size_out,
+    the packet's SRTP_REC record); in_place: the packet sits in that buffer and in == out."""
+    assert state.dtype == SRTP_STATE and state.flags["C_CONTIGUOUS"] and state.flags["WRITEABLE"]
+    pkt = np.frombuffer(bytes(packet), np.uint8).copy()
+    out = np.full(max(int(capacity), 1), fill, np.uint8)
+    if in_place:
+        assert pkt.size <= capacity
+        out[:pkt.size] = pkt
+    src = out if in_place else (pkt if pkt.size else np.zeros(1, np.uint8))
+    size_out, rec = _u32(0), np.zeros((), SRTP_REC)
+    fn = load().igdsp_srtp_unprotect_packet if unprotect else load().igdsp_srtp_protect_packet
+    rc = fn(state.ctypes.data_as(_vp), int(ctl), src.ctypes.data_as(_vp), pkt.size, out.ctypes.data_as(_vp), int(capacity), C.byref(size_out),
+            rec.ctypes.data_as(_vp))
+    if rc != 0:
+        raise IgdspError(rc, "igdsp_srtp_unprotect_packet" if unprotect else "igdsp_srtp_protect_packet")
+    return out, int(size_out.value), rec
+
+
 def ns_cfg_default() -> np.ndarray:
     """igdsp_ns_cfg_default (host only, no GPU): one NS_CFG record, the defaults."""
     out = np.zeros((), NS_CFG)
@@ -1188,6 +1236,17 @@ class Context:
         c = np.ascontiguousarray(ns_cfg_default() if cfg is None else cfg, NS_CFG)
         self._ck(self.L.igdsp_ns_run(self.h, _ptr(g711), _ptr(codec), _ptr(pcm), _ptr(ctl), c.ctypes.data_as(_vp), C_, F_, n, _ptr(state), _ptr(out),
                                      _ptr(rec), _ptr(stats), stream), "igdsp_ns_run")
+
+    def srtp_protect(self, state, packets, sizes, C_, F_, pkt_stride, out, out_stride, sizes_out, rec=None, ctl=None, unprotect=False, stream=None):
+        """igdsp_srtp_protect (unprotect: igdsp_srtp_unprotect): packets [F][C][pkt_stride] u8 + sizes [F][C] u16 (what tx_packetize writes,
+        depayload / jb_receive read); ctl [F][C] u8 or None (SRTP_RUN); state [C] SRTP_STATE (in and out) -> out [F][C][out_stride] u8,
+        sizes_out [F][C] u16, rec [F][C] SRTP_REC (optional).  In place: out is packets with equal strides, sizes_out is sizes."""
+        fn, name = (self.L.igdsp_srtp_unprotect, "igdsp_srtp_unprotect") if unprotect else (self.L.igdsp_srtp_protect, "igdsp_srtp_protect")
+        self._ck(fn(self.h, _ptr(ctl), _ptr(packets), _ptr(sizes), C_, F_, pkt_stride, _ptr(state), _ptr(out), out_stride, _ptr(sizes_out), _ptr(rec), stream), name)
+
+    def srtp_unprotect(self, state, packets, sizes, C_, F_, pkt_stride, out, out_stride, sizes_out, rec=None, ctl=None, stream=None):
+        """igdsp_srtp_unprotect: sizes include the tag; a refused packet gets size 0 and its output slot is not written."""
+        self.srtp_protect(state, packets, sizes, C_, F_, pkt_stride, out, out_stride, sizes_out, rec=rec, ctl=ctl, unprotect=True, stream=stream)
 
     def bss_select(self, info, group_ptr, members, n_members, state, words, C_, G_, F_, n=160, payload=None, codec=None, pcm=None,
                    length=None, gain=None, mute=None, vote_frames=0, sel=None, out=None, stats=None, stream=None):

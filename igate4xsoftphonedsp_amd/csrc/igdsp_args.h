@@ -671,4 +671,34 @@ inline Verdict ns_run(P d_g711, P d_codec, P d_pcm, P d_ctl, const igdsp_ns_cfg 
     return kRun;
 }
 
+// ---- SRTP: one rule for igdsp_srtp_protect and igdsp_srtp_unprotect.  The strides are checked whether or not there is work.  In place
+// is the one overlap allowed: d_out == d_packets with equal strides, d_sizes_out == d_sizes
+inline Verdict srtp_run(P d_ctl, P d_packets, P d_sizes, uint32_t C, uint32_t F, uint32_t pkt_stride, P d_state, P d_out, uint32_t out_stride, P d_sizes_out,
+                        P d_rec)
+{
+    if (!stride_ok(pkt_stride, 12u) || !stride_ok(out_stride, 12u)) return kInvalid;
+    if (empty(C, F)) return kNothing;
+    if (!d_sizes) return reject(IGDSP_EINVAL, "d_sizes is required: a protected packet never fills its slot");
+    if (any_null({d_packets, d_state, d_out, d_sizes_out})) return kInvalid;
+    if ((uint64_t)C * F >= 0xFFFFFFE0ull) return reject(IGDSP_ERANGE);
+    // a packet goes as 16-byte pieces at dword alignment, a record as one 8-byte store, the state as 16-byte pieces
+    if (misaligned(2, {d_sizes, d_sizes_out}) || misaligned(4, {d_packets, d_out}) || misaligned(8, {d_rec}) || misaligned(16, {d_state})) return kInvalid;
+    const uint64_t frames = (uint64_t)C * F;
+    struct Buf { P p; uint64_t bytes; };
+    const Buf ins[3] = {{d_ctl, frames}, {d_packets, frames * pkt_stride}, {d_sizes, frames * 2u}};
+    const Buf outs[4] = {{d_state, (uint64_t)C * sizeof(igdsp_srtp_state)}, {d_out, frames * out_stride}, {d_sizes_out, frames * 2u},
+                         {d_rec, frames * sizeof(igdsp_srtp_rec)}};
+    for (int i = 0; i < 4; ++i) {
+        for (int k = 0; k < 3; ++k) {
+            const bool in_place = (i == 1 && k == 1 && d_out == d_packets && out_stride == pkt_stride) || (i == 2 && k == 2 && d_sizes_out == d_sizes);
+            if (!in_place && ranges_overlap(outs[i].p, outs[i].bytes, ins[k].p, ins[k].bytes))
+                return reject(IGDSP_EINVAL, "the state and the outputs must not overlap an input, except in place");
+        }
+        for (int j = 0; j < i; ++j)
+            if (ranges_overlap(outs[i].p, outs[i].bytes, outs[j].p, outs[j].bytes))
+                return reject(IGDSP_EINVAL, "the state and the outputs must not overlap each other");
+    }
+    return kRun;
+}
+
 }  // namespace igdsp::args

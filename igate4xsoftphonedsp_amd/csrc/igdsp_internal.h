@@ -213,6 +213,13 @@ hipError_t launch_filt(const LaunchCfg &cfg, const uint8_t *g711, const uint8_t 
 hipError_t launch_ns(const LaunchCfg &cfg, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm, const uint8_t *ctl, const igdsp_ns_cfg &ns,
                      uint32_t C, uint32_t F, uint32_t n, igdsp_ns_state *state, int16_t *out, igdsp_ns_rec *rec, igdsp_frame_stats *stats, bool yardstick,
                      hipStream_t s);
+// igdsp_srtp_protect / igdsp_srtp_unprotect: dir kSrtpDirProtect or kSrtpDirUnprotect; ctl and rec may be nullptr.  yardstick: the
+// compute-free form of protect: the same loads, tile traffic, state load and store and stores, the header parse and the size rules, no
+// AES round and no compression: a packet goes out as it came with tag_len zero bytes behind it, its record says BYPASSED, the state's
+// words are stored as read; ctl is not read
+hipError_t launch_srtp(const LaunchCfg &cfg, int dir, const uint8_t *ctl, const uint8_t *packets, const uint16_t *sizes, uint32_t C, uint32_t F,
+                       uint32_t pkt_stride, igdsp_srtp_state *state, uint8_t *out, uint32_t out_stride, uint16_t *sizes_out, igdsp_srtp_rec *rec,
+                       bool yardstick, hipStream_t s);
 hipError_t launch_wav_expand(const LaunchCfg &cfg, const uint8_t *payload, uint32_t C, uint32_t F, uint32_t n, uint32_t rate,
                              uint8_t *files, uint64_t file_stride, hipStream_t s);
 hipError_t launch_g726(const LaunchCfg &cfg, const uint8_t *in, uint8_t *out, uint64_t n_bytes, int mode, hipStream_t s);

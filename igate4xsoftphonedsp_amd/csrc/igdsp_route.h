@@ -1324,6 +1324,44 @@ inline NsRoute ns_route(uint32_t C, uint32_t F, uint32_t n, bool g711, bool yard
     return r;
 }
 
+// ---- igdsp_srtp_protect / igdsp_srtp_unprotect (launch_srtp): k_srtp<DIR, MOVE>.  A lane owns a channel for the whole launch (index
+// and replay window are serial in its frames); a block is one wave and kSrtpChans = 64 channels.  A frame's packets pass through an LDS
+// tile in pieces of 64 bytes (one SHA-1 block, four AES blocks) of every packet: 64 rows of 16 words at a pitch of kSrtpPitch = 17
+// words, whatever the stride; a piece is four turns of 16-byte items, item i = turn * 64 + lane being quarter i & 3 of row i >> 2.
+// Beside the tile: the 1 KiB AES table, the lanes' round keys as [44][64] words and two words per row (the bytes to load, the bytes to
+// store whole).  LDS is static.  Registers:
+// the route is written for kSrtpResident = 8 blocks per CU, two waves per SIMD (kSrtpVgprs = 256 of a SIMD's 512 each).
+constexpr uint32_t kSrtpChans = 64;                       // channels per block: the lanes of its one wave
+constexpr uint32_t kSrtpPitch = 17;                       // words between two rows of the tile: odd, so the lanes' reads of word i spread over the banks
+constexpr uint32_t kSrtpTurns = 4;                        // 16-byte items per lane and piece
+constexpr uint32_t kSrtpResident = 8;                     // blocks per CU
+constexpr uint32_t kSrtpVgprs = 256;
+constexpr uint32_t kSrtpMaxStride = 2048;
+constexpr uint32_t kSrtpLdsBytes = 256u * 4u + kSrtpChans * kSrtpPitch * 4u + 2u * kSrtpChans * 4u + 44u * kSrtpChans * 4u;   // table, tile, two words a row, round keys [44][64]
+constexpr int kSrtpDirProtect = 0, kSrtpDirUnprotect = 1; // k_srtp<DIR, >
+static_assert(kSrtpTurns * 64u * 16u == kSrtpChans * 64u && (kSrtpPitch & 1u) == 1u && kSrtpPitch >= 16u && kSrtpResident * kSrtpLdsBytes <= 160u * 1024u &&
+              (kSrtpResident / 4u) * kSrtpVgprs <= 512u, "the turns cover a piece of every row; the resident blocks fit a CU");
+struct SrtpRoute {
+    uint32_t grid = 0, threads = 0, lds = 0;
+    int dir = 0;                           // k_srtp<DIR, MOVE>
+    bool move = false;
+    uint32_t max_pieces = 0;               // pieces of 64 bytes a slot holds: the most a pass walks
+};
+inline SrtpRoute srtp_route(uint32_t C, uint32_t F, uint32_t pkt_stride, uint32_t out_stride, int dir, bool yardstick)
+{
+    SrtpRoute r;
+    if ((uint64_t)C * F == 0 || (uint64_t)C * F >= 0xFFFFFFE0ull) return r;
+    if (pkt_stride < 12u || pkt_stride > kSrtpMaxStride || (pkt_stride & 3u) || out_stride < 12u || out_stride > kSrtpMaxStride || (out_stride & 3u)) return r;
+    if (dir != kSrtpDirProtect && dir != kSrtpDirUnprotect) return r;
+    r.grid = (uint32_t)(((uint64_t)C + kSrtpChans - 1u) / kSrtpChans);
+    r.threads = 64;
+    r.lds = kSrtpLdsBytes;
+    r.dir = yardstick ? kSrtpDirProtect : dir;
+    r.move = yardstick;
+    r.max_pieces = (pkt_stride + 63u) / 64u + 1u;                           // (the hash's padding may need a block behind the data's last)
+    return r;
+}
+
 // ---- igdsp_tx_flush (launch_tx_staged): a wave owns kTsLegs staged legs (runs) of the flush; lanes 0 .. kTsLegs-1 decide, the
 // whole wave writes the packets.  No dynamic LDS: each wave's records (kTsLegs x IGDSP_STAGE_DEPTH) are static.
 constexpr int kTsWaves = 4;

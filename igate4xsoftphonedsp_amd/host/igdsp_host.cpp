@@ -1386,6 +1386,65 @@ int igdsp_host_ns_rec(void *v, igdsp_ns_rec *out)
 }
 void igdsp_host_ns_reset(void *v) { if (v) static_cast<LegDenoiser *>(v)->reset(); }
 
+// ---- SRTP on one leg and direction, no context needed
+LegSrtp::LegSrtp(const uint8_t key_salt[30], uint32_t tag_len, uint32_t roc0) : ctl(IGDSP_SRTP_RUN), resetNext(false)
+{
+    std::memset(&state, 0, sizeof(state));                   // no tag word: NO_KEY until a key is derived
+    std::memset(&last, 0, sizeof(last));
+    ok = key_salt && igdsp_srtp_derive(key_salt, tag_len, roc0, &state) == IGDSP_OK;
+}
+
+void LegSrtp::reset() { resetNext = true; }
+
+int LegSrtp::protect(const uint8_t *in, uint32_t size, uint8_t *out, uint32_t out_capacity)
+{
+    if (!ok || !in || !out) return IGDSP_EINVAL;
+    uint32_t n = 0;
+    const uint32_t c = (resetNext && ctl == IGDSP_SRTP_RUN) ? (uint32_t)IGDSP_SRTP_RESET : ctl;
+    if (igdsp_srtp_protect_packet(&state, c, in, size, out, out_capacity, &n, &last) != IGDSP_OK) return IGDSP_EINVAL;
+    if (c == IGDSP_SRTP_RESET) resetNext = false;
+    return (int)n;
+}
+
+int LegSrtp::unprotect(const uint8_t *in, uint32_t size, uint8_t *out, uint32_t out_capacity)
+{
+    if (!ok || !in || !out) return IGDSP_EINVAL;
+    uint32_t n = 0;
+    const uint32_t c = (resetNext && ctl == IGDSP_SRTP_RUN) ? (uint32_t)IGDSP_SRTP_RESET : ctl;
+    if (igdsp_srtp_unprotect_packet(&state, c, in, size, out, out_capacity, &n, &last) != IGDSP_OK) return IGDSP_EINVAL;
+    if (c == IGDSP_SRTP_RESET) resetNext = false;
+    return (int)n;
+}
+
+void *igdsp_host_srtp_new(const uint8_t *key_salt, uint32_t tag_len, uint32_t roc0)
+{
+    LegSrtp *e = new (std::nothrow) LegSrtp(key_salt, tag_len, roc0);
+    if (e && !e->ok) { delete e; e = nullptr; }
+    return e;
+}
+void igdsp_host_srtp_free(void *v) { delete static_cast<LegSrtp *>(v); }
+int igdsp_host_srtp_control(void *v, uint32_t ctl)
+{
+    if (!v || ctl > IGDSP_SRTP_BYPASS) return IGDSP_EINVAL;
+    static_cast<LegSrtp *>(v)->ctl = ctl;
+    return IGDSP_OK;
+}
+int igdsp_host_srtp_protect(void *v, const uint8_t *in, uint32_t size, uint8_t *out, uint32_t out_capacity)
+{
+    return v ? static_cast<LegSrtp *>(v)->protect(in, size, out, out_capacity) : IGDSP_EINVAL;
+}
+int igdsp_host_srtp_unprotect(void *v, const uint8_t *in, uint32_t size, uint8_t *out, uint32_t out_capacity)
+{
+    return v ? static_cast<LegSrtp *>(v)->unprotect(in, size, out, out_capacity) : IGDSP_EINVAL;
+}
+int igdsp_host_srtp_rec(void *v, igdsp_srtp_rec *out)
+{
+    if (!v || !out) return IGDSP_EINVAL;
+    *out = static_cast<LegSrtp *>(v)->last;
+    return IGDSP_OK;
+}
+void igdsp_host_srtp_reset(void *v) { if (v) static_cast<LegSrtp *>(v)->reset(); }
+
 // ---- conference receive levels, no context needed
 void *igdsp_host_levels_new(uint32_t n_channels)
 {

@@ -420,6 +420,27 @@ public:
     void reset();                            // the estimate, the gains and the overlap forgotten, the cfg stays
 };
 
+// SRTP on one leg and direction, without a context: one igdsp_srtp_state through igdsp_srtp_protect_packet / igdsp_srtp_unprotect_packet,
+// what pjmedia's transport_srtp keeps per stream and direction.  A sender and a receiver are two objects from the same 30 bytes of
+// pjmedia_srtp_crypto.key.  RFC 3711, AES_CM_128_HMAC_SHA1_80 or _32, RTP only; igdsp_srtp_protect / igdsp_srtp_unprotect take the same
+// states for thousands of legs.
+class LegSrtp {
+public:
+    LegSrtp(const uint8_t key_salt[30], uint32_t tag_len = 10, uint32_t roc0 = 0);
+    bool ok;                                 // tag_len is 4 or 10 and a key was given
+    igdsp_srtp_state state;
+    igdsp_srtp_rec last;                     // the record of the last packet
+    uint32_t ctl;                            // IGDSP_SRTP_RUN or _BYPASS: what protect() / unprotect() pass
+    void bypass(bool on) { ctl = on ? (uint32_t)IGDSP_SRTP_BYPASS : (uint32_t)IGDSP_SRTP_RUN; }
+    // the output's size, 0 for a packet that is refused (it did not arrive / is not sent), IGDSP_EINVAL for a NULL argument; in == out is allowed
+    int protect(const uint8_t *in, uint32_t size, uint8_t *out, uint32_t out_capacity);
+    int unprotect(const uint8_t *in, uint32_t size, uint8_t *out, uint32_t out_capacity);
+    bool authFailed() const { return (last.flags & IGDSP_SRTP_AUTH_FAIL) != 0; }
+    void reset();                            // roc, s_l and the replay window start over with the next packet; the keys stay
+private:
+    bool resetNext;
+};
+
 class RoIP_ED137 {
 public:
     // Unlike the reference singleton (roip_ed137.cpp:192) the instance owns an igdsp context; device < 0
@@ -610,6 +631,16 @@ int   igdsp_host_ns_control(void *v, uint32_t ctl);
 int   igdsp_host_ns_process(void *v, const int16_t *pcm, int16_t *out);
 int   igdsp_host_ns_rec(void *v, igdsp_ns_rec *out);
 void  igdsp_host_ns_reset(void *v);
+// SRTP on one leg and direction without a context (LegSrtp): NULL from _new for a NULL key or a tag_len that is not 4 or 10; _protect /
+// _unprotect one packet: the output's size, 0 for a refused packet, IGDSP_EINVAL for a NULL argument; _control sets IGDSP_SRTP_RUN or
+// _BYPASS (anything else IGDSP_EINVAL); _rec a copy of the last packet's record; _reset starts index and window over, the keys stay
+void *igdsp_host_srtp_new(const uint8_t *key_salt, uint32_t tag_len, uint32_t roc0);
+void  igdsp_host_srtp_free(void *v);
+int   igdsp_host_srtp_control(void *v, uint32_t ctl);
+int   igdsp_host_srtp_protect(void *v, const uint8_t *in, uint32_t size, uint8_t *out, uint32_t out_capacity);
+int   igdsp_host_srtp_unprotect(void *v, const uint8_t *in, uint32_t size, uint8_t *out, uint32_t out_capacity);
+int   igdsp_host_srtp_rec(void *v, igdsp_srtp_rec *out);
+void  igdsp_host_srtp_reset(void *v);
 // the spectrum graph without a context (SpectrumGraph): NULL from _new for sizes igdsp_spec_frame rejects; _feed one frame in (1: it
 // computed a spectrum, 0: not, IGDSP_EINVAL for a NULL argument); _real / _iir the two arrays of 512 floats, owned by the handle; _clear
 // is spectClear; _fft_avg is d_fftAvg

@@ -2222,6 +2222,95 @@ int  igdsp_ns_run(igdsp_ctx *ctx, const uint8_t *d_g711 /* [F][C][n] */, const u
                   uint32_t samples_per_frame, igdsp_ns_state *d_state /* [C], in and out */, int16_t *d_out /* [F][C][n] */,
                   igdsp_ns_rec *d_rec /* [F][C] */, igdsp_frame_stats *d_stats /* [F][C] */, void *stream);
 
+/* ---- SRTP: RFC 3711 protection of the RTP packets, per leg and direction -------------------------------------------------------------------
+ * What pjmedia's transport_srtp does between the adapter and the socket when `use_srtp` is on: igdsp_srtp_protect stands behind
+ * igdsp_tx_packetize (in front of transport_send_rtp), igdsp_srtp_unprotect in front of igdsp_jb_receive / igdsp_depayload /
+ * igdsp_decode_meter_packets* (behind transport_rtp_cb).  The rule is pinned bit for bit by RFC 3711, FIPS-197 and FIPS 180 / RFC 2104;
+ * tests/golden/srtp_kat.json holds the standards' known answers.  The host entries (igdsp_srtp_*_packet) and the device entries run
+ * the same code (csrc/igdsp_srtp.h; independent restatement: tests/srtp_model.py) and give the same bytes, records and states for any
+ * split of the frames over launches and at any channel count and position.
+ * SCOPE: AES_CM_128_HMAC_SHA1_80 and its _32 tag length, for RTP.  NOT built: SRTCP, MKI, a non-zero key derivation rate, AES-256, GCM,
+ * F8, the NULL cipher, and SDES / DTLS key exchange: the caller brings the 30 bytes of master key and salt that pjmedia keeps in
+ * pjmedia_srtp_crypto.key.
+ *
+ * HEADER LENGTH.  h = 12 + 4 CC; with X set h += 4 + 4 ext_len, ext_len the big-endian u16 at h + 2.  Every read is bounded by the
+ * packet's size.  MALFORMED: version not 2, size < 12, the header passing size at any step, size > 2048, size above the input slot,
+ * size_out above the output slot or capacity, and on unprotect size < h + tag_len.  The header, an ED-137 extension included, stays
+ * in the clear and under the tag.
+ * INDEX.  The state holds roc, s_l and have_s_l.  First packet: s_l := seq.  v as RFC 3711 Appendix A: s_l < 32768: v = (seq - s_l >
+ * 32768) ? roc - 1 : roc; else v = (s_l - 32768 > seq) ? roc + 1 : roc (integer comparisons, v mod 2^32).  index = v 2^16 + seq, a
+ * 48-bit number, compared against top = roc 2^16 + s_l.
+ * KEYSTREAM.  IV = (k_s 2^16) xor (SSRC 2^64) xor (index 2^16), 128 bits big-endian, the packet's own SSRC; block j = AES_k_e(IV + j),
+ * XORed onto the bytes from h on.  An empty payload is legal.
+ * TAG.  The first tag_len bytes of HMAC-SHA1(k_a, header || encrypted payload || v as 4 big-endian bytes).
+ * PROTECT.  The estimate, no replay test; writes header || ciphertext || tag, size_out = size + tag_len; roc = v, s_l = seq when index
+ * > top or on the first packet; ROLLED when roc changed.  size == 0 (igdsp_tx_packetize's unsent frames): EMPTY, size_out 0.
+ * UNPROTECT.  size includes the tag.  Estimate; against a 64-packet window top - index >= 64 is OLD, a set bit REPLAY; the tag is
+ * computed with v and compared, a mismatch is AUTH_FAIL; decrypt, size_out = size - tag_len; the window moves (an index ahead shifts
+ * it by the distance, >= 64 clears it, sets bit 0 and takes roc / s_l; otherwise the index's bit is set).  Any failure leaves the
+ * state as it was except its counter, gives size_out 0 and writes nothing into the output slot.
+ * FAIL CLOSED.  A state whose tag word is not IGDSP_SRTP_TAG | 4 or | 10 gives NO_KEY (the record's flags are 0) and size_out 0 in both
+ * directions, whatever its other bytes; protect never emits a clear packet.
+ * CONTROL d_ctl[f][c] (NULL or another value: RUN): BYPASS copies the packet through unchanged, the state untouched, with or without a
+ * key; RESET sets roc = 0, have_s_l = 0 and clears the window before the frame, the keys kept.
+ * RECORD, 8 bytes: roc_used = v (0 where no index was estimated), size_out, flags.  The outcomes OK, AUTH_FAIL, REPLAY, OLD, MALFORMED,
+ * EMPTY, BYPASSED exclude each other; ROLLED comes with OK; NO_KEY is the value 0.
+ * STATE, 288 bytes, one per leg and direction, from igdsp_srtp_derive: the tag word, roc, s_l, have_s_l, the replay window, four
+ * counters (ok, auth failures, replays and old, malformed), the 44 words of k_e's key schedule, k_s, and the two SHA-1 states after
+ * k_a xor ipad and k_a xor opad.
+ *
+ * ARGUMENTS of the two batched entries.  packets[f][c][pkt_stride] + sizes[f][c] is what igdsp_tx_packetize writes and igdsp_depayload
+ * / igdsp_jb_receive read.  Both strides multiples of 4, 12..2048.  d_sizes is required (a protected packet never fills its slot).
+ * n_channels * n_frames < 2^32 - 32 (IGDSP_ERANGE).  d_packets, d_out 4-byte, d_sizes, d_sizes_out 2-byte, d_rec 8-byte, d_state 16-byte
+ * aligned.  In place is allowed: d_out == d_packets with equal strides, d_sizes_out == d_sizes; any other overlap of an output with an
+ * input, the state or another output is IGDSP_EINVAL.  Bytes of an output slot past size_out are never written.  Enqueued on `stream`.
+ * Host only, no GPU: igdsp_srtp_derive (RFC 3711 4.3.1, labels 0, 1, 2; tag_len 4 or 10, anything else IGDSP_EINVAL);
+ * igdsp_srtp_protect_packet / igdsp_srtp_unprotect_packet: one packet by the same rule, in == out allowed. */
+#define IGDSP_SRTP_TAG        0x53525000u /* igdsp_srtp_state.tag, | tag_len (4 or 10)                */
+#define IGDSP_SRTP_MAX_PACKET 2048
+#define IGDSP_SRTP_RUN        0           /* d_ctl                                                    */
+#define IGDSP_SRTP_BYPASS     1
+#define IGDSP_SRTP_RESET      2
+#define IGDSP_SRTP_NO_KEY     0x00        /* igdsp_srtp_rec.flags: no flag at all                     */
+#define IGDSP_SRTP_OK         0x01
+#define IGDSP_SRTP_AUTH_FAIL  0x02
+#define IGDSP_SRTP_REPLAY     0x04
+#define IGDSP_SRTP_OLD        0x08
+#define IGDSP_SRTP_MALFORMED  0x10
+#define IGDSP_SRTP_EMPTY      0x20
+#define IGDSP_SRTP_ROLLED     0x40
+#define IGDSP_SRTP_BYPASSED   0x80
+typedef struct igdsp_srtp_state {
+    uint32_t tag;                   /* IGDSP_SRTP_TAG | tag_len                                  */
+    uint32_t roc;
+    uint16_t s_l, have_s_l;
+    uint32_t reserved;
+    uint64_t window;                /* bit i: index top - i was accepted (unprotect)             */
+    uint32_t n_ok, n_auth_fail, n_replay, n_malformed;
+    uint32_t rk[44];                /* AES-128 encryption key schedule of k_e                    */
+    uint8_t  ks[16];                /* k_s, 14 bytes, then two zero bytes: k_s 2^16, big-endian  */
+    uint32_t mid_i[5], mid_o[5];    /* SHA-1 after the block k_a xor ipad / k_a xor opad         */
+    uint32_t reserved2[4];
+} igdsp_srtp_state;                 /* 288 bytes */
+typedef struct igdsp_srtp_rec {
+    uint32_t roc_used;
+    uint16_t size_out;
+    uint8_t  flags, reserved;
+} igdsp_srtp_rec;                   /* 8 bytes */
+int  igdsp_srtp_derive(const uint8_t key_salt[30], uint32_t tag_len, uint32_t roc0, igdsp_srtp_state *out);
+int  igdsp_srtp_protect_packet(igdsp_srtp_state *st, uint32_t ctl, const uint8_t *in, uint32_t size, uint8_t *out, uint32_t out_capacity,
+                               uint32_t *size_out, igdsp_srtp_rec *rec);
+int  igdsp_srtp_unprotect_packet(igdsp_srtp_state *st, uint32_t ctl, const uint8_t *in, uint32_t size, uint8_t *out, uint32_t out_capacity,
+                                 uint32_t *size_out, igdsp_srtp_rec *rec);
+int  igdsp_srtp_protect(igdsp_ctx *ctx, const uint8_t *d_ctl /* [F][C], NULL: RUN */, const uint8_t *d_packets /* [F][C][pkt_stride] */,
+                        const uint16_t *d_sizes /* [F][C] */, uint32_t n_channels, uint32_t n_frames, uint32_t pkt_stride,
+                        igdsp_srtp_state *d_state /* [C], in and out */, uint8_t *d_out /* [F][C][out_stride] */, uint32_t out_stride,
+                        uint16_t *d_sizes_out /* [F][C] */, igdsp_srtp_rec *d_rec /* [F][C] */, void *stream);
+int  igdsp_srtp_unprotect(igdsp_ctx *ctx, const uint8_t *d_ctl /* [F][C], NULL: RUN */, const uint8_t *d_packets /* [F][C][pkt_stride] */,
+                          const uint16_t *d_sizes /* [F][C] */, uint32_t n_channels, uint32_t n_frames, uint32_t pkt_stride,
+                          igdsp_srtp_state *d_state /* [C], in and out */, uint8_t *d_out /* [F][C][out_stride] */, uint32_t out_stride,
+                          uint16_t *d_sizes_out /* [F][C] */, igdsp_srtp_rec *d_rec /* [F][C] */, void *stream);
+
 /* ---- synthetic input generators (device side; SURVEY 8(d) definitions) ---------
  * D-uniform: byte k of global byte index g is
  *   (splitmix64(seed + (g>>3)) >> (8*(g&7))) & 0xFF,  g = first_byte + k

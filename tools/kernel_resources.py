@@ -91,6 +91,13 @@ def block_counts(path, mangled):
     return blocks
 
 
+def blocks_with(path, mangled, name, at_least, lds_at_least=0):
+    """The basic blocks of kernel `mangled` (block_counts) in which the v_ mnemonic `name` stands at least `at_least` times and that hold
+    at least `lds_at_least` LDS instructions (k_srtp: one AES-128 block is the block with at least 100 v_alignbit_b32, the table words'
+    rotations, and at least 160 LDS reads; one SHA-1 compression the block with at least 200 v_alignbit_b32 and no LDS instruction)"""
+    return [b for b in block_counts(path, mangled) if b["names"].get(name, 0) >= at_least and b["lds"] >= lds_at_least]
+
+
 if __name__ == "__main__":
     for r in resources():
         if len(sys.argv) < 2 or sys.argv[1] in r["demangled"]:
