@@ -210,6 +210,22 @@ PLC_STATE = np.dtype(
 JB_PRIOR = np.dtype([("expected_prior", "<u4"), ("received_prior", "<u4"), ("epoch", "<u4"), ("reserved", "<u4")], align=True)
 JB_RR = np.dtype([("ssrc", "<u4"), ("ext_max_seq", "<u4"), ("cum_lost", "<i4"), ("jitter", "<u4"), ("fraction_lost", "u1"), ("valid", "u1"),
                   ("reserved", "<u2")], align=True)
+# RTCP / SRTCP (igdsp_rtcp_build / igdsp_rtcp_parse / igdsp_srtcp_protect / igdsp_srtcp_unprotect and their host entries)
+RTCP_MAX_BUILT, RTCP_CNAME_MAX = 136, 64
+RTCP_NONE, RTCP_REPORT, RTCP_BYE = 0, 1, 2
+RTCP_SR, RTCP_RR, RTCP_HAS_BLOCK, RTCP_BYE_SENT = 1, 2, 4, 8                         # RTCP_BUILT.flags
+RTCP_HAVE_SR, RTCP_PEER_VALID, RTCP_RTT_VALID, RTCP_BYE_SEEN = 1, 2, 4, 8            # RTCP_STATE.flags
+RTCP_PARSED, RTCP_MALFORMED, RTCP_EMPTY, RTCP_GOT_SR, RTCP_GOT_BLOCK, RTCP_GOT_RTT, RTCP_RTT_NEGATIVE, RTCP_GOT_BYE = 1, 2, 4, 8, 16, 32, 64, 128   # RTCP_SEEN.flags
+SRTCP_TAG, SRTCP_TRAILER, SRTCP_CLEAR = 0x53524300, 14, 0x40
+RTCP_SRC = np.dtype([("ssrc", "<u4"), ("rtp_ts", "<u4"), ("packets", "<u4"), ("octets", "<u4")], align=True)   # igdsp_rtcp_src, 16 bytes
+RTCP_STATE = np.dtype([("prior", JB_PRIOR), ("sent_prior", "<u4"), ("n_built", "<u4"), ("lsr", "<u4"), ("lsr_arrival", "<u4"), ("flags", "<u4"),
+                       ("n_parsed", "<u4"), ("n_malformed", "<u4"), ("rtt_last", "<u4"), ("rtt_count", "<u4"), ("peer_fraction_lost", "<u4"),
+                       ("peer_cum_lost", "<i4"), ("peer_ext_seq", "<u4"), ("peer_jitter", "<u4"), ("reserved", "<u4", (3,))], align=True)   # igdsp_rtcp_state, 80 bytes
+RTCP_BUILT = np.dtype([("size", "<u2"), ("flags", "u1"), ("reserved", "u1"), ("reserved2", "<u4")], align=True)   # igdsp_rtcp_built, 8 bytes
+RTCP_SEEN = np.dtype([("flags", "u1"), ("n_sub", "u1"), ("peer_fraction_lost", "u1"), ("reserved", "u1"), ("sender_ssrc", "<u4"), ("rtt", "<u4"),
+                      ("peer_cum_lost", "<i4"), ("peer_ext_seq", "<u4"), ("peer_jitter", "<u4"), ("sr_packets", "<u4"), ("sr_octets", "<u4")],
+                     align=True)                                                    # igdsp_rtcp_seen, 32 bytes
+assert RTCP_SRC.itemsize == 16 and RTCP_STATE.itemsize == 80 and RTCP_BUILT.itemsize == 8 and RTCP_SEEN.itemsize == 32
 # the adaptive playout delay (igdsp_jb_receive_adaptive / igdsp_jb_adapt_next)
 JB_ADAPT_CFG = np.dtype([("min_frames", "u1"), ("max_frames", "u1"), ("init_frames", "u1"), ("jitter_mult", "u1"), ("late_restart", "u1"),
                          ("reserved", "u1", (3,))], align=True)   # igdsp_jb_adapt_cfg
@@ -406,6 +422,15 @@ PROTOTYPES = [
     ("igdsp_srtp_unprotect_packet", _int, [_vp, _u32, _vp, _u32, _vp, _u32, C.POINTER(_u32), _vp]),
     ("igdsp_srtp_protect", _int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _u32, _vp, _vp, _vp]),
     ("igdsp_srtp_unprotect", _int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _u32, _vp, _vp, _vp]),
+    ("igdsp_rtcp_build_packet", _int, [_vp, _u32, _vp, _vp, _u64, _vp, _u32, _vp, _u32, C.POINTER(_u32), _vp]),
+    ("igdsp_rtcp_parse_packet", _int, [_vp, _vp, _u32, _u32, _u32, _vp]),
+    ("igdsp_srtcp_derive", _int, [_vp, _u32, _vp]),
+    ("igdsp_srtcp_protect_packet", _int, [_vp, _u32, _vp, _u32, _vp, _u32, C.POINTER(_u32), _vp]),
+    ("igdsp_srtcp_unprotect_packet", _int, [_vp, _u32, _vp, _u32, _vp, _u32, C.POINTER(_u32), _vp]),
+    ("igdsp_rtcp_build", _int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _u32, _vp, _vp, _vp]),
+    ("igdsp_rtcp_parse", _int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp]),
+    ("igdsp_srtcp_protect", _int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _u32, _vp, _vp, _vp]),
+    ("igdsp_srtcp_unprotect", _int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _u32, _vp, _vp, _vp]),
     ("igdsp_g726_reorder", _int, [_vp, _vp, _vp, _u64, _int, _vp]),
     ("igdsp_gen_uniform", _int, [_vp, _vp, _u64, _u64, _u64, _vp]),
     ("igdsp_dev_alloc", _int, [_vp, C.POINTER(_vp), C.c_size_t]),
@@ -449,7 +474,9 @@ INTERNAL_MORE_TWIN = {"igdsp_internal_dbuf_move": "igdsp_dbuf_run", "igdsp_inter
                       "igdsp_internal_tdet_move": "igdsp_tone_detect", "igdsp_internal_ec_move": "igdsp_echo_cancel",
                       "igdsp_internal_agc_move": "igdsp_agc_run", "igdsp_internal_vad_move": "igdsp_vad_run",
                       "igdsp_internal_cng_move": "igdsp_cng_run", "igdsp_internal_filt_move": "igdsp_filt_run",
-                      "igdsp_internal_ns_move": "igdsp_ns_run", "igdsp_internal_srtp_move": "igdsp_srtp_protect"}
+                      "igdsp_internal_ns_move": "igdsp_ns_run", "igdsp_internal_srtp_move": "igdsp_srtp_protect",
+                      "igdsp_internal_srtcp_move": "igdsp_srtcp_protect",
+                      "igdsp_internal_rtcp_build_move": "igdsp_rtcp_build", "igdsp_internal_rtcp_parse_move": "igdsp_rtcp_parse"}
 INTERNAL_MORE = {name: _PUBLIC[twin] for name, twin in INTERNAL_MORE_TWIN.items()}
 
 _lib = None
@@ -872,6 +899,70 @@ def srtp_packet(state, packet, unprotect: bool = False, ctl: int = SRTP_RUN, cap
     return out, int(size_out.value), rec
 
 
+def srtcp_derive(key_salt, index0: int = 0):
+    """igdsp_srtcp_derive (host only, no GPU): the 30 bytes of master key and salt -> one SRTP_STATE record for SRTCP (RFC 3711 4.3.1, labels
+    3, 4, 5; the tag word SRTCP_TAG | 10); roc holds the 31-bit index, index0 the first a protecting leg sends."""
+    ks = np.frombuffer(bytes(key_salt), np.uint8).copy()
+    assert ks.size == 30
+    out = np.zeros((), SRTP_STATE)
+    rc = load().igdsp_srtcp_derive(ks.ctypes.data_as(_vp), int(index0) & 0xFFFFFFFF, out.ctypes.data_as(_vp))
+    if rc != 0:
+        raise IgdspError(rc, "igdsp_srtcp_derive")
+    return out
+
+
+def srtcp_packet(state, packet, unprotect: bool = False, ctl: int = SRTP_RUN, capacity: int = SRTP_MAX_PACKET, in_place: bool = False, fill: int = 0xA5):
+    """igdsp_srtcp_protect_packet / igdsp_srtcp_unprotect_packet (host only, no GPU): one packet of one leg; arguments and return as
+    srtp_packet."""
+    assert state.dtype == SRTP_STATE and state.flags["C_CONTIGUOUS"] and state.flags["WRITEABLE"]
+    pkt = np.frombuffer(bytes(packet), np.uint8).copy()
+    out = np.full(max(int(capacity), 1), fill, np.uint8)
+    if in_place:
+        assert pkt.size <= capacity
+        out[:pkt.size] = pkt
+    src = out if in_place else (pkt if pkt.size else np.zeros(1, np.uint8))
+    size_out, rec = _u32(0), np.zeros((), SRTP_REC)
+    fn = load().igdsp_srtcp_unprotect_packet if unprotect else load().igdsp_srtcp_protect_packet
+    rc = fn(state.ctypes.data_as(_vp), int(ctl), src.ctypes.data_as(_vp), pkt.size, out.ctypes.data_as(_vp), int(capacity), C.byref(size_out),
+            rec.ctypes.data_as(_vp))
+    if rc != 0:
+        raise IgdspError(rc, "igdsp_srtcp_unprotect_packet" if unprotect else "igdsp_srtcp_protect_packet")
+    return out, int(size_out.value), rec
+
+
+def rtcp_build_packet(state, ctl: int, src, now: int, jb=None, cname=None, capacity: int = RTCP_MAX_BUILT, fill: int = 0xA5, raw: bool = False):
+    """igdsp_rtcp_build_packet (host only, no GPU): one report of one leg.  state an RTCP_STATE record updated in place, src an RTCP_SRC
+    record, now the 64-bit NTP time, jb a JB_STATE record or None, cname bytes or None.  Returns (the output buffer of `capacity` bytes
+    prefilled with `fill`, the size, the RTCP_BUILT record); raw: the return code alone."""
+    assert state.dtype == RTCP_STATE and state.flags["C_CONTIGUOUS"] and state.flags["WRITEABLE"]
+    s = np.ascontiguousarray(np.asarray(src, dtype=RTCP_SRC).reshape(()))
+    j = None if jb is None else np.ascontiguousarray(np.asarray(jb, dtype=JB_STATE).reshape(()))
+    cn = None if cname is None else np.frombuffer(bytes(cname) + b"\0", np.uint8).copy()
+    out = np.full(max(int(capacity), 1), fill, np.uint8)
+    size_out, rec = _u32(0), np.zeros((), RTCP_BUILT)
+    rc = load().igdsp_rtcp_build_packet(state.ctypes.data_as(_vp), int(ctl), None if j is None else j.ctypes.data_as(_vp), s.ctypes.data_as(_vp), int(now),
+                                        None if cn is None else cn.ctypes.data_as(_vp), 0 if cname is None else len(cname), out.ctypes.data_as(_vp),
+                                        int(capacity), C.byref(size_out), rec.ctypes.data_as(_vp))
+    if raw:
+        return int(rc)
+    if rc != 0:
+        raise IgdspError(rc, "igdsp_rtcp_build_packet")
+    return out, int(size_out.value), rec
+
+
+def rtcp_parse_packet(state, packet, arrival: int, local_ssrc: int):
+    """igdsp_rtcp_parse_packet (host only, no GPU): one received compound packet of one leg.  state an RTCP_STATE record updated in place;
+    arrival the arrival time's middle 32 NTP bits.  Returns the RTCP_SEEN record."""
+    assert state.dtype == RTCP_STATE and state.flags["C_CONTIGUOUS"] and state.flags["WRITEABLE"]
+    pkt = np.frombuffer(bytes(packet), np.uint8).copy()
+    rec = np.zeros((), RTCP_SEEN)
+    rc = load().igdsp_rtcp_parse_packet(state.ctypes.data_as(_vp), pkt.ctypes.data_as(_vp) if pkt.size else None, pkt.size, int(arrival) & 0xFFFFFFFF,
+                                        int(local_ssrc) & 0xFFFFFFFF, rec.ctypes.data_as(_vp))
+    if rc != 0:
+        raise IgdspError(rc, "igdsp_rtcp_parse_packet")
+    return rec
+
+
 def ns_cfg_default() -> np.ndarray:
     """igdsp_ns_cfg_default (host only, no GPU): one NS_CFG record, the defaults."""
     out = np.zeros((), NS_CFG)
@@ -1247,6 +1338,29 @@ class Context:
     def srtp_unprotect(self, state, packets, sizes, C_, F_, pkt_stride, out, out_stride, sizes_out, rec=None, ctl=None, stream=None):
         """igdsp_srtp_unprotect: sizes include the tag; a refused packet gets size 0 and its output slot is not written."""
         self.srtp_protect(state, packets, sizes, C_, F_, pkt_stride, out, out_stride, sizes_out, rec=rec, ctl=ctl, unprotect=True, stream=stream)
+
+    def srtcp_protect(self, state, packets, sizes, C_, F_, pkt_stride, out, out_stride, sizes_out, rec=None, ctl=None, unprotect=False, stream=None):
+        """igdsp_srtcp_protect (unprotect: igdsp_srtcp_unprotect): srtp_protect's arguments on RTCP packets; state [C] SRTP_STATE from
+        srtcp_derive; a protected packet is 14 bytes longer."""
+        fn, name = (self.L.igdsp_srtcp_unprotect, "igdsp_srtcp_unprotect") if unprotect else (self.L.igdsp_srtcp_protect, "igdsp_srtcp_protect")
+        self._ck(fn(self.h, _ptr(ctl), _ptr(packets), _ptr(sizes), C_, F_, pkt_stride, _ptr(state), _ptr(out), out_stride, _ptr(sizes_out), _ptr(rec), stream), name)
+
+    def srtcp_unprotect(self, state, packets, sizes, C_, F_, pkt_stride, out, out_stride, sizes_out, rec=None, ctl=None, stream=None):
+        """igdsp_srtcp_unprotect: sizes include the index word and the tag; a refused packet gets size 0 and its output slot is not written."""
+        self.srtcp_protect(state, packets, sizes, C_, F_, pkt_stride, out, out_stride, sizes_out, rec=rec, ctl=ctl, unprotect=True, stream=stream)
+
+    def rtcp_build(self, ctl, src, now, C_, F_, state, packets, pkt_stride, sizes, jb=None, cname=None, cname_len=None, rec=None, stream=None):
+        """igdsp_rtcp_build: ctl [F][C] u8 (RTCP_NONE / REPORT / BYE), src [F][C] RTCP_SRC, now [F] u64 NTP, jb [C] JB_STATE or None, cname
+        [C][64] u8 + cname_len [C] u8 or both None; state [C] RTCP_STATE (in and out) -> packets [F][C][pkt_stride] u8, sizes [F][C] u16, rec
+        [F][C] RTCP_BUILT (optional)."""
+        self._ck(self.L.igdsp_rtcp_build(self.h, _ptr(ctl), _ptr(jb), _ptr(src), _ptr(now), _ptr(cname), _ptr(cname_len), C_, F_, _ptr(state), _ptr(packets),
+                                         pkt_stride, _ptr(sizes), _ptr(rec), stream), "igdsp_rtcp_build")
+
+    def rtcp_parse(self, packets, sizes, arrival, local_ssrc, C_, F_, pkt_stride, state, rec=None, stream=None):
+        """igdsp_rtcp_parse: packets [F][C][pkt_stride] u8 + sizes [F][C] u16, arrival [F][C] u32 (middle 32 NTP bits), local_ssrc [C] u32;
+        state [C] RTCP_STATE (in and out) -> rec [F][C] RTCP_SEEN (optional)."""
+        self._ck(self.L.igdsp_rtcp_parse(self.h, _ptr(packets), _ptr(sizes), _ptr(arrival), _ptr(local_ssrc), C_, F_, pkt_stride, _ptr(state), _ptr(rec), stream),
+                 "igdsp_rtcp_parse")
 
     def bss_select(self, info, group_ptr, members, n_members, state, words, C_, G_, F_, n=160, payload=None, codec=None, pcm=None,
                    length=None, gain=None, mute=None, vote_frames=0, sel=None, out=None, stats=None, stream=None):

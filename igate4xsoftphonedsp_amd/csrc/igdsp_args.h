@@ -701,4 +701,58 @@ inline Verdict srtp_run(P d_ctl, P d_packets, P d_sizes, uint32_t C, uint32_t F,
     return kRun;
 }
 
+// ---- SRTCP: igdsp_srtcp_protect and igdsp_srtcp_unprotect take SRTP's arguments under SRTP's rule
+inline Verdict srtcp_run(P d_ctl, P d_packets, P d_sizes, uint32_t C, uint32_t F, uint32_t pkt_stride, P d_state, P d_out, uint32_t out_stride, P d_sizes_out,
+                         P d_rec)
+{
+    return srtp_run(d_ctl, d_packets, d_sizes, C, F, pkt_stride, d_state, d_out, out_stride, d_sizes_out, d_rec);
+}
+
+// ---- RTCP.  The stride is checked whether or not there is work.  Build writes its packets, sizes, records and the state; parse its
+// records and the state: none of them may overlap an input or another of them
+inline Verdict rtcp_build(P d_ctl, P d_jb, P d_src, P d_now, P d_cname, P d_cname_len, uint32_t C, uint32_t F, P d_state, P d_packets, uint32_t pkt_stride,
+                          P d_sizes, P d_rec)
+{
+    if (!stride_ok(pkt_stride, (uint32_t)IGDSP_RTCP_MAX_BUILT)) return kInvalid;
+    if (empty(C, F)) return kNothing;
+    if (any_null({d_ctl, d_src, d_now, d_state, d_packets, d_sizes})) return kInvalid;
+    if ((d_cname == nullptr) != (d_cname_len == nullptr)) return reject(IGDSP_EINVAL, "d_cname and d_cname_len come together");
+    if ((uint64_t)C * F >= 0xFFFFFFE0ull) return reject(IGDSP_ERANGE);
+    // a packet goes as 16-byte pieces at dword alignment, a record as one 8-byte store, the states, a source and a CNAME as 16-byte pieces
+    if (misaligned(2, {d_sizes}) || misaligned(4, {d_packets}) || misaligned(8, {d_now, d_rec}) || misaligned(16, {d_jb, d_src, d_cname, d_state})) return kInvalid;
+    const uint64_t frames = (uint64_t)C * F;
+    struct Buf { P p; uint64_t bytes; };
+    const Buf ins[6] = {{d_ctl, frames}, {d_jb, (uint64_t)C * sizeof(igdsp_jb_state)}, {d_src, frames * sizeof(igdsp_rtcp_src)}, {d_now, (uint64_t)F * 8u},
+                        {d_cname, (uint64_t)C * IGDSP_RTCP_CNAME_MAX}, {d_cname_len, C}};
+    const Buf outs[4] = {{d_state, (uint64_t)C * sizeof(igdsp_rtcp_state)}, {d_packets, frames * pkt_stride}, {d_sizes, frames * 2u},
+                         {d_rec, frames * sizeof(igdsp_rtcp_built)}};
+    for (int i = 0; i < 4; ++i) {
+        for (const Buf &b : ins)
+            if (ranges_overlap(outs[i].p, outs[i].bytes, b.p, b.bytes)) return reject(IGDSP_EINVAL, "the state and the outputs must not overlap an input");
+        for (int j = 0; j < i; ++j)
+            if (ranges_overlap(outs[i].p, outs[i].bytes, outs[j].p, outs[j].bytes))
+                return reject(IGDSP_EINVAL, "the state and the outputs must not overlap each other");
+    }
+    return kRun;
+}
+inline Verdict rtcp_parse(P d_packets, P d_sizes, P d_arrival, P d_local_ssrc, uint32_t C, uint32_t F, uint32_t pkt_stride, P d_state, P d_rec)
+{
+    if (!stride_ok(pkt_stride, 8u)) return kInvalid;
+    if (empty(C, F)) return kNothing;
+    if (any_null({d_packets, d_sizes, d_arrival, d_local_ssrc, d_state})) return kInvalid;
+    if ((uint64_t)C * F >= 0xFFFFFFE0ull) return reject(IGDSP_ERANGE);
+    if (misaligned(2, {d_sizes}) || misaligned(4, {d_packets, d_arrival, d_local_ssrc}) || misaligned(16, {d_state, d_rec})) return kInvalid;
+    const uint64_t frames = (uint64_t)C * F;
+    struct Buf { P p; uint64_t bytes; };
+    const Buf ins[4] = {{d_packets, frames * pkt_stride}, {d_sizes, frames * 2u}, {d_arrival, frames * 4u}, {d_local_ssrc, (uint64_t)C * 4u}};
+    const Buf outs[2] = {{d_state, (uint64_t)C * sizeof(igdsp_rtcp_state)}, {d_rec, frames * sizeof(igdsp_rtcp_seen)}};
+    for (int i = 0; i < 2; ++i) {
+        for (const Buf &b : ins)
+            if (ranges_overlap(outs[i].p, outs[i].bytes, b.p, b.bytes)) return reject(IGDSP_EINVAL, "the state and the records must not overlap an input");
+        for (int j = 0; j < i; ++j)
+            if (ranges_overlap(outs[i].p, outs[i].bytes, outs[j].p, outs[j].bytes)) return reject(IGDSP_EINVAL, "the state and the records must not overlap each other");
+    }
+    return kRun;
+}
+
 }  // namespace igdsp::args

@@ -220,6 +220,19 @@ hipError_t launch_ns(const LaunchCfg &cfg, const uint8_t *g711, const uint8_t *c
 hipError_t launch_srtp(const LaunchCfg &cfg, int dir, const uint8_t *ctl, const uint8_t *packets, const uint16_t *sizes, uint32_t C, uint32_t F,
                        uint32_t pkt_stride, igdsp_srtp_state *state, uint8_t *out, uint32_t out_stride, uint16_t *sizes_out, igdsp_srtp_rec *rec,
                        bool yardstick, hipStream_t s);
+// igdsp_srtcp_protect / igdsp_srtcp_unprotect: launch_srtp's arguments and yardstick, RFC 3711 3.4 (the trailer's 14 bytes go out as zeros)
+hipError_t launch_srtcp(const LaunchCfg &cfg, int dir, const uint8_t *ctl, const uint8_t *packets, const uint16_t *sizes, uint32_t C, uint32_t F,
+                        uint32_t pkt_stride, igdsp_srtp_state *state, uint8_t *out, uint32_t out_stride, uint16_t *sizes_out, igdsp_srtp_rec *rec,
+                        bool yardstick, hipStream_t s);
+// igdsp_rtcp_build: jb, rec and (together) cname, cname_len may be nullptr.  igdsp_rtcp_parse: rec may be nullptr.  yardstick: the
+// compute-free forms.  Build: the same loads, the size rule, a row of the packet's size filled with one loaded word, the same stores,
+// a record with the size and no flag, the state as read.  Parse: the same loads, tile traffic and row reads; the record is the size's
+// verdict alone (PARSED, EMPTY or MALFORMED), the state as read
+hipError_t launch_rtcp_build(const LaunchCfg &cfg, const uint8_t *ctl, const igdsp_jb_state *jb, const igdsp_rtcp_src *src, const uint64_t *now,
+                             const uint8_t *cname, const uint8_t *cname_len, uint32_t C, uint32_t F, igdsp_rtcp_state *state, uint8_t *packets,
+                             uint32_t pkt_stride, uint16_t *sizes, igdsp_rtcp_built *rec, bool yardstick, hipStream_t s);
+hipError_t launch_rtcp_parse(const LaunchCfg &cfg, const uint8_t *packets, const uint16_t *sizes, const uint32_t *arrival, const uint32_t *local_ssrc, uint32_t C,
+                             uint32_t F, uint32_t pkt_stride, igdsp_rtcp_state *state, igdsp_rtcp_seen *rec, bool yardstick, hipStream_t s);
 hipError_t launch_wav_expand(const LaunchCfg &cfg, const uint8_t *payload, uint32_t C, uint32_t F, uint32_t n, uint32_t rate,
                              uint8_t *files, uint64_t file_stride, hipStream_t s);
 hipError_t launch_g726(const LaunchCfg &cfg, const uint8_t *in, uint8_t *out, uint64_t n_bytes, int mode, hipStream_t s);

@@ -1362,6 +1362,59 @@ inline SrtpRoute srtp_route(uint32_t C, uint32_t F, uint32_t pkt_stride, uint32_
     return r;
 }
 
+// ---- igdsp_srtcp_protect / igdsp_srtcp_unprotect (launch_srtcp): k_srtcp<DIR, MOVE> has k_srtp's geometry, LDS and residency: the 14-byte
+// trailer does not pass the tile, so a slot's pieces and the strides' bounds are SRTP's
+inline SrtpRoute srtcp_route(uint32_t C, uint32_t F, uint32_t pkt_stride, uint32_t out_stride, int dir, bool yardstick)
+{
+    return srtp_route(C, F, pkt_stride, out_stride, dir, yardstick);
+}
+
+// ---- igdsp_rtcp_build (launch_rtcp_build): k_rtcp_build, and igdsp_rtcp_parse (launch_rtcp_parse): k_rtcp_parse.  A lane owns a leg for
+// the launch (the report's prior and the last SR heard are serial in its ticks); a block is one wave and kRtcpChans = 64 legs.  Build:
+// a row of the LDS tile is a whole packet, kRtcpRowWords = 34 words at a pitch of kRtcpRowPitch = 35 (odd), stored as kRtcpRowItems = 9
+// turns of 16-byte items, item i = turn * 64 + lane being sixteenth i % 9 of row i / 9.  Parse: SRTP's tile, 64 rows of one 64-byte
+// piece at pitch kSrtpPitch, and a word per row for the bytes to load.  LDS is static.  Written for kRtcpResident = 8 blocks per CU,
+// two waves per SIMD (kRtcpVgprs = 256 of a SIMD's 512 each).
+constexpr uint32_t kRtcpChans = 64;
+constexpr uint32_t kRtcpRowWords = 34;                    // IGDSP_RTCP_MAX_BUILT / 4
+constexpr uint32_t kRtcpRowPitch = 35;
+constexpr uint32_t kRtcpRowItems = 9;                     // 16-byte items that cover a row
+constexpr uint32_t kRtcpResident = 8;
+constexpr uint32_t kRtcpVgprs = 256;
+constexpr uint32_t kRtcpBuildLdsBytes = kRtcpChans * kRtcpRowPitch * 4u + kRtcpChans * 4u;        // the rows, a size a row
+constexpr uint32_t kRtcpParseLdsBytes = kSrtpChans * kSrtpPitch * 4u + kSrtpChans * 4u;           // the tile, a limit a row
+static_assert(kRtcpRowWords * 4u == 136u && kRtcpRowItems * 16u >= kRtcpRowWords * 4u && (kRtcpRowPitch & 1u) == 1u && kRtcpRowPitch >= kRtcpRowWords &&
+              kRtcpChans == kSrtpChans && kRtcpResident * kRtcpBuildLdsBytes <= 160u * 1024u && (kRtcpResident / 4u) * kRtcpVgprs <= 512u,
+              "a row holds the largest packet; the items cover it; parse uses SRTP's tile; the resident blocks fit a CU");
+struct RtcpRoute {
+    uint32_t grid = 0, threads = 0, lds = 0;
+    bool move = false;                     // k_rtcp_build<MOVE>, k_rtcp_parse<MOVE>
+    uint32_t max_pieces = 0;               // parse: pieces of 64 bytes a slot holds
+};
+inline RtcpRoute rtcp_build_route(uint32_t C, uint32_t F, uint32_t pkt_stride, bool yardstick)
+{
+    RtcpRoute r;
+    if ((uint64_t)C * F == 0 || (uint64_t)C * F >= 0xFFFFFFE0ull) return r;
+    if (pkt_stride < kRtcpRowWords * 4u || pkt_stride > kSrtpMaxStride || (pkt_stride & 3u)) return r;
+    r.grid = (uint32_t)(((uint64_t)C + kRtcpChans - 1u) / kRtcpChans);
+    r.threads = 64;
+    r.lds = kRtcpBuildLdsBytes;
+    r.move = yardstick;
+    return r;
+}
+inline RtcpRoute rtcp_parse_route(uint32_t C, uint32_t F, uint32_t pkt_stride, bool yardstick)
+{
+    RtcpRoute r;
+    if ((uint64_t)C * F == 0 || (uint64_t)C * F >= 0xFFFFFFE0ull) return r;
+    if (pkt_stride < 8u || pkt_stride > kSrtpMaxStride || (pkt_stride & 3u)) return r;
+    r.grid = (uint32_t)(((uint64_t)C + kRtcpChans - 1u) / kRtcpChans);
+    r.threads = 64;
+    r.lds = kRtcpParseLdsBytes;
+    r.move = yardstick;
+    r.max_pieces = (pkt_stride + 63u) / 64u;
+    return r;
+}
+
 // ---- igdsp_tx_flush (launch_tx_staged): a wave owns kTsLegs staged legs (runs) of the flush; lanes 0 .. kTsLegs-1 decide, the
 // whole wave writes the packets.  No dynamic LDS: each wave's records (kTsLegs x IGDSP_STAGE_DEPTH) are static.
 constexpr int kTsWaves = 4;

@@ -337,16 +337,16 @@ inline void srtp_kdf(const uint32_t (&mrk)[44], const uint8_t salt[14], uint8_t 
     }
 }
 
-inline bool srtp_derive(const uint8_t key_salt[30], uint32_t tag_len, uint32_t roc0, igdsp_srtp_state &st)
+// the session keys of the labels label0, label0 + 1, label0 + 2 (k_e, k_a, k_s) into a zeroed state: k_e's key schedule, k_s, the two midstates
+inline void srtp_derive_keys(const uint8_t key_salt[30], uint8_t label0, igdsp_srtp_state &st)
 {
-    if (tag_len != 4u && tag_len != 10u) return false;
     std::memset(&st, 0, sizeof(st));
     uint32_t mrk[44];
     uint8_t ke[16], ka[20];
     srtp_aes_expand(key_salt, mrk);
-    srtp_kdf(mrk, key_salt + 16, 0, ke, 16);
-    srtp_kdf(mrk, key_salt + 16, 1, ka, 20);
-    srtp_kdf(mrk, key_salt + 16, 2, st.ks, 14);                            // ks[14], ks[15] stay 0
+    srtp_kdf(mrk, key_salt + 16, label0, ke, 16);
+    srtp_kdf(mrk, key_salt + 16, (uint8_t)(label0 + 1u), ka, 20);
+    srtp_kdf(mrk, key_salt + 16, (uint8_t)(label0 + 2u), st.ks, 14);        // ks[14], ks[15] stay 0
     srtp_aes_expand(ke, st.rk);
     for (int side = 0; side < 2; ++side) {
         uint8_t blk[64];
@@ -357,6 +357,12 @@ inline bool srtp_derive(const uint8_t key_salt[30], uint32_t tag_len, uint32_t r
         srtp_sha1(hs, w);
         std::memcpy(side ? st.mid_o : st.mid_i, hs, 20);
     }
+}
+
+inline bool srtp_derive(const uint8_t key_salt[30], uint32_t tag_len, uint32_t roc0, igdsp_srtp_state &st)
+{
+    if (tag_len != 4u && tag_len != 10u) return false;
+    srtp_derive_keys(key_salt, 0, st);
     st.tag = IGDSP_SRTP_TAG | tag_len;
     st.roc = roc0;
     return true;

@@ -1416,6 +1416,75 @@ int LegSrtp::unprotect(const uint8_t *in, uint32_t size, uint8_t *out, uint32_t 
     return (int)n;
 }
 
+// ---- RTCP on one leg, clear or under SRTCP, no context needed
+LegRtcp::LegRtcp(uint32_t ssrc_, const char *cname_, const uint8_t *key_salt, const uint8_t *peer_key_salt, uint32_t index0)
+    : secure(key_salt && peer_key_salt), ssrc(ssrc_), cnameLen(0)
+{
+    std::memset(cname, 0, sizeof(cname));
+    std::memset(&state, 0, sizeof(state));
+    std::memset(&tx, 0, sizeof(tx));                          // no tag word: NO_KEY
+    std::memset(&rx, 0, sizeof(rx));
+    std::memset(&lastBuilt, 0, sizeof(lastBuilt));
+    std::memset(&lastSeen, 0, sizeof(lastSeen));
+    std::memset(&lastSrtcp, 0, sizeof(lastSrtcp));
+    if (cname_) {
+        cnameLen = (uint32_t)std::strlen(cname_);
+        if (cnameLen > IGDSP_RTCP_CNAME_MAX) cnameLen = IGDSP_RTCP_CNAME_MAX;
+        std::memcpy(cname, cname_, cnameLen);
+    }
+    if (secure) secure = igdsp_srtcp_derive(key_salt, index0, &tx) == IGDSP_OK && igdsp_srtcp_derive(peer_key_salt, 0, &rx) == IGDSP_OK;
+}
+
+int LegRtcp::report(const igdsp_jb_state *jb, uint32_t rtp_ts, uint32_t packets, uint32_t octets, uint64_t now_ntp, bool bye, uint8_t *out, uint32_t out_capacity)
+{
+    if (!out) return IGDSP_EINVAL;
+    const igdsp_rtcp_src src = {ssrc, rtp_ts, packets, octets};
+    uint32_t n = 0;
+    if (igdsp_rtcp_build_packet(&state, bye ? IGDSP_RTCP_BYE : IGDSP_RTCP_REPORT, jb, &src, now_ntp, cname, cnameLen, out, out_capacity, &n, &lastBuilt) != IGDSP_OK)
+        return IGDSP_EINVAL;
+    if (secure && igdsp_srtcp_protect_packet(&tx, IGDSP_SRTP_RUN, out, n, out, out_capacity, &n, &lastSrtcp) != IGDSP_OK) return IGDSP_EINVAL;
+    return (int)n;
+}
+
+int LegRtcp::received(const uint8_t *in, uint32_t size, uint32_t arrival)
+{
+    if (!in) return IGDSP_EINVAL;
+    uint8_t clear[IGDSP_SRTP_MAX_PACKET];
+    if (secure) {
+        uint32_t n = 0;
+        if (igdsp_srtcp_unprotect_packet(&rx, IGDSP_SRTP_RUN, in, size, clear, sizeof(clear), &n, &lastSrtcp) != IGDSP_OK) return IGDSP_EINVAL;
+        if (!(lastSrtcp.flags & IGDSP_SRTP_OK)) return 0;
+        in = clear;
+        size = n;
+    }
+    if (igdsp_rtcp_parse_packet(&state, in, size, arrival, ssrc, &lastSeen) != IGDSP_OK) return IGDSP_EINVAL;
+    return (lastSeen.flags & IGDSP_RTCP_PARSED) ? 1 : 0;
+}
+
+void *igdsp_host_rtcp_new(uint32_t ssrc, const char *cname, const uint8_t *key_salt, const uint8_t *peer_key_salt, uint32_t index0)
+{
+    if ((key_salt == 0) != (peer_key_salt == 0)) return 0;
+    LegRtcp *e = new (std::nothrow) LegRtcp(ssrc, cname, key_salt, peer_key_salt, index0);
+    if (e && key_salt && !e->secure) { delete e; e = 0; }
+    return e;
+}
+void igdsp_host_rtcp_free(void *v) { delete static_cast<LegRtcp *>(v); }
+int igdsp_host_rtcp_report(void *v, const igdsp_jb_state *jb, uint32_t rtp_ts, uint32_t packets, uint32_t octets, uint64_t now_ntp, int bye, uint8_t *out,
+                           uint32_t out_capacity)
+{
+    return v ? static_cast<LegRtcp *>(v)->report(jb, rtp_ts, packets, octets, now_ntp, bye != 0, out, out_capacity) : IGDSP_EINVAL;
+}
+int igdsp_host_rtcp_received(void *v, const uint8_t *in, uint32_t size, uint32_t arrival)
+{
+    return v ? static_cast<LegRtcp *>(v)->received(in, size, arrival) : IGDSP_EINVAL;
+}
+int igdsp_host_rtcp_state(void *v, igdsp_rtcp_state *out)
+{
+    if (!v || !out) return IGDSP_EINVAL;
+    *out = static_cast<LegRtcp *>(v)->state;
+    return IGDSP_OK;
+}
+
 void *igdsp_host_srtp_new(const uint8_t *key_salt, uint32_t tag_len, uint32_t roc0)
 {
     LegSrtp *e = new (std::nothrow) LegSrtp(key_salt, tag_len, roc0);

@@ -441,6 +441,32 @@ private:
     bool resetNext;
 };
 
+// RTCP on one leg, without a context: one igdsp_rtcp_state through igdsp_rtcp_build_packet / igdsp_rtcp_parse_packet and, when a key is
+// given, two SRTCP states (ours to send, the peer's to receive) through igdsp_srtcp_protect_packet / igdsp_srtcp_unprotect_packet: what
+// pjmedia's rtcp session and transport_srtp keep per stream for transport_send_rtcp and transport_rtcp_cb.  igdsp_rtcp_build /
+// igdsp_rtcp_parse / igdsp_srtcp_protect / igdsp_srtcp_unprotect take the same states for thousands of legs.
+class LegRtcp {
+public:
+    // key_salt: our 30 bytes of master key and salt, peer_key_salt the far end's; both NULL: RTCP in the clear
+    LegRtcp(uint32_t ssrc, const char *cname, const uint8_t *key_salt = 0, const uint8_t *peer_key_salt = 0, uint32_t index0 = 0);
+    bool secure;
+    uint32_t ssrc;
+    uint8_t cname[IGDSP_RTCP_CNAME_MAX];
+    uint32_t cnameLen;
+    igdsp_rtcp_state state;
+    igdsp_srtp_state tx, rx;
+    igdsp_rtcp_built lastBuilt;              // the records of the last report sent and the last packet received
+    igdsp_rtcp_seen lastSeen;
+    igdsp_srtp_rec lastSrtcp;
+    // one report (SR when `packets` moved since the last one, else RR; with a BYE when bye) from the leg's jitter buffer state (or NULL)
+    // into out (at least IGDSP_RTCP_MAX_BUILT, secure: + IGDSP_SRTCP_TRAILER bytes): its size, or IGDSP_EINVAL
+    int report(const igdsp_jb_state *jb, uint32_t rtp_ts, uint32_t packets, uint32_t octets, uint64_t now_ntp, bool bye, uint8_t *out, uint32_t out_capacity);
+    // one packet from the RTCP port, arrival its time's middle 32 NTP bits: 1 parsed, 0 refused (lastSrtcp / lastSeen say why), IGDSP_EINVAL
+    int received(const uint8_t *in, uint32_t size, uint32_t arrival);
+    bool rttValid() const { return (state.flags & IGDSP_RTCP_RTT_VALID) != 0; }
+    uint32_t rtt() const { return state.rtt_last; }   // 1 / 65536 s
+};
+
 class RoIP_ED137 {
 public:
     // Unlike the reference singleton (roip_ed137.cpp:192) the instance owns an igdsp context; device < 0
@@ -634,6 +660,14 @@ void  igdsp_host_ns_reset(void *v);
 // SRTP on one leg and direction without a context (LegSrtp): NULL from _new for a NULL key or a tag_len that is not 4 or 10; _protect /
 // _unprotect one packet: the output's size, 0 for a refused packet, IGDSP_EINVAL for a NULL argument; _control sets IGDSP_SRTP_RUN or
 // _BYPASS (anything else IGDSP_EINVAL); _rec a copy of the last packet's record; _reset starts index and window over, the keys stay
+// RTCP on one leg without a context (LegRtcp): key_salt and peer_key_salt both NULL for RTCP in the clear (NULL from _new for one
+// alone); _report / _received as the class's; _state copies the igdsp_rtcp_state out
+void *igdsp_host_rtcp_new(uint32_t ssrc, const char *cname, const uint8_t *key_salt, const uint8_t *peer_key_salt, uint32_t index0);
+void  igdsp_host_rtcp_free(void *v);
+int   igdsp_host_rtcp_report(void *v, const igdsp_jb_state *jb, uint32_t rtp_ts, uint32_t packets, uint32_t octets, uint64_t now_ntp, int bye, uint8_t *out,
+                             uint32_t out_capacity);
+int   igdsp_host_rtcp_received(void *v, const uint8_t *in, uint32_t size, uint32_t arrival);
+int   igdsp_host_rtcp_state(void *v, igdsp_rtcp_state *out);
 void *igdsp_host_srtp_new(const uint8_t *key_salt, uint32_t tag_len, uint32_t roc0);
 void  igdsp_host_srtp_free(void *v);
 int   igdsp_host_srtp_control(void *v, uint32_t ctl);

@@ -2229,7 +2229,8 @@ int  igdsp_ns_run(igdsp_ctx *ctx, const uint8_t *d_g711 /* [F][C][n] */, const u
  * tests/golden/srtp_kat.json holds the standards' known answers.  The host entries (igdsp_srtp_*_packet) and the device entries run
  * the same code (csrc/igdsp_srtp.h; independent restatement: tests/srtp_model.py) and give the same bytes, records and states for any
  * split of the frames over launches and at any channel count and position.
- * SCOPE: AES_CM_128_HMAC_SHA1_80 and its _32 tag length, for RTP.  NOT built: SRTCP, MKI, a non-zero key derivation rate, AES-256, GCM,
+ * SCOPE: AES_CM_128_HMAC_SHA1_80 and its _32 tag length, for RTP (SRTCP: the section "RTCP / SRTCP" below).  NOT built: MKI, a non-zero
+ * key derivation rate, AES-256, GCM,
  * F8, the NULL cipher, and SDES / DTLS key exchange: the caller brings the 30 bytes of master key and salt that pjmedia keeps in
  * pjmedia_srtp_crypto.key.
  *
@@ -2310,6 +2311,142 @@ int  igdsp_srtp_unprotect(igdsp_ctx *ctx, const uint8_t *d_ctl /* [F][C], NULL: 
                           const uint16_t *d_sizes /* [F][C] */, uint32_t n_channels, uint32_t n_frames, uint32_t pkt_stride,
                           igdsp_srtp_state *d_state /* [C], in and out */, uint8_t *d_out /* [F][C][out_stride] */, uint32_t out_stride,
                           uint16_t *d_sizes_out /* [F][C] */, igdsp_srtp_rec *d_rec /* [F][C] */, void *stream);
+
+/* ---- RTCP / SRTCP: the reports of RFC 3550 per leg, clear and protected (RFC 3711 3.4) ------------------------------------------------------
+ * The other two per-packet slots of the pjmedia adapter: igdsp_rtcp_build -> igdsp_srtcp_protect stand in front of transport_send_rtcp /
+ * transport_send_rtcp2, igdsp_srtcp_unprotect -> igdsp_rtcp_parse behind transport_rtcp_cb.  The caller decides the ticks (the report
+ * interval's timing is not built).  The host entries (igdsp_rtcp_*_packet, igdsp_srtcp_*_packet) and the device entries run the same
+ * code (csrc/igdsp_rtcp.h; independent restatement: tests/rtcp_model.py) and give the same bytes, records and states for any split of
+ * the ticks over launches and at any leg count and position.
+ * Fidelity.  PINNED to RFC 3550 6.4, 6.5, 6.6, A.2, A.3 and RFC 3711 3.4, 4.3.1.  UNVERIFIED against pjmedia's rtcp.c and against libsrtp
+ * (neither is in this tree).  NOT built: XR, APP, feedback packets, reason text in BYE, more than one report block, the report
+ * interval's timing, MKI.
+ *
+ * BUILD, per leg, ticks in order.  d_ctl[f][c]: NONE (or any other value) builds nothing: size 0, the slot, the state untouched, the
+ * record's flags 0.  REPORT builds a compound packet, BYE the same with a BYE appended.
+ *   Packet type: SR (200) when src.packets != state.sent_prior, else RR (201) (RFC 3550 6.4).  Report count 1 when d_jb[c] has
+ *   IGDSP_JB_HEARD, else 0 (d_jb NULL: 0).  The block: the source's SSRC; fraction lost, 24-bit cumulative lost, extended highest seq
+ *   and jitter exactly what igdsp_jb_report returns for that state and state.prior (A.3, the epoch rule included); LSR = state.lsr and
+ *   DLSR = mid - state.lsr_arrival mod 2^32, mid = (d_now[f] >> 16) & 0xFFFFFFFF, both 0 without HAVE_SR.  state.prior advances only
+ *   when a block is written.  SR sender info: NTP msw, NTP lsw of d_now[f], src.rtp_ts, src.packets, src.octets.
+ *   SDES (202), one chunk: SSRC, item 1 (CNAME) of length L = min(d_cname_len[c], 64) and the text, then at least one null octet up to
+ *   a 4-byte boundary: 4 * ceil((7 + L) / 4) bytes.  d_cname and d_cname_len both NULL: L = 0.  With BYE: 0x81, 203, length 1, SSRC.
+ *   Byte 0 of every header is 0x80 | count, lengths are words minus one, every field big-endian, every SSRC of ours src.ssrc.  The
+ *   largest packet is 52 + 76 + 8 = IGDSP_RTCP_MAX_BUILT bytes.  After the packet: sent_prior = src.packets, n_built += 1.
+ *   Record, 8 bytes: size, flags (SR or RR, HAS_BLOCK, BYE_SENT).  Bytes of the slot past the size are never written.
+ * PARSE.  size 0: EMPTY.  d_arrival[f][c]: the arrival time's middle 32 NTP bits.  Every read is bounded by the packet's size and slot.
+ *   MALFORMED (RFC 3550 A.2, integer comparisons; the state unchanged except n_malformed): size < 8, size % 4 != 0, size > pkt_stride;
+ *   the first sub-packet without V = 2, P = 0 and PT 200 or 201; a sub-packet without V = 2 or whose 4 * (length + 1) bytes pass the
+ *   packet's end (the walk ends exactly at size); P on another sub-packet than the last; an SR shorter than 28 + 24 RC, an RR shorter
+ *   than 8 + 24 RC, a BYE shorter than 4 + 4 SC.
+ *   A valid packet: the record's sender SSRC is the first sub-packet's.  An SR gives lsr = (msw << 16) | (lsw >> 16), lsr_arrival =
+ *   arrival, HAVE_SR, and its counts go into the record (of several SRs the last).  In SR and RR the first block of the packet whose
+ *   source SSRC equals d_local_ssrc[c] gives peer_fraction_lost, peer_cum_lost (24 bits, sign-extended), peer_ext_seq, peer_jitter:
+ *   kept in the state (PEER_VALID) and the record.  With a non-zero LSR in that block rtt = arrival - LSR - DLSR mod 2^32, in units of
+ *   1 / 65536 s: below 2^31 it is stored as rtt_last, rtt_count += 1, RTT_VALID; otherwise the record gets RTT_NEGATIVE and nothing is
+ *   stored.  BYE sets BYE_SEEN.  SDES and every other type are stepped over by their length.  n_parsed += 1.
+ * igdsp_rtcp_state: 80 bytes per leg, shared by build and parse; all-zero is the reset state; nothing in it is used as an index.
+ *
+ * SRTCP (RFC 3711 3.4), AES_CM_128_HMAC_SHA1_80 and _32 (the RTCP tag is 10 bytes in both: RFC 3711 / RFC 4568).  The state is an
+ * igdsp_srtp_state from igdsp_srtcp_derive: key derivation labels 3 (k_e), 4 (k_a), 5 (k_s), the tag word IGDSP_SRTCP_TAG | 10.  A state
+ * of igdsp_srtp_derive handed to an SRTCP entry is NO_KEY, and the other way round: both fail closed.  `roc` holds the 31-bit SRTCP index:
+ * on protect the index the next packet carries (the packet takes it, then roc = (roc + 1) mod 2^31; index0 lets the caller start at 0,
+ * as the RFC says, or at 1, libsrtp's habit: UNVERIFIED); on unprotect the highest index accepted, with have_s_l and the 64-bit window
+ * as in SRTP.  s_l stays 0.
+ *   Packet: header (8) || AES-CM(bytes 8 .. size) || (E << 31 | index) || tag (10).  IV as in SRTP with the packet's SSRC (bytes 4..7)
+ *   and the index as the 48-bit index.  Tag: the first 10 bytes of HMAC-SHA1 over the packet and the index word.
+ *   PROTECT: V = 2, size >= 8, size % 4 == 0 and size + 14 <= the output slot, else MALFORMED; E = 1 always; size_out = size + 14;
+ *   size 0: EMPTY.  UNPROTECT: size >= 22 and (size - 14) % 4 == 0, else MALFORMED; then OLD / REPLAY against the window, then
+ *   AUTH_FAIL.  E = 0: authenticated and copied without decryption (IGDSP_SRTCP_CLEAR beside OK).  Indices are compared as plain 31-bit
+ *   numbers: a wrap of the received index is not handled (2^31 reports).
+ *   Records are igdsp_srtp_rec with roc_used = the index word; flags, RUN / BYPASS / RESET, in place, a refused packet's slot never
+ *   written, the counters and the argument rules are SRTP's (strides multiples of 4, 12..2048).
+ *
+ * ARGUMENTS of igdsp_rtcp_build: d_ctl, d_src, d_now, d_state, d_packets, d_sizes required; d_jb, d_rec optional; d_cname and
+ * d_cname_len both or neither.  pkt_stride a multiple of 4, IGDSP_RTCP_MAX_BUILT..2048.  d_packets 4-byte, d_sizes 2-byte, d_now, d_rec 8-byte, d_jb, d_src,
+ * d_cname (rows of 64 bytes), d_state 16-byte aligned.  Of igdsp_rtcp_parse: d_packets, d_sizes, d_arrival,
+ * d_local_ssrc, d_state required, d_rec optional (32-byte records, 16-byte aligned); pkt_stride a multiple of 4, 8..2048.  No output may
+ * overlap an input or another output.  n_channels * n_frames < 2^32 - 32 (IGDSP_ERANGE).  Enqueued on `stream`.
+ * Host only, no GPU: igdsp_srtcp_derive, igdsp_srtcp_protect_packet / igdsp_srtcp_unprotect_packet (in == out allowed),
+ * igdsp_rtcp_build_packet (out_capacity >= IGDSP_RTCP_MAX_BUILT, else IGDSP_EINVAL) / igdsp_rtcp_parse_packet: one packet by the same rule. */
+#define IGDSP_RTCP_MAX_BUILT  136
+#define IGDSP_RTCP_CNAME_MAX  64
+#define IGDSP_RTCP_NONE       0           /* d_ctl of igdsp_rtcp_build                                */
+#define IGDSP_RTCP_REPORT     1
+#define IGDSP_RTCP_BYE        2
+#define IGDSP_RTCP_SR         0x01        /* igdsp_rtcp_built.flags                                   */
+#define IGDSP_RTCP_RR         0x02
+#define IGDSP_RTCP_HAS_BLOCK  0x04
+#define IGDSP_RTCP_BYE_SENT   0x08
+#define IGDSP_RTCP_HAVE_SR    0x01        /* igdsp_rtcp_state.flags                                   */
+#define IGDSP_RTCP_PEER_VALID 0x02
+#define IGDSP_RTCP_RTT_VALID  0x04
+#define IGDSP_RTCP_BYE_SEEN   0x08
+#define IGDSP_RTCP_PARSED       0x01      /* igdsp_rtcp_seen.flags: PARSED, MALFORMED, EMPTY exclude each other; the rest come with PARSED */
+#define IGDSP_RTCP_MALFORMED    0x02
+#define IGDSP_RTCP_EMPTY        0x04
+#define IGDSP_RTCP_GOT_SR       0x08
+#define IGDSP_RTCP_GOT_BLOCK    0x10
+#define IGDSP_RTCP_GOT_RTT      0x20
+#define IGDSP_RTCP_RTT_NEGATIVE 0x40
+#define IGDSP_RTCP_GOT_BYE      0x80
+typedef struct igdsp_rtcp_src {     /* the local sender as of a tick */
+    uint32_t ssrc, rtp_ts, packets, octets;
+} igdsp_rtcp_src;                   /* 16 bytes */
+typedef struct igdsp_rtcp_state {   /* per leg, ALL-ZERO = reset */
+    igdsp_jb_prior prior;           /* what igdsp_jb_report keeps between two reports: advances when a block is written */
+    uint32_t sent_prior;            /* src.packets at the last packet built                      */
+    uint32_t n_built;
+    uint32_t lsr, lsr_arrival;      /* the last SR heard: its NTP time's middle 32 bits, and ours when it came */
+    uint32_t flags;                 /* IGDSP_RTCP_HAVE_SR | PEER_VALID | RTT_VALID | BYE_SEEN     */
+    uint32_t n_parsed, n_malformed;
+    uint32_t rtt_last, rtt_count;   /* 1 / 65536 s                                               */
+    uint32_t peer_fraction_lost;    /* what the far end reports about our stream                 */
+    int32_t  peer_cum_lost;
+    uint32_t peer_ext_seq, peer_jitter;
+    uint32_t reserved[3];
+} igdsp_rtcp_state;                 /* 80 bytes */
+typedef struct igdsp_rtcp_built {
+    uint16_t size;
+    uint8_t  flags, reserved;
+    uint32_t reserved2;
+} igdsp_rtcp_built;                 /* 8 bytes */
+typedef struct igdsp_rtcp_seen {
+    uint8_t  flags, n_sub, peer_fraction_lost, reserved;
+    uint32_t sender_ssrc;
+    uint32_t rtt;                   /* as computed, with GOT_RTT or RTT_NEGATIVE; else 0         */
+    int32_t  peer_cum_lost;
+    uint32_t peer_ext_seq, peer_jitter;
+    uint32_t sr_packets, sr_octets; /* with GOT_SR                                               */
+} igdsp_rtcp_seen;                  /* 32 bytes */
+#define IGDSP_SRTCP_TAG       0x53524300u /* igdsp_srtp_state.tag of an SRTCP state, | 10             */
+#define IGDSP_SRTCP_TRAILER   14          /* the index word and the tag                               */
+#define IGDSP_SRTCP_CLEAR     IGDSP_SRTP_ROLLED /* igdsp_srtp_rec.flags, with OK: E was 0, nothing decrypted */
+int  igdsp_rtcp_build_packet(igdsp_rtcp_state *st, uint32_t ctl, const igdsp_jb_state *jb /* or NULL */, const igdsp_rtcp_src *src, uint64_t now,
+                             const uint8_t *cname /* or NULL */, uint32_t cname_len, uint8_t *out, uint32_t out_capacity, uint32_t *size_out,
+                             igdsp_rtcp_built *rec /* or NULL */);
+int  igdsp_rtcp_parse_packet(igdsp_rtcp_state *st, const uint8_t *in, uint32_t size, uint32_t arrival, uint32_t local_ssrc, igdsp_rtcp_seen *rec /* or NULL */);
+int  igdsp_srtcp_derive(const uint8_t key_salt[30], uint32_t index0, igdsp_srtp_state *out);
+int  igdsp_srtcp_protect_packet(igdsp_srtp_state *st, uint32_t ctl, const uint8_t *in, uint32_t size, uint8_t *out, uint32_t out_capacity,
+                                uint32_t *size_out, igdsp_srtp_rec *rec);
+int  igdsp_srtcp_unprotect_packet(igdsp_srtp_state *st, uint32_t ctl, const uint8_t *in, uint32_t size, uint8_t *out, uint32_t out_capacity,
+                                  uint32_t *size_out, igdsp_srtp_rec *rec);
+int  igdsp_rtcp_build(igdsp_ctx *ctx, const uint8_t *d_ctl /* [F][C] */, const igdsp_jb_state *d_jb /* [C], read only, or NULL */,
+                      const igdsp_rtcp_src *d_src /* [F][C] */, const uint64_t *d_now /* [F] */, const uint8_t *d_cname /* [C][64] or NULL */,
+                      const uint8_t *d_cname_len /* [C] or NULL */, uint32_t n_channels, uint32_t n_frames, igdsp_rtcp_state *d_state /* [C], in and out */,
+                      uint8_t *d_packets /* [F][C][pkt_stride] */, uint32_t pkt_stride, uint16_t *d_sizes /* [F][C] */, igdsp_rtcp_built *d_rec /* [F][C] or NULL */,
+                      void *stream);
+int  igdsp_rtcp_parse(igdsp_ctx *ctx, const uint8_t *d_packets /* [F][C][pkt_stride] */, const uint16_t *d_sizes /* [F][C] */,
+                      const uint32_t *d_arrival /* [F][C] */, const uint32_t *d_local_ssrc /* [C] */, uint32_t n_channels, uint32_t n_frames,
+                      uint32_t pkt_stride, igdsp_rtcp_state *d_state /* [C], in and out */, igdsp_rtcp_seen *d_rec /* [F][C] or NULL */, void *stream);
+int  igdsp_srtcp_protect(igdsp_ctx *ctx, const uint8_t *d_ctl /* [F][C], NULL: RUN */, const uint8_t *d_packets /* [F][C][pkt_stride] */,
+                         const uint16_t *d_sizes /* [F][C] */, uint32_t n_channels, uint32_t n_frames, uint32_t pkt_stride,
+                         igdsp_srtp_state *d_state /* [C], in and out */, uint8_t *d_out /* [F][C][out_stride] */, uint32_t out_stride,
+                         uint16_t *d_sizes_out /* [F][C] */, igdsp_srtp_rec *d_rec /* [F][C] */, void *stream);
+int  igdsp_srtcp_unprotect(igdsp_ctx *ctx, const uint8_t *d_ctl /* [F][C], NULL: RUN */, const uint8_t *d_packets /* [F][C][pkt_stride] */,
+                           const uint16_t *d_sizes /* [F][C] */, uint32_t n_channels, uint32_t n_frames, uint32_t pkt_stride,
+                           igdsp_srtp_state *d_state /* [C], in and out */, uint8_t *d_out /* [F][C][out_stride] */, uint32_t out_stride,
+                           uint16_t *d_sizes_out /* [F][C] */, igdsp_srtp_rec *d_rec /* [F][C] */, void *stream);
 
 /* ---- synthetic input generators (device side; SURVEY 8(d) definitions) ---------
  * D-uniform: byte k of global byte index g is
