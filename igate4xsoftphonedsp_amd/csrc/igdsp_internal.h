@@ -156,10 +156,21 @@ hipError_t launch_dbuf_run(const LaunchCfg &cfg, const uint8_t *ops, const int16
 hipError_t launch_spectrum(const LaunchCfg &cfg, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm, uint32_t C, uint32_t F, uint32_t n,
                            uint32_t hop_frames, float alpha, igdsp_spec_state *state, igdsp_spec_rec *rec, float *avg, float *raw, bool yardstick,
                            hipStream_t s);
-// the link stage's scan (igdsp_k_link.hip), which igdsp_tone_detect's list launches as well: counts[0 .. N) behind the 16-byte head of
+// the link stage's scan (igdsp_k_link.hip), which launch_event_list launches as well: counts[0 .. N) behind the 16-byte head of
 // `head` -> exclusive offsets in place; first: start at 0, else at head[0]; last: event_count = {total, min(total, cap)}.  One block of
 // kLinkScanThreads
 __global__ void k_link_scan(uint32_t *head, uint64_t N, uint32_t first, uint32_t last, uint32_t cap, uint32_t *event_count);
+// The event list behind a stage's dense records (ListRoute; igdsp_tone_detect, igdsp_vad_run), called behind the stage's own kernel;
+// event_count nullptr = no list.  pass<false> / pass<true>: the stage's list kernel (event_list_pass, igdsp_lanes.h).  empty: the
+// stage launched nothing (C * F == 0) and only the two counts are written (0).  list_records: where the stage's kernel writes the
+// records the list reads when the caller gave no d_rec: d_work, behind the counts.  (Defined in igdsp_k_link.hip for the two stages.)
+template <class Rec>
+inline Rec *list_records(Rec *rec, bool list, void *work, const ListRoute &r) { return list && !rec ? reinterpret_cast<Rec *>(static_cast<uint8_t *>(work) + r.counts_bytes) : rec; }
+template <class Rec, class Event>
+using ListPass = void (*)(const Rec *rec, uint32_t C, uint32_t F, uint32_t W, uint32_t mask, uint32_t *counts, Event *events, uint32_t cap);
+template <class Rec, class Event>
+hipError_t launch_event_list(ListPass<Rec, Event> count, ListPass<Rec, Event> store, const ListRoute &r, bool empty, const Rec *rec, uint32_t C,
+                             uint32_t F, uint32_t mask, Event *events, uint32_t event_cap, uint32_t *event_count, void *work, hipStream_t s);
 // igdsp_tone_detect: exactly one of g711 (with codec) and pcm; plan_of, rec, events may each be nullptr; event_count nullptr = no list
 // (work unused), else work is igdsp_tdet_work_bytes bytes, 16-byte aligned; event_mask 0 = IGDSP_TDET_EVENT_DEFAULT.  C * F == 0 with a
 // list: only the two counts are written (0).  yardstick: the compute-free form, the same rows into the same buffers, the same records,

@@ -17,9 +17,9 @@
 // The next frame's row is loaded before this one's arithmetic.  A bypassed channel runs the same instructions and selects the row.
 // COPY (the compute-free yardstick, tools/agc_bench.py): the same row loads, decode, state load and store, row, record and PCM-record
 // stores and their reductions; no block peak, division, recurrence or gain; d_ctl is not read.
+// The DPP steps, the pack and the G.711 magnitude and sign are igdsp_lanes.h's.
 // Everything is written with vector stores in plain C++: a block of the row, the record and the state as 16 bytes each.
-#include "igdsp_device.h"
-#include "igdsp_pcmrec.h"
+#include "igdsp_lanes.h"
 #include "igdsp_agc.h"
 
 namespace igdsp {
@@ -36,16 +36,14 @@ struct AgcArgs {
     igdsp_frame_stats *stats;
 };
 
-template <int CTRL>
-__device__ __forceinline__ uint32_t agc_dpp(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, false); }
 // op over the 32 lanes of a half, in each of them: row_ror 8, 4, 2, 1 inside a row of 16, then the other row of the half
 template <typename Op>
 __device__ __forceinline__ uint32_t agc_half_all(uint32_t v, Op op)
 {
-    v = op(v, agc_dpp<0x128>(v));
-    v = op(v, agc_dpp<0x124>(v));
-    v = op(v, agc_dpp<0x122>(v));
-    v = op(v, agc_dpp<0x121>(v));
+    v = op(v, dpp<0x128>(v));
+    v = op(v, dpp<0x124>(v));
+    v = op(v, dpp<0x122>(v));
+    v = op(v, dpp<0x121>(v));
     return op(v, (uint32_t)__shfl_xor((int)v, 16, 64));
 }
 struct OpMin { __device__ __forceinline__ uint32_t operator()(uint32_t a, uint32_t b) const { return min(a, b); } };
@@ -53,7 +51,6 @@ __device__ __forceinline__ uint64_t agc_half_sum64(uint64_t v)             // ex
 {
     return (uint64_t)agc_half_all((uint32_t)v & 0xFFFFFFu, OpAdd{}) + ((uint64_t)agc_half_all((uint32_t)(v >> 24), OpAdd{}) << 24);
 }
-__device__ __forceinline__ uint32_t agc_pack(int32_t lo, int32_t hi) { return ((uint32_t)lo & 0xFFFFu) | ((uint32_t)hi << 16); }
 
 // block `blk` of row o as it lies in memory: 16 bytes of PCM, or 8 bytes of codes in .x, .y
 template <bool G711>
@@ -77,8 +74,8 @@ __device__ __forceinline__ void agc_samples(const uint4 v, bool alaw, bool busy,
 #pragma unroll
         for (uint32_t i = 0; i < 8u; ++i) {
             const uint32_t code = ((i < 4u ? v.x : v.y) >> (8u * (i & 3u))) & 0xFFu;
-            const int32_t m = busy ? (int32_t)(alaw ? alaw_abs(code) : ulaw_abs(code)) : 0;      // no code of either law decodes to an idle lane's zero
-            x[i] = (code & 0x80u) ? m : -m;
+            const int32_t m = busy ? (int32_t)g711_abs(code, alaw) : 0;                          // no code of either law decodes to an idle lane's zero
+            x[i] = g711_signed(code, m);
         }
     } else {
         const uint32_t w[4] = {v.x, v.y, v.z, v.w};
@@ -165,7 +162,7 @@ __global__ __launch_bounds__(kAgcWaves * 64, kAgcWaves * kAgcResident / 4) void 
                     e1 = agc_out(e1, agc_gain_at(Tl, Tr, 2u * i + 1u));
                 }
             }
-            ow[i] = agc_pack(e0, e1);
+            ow[i] = pack2(e0, e1);
             pcm_acc2(ow[i], sq, pko);
         }
         if (a.out && chan && busy) reinterpret_cast<uint4 *>(a.out + (uint64_t)o * n)[b] = make_uint4(ow[0], ow[1], ow[2], ow[3]);

@@ -19,9 +19,10 @@
 // COPY (the compute-free yardstick, tools/cng_bench.py): every channel as under BYPASS, so the same kind, length, voice-row loads and
 // decode, tile stores and reads, state load and store and output stores; a row that is not voice is written to the tile by its lane as
 // zeros (the LDS traffic of a generated row); no excitation, lattice, gain step or SID step; d_ctl and the payloads are not read.
+// The tile's addressing (tile_item, tile_piece) and the G.711 piece (g711_decode8) are igdsp_lanes.h's.
 // Everything is written with vector stores in plain C++.
 #include "igdsp_cng.h"
-#include "igdsp_device.h"
+#include "igdsp_lanes.h"
 
 namespace igdsp {
 
@@ -43,24 +44,11 @@ struct CngArgs {
 constexpr uint32_t kCngRowZero = 0, kCngRowVoice = 1, kCngRowLane = 2;    // who fills a row of the tile (bits 0..1 of its byte)
 constexpr uint32_t kCngRowAlaw = 4;                                       // and its law, for the wave that decodes it
 
-// eight codes (two dwords) as eight int16 in four dwords, decoded as igdsp_decode_meter decodes: a code is negative iff its bit 7 is clear
-__device__ __forceinline__ uint4 cng_decode(uint32_t lo, uint32_t hi, bool alaw)
-{
-    uint32_t w[4];
-#pragma unroll
-    for (uint32_t i = 0; i < 4u; ++i) {
-        const uint32_t d = i < 2u ? lo : hi, c0 = (d >> (16u * (i & 1u))) & 0xFFu, c1 = (d >> (16u * (i & 1u) + 8u)) & 0xFFu;
-        const int32_t m0 = (int32_t)(alaw ? alaw_abs(c0) : ulaw_abs(c0)), m1 = (int32_t)(alaw ? alaw_abs(c1) : ulaw_abs(c1));
-        w[i] = ((uint32_t)((c0 & 0x80u) ? m0 : -m0) & 0xFFFFu) | ((uint32_t)((c1 & 0x80u) ? m1 : -m1) << 16);
-    }
-    return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
 template <int IN, bool COPY>
 __global__ __launch_bounds__(64) void k_cng(const CngArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t cng_lds[];
-    const uint32_t lane = threadIdx.x, n = a.n, P = n >> 3, stride = cng_row_dwords(n);
+    const uint32_t lane = threadIdx.x, n = a.n, P = n >> 3, stride = tile_row_dwords(n);
     uint32_t *tile = cng_lds;                                              // [kCngChans][stride]
     uint8_t *who = reinterpret_cast<uint8_t *>(cng_lds + kCngChans * stride);   // [kCngChans]
     const uint64_t c0 = (uint64_t)blockIdx.x * kCngChans;                  // < C: the grid
@@ -129,8 +117,8 @@ __global__ __launch_bounds__(64) void k_cng(const CngArgs a)
                 uint32_t wh[kCngBatch];
 #pragma unroll
                 for (uint32_t u = 0; u < kCngBatch; ++u) {
-                    const uint32_t i = (it0 + u) * 64u + lane, rw = (i * a.inv) >> 20;    // i < 2^12: the product fits
-                    wh[u] = i < items ? who[rw] : (uint32_t)kCngRowZero;   // items <= 64 passes: a turn past the last holds no item
+                    const uint32_t i = (it0 + u) * 64u + lane;
+                    wh[u] = i < items ? who[tile_item(i, a.inv, P).row] : (uint32_t)kCngRowZero;   // items <= 64 passes: a turn past the last holds no item
                     v[u] = make_uint4(0u, 0u, 0u, 0u);
                     if ((wh[u] & 3u) == kCngRowVoice) {
                         if constexpr (IN == kCngG711) {
@@ -143,10 +131,10 @@ __global__ __launch_bounds__(64) void k_cng(const CngArgs a)
                 }
 #pragma unroll
                 for (uint32_t u = 0; u < kCngBatch; ++u) {
-                    const uint32_t i = (it0 + u) * 64u + lane, rw = (i * a.inv) >> 20, pc = i - rw * P;
+                    const uint32_t i = (it0 + u) * 64u + lane;
                     if ((wh[u] & 3u) == kCngRowVoice) {
-                        const uint4 x = IN == kCngG711 ? cng_decode(v[u].x, v[u].y, (wh[u] & kCngRowAlaw) != 0u) : v[u];
-                        uint32_t *d = tile + rw * stride + 4u * pc;
+                        const uint4 x = IN == kCngG711 ? g711_decode8(v[u].x, v[u].y, (wh[u] & kCngRowAlaw) != 0u) : v[u];
+                        uint32_t *d = tile_piece(tile, stride, tile_item(i, a.inv, P));
                         d[0] = x.x; d[1] = x.y; d[2] = x.z; d[3] = x.w;
                     }
                 }
@@ -176,11 +164,12 @@ __global__ __launch_bounds__(64) void k_cng(const CngArgs a)
         {
             uint4 *dst = reinterpret_cast<uint4 *>(a.out + t0 * n);       // d_out 16-byte aligned, n a multiple of 8: the argument rule
             for (uint32_t it = 0; it < a.passes; ++it) {
-                const uint32_t i = it * 64u + lane, rw = (i * a.inv) >> 20, pc = i - rw * P;
+                const uint32_t i = it * 64u + lane;
+                const TileItem t = tile_item(i, a.inv, P);
                 if (i < items) {
                     uint4 v = make_uint4(0u, 0u, 0u, 0u);
-                    if ((who[rw] & 3u) != kCngRowZero) {
-                        const uint32_t *s = tile + rw * stride + 4u * pc;
+                    if ((who[t.row] & 3u) != kCngRowZero) {
+                        const uint32_t *s = tile_piece(tile, stride, t);
                         v = make_uint4(s[0], s[1], s[2], s[3]);
                     }
                     dst[i] = v;

@@ -20,9 +20,9 @@
 // A wave whose four channels are all bypassed (or COPY) skips the block loop: the output is the near row as it lies in nr.
 // COPY (the compute-free yardstick, tools/ec_bench.py): every channel as IGDSP_EC_BYPASS, d_ctl not read: the same row loads, buffer
 // stores, history moves, records, row and state stores; no window read, dot product, reduction or update.
+// The row's reductions, the packed dot product, the pack and the G.711 pair are igdsp_lanes.h's.
 // Everything is written with vector stores: rows as dwords of a lane's two samples, the weights and the record as 16 bytes.
-#include "igdsp_device.h"
-#include "igdsp_pcmrec.h"
+#include "igdsp_lanes.h"
 #include "igdsp_ec.h"
 
 namespace igdsp {
@@ -46,43 +46,15 @@ struct EcLds {
 };
 static_assert(sizeof(EcLds) == kEcLdsBytes, "ec_route's LDS");
 
-template <int CTRL>
-__device__ __forceinline__ uint32_t ec_dpp(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, false); }
-// the sum / the maximum over the 16 lanes of a row, in each of them (row_ror 8, 4, 2, 1)
-__device__ __forceinline__ uint32_t ec_row_sum(uint32_t v)
-{
-    v += ec_dpp<0x128>(v);
-    v += ec_dpp<0x124>(v);
-    v += ec_dpp<0x122>(v);
-    return v + ec_dpp<0x121>(v);
-}
-__device__ __forceinline__ uint32_t ec_row_max(uint32_t v)
-{
-    v = max(v, ec_dpp<0x128>(v));
-    v = max(v, ec_dpp<0x124>(v));
-    v = max(v, ec_dpp<0x122>(v));
-    return max(v, ec_dpp<0x121>(v));
-}
-__device__ __forceinline__ uint64_t ec_row_sum64(uint64_t v)              // exact while the row's total is below 2^56
-{
-    return (uint64_t)ec_row_sum((uint32_t)v & 0xFFFFFFu) + ((uint64_t)ec_row_sum((uint32_t)(v >> 24)) << 24);
-}
-__device__ __forceinline__ uint32_t ec_dot2(uint32_t x, uint32_t w, uint32_t acc)
-{
-    return (uint32_t)__builtin_amdgcn_sdot2(__builtin_bit_cast(v2i16, x), __builtin_bit_cast(v2i16, w), (int)acc, false);
-}
-__device__ __forceinline__ uint32_t ec_pack(int32_t lo, int32_t hi) { return ((uint32_t)lo & 0xFFFFu) | ((uint32_t)hi << 16); }
 // two near samples as they lie in memory (two codes, or two PCM samples) -> two int16
 template <bool G711>
 __device__ __forceinline__ uint32_t ec_near_unit(uint32_t u, bool alaw)
 {
     if constexpr (!G711) return u;
-    const uint32_t c0 = u & 0xFFu, c1 = (u >> 8) & 0xFFu;
-    const int32_t m0 = (int32_t)(alaw ? alaw_abs(c0) : ulaw_abs(c0)), m1 = (int32_t)(alaw ? alaw_abs(c1) : ulaw_abs(c1));
-    return ec_pack((c0 & 0x80u) ? m0 : -m0, (c1 & 0x80u) ? m1 : -m1);
+    return g711_pair(u, alaw);
 }
-__device__ __forceinline__ uint32_t ec_far_unit(uint32_t u) { return ec_pack(ec_xs((int16_t)(u & 0xFFFFu)), ec_xs((int16_t)(u >> 16))); }
-__device__ __forceinline__ uint32_t ec_hist_unit(uint32_t u) { return ec_pack(ec_hist((int16_t)(u & 0xFFFFu)), ec_hist((int16_t)(u >> 16))); }
+__device__ __forceinline__ uint32_t ec_far_unit(uint32_t u) { return pack2(ec_xs((int16_t)(u & 0xFFFFu)), ec_xs((int16_t)(u >> 16))); }
+__device__ __forceinline__ uint32_t ec_hist_unit(uint32_t u) { return pack2(ec_hist((int16_t)(u & 0xFFFFu)), ec_hist((int16_t)(u >> 16))); }
 
 // units k, k + 16, .. of row o: near (codes: 2-byte units, PCM: dwords) and far (row fo; far absent: zeros)
 template <bool G711>
@@ -135,7 +107,7 @@ __global__ __launch_bounds__(kEcWaves * 64, kEcWaves * kEcResident / 4) void k_e
         w[4u * q + 2u] = keep ? (int32_t)v.z : 0; w[4u * q + 3u] = keep ? (int32_t)v.w : 0;
     }
 #pragma unroll
-    for (uint32_t m = 0; m < T / 2u; ++m) wp[m] = ec_pack(ec_wh(w[2u * m + 1u]), ec_wh(w[2u * m]));
+    for (uint32_t m = 0; m < T / 2u; ++m) wp[m] = pack2(ec_wh(w[2u * m + 1u]), ec_wh(w[2u * m]));
     if (k < kEcPad / 2u) {                                                 // the pads: read only into masked positions; zero all the same
         x32[k] = 0u;
         x32[(kEcXBuf - kEcPad) / 2u + k] = 0u;
@@ -164,7 +136,7 @@ __global__ __launch_bounds__(kEcWaves * 64, kEcWaves * kEcResident / 4) void k_e
             const uint32_t m = k + 16u * q;
             if (m < h) {
                 const uint32_t u = ec_near_unit<G711>(cn[q], alaw);
-                sq_near += ec_dot2(u, u, 0u);
+                sq_near += dot2(u, u, 0u);
                 n32[kEcPad / 2u + m] = u;
                 x32[(kEcPad + (uint32_t)L) / 2u + m] = ec_far_unit(cf[q]);
             }
@@ -194,16 +166,16 @@ __global__ __launch_bounds__(kEcWaves * 64, kEcWaves * kEcResident / 4) void k_e
                     acc[j] = 0u;
 #pragma unroll
                     for (uint32_t m = 0; m < T / 2u; ++m)
-                        acc[j] = (j & 1u) ? ec_dot2(D[(T + j - 2u * m - 1u) / 2u], wp[m], acc[j]) : ec_dot2(O[(T + j - 2u * m - 2u) / 2u], wp[m], acc[j]);
+                        acc[j] = (j & 1u) ? dot2(D[(T + j - 2u * m - 1u) / 2u], wp[m], acc[j]) : dot2(O[(T + j - 2u * m - 2u) / 2u], wp[m], acc[j]);
                 }
                 // the batched row reduction, the outputs, dmax
                 int32_t e[8];
                 uint32_t dmax = 0u;
 #pragma unroll
                 for (uint32_t i = 0; i < 4u; ++i) {
-                    const uint32_t ls = ec_row_sum((acc[2u * i] & 0xFFFu) | (acc[2u * i + 1u] & 0xFFFu) << 16);
-                    const int32_t hs0 = (int32_t)ec_row_sum((uint32_t)((int32_t)acc[2u * i] >> 12));
-                    const int32_t hs1 = (int32_t)ec_row_sum((uint32_t)((int32_t)acc[2u * i + 1u] >> 12));
+                    const uint32_t ls = row16_sum((acc[2u * i] & 0xFFFu) | (acc[2u * i + 1u] & 0xFFFu) << 16);
+                    const int32_t hs0 = (int32_t)row16_sum((uint32_t)((int32_t)acc[2u * i] >> 12));
+                    const int32_t hs1 = (int32_t)row16_sum((uint32_t)((int32_t)acc[2u * i + 1u] >> 12));
                     const int32_t y0 = ec_clamp16(2 * hs0 + (int32_t)(((ls & 0xFFFFu) + 1024u) >> 11));    // (4096 hs + ls + 1024) >> 11
                     const int32_t y1 = ec_clamp16(2 * hs1 + (int32_t)(((ls >> 16) + 1024u) >> 11));
                     const int32_t d0 = (int16_t)(nr4[i] & 0xFFFFu), d1 = (int16_t)(nr4[i] >> 16);
@@ -221,11 +193,11 @@ __global__ __launch_bounds__(kEcWaves * 64, kEcWaves * kEcResident / 4) void k_e
                     pk = __builtin_elementwise_max(pk, __builtin_bit_cast(v2u16_t, __builtin_elementwise_max(xv, __builtin_bit_cast(v2i16, neg))));
                 };
 #pragma unroll
-                for (uint32_t i = 4u; i < ND; ++i) { ps = ec_dot2(D[i], D[i], ps); fold(D[i]); }
+                for (uint32_t i = 4u; i < ND; ++i) { ps = dot2(D[i], D[i], ps); fold(D[i]); }
 #pragma unroll
                 for (uint32_t i = 0; i < 4u; ++i) if (k == 15u && 2u * i >= j0) fold(D[i]);
-                const uint64_t P = ec_row_sum64(ps);
-                const uint32_t xm = ec_row_max(max((uint32_t)pk.x, (uint32_t)pk.y));
+                const uint64_t P = row16_sum64(ps);
+                const uint32_t xm = row16_max(max((uint32_t)pk.x, (uint32_t)pk.y));
                 if (!bypass) {
                     hang = ec_hang(hang, xm, dmax, a.hang, a.dmin);
                     if (hang > 0u) { ++n_dt; flags |= IGDSP_EC_DOUBLETALK; }
@@ -235,7 +207,7 @@ __global__ __launch_bounds__(kEcWaves * 64, kEcWaves * kEcResident / 4) void k_e
                 if (__builtin_amdgcn_ballot_w64(adapt) != 0u) {            // wave-uniform: one of the wave's four channels adapts
                     uint32_t ep[4];
 #pragma unroll
-                    for (uint32_t i = 0; i < 4u; ++i) ep[i] = 2u * i >= j0 ? ec_pack(ec_es(e[2u * i]), ec_es(e[2u * i + 1u])) : 0u;
+                    for (uint32_t i = 0; i < 4u; ++i) ep[i] = 2u * i >= j0 ? pack2(ec_es(e[2u * i]), ec_es(e[2u * i + 1u])) : 0u;
                     const int32_t sh = 31 - (int32_t)a.mu_shift - ec_bit_length(P);
                     bool sat = false;
 #pragma unroll
@@ -243,12 +215,12 @@ __global__ __launch_bounds__(kEcWaves * 64, kEcWaves * kEcResident / 4) void k_e
                         uint32_t g = 0u;
 #pragma unroll
                         for (uint32_t i = 0; i < 4u; ++i)
-                            g = (u & 1u) ? ec_dot2(O[(T + 2u * i - u - 1u) / 2u], ep[i], g) : ec_dot2(D[(T + 2u * i - u) / 2u], ep[i], g);
+                            g = (u & 1u) ? dot2(O[(T + 2u * i - u - 1u) / 2u], ep[i], g) : dot2(D[(T + 2u * i - u) / 2u], ep[i], g);
                         const int32_t nw32 = ec_update(w[u], (int32_t)g, sh, sat);
                         w[u] = adapt ? nw32 : w[u];
                     }
 #pragma unroll
-                    for (uint32_t m = 0; m < T / 2u; ++m) wp[m] = ec_pack(ec_wh(w[2u * m + 1u]), ec_wh(w[2u * m]));
+                    for (uint32_t m = 0; m < T / 2u; ++m) wp[m] = pack2(ec_wh(w[2u * m + 1u]), ec_wh(w[2u * m]));
                     const uint64_t sb = __builtin_amdgcn_ballot_w64(sat && adapt);     // a lane clipped one of its taps: the row's 16 bits
                     if (adapt) {
                         ++n_adapt;
@@ -258,7 +230,7 @@ __global__ __launch_bounds__(kEcWaves * 64, kEcWaves * kEcResident / 4) void k_e
                 }
                 // the outputs over the near samples, in place: lane i < 4 stores pair i of the block
                 {
-                    const uint32_t p0 = ec_pack(e[0], e[1]), p1 = ec_pack(e[2], e[3]), p2 = ec_pack(e[4], e[5]), p3 = ec_pack(e[6], e[7]);
+                    const uint32_t p0 = pack2(e[0], e[1]), p1 = pack2(e[2], e[3]), p2 = pack2(e[4], e[5]), p3 = pack2(e[6], e[7]);
                     const uint32_t mine = k == 0u ? p0 : (k == 1u ? p1 : (k == 2u ? p2 : p3));
                     if (k < 4u && 2u * k >= j0) n32[(kEcPad + E - 8u) / 2u + k] = mine;
                 }
@@ -270,7 +242,7 @@ __global__ __launch_bounds__(kEcWaves * 64, kEcWaves * kEcResident / 4) void k_e
         uint32_t wm = 0u;
 #pragma unroll
         for (uint32_t u = 0; u < T; ++u) { const int32_t v = ec_wh(w[u]); wm = max(wm, (uint32_t)(v < 0 ? -v : v)); }
-        wm = ec_row_max(wm);
+        wm = row16_max(wm);
         uint64_t sq_out = 0;
         v2u16_t pko = (v2u16_t)(0);
 #pragma unroll
@@ -282,8 +254,8 @@ __global__ __launch_bounds__(kEcWaves * 64, kEcWaves * kEcResident / 4) void k_e
                 if (a.out && chan) reinterpret_cast<uint32_t *>(a.out + (uint64_t)o * n)[m] = u;
             }
         }
-        const uint64_t tn = ec_row_sum64(sq_near), to = ec_row_sum64(sq_out);
-        const uint32_t peak = ec_row_max(max((uint32_t)pko.x, (uint32_t)pko.y));
+        const uint64_t tn = row16_sum64(sq_near), to = row16_sum64(sq_out);
+        const uint32_t peak = row16_max(max((uint32_t)pko.x, (uint32_t)pko.y));
         if (chan && k == 0u) {
             if (a.rec) *reinterpret_cast<uint4 *>(a.rec + o) = make_uint4((uint32_t)(tn >> 8), (uint32_t)(to >> 8), flags | n_adapt << 8 | n_dt << 16, wm);
             if (a.stats) a.stats[o] = as_stats(pcm_record(to, peak, n, 0u));

@@ -20,9 +20,10 @@
 // COPY (the compute-free yardstick, tools/filt_bench.py): every channel as under BYPASS, so the same loads, decode, tile stores, the
 // lane's read and write of every dword of its row with the peak fold a bypassed row's record needs, tile reads, state load and store
 // and output stores; no section runs; d_ctl is not read, of a plan only its first dword.
+// The tile's addressing (tile_item, tile_piece) and the G.711 piece (g711_decode8) are igdsp_lanes.h's.
 // Everything is written with vector stores in plain C++.
 #include "igdsp_filt.h"
-#include "igdsp_device.h"
+#include "igdsp_lanes.h"
 
 namespace igdsp {
 
@@ -38,19 +39,6 @@ struct FiltArgs {
     igdsp_filt_rec *rec;
     igdsp_frame_stats *stats;
 };
-
-// eight codes (two dwords) as eight int16 in four dwords, decoded as igdsp_decode_meter decodes: a code is negative iff its bit 7 is clear
-__device__ __forceinline__ uint4 filt_decode(uint32_t lo, uint32_t hi, bool alaw)
-{
-    uint32_t w[4];
-#pragma unroll
-    for (uint32_t i = 0; i < 4u; ++i) {
-        const uint32_t d = i < 2u ? lo : hi, c0 = (d >> (16u * (i & 1u))) & 0xFFu, c1 = (d >> (16u * (i & 1u) + 8u)) & 0xFFu;
-        const int32_t m0 = (int32_t)(alaw ? alaw_abs(c0) : ulaw_abs(c0)), m1 = (int32_t)(alaw ? alaw_abs(c1) : ulaw_abs(c1));
-        w[i] = ((uint32_t)((c0 & 0x80u) ? m0 : -m0) & 0xFFFFu) | ((uint32_t)((c1 & 0x80u) ? m1 : -m1) << 16);
-    }
-    return make_uint4(w[0], w[1], w[2], w[3]);
-}
 
 template <int IN> struct FiltPiece { using type = uint4; };
 template <> struct FiltPiece<kFiltG711> { using type = uint2; };
@@ -74,12 +62,13 @@ __device__ __forceinline__ void filt_fill(const FiltArgs &a, uint32_t *tile, con
 {
 #pragma unroll
     for (uint32_t u = 0; u < kFiltAhead; ++u) {
-        const uint32_t i = (U0 + u) * 64u + lane, rw = (i * a.inv) >> 20, pc = i - rw * P;   // i < 2^11: the product fits
-        if (i < items) {                                                   // rw < 64, pc < P: the piece lies in its row, the row in the tile
+        const uint32_t i = (U0 + u) * 64u + lane;                          // i < 2^11
+        if (i < items) {                                                   // row < 64, piece < P: the piece lies in its row, the row in the tile
+            const TileItem t = tile_item(i, a.inv, P);
             uint4 x;
-            if constexpr (IN == kFiltG711) x = filt_decode(nx[u].x, nx[u].y, law[rw] != 0u);
+            if constexpr (IN == kFiltG711) x = g711_decode8(nx[u].x, nx[u].y, law[t.row] != 0u);
             else x = nx[u];
-            uint32_t *d = tile + rw * stride + 4u * pc;
+            uint32_t *d = tile_piece(tile, stride, t);
             d[0] = x.x; d[1] = x.y; d[2] = x.z; d[3] = x.w;
         }
     }
@@ -106,7 +95,7 @@ template <int IN, int S, bool COPY>
 __global__ __launch_bounds__(64) void k_filt(const FiltArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t filt_lds[];
-    const uint32_t lane = threadIdx.x, n = a.n, P = n >> 3, stride = filt_row_dwords(n);
+    const uint32_t lane = threadIdx.x, n = a.n, P = n >> 3, stride = tile_row_dwords(n);
     uint32_t *tile = filt_lds;                                             // [kFiltChans][stride]
     uint8_t *law = reinterpret_cast<uint8_t *>(filt_lds + kFiltChans * stride);   // [kFiltChans]
     const uint64_t c0 = (uint64_t)blockIdx.x * kFiltChans;                 // < C: the grid
@@ -197,9 +186,9 @@ __global__ __launch_bounds__(64) void k_filt(const FiltArgs a)
         if (a.out) {
             uint4 *dst = reinterpret_cast<uint4 *>(a.out + t0 * n);       // d_out 16-byte aligned, n a multiple of 8: the argument rule
             for (uint32_t it = 0; it < P; ++it) {
-                const uint32_t i = it * 64u + lane, rw = (i * a.inv) >> 20, pc = i - rw * P;
+                const uint32_t i = it * 64u + lane;
                 if (i < items) {
-                    const uint32_t *s = tile + rw * stride + 4u * pc;
+                    const uint32_t *s = tile_piece(tile, stride, tile_item(i, a.inv, P));
                     dst[i] = make_uint4(s[0], s[1], s[2], s[3]);
                 }
             }

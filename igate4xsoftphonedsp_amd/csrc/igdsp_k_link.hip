@@ -230,4 +230,28 @@ hipError_t launch_link_watch(const LaunchCfg &, const igdsp_rtp_info *info, cons
     return hipSuccess;
 }
 
+// the event list behind a stage's dense records: count -> k_link_scan -> store (igdsp_internal.h)
+template <class Rec, class Event>
+hipError_t launch_event_list(ListPass<Rec, Event> count, ListPass<Rec, Event> store, const ListRoute &r, bool empty, const Rec *rec, uint32_t C,
+                             uint32_t F, uint32_t mask, Event *events, uint32_t event_cap, uint32_t *event_count, void *work, hipStream_t s)
+{
+    const bool list = event_count != nullptr;
+    uint32_t *head = static_cast<uint32_t *>(work), *counts = head + kLinkWorkHead / 4;
+    if (empty) {                                                           // nothing to do: the counts are 0
+        if (list) hipLaunchKernelGGL(k_link_scan, dim3(1), dim3(kLinkScanThreads), 0, s, head, (uint64_t)0, 1u, 1u, event_cap, event_count);
+        return hipGetLastError();
+    }
+    if (hipError_t e = hipGetLastError(); e != hipSuccess || !list) return e;          // the stage's own kernel
+    hipLaunchKernelGGL(count, dim3(r.list_grid), dim3(kListWaves * 64), 0, s, rec, C, F, r.waves, mask, counts, events, event_cap);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_link_scan, dim3(1), dim3(kLinkScanThreads), 0, s, head, (uint64_t)F * r.waves, 1u, 1u, event_cap, event_count);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    hipLaunchKernelGGL(store, dim3(r.list_grid), dim3(kListWaves * 64), 0, s, rec, C, F, r.waves, mask, counts, events, event_cap);
+    return hipGetLastError();
+}
+template hipError_t launch_event_list(ListPass<igdsp_tdet_rec, igdsp_tdet_event>, ListPass<igdsp_tdet_rec, igdsp_tdet_event>, const ListRoute &, bool,
+                                      const igdsp_tdet_rec *, uint32_t, uint32_t, uint32_t, igdsp_tdet_event *, uint32_t, uint32_t *, void *, hipStream_t);
+template hipError_t launch_event_list(ListPass<igdsp_vad_rec, igdsp_vad_event>, ListPass<igdsp_vad_rec, igdsp_vad_event>, const ListRoute &, bool,
+                                      const igdsp_vad_rec *, uint32_t, uint32_t, uint32_t, igdsp_vad_event *, uint32_t, uint32_t *, void *, hipStream_t);
+
 }  // namespace igdsp

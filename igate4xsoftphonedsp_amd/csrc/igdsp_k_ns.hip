@@ -14,12 +14,12 @@
 //     in flight through the frame's hops;
 //   - the hops (ns_frame_core), the record's sums folded over the 16 lanes through LDS;
 //   - the row goes out as 16-byte pieces, record and PCM record as one 16-byte store each by the channel's first lane;
-//   - the next frame's pieces go from the registers to the row, G.711 decoded on the way.
+//   - the next frame's pieces go from the registers to the row, G.711 decoded on the way (g711_decode8, igdsp_lanes.h).
 // COPY (the compute-free yardstick, tools/ns_bench.py): every channel as under BYPASS, so the same loads, decode, row stores and
 // reads, state load and store, folds and output stores, and the delay's pass over the row; no transform, no band runs; d_ctl is not read.
 // Everything is written with vector stores in plain C++.
 #include "igdsp_ns.h"
-#include "igdsp_device.h"
+#include "igdsp_lanes.h"
 
 namespace igdsp {
 
@@ -43,19 +43,6 @@ struct NsArgs {
 struct NsFence {
     __device__ __forceinline__ void operator()() const { wave_lds_fence(); }
 };
-
-// eight codes (two dwords) as eight int16 in four dwords, decoded as igdsp_decode_meter decodes: a code is negative iff its bit 7 is clear
-__device__ __forceinline__ uint4 ns_decode8(uint32_t lo, uint32_t hi, bool alaw)
-{
-    uint32_t w[4];
-#pragma unroll
-    for (uint32_t i = 0; i < 4u; ++i) {
-        const uint32_t d = i < 2u ? lo : hi, c0 = (d >> (16u * (i & 1u))) & 0xFFu, c1 = (d >> (16u * (i & 1u) + 8u)) & 0xFFu;
-        const int32_t m0 = (int32_t)(alaw ? alaw_abs(c0) : ulaw_abs(c0)), m1 = (int32_t)(alaw ? alaw_abs(c1) : ulaw_abs(c1));
-        w[i] = ((uint32_t)((c0 & 0x80u) ? m0 : -m0) & 0xFFFFu) | ((uint32_t)((c1 & 0x80u) ? m1 : -m1) << 16);
-    }
-    return make_uint4(w[0], w[1], w[2], w[3]);
-}
 
 // a piece in registers: native vectors, so that the turns' array stays registers
 typedef uint32_t ns_u32x2_t __attribute__((ext_vector_type(2)));
@@ -82,7 +69,7 @@ __device__ __forceinline__ void ns_fill(uint4 *row, bool alaw, uint32_t P, uint3
     for (uint32_t u = 0; u < kNsTurns; ++u) {
         const uint32_t p = u * kNsLanes + lane;
         if (p < P) {                                                       // 16 p + 16 <= 2 n: inside the row
-            if constexpr (IN == kNsG711) row[p] = ns_decode8(nx[u].x, nx[u].y, alaw);
+            if constexpr (IN == kNsG711) row[p] = g711_decode8(nx[u].x, nx[u].y, alaw);
             else row[p] = make_uint4(nx[u].x, nx[u].y, nx[u].z, nx[u].w);
         }
     }

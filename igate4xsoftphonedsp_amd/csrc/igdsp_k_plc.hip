@@ -21,8 +21,7 @@
 //      part has refilled it.
 // COPY (the compute-free yardstick, tools/plc_bench.py): phases A, B and D with every tick taken as PLAIN and no decode, stats or
 // ring arithmetic: the input bits are widened to the output, the records carry only the length.
-#include "igdsp_device.h"
-#include "igdsp_pcmrec.h"
+#include "igdsp_lanes.h"
 
 namespace igdsp {
 
@@ -60,18 +59,13 @@ struct PlcLds {
     uint32_t first[kPlcCh];                                // first START tick of the part, or kPlcPart; 0xFFFF: no loss work at all
 };
 
-__device__ __forceinline__ int32_t g711_dec(uint32_t code, bool alaw)
-{
-    const int32_t m = (int32_t)(alaw ? alaw_abs(code) : ulaw_abs(code));
-    return (code & 0x80u) ? m : -m;
-}
 __device__ __forceinline__ bool plc_alaw(const PlcArgs &a, uint32_t c) { return a.g711 && a.codec[c] == IGDSP_PT_PCMA; }
 // x[i] of tick t (in the part) of channel c: the decoded sample, 0 at or past l
 __device__ __forceinline__ int32_t plc_x(const PlcArgs &a, uint32_t t, uint32_t c, uint32_t i, uint32_t l)
 {
     if (i >= l) return 0;
     const uint64_t o = ((uint64_t)(a.t0 + t) * a.C + c) * a.n + i;
-    return a.g711 ? g711_dec(a.g711[o], plc_alaw(a, c)) : (int32_t)a.pcm[o];
+    return a.g711 ? g711_s16(a.g711[o], plc_alaw(a, c)) : (int32_t)a.pcm[o];
 }
 __device__ __forceinline__ int32_t plc_gain(uint32_t m)
 {
@@ -149,7 +143,7 @@ __device__ __forceinline__ void plc_bulk(const PlcArgs &a, PlcLds &L, uint32_t c
                     int32_t x;
                     if (COPY) x = a.g711 ? (int32_t)((in[k >> 2] >> (8u * (k & 3u))) & 0xFFu) : (int32_t)(int16_t)(in[k >> 1] >> (16u * (k & 1u)));
                     else if (kind == kPkIdle || s >= l) x = 0;
-                    else if (a.g711) x = g711_dec((in[k >> 2] >> (8u * (k & 3u))) & 0xFFu, alaw);
+                    else if (a.g711) x = g711_s16((in[k >> 2] >> (8u * (k & 3u))) & 0xFFu, alaw);
                     else x = (int32_t)(int16_t)(in[k >> 1] >> (16u * (k & 1u)));
                     o[k >> 1] |= ((uint32_t)x & 0xFFFFu) << (16u * (k & 1u));
                     if (!COPY) {

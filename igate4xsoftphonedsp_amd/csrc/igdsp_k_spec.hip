@@ -19,7 +19,7 @@
 // COPY (the compute-free yardstick, tools/spec_bench.py): the same rows into the ring, the same ring loads, tile stores and loads and
 // global stores at a hop, no window, butterfly, twiddle, mirror fetch, split, log or average: raw is the lane's points as they came back
 // from the tile, a record carries only IGDSP_SPEC_HOP, the averaged array is stored as it was read.
-#include "igdsp_device.h"
+#include "igdsp_lanes.h"
 #include "igdsp_spec.h"
 
 namespace igdsp {
@@ -60,9 +60,7 @@ __device__ __forceinline__ void spec_row_load(const SpecArgs &a, uint32_t o, uin
 }
 __device__ __forceinline__ int16_t spec_decode(uint32_t v, bool g711, bool alaw)
 {
-    if (!g711) return (int16_t)v;
-    const int32_t m = (int32_t)(alaw ? alaw_abs(v) : ulaw_abs(v));
-    return (int16_t)((v & 0x80u) ? m : -m);
+    return (int16_t)(g711 ? g711_s16(v, alaw) : (int32_t)v);
 }
 // sample pair m of the history (samples 2 m, 2 m + 1, oldest first) from the ring whose oldest sample is at head
 __device__ __forceinline__ uint32_t spec_pair(const SpecLds &L, uint32_t head, uint32_t m)

@@ -19,10 +19,9 @@
 // up by n.  E0 (0, 1, 2): n % 8 == 0, n % 4 == 0, else: how evaluation 0's window, which starts n / 2 values before the frame, can be read.
 // COPY (the compute-free yardstick, tools/tdet_bench.py): the same row loads, buffer stores, history move, records and state stores;
 // no table, no pair reads, no dot product, decision or debounce.
-// The list (launch_tone_detect): k_tdet_list counts per (frame, 64 channels) the records whose flags meet the mask, the link stage's
-// k_link_scan makes offsets and totals of the counts, k_tdet_list<true> stores the events.  Everything is written with vector stores.
-#include "igdsp_device.h"
-#include "igdsp_pcmrec.h"
+// The list (launch_tone_detect, launch_event_list): k_tdet_list is event_list_pass over the records whose flags meet the mask.
+// The row's DPP steps and sums, the packed dot product and the G.711 pair are igdsp_lanes.h's.  Everything is written with vector stores.
+#include "igdsp_lanes.h"
 #include "igdsp_tdet.h"
 
 namespace igdsp {
@@ -48,35 +47,26 @@ static_assert(sizeof(TdetLds) == kTdetLdsBytes, "tdet_route's LDS");
 
 constexpr uint32_t kTdetNone = 0xFFFFFFFFu;
 
-template <int CTRL>
-__device__ __forceinline__ uint32_t tdet_dpp(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, false); }
-template <int CTRL>
-__device__ __forceinline__ uint64_t tdet_dpp64(uint64_t v) { return (uint64_t)tdet_dpp<CTRL>((uint32_t)v) | (uint64_t)tdet_dpp<CTRL>((uint32_t)(v >> 32)) << 32; }
 // the maximum over the eight lanes of a group, in each of them: xor 1, xor 2 (quad_perm), then the other quad (row_half_mirror)
 __device__ __forceinline__ uint64_t tdet_max8(uint64_t v)
 {
-    v = max(v, tdet_dpp64<0xB1>(v));
-    v = max(v, tdet_dpp64<0x4E>(v));
-    return max(v, tdet_dpp64<0x141>(v));
+    v = max(v, dpp64<0xB1>(v));
+    v = max(v, dpp64<0x4E>(v));
+    return max(v, dpp64<0x141>(v));
 }
-__device__ __forceinline__ uint32_t tdet_dot2(uint32_t x, uint32_t w, uint32_t acc)
-{
-    return (uint32_t)__builtin_amdgcn_sdot2(__builtin_bit_cast(v2i16, x), __builtin_bit_cast(v2i16, w), (int)acc, false);
-}
-// two samples as they lie in memory (two codes, or two PCM samples) -> the two values v
+// two samples as they lie in memory (two codes, or two PCM samples) -> the two values v = x >> 3, the shift on the SIGNED sample
 __device__ __forceinline__ uint32_t tdet_unit(uint32_t u, bool g711, bool alaw)
 {
     int32_t x0, x1;
     if (g711) {
-        const uint32_t c0 = u & 0xFFu, c1 = (u >> 8) & 0xFFu;
-        const int32_t m0 = (int32_t)(alaw ? alaw_abs(c0) : ulaw_abs(c0)), m1 = (int32_t)(alaw ? alaw_abs(c1) : ulaw_abs(c1));
-        x0 = (c0 & 0x80u) ? m0 : -m0;
-        x1 = (c1 & 0x80u) ? m1 : -m1;
+        const G711Two x = g711_two(u, alaw);
+        x0 = x.x0;
+        x1 = x.x1;
     } else {
         x0 = (int16_t)(u & 0xFFFFu);
         x1 = (int16_t)(u >> 16);
     }
-    return ((uint32_t)(x0 >> 3) & 0xFFFFu) | ((uint32_t)(x1 >> 3) << 16);
+    return pack2(x0 >> 3, x1 >> 3);
 }
 __device__ __forceinline__ void tdet_row_load(const TdetArgs &a, uint32_t o, uint32_t k, uint32_t (&u)[8])
 {
@@ -107,18 +97,6 @@ __device__ __forceinline__ uint32_t tdet_pair0(const int16_t *buf, uint32_t h, u
     if constexpr (E0 != 2) return *reinterpret_cast<const uint32_t *>(p);
     return (uint32_t)(uint16_t)p[0] | (uint32_t)(uint16_t)p[1] << 16;
 }
-// the sum over the 16 lanes of a row, in each of them (row_ror 8, 4, 2, 1)
-__device__ __forceinline__ uint32_t tdet_row_sum(uint32_t v)
-{
-    v += tdet_dpp<0x128>(v);
-    v += tdet_dpp<0x124>(v);
-    v += tdet_dpp<0x122>(v);
-    return v + tdet_dpp<0x121>(v);
-}
-__device__ __forceinline__ uint64_t tdet_row_sum64(uint64_t v)            // exact while the row's total is below 2^56
-{
-    return (uint64_t)tdet_row_sum((uint32_t)v & 0xFFFFFFu) + ((uint64_t)tdet_row_sum((uint32_t)(v >> 24)) << 24);
-}
 
 // both evaluations' sums of a frame: I and Q of the lane's bin (split: the half of the window the lane takes), E of the row
 struct TdetSums { uint32_t I0, Q0, I1, Q1; uint64_t E0, E1; };
@@ -133,23 +111,23 @@ __device__ __forceinline__ TdetSums tdet_sums(const TdetLds &L, const int16_t *b
         const uint4 t = tab[16u * j2];
         const uint2 s1 = *reinterpret_cast<const uint2 *>(frame + 4u * j2);
         const uint2 s0 = tdet_pairs0<E0>(buf, h, j2);
-        r.I0 = tdet_dot2(s0.x, t.x, r.I0); r.Q0 = tdet_dot2(s0.x, t.y, r.Q0);
-        r.I1 = tdet_dot2(s1.x, t.x, r.I1); r.Q1 = tdet_dot2(s1.x, t.y, r.Q1);
-        r.I0 = tdet_dot2(s0.y, t.z, r.I0); r.Q0 = tdet_dot2(s0.y, t.w, r.Q0);
-        r.I1 = tdet_dot2(s1.y, t.z, r.I1); r.Q1 = tdet_dot2(s1.y, t.w, r.Q1);
+        r.I0 = dot2(s0.x, t.x, r.I0); r.Q0 = dot2(s0.x, t.y, r.Q0);
+        r.I1 = dot2(s1.x, t.x, r.I1); r.Q1 = dot2(s1.x, t.y, r.Q1);
+        r.I0 = dot2(s0.y, t.z, r.I0); r.Q0 = dot2(s0.y, t.w, r.Q0);
+        r.I1 = dot2(s1.y, t.z, r.I1); r.Q1 = dot2(s1.y, t.w, r.Q1);
     }
     if (split) {                                                           // plan-uniform: lane k + 4 took the other half of lane k's window
-        r.I0 += tdet_dpp<0x104>(r.I0); r.Q0 += tdet_dpp<0x104>(r.Q0);
-        r.I1 += tdet_dpp<0x104>(r.I1); r.Q1 += tdet_dpp<0x104>(r.Q1);
+        r.I0 += dpp<0x104>(r.I0); r.Q0 += dpp<0x104>(r.Q0);
+        r.I1 += dpp<0x104>(r.I1); r.Q1 += dpp<0x104>(r.Q1);
     }
     uint64_t e0 = 0, e1 = 0;
     for (uint32_t j = k; j < h; j += 16u) {
         const uint32_t a0 = tdet_pair0<E0>(buf, h, j), a1 = *reinterpret_cast<const uint32_t *>(frame + 2u * j);
-        e0 += tdet_dot2(a0, a0, 0u);
-        e1 += tdet_dot2(a1, a1, 0u);
+        e0 += dot2(a0, a0, 0u);
+        e1 += dot2(a1, a1, 0u);
     }
-    r.E0 = tdet_row_sum64(e0);
-    r.E1 = tdet_row_sum64(e1);
+    r.E0 = row16_sum64(e0);
+    r.E1 = row16_sum64(e1);
     return r;
 }
 
@@ -166,8 +144,8 @@ __device__ __forceinline__ uint32_t tdet_hit_dev(uint32_t I, uint32_t Q, uint64_
     const uint32_t ci = tops ? (uint32_t)__builtin_ctz(tops) : 0u;
     const uint32_t bad = (uint32_t)(__builtin_amdgcn_ballot_w64(valid && (k & 7u) != ci && tdet_rel_fails(M, P, thr.rel_q8)) >> sh) & 0xFFu;
     const uint32_t ok = (tops != 0u && bad == 0u && M >= floor) ? 1u : 0u;
-    const uint64_t Mo = tdet_dpp64<0x128>(M);
-    const uint32_t cio = tdet_dpp<0x128>(ci), oko = tdet_dpp<0x128>(ok);
+    const uint64_t Mo = dpp64<0x128>(M);
+    const uint32_t cio = dpp<0x128>(ci), oko = dpp<0x128>(ok);
     const bool hi = (k & 8u) != 0u;
     return tdet_decide(thr, nhi, (hi ? oko : ok) != 0u, hi ? cio : ci, hi ? Mo : M, (hi ? ok : oko) != 0u, hi ? ci : cio, hi ? M : Mo, tdet_eref(E, n));
 }
@@ -294,26 +272,17 @@ __global__ __launch_bounds__(kTdetWaves * 64, kTdetWaves * kTdetResident / 4) vo
     }
 }
 
-// the list's two passes over the dense records: a wave is 64 consecutive channels of one frame
+// the list's two passes over the dense records (event_list_pass): an event is a record whose flags meet the mask
+struct TdetListRule {
+    using Vec = uint2;
+    static __device__ __forceinline__ bool is_event(const uint2 &r, uint32_t mask) { return ((r.x >> 24) & mask) != 0u; }
+    static __device__ __forceinline__ uint4 make_event(uint32_t c, uint32_t f, const uint2 &r) { return make_uint4(c, f, r.x, r.y); }
+};
 template <bool WRITE>
-__global__ __launch_bounds__(kTdetListWaves * 64) void k_tdet_list(const igdsp_tdet_rec *rec, uint32_t C, uint32_t F, uint32_t W, uint32_t mask,
-                                                                   uint32_t *counts, igdsp_tdet_event *events, uint32_t cap)
+__global__ __launch_bounds__(kListWaves * 64) void k_tdet_list(const igdsp_tdet_rec *rec, uint32_t C, uint32_t F, uint32_t W, uint32_t mask,
+                                                               uint32_t *counts, igdsp_tdet_event *events, uint32_t cap)
 {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t item = (uint64_t)blockIdx.x * kTdetListWaves + (threadIdx.x >> 6);
-    if (item >= (uint64_t)F * W) return;                                   // wave-uniform
-    const uint32_t f = (uint32_t)(item / W), w = (uint32_t)(item - (uint64_t)f * W);
-    const uint64_t c = (uint64_t)w * 64u + lane;
-    uint2 r = make_uint2(0u, 0u);
-    if (c < C) r = *reinterpret_cast<const uint2 *>(rec + (uint64_t)f * C + c);
-    const bool ev = ((r.x >> 24) & mask) != 0u;
-    const uint64_t bal = __builtin_amdgcn_ballot_w64(ev);
-    if (!WRITE) {
-        if (lane == 0u) counts[item] = (uint32_t)__popcll(bal);
-    } else if (ev) {
-        const uint32_t idx = counts[item] + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-        if (idx < cap) *reinterpret_cast<uint4 *>(events + idx) = make_uint4((uint32_t)c, f, r.x, r.y);
-    }
+    event_list_pass<WRITE, TdetListRule>(rec, C, F, W, mask, counts, events, cap);
 }
 
 hipError_t launch_tone_detect(const LaunchCfg &, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm, const igdsp_tdet_plan *plans,
@@ -323,24 +292,14 @@ hipError_t launch_tone_detect(const LaunchCfg &, const uint8_t *g711, const uint
 {
     const bool list = event_count != nullptr;
     const TdetRoute r = tdet_route(C, F, n, list, rec != nullptr);
-    uint32_t *head = static_cast<uint32_t *>(work);
-    if (r.grid == 0) {                                                     // nothing to do: the counts are 0
-        if (list) hipLaunchKernelGGL(k_link_scan, dim3(1), dim3(kLinkScanThreads), 0, s, head, (uint64_t)0, 1u, 1u, event_cap, event_count);
-        return hipGetLastError();
+    if (r.grid != 0) {
+        rec = list_records(rec, list, work, r);
+        const TdetArgs a{g711, codec, pcm, plans, plan_of, n_plans, C, F, n, state, rec};
+        with_bool(yardstick, [&](auto Y) { with_key(Keys<0, 1, 2>{}, (int)r.e0, [&](auto O) {
+            hipLaunchKernelGGL((k_tdet<Y, O>), dim3(r.grid), dim3(r.threads), 0, s, a); }); });
     }
-    if (list && !rec) rec = reinterpret_cast<igdsp_tdet_rec *>(static_cast<uint8_t *>(work) + r.counts_bytes);
-    const TdetArgs a{g711, codec, pcm, plans, plan_of, n_plans, C, F, n, state, rec};
-    with_bool(yardstick, [&](auto Y) { with_key(Keys<0, 1, 2>{}, (int)r.e0, [&](auto O) {
-        hipLaunchKernelGGL((k_tdet<Y, O>), dim3(r.grid), dim3(r.threads), 0, s, a); }); });
-    if (hipError_t e = hipGetLastError(); e != hipSuccess || !list) return e;
-    uint32_t *counts = head + kLinkWorkHead / 4;
     const uint32_t mask = event_mask ? event_mask : (uint32_t)IGDSP_TDET_EVENT_DEFAULT;
-    hipLaunchKernelGGL(k_tdet_list<false>, dim3(r.list_grid), dim3(kTdetListWaves * 64), 0, s, rec, C, F, r.waves, mask, counts, events, event_cap);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_link_scan, dim3(1), dim3(kLinkScanThreads), 0, s, head, (uint64_t)F * r.waves, 1u, 1u, event_cap, event_count);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_tdet_list<true>, dim3(r.list_grid), dim3(kTdetListWaves * 64), 0, s, rec, C, F, r.waves, mask, counts, events, event_cap);
-    return hipGetLastError();
+    return launch_event_list(k_tdet_list<false>, k_tdet_list<true>, r, r.grid == 0, rec, C, F, mask, events, event_cap, event_count, work, s);
 }
 
 }  // namespace igdsp

@@ -20,9 +20,9 @@
 // indexes LDS, never a register array.  Lanes 0..3 of the row store the record, the payload, the kind and the control byte.
 // COPY (the compute-free yardstick, tools/vad_bench.py): the same row loads, decode, LDS stores, state load and store and output stores;
 // no lag sum, level, decision, model or recursion; d_ctl is not read.
-// The list (launch_vad): k_vad_list counts per (frame, 64 channels) the records whose flags meet the mask, the link stage's k_link_scan
-// makes offsets and totals of the counts, k_vad_list<true> stores the events.  Everything is written with vector stores in plain C++.
-#include "igdsp_device.h"
+// The list (launch_vad, launch_event_list): k_vad_list is event_list_pass over the records whose flags meet the mask.
+// The row's sum, the packed dot product and the G.711 magnitude and sign are igdsp_lanes.h's.  Everything is written with vector stores in plain C++.
+#include "igdsp_lanes.h"
 #include "igdsp_vad.h"
 
 namespace igdsp {
@@ -50,10 +50,8 @@ struct VadLds {
 };
 static_assert(sizeof(VadLds) == kVadLdsBytes, "vad_route's LDS");
 
-template <int CTRL>
-__device__ __forceinline__ uint32_t vad_dpp(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, false); }
 // level(e0) and level(e1) in every lane of the row: lane k counts the entries 8 k .. 8 k + 7 of tab = n * T8 that lie above e << 8, the
-// row adds the counts (row_ror 8, 4, 2, 1).  T8 never rises and T8[127] is 0, so the count is the least d with (e << 8) >= n * T8[d],
+// row adds the counts (row16_sum).  T8 never rises and T8[127] is 0, so the count is the least d with (e << 8) >= n * T8[d],
 // 127 if there is none in 0..126: vad_level's value
 __device__ __forceinline__ void vad_levels(int64_t e0, int64_t e1, const uint64_t *tab, uint32_t k, uint32_t &l0, uint32_t &l1)
 {
@@ -64,18 +62,11 @@ __device__ __forceinline__ void vad_levels(int64_t e0, int64_t e1, const uint64_
         const uint64_t t = tab[8u * k + i];
         c += (a < t ? 1u : 0u) + (b < t ? 0x10000u : 0u);
     }
-    c += vad_dpp<0x128>(c);
-    c += vad_dpp<0x124>(c);
-    c += vad_dpp<0x122>(c);
-    c += vad_dpp<0x121>(c);
+    c = row16_sum(c);
     l0 = e0 > 0 ? c & 0xFFFFu : 127u;
     l1 = e1 > 0 ? c >> 16 : 127u;
 }
 
-__device__ __forceinline__ uint32_t vad_dot2(uint32_t x, uint32_t w, uint32_t acc)
-{
-    return (uint32_t)__builtin_amdgcn_sdot2(__builtin_bit_cast(v2i16, x), __builtin_bit_cast(v2i16, w), (int)acc, false);
-}
 // a value of lane 0 of the row, in each of its lanes
 __device__ __forceinline__ uint64_t vad_row0(uint64_t v)
 {
@@ -96,7 +87,8 @@ __device__ __forceinline__ uint4 vad_load(const VadArgs &a, uint32_t o, uint32_t
     }
     return v;
 }
-// the piece's eight values v = x >> 2 as four dwords of two int16
+// the piece's eight values v = x >> 2 as four dwords of two int16; codes: the shift on the MAGNITUDE (a multiple of 4), then the sign
+// (g711_abs, g711_signed: igdsp_lanes.h), which is why g711_decode8 does not serve here
 template <bool G711>
 __device__ __forceinline__ uint4 vad_values(const uint4 v, bool alaw)
 {
@@ -105,14 +97,13 @@ __device__ __forceinline__ uint4 vad_values(const uint4 v, bool alaw)
 #pragma unroll
         for (uint32_t i = 0; i < 4u; ++i) {
             const uint32_t d = i < 2u ? v.x : v.y, c0 = (d >> (16u * (i & 1u))) & 0xFFu, c1 = (d >> (16u * (i & 1u) + 8u)) & 0xFFu;
-            const int32_t m0 = (int32_t)(alaw ? alaw_abs(c0) : ulaw_abs(c0)) >> 2, m1 = (int32_t)(alaw ? alaw_abs(c1) : ulaw_abs(c1)) >> 2;   // multiples of 4
-            w[i] = ((uint32_t)((c0 & 0x80u) ? m0 : -m0) & 0xFFFFu) | ((uint32_t)((c1 & 0x80u) ? m1 : -m1) << 16);
+            const int32_t m0 = (int32_t)g711_abs(c0, alaw) >> 2, m1 = (int32_t)g711_abs(c1, alaw) >> 2;   // multiples of 4
+            w[i] = ((uint32_t)g711_signed(c0, m0) & 0xFFFFu) | ((uint32_t)g711_signed(c1, m1) << 16);
         }
     } else {
         const uint32_t s[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-        for (uint32_t i = 0; i < 4u; ++i)
-            w[i] = ((uint32_t)((int32_t)(int16_t)(s[i] & 0xFFFFu) >> 2) & 0xFFFFu) | ((uint32_t)((int32_t)(int16_t)(s[i] >> 16) >> 2) << 16);
+        for (uint32_t i = 0; i < 4u; ++i) w[i] = pack2((int32_t)(int16_t)(s[i] & 0xFFFFu) >> 2, (int32_t)(int16_t)(s[i] >> 16) >> 2);
     }
     return make_uint4(w[0], w[1], w[2], w[3]);
 }
@@ -177,7 +168,7 @@ __global__ __launch_bounds__(kVadWaves * 64, kVadWaves * kVadResident / 4) void 
             auto step = [&](uint32_t j, uint32_t acc) -> uint32_t {        // 8 samples of the lane's lag
                 const uint4 x = xb[j];
                 const uint32_t *lp = lb + 4u * j;
-                return vad_dot2(x.w, lp[3], vad_dot2(x.z, lp[2], vad_dot2(x.y, lp[1], vad_dot2(x.x, lp[0], acc))));
+                return dot2(x.w, lp[3], dot2(x.z, lp[2], dot2(x.y, lp[1], dot2(x.x, lp[0], acc))));
             };
             uint32_t j = 0;
             for (; j + 2u <= P; j += 2u) rk += (int32_t)step(j + 1u, step(j, 0u));   // wave-uniform; 16 products of at most 2^26 fit 32 bits
@@ -238,26 +229,17 @@ __global__ __launch_bounds__(kVadWaves * 64, kVadWaves * kVadResident / 4) void 
     }
 }
 
-// the list's two passes over the dense records: a wave is 64 consecutive channels of one frame
+// the list's two passes over the dense records (event_list_pass): an event is a record whose flags meet the mask
+struct VadListRule {
+    using Vec = uint4;
+    static __device__ __forceinline__ bool is_event(const uint4 &r, uint32_t mask) { return ((r.z >> 16) & 0xFFu & mask) != 0u; }
+    static __device__ __forceinline__ uint4 make_event(uint32_t c, uint32_t f, const uint4 &r) { return make_uint4(c, f, r.x, (r.z & 0x00FFFFFFu) | (r.w & 0xFFu) << 24); }
+};
 template <bool WRITE>
-__global__ __launch_bounds__(kVadListWaves * 64) void k_vad_list(const igdsp_vad_rec *rec, uint32_t C, uint32_t F, uint32_t W, uint32_t mask,
-                                                                 uint32_t *counts, igdsp_vad_event *events, uint32_t cap)
+__global__ __launch_bounds__(kListWaves * 64) void k_vad_list(const igdsp_vad_rec *rec, uint32_t C, uint32_t F, uint32_t W, uint32_t mask,
+                                                              uint32_t *counts, igdsp_vad_event *events, uint32_t cap)
 {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t item = (uint64_t)blockIdx.x * kVadListWaves + (threadIdx.x >> 6);
-    if (item >= (uint64_t)F * W) return;                                   // wave-uniform
-    const uint32_t f = (uint32_t)(item / W), w = (uint32_t)(item - (uint64_t)f * W);
-    const uint64_t c = (uint64_t)w * 64u + lane;
-    uint4 r = make_uint4(0u, 0u, 0u, 0u);
-    if (c < C) r = *reinterpret_cast<const uint4 *>(rec + (uint64_t)f * C + c);
-    const bool ev = ((r.z >> 16) & 0xFFu & mask) != 0u;
-    const uint64_t bal = __builtin_amdgcn_ballot_w64(ev);
-    if (!WRITE) {
-        if (lane == 0u) counts[item] = (uint32_t)__popcll(bal);
-    } else if (ev) {
-        const uint32_t idx = counts[item] + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-        if (idx < cap) *reinterpret_cast<uint4 *>(events + idx) = make_uint4((uint32_t)c, f, r.x, (r.z & 0x00FFFFFFu) | (r.w & 0xFFu) << 24);
-    }
+    event_list_pass<WRITE, VadListRule>(rec, C, F, W, mask, counts, events, cap);
 }
 
 hipError_t launch_vad(const LaunchCfg &, const uint8_t *g711, const uint8_t *codec, const int16_t *pcm, const uint8_t *ctl, const igdsp_vad_cfg &vad,
@@ -266,23 +248,13 @@ hipError_t launch_vad(const LaunchCfg &, const uint8_t *g711, const uint8_t *cod
 {
     const bool list = event_count != nullptr;
     const VadRoute r = vad_route(C, F, n, g711 != nullptr, yardstick, list, rec != nullptr);
-    uint32_t *head = static_cast<uint32_t *>(work);
-    if (r.grid == 0) {                                                     // nothing to do: the counts are 0
-        if (list) hipLaunchKernelGGL(k_link_scan, dim3(1), dim3(kLinkScanThreads), 0, s, head, (uint64_t)0, 1u, 1u, event_cap, event_count);
-        return hipGetLastError();
+    if (r.grid != 0) {
+        rec = list_records(rec, list, work, r);
+        const VadArgs a{g711, codec, pcm, ctl, vad_k(vad), C, F, n, state, kind, rec, sid, txctl};
+        with_bool(r.g711, [&](auto G) { with_bool(r.copy, [&](auto Y) { hipLaunchKernelGGL((k_vad<G, Y>), dim3(r.grid), dim3(r.threads), 0, s, a); }); });
     }
-    if (list && !rec) rec = reinterpret_cast<igdsp_vad_rec *>(static_cast<uint8_t *>(work) + r.counts_bytes);
-    const VadArgs a{g711, codec, pcm, ctl, vad_k(vad), C, F, n, state, kind, rec, sid, txctl};
-    with_bool(r.g711, [&](auto G) { with_bool(r.copy, [&](auto Y) { hipLaunchKernelGGL((k_vad<G, Y>), dim3(r.grid), dim3(r.threads), 0, s, a); }); });
-    if (hipError_t e = hipGetLastError(); e != hipSuccess || !list) return e;
-    uint32_t *counts = head + kLinkWorkHead / 4;
     const uint32_t mask = event_mask ? event_mask : (uint32_t)IGDSP_VAD_EVENT_DEFAULT;
-    hipLaunchKernelGGL(k_vad_list<false>, dim3(r.list_grid), dim3(kVadListWaves * 64), 0, s, rec, C, F, r.waves, mask, counts, events, event_cap);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_link_scan, dim3(1), dim3(kLinkScanThreads), 0, s, head, (uint64_t)F * r.waves, 1u, 1u, event_cap, event_count);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_vad_list<true>, dim3(r.list_grid), dim3(kVadListWaves * 64), 0, s, rec, C, F, r.waves, mask, counts, events, event_cap);
-    return hipGetLastError();
+    return launch_event_list(k_vad_list<false>, k_vad_list<true>, r, r.grid == 0, rec, C, F, mask, events, event_cap, event_count, work, s);
 }
 
 }  // namespace igdsp

@@ -579,6 +579,30 @@ inline LinkRoute link_route(uint32_t C, uint32_t T, bool list)
     return r;
 }
 
+// ---- the event list behind a stage's dense records [F][C] (igdsp_tone_detect, igdsp_vad_run; launch_event_list): the records lie in
+// d_rec, or in d_work behind the counts when there is none; the stage's list kernel counts the event lanes per (frame, wave of 64
+// channels), k_link_scan turns the counts into offsets and writes the two totals, the list kernel's second pass stores the events.
+constexpr int kListWaves = 4;                             // waves per block of a list kernel, independent of each other
+struct ListRoute {
+    uint32_t waves = 0;                    // waves of 64 channels: the counts' row
+    uint32_t list_grid = 0;                // the list kernel, both passes (0: no list)
+    uint64_t counts_bytes = 0;             // d_work: head + counts, rounded to 16
+    uint64_t work_bytes = 0;               // d_work in all: + the records when d_rec is NULL
+};
+inline uint64_t list_counts_bytes(uint32_t C, uint32_t F) { return kLinkWorkHead + (((uint64_t)F * link_waves(C) * 4u + 15u) & ~15ull); }
+inline uint64_t list_work_bytes(uint32_t C, uint32_t F, bool with_rec, uint32_t rec_bytes) { return list_counts_bytes(C, F) + (with_rec ? 0u : (uint64_t)C * F * rec_bytes); }
+inline ListRoute list_route(uint32_t C, uint32_t F, bool list, bool with_rec, uint32_t rec_bytes)
+{
+    ListRoute r;
+    r.waves = link_waves(C);
+    if (list) {
+        r.list_grid = (uint32_t)(((uint64_t)F * r.waves + kListWaves - 1u) / kListWaves);
+        r.counts_bytes = list_counts_bytes(C, F);
+        r.work_bytes = list_work_bytes(C, F, with_rec, rec_bytes);
+    }
+    return r;
+}
+
 // ---- igdsp_jb_receive (launch_jb_receive): k_jb_receive<COPY>.  A wave owns kJbCh consecutive channels for the ticks
 // of one part (<= kJbPart ticks).  Lanes 0 .. kJbCh - 1 step their channel's state machine over the part's arrivals with the ring tags in
 // LDS and leave a source descriptor per (tick, channel) there: an arrival of the part, a ring slot, or none; then the whole wave writes
@@ -1065,38 +1089,26 @@ inline SpecRoute spec_route(uint32_t C, uint32_t F, uint32_t n)
 // cosine and sine values), and per channel 128 + 256 values v: the history and the frame, which the 16 lanes read as broadcasts.  The
 // block walks the distinct plans of its channels one after the other (one pass when they share a plan).  E0: how evaluation 0's window
 // is aligned (n % 8 == 0: 8-byte reads, n % 4 == 0: dwords, else halves).  Registers: the route is written for kTdetResident blocks per CU (80 VGPRs).
-// The list: the records are dense (in d_rec, or in d_work when there is none); k_tdet_list counts the event lanes per (frame, wave of 64
-// channels), k_link_scan turns the counts into offsets and writes the two totals, k_tdet_list<true> stores the events.
+// The list: ListRoute.
 constexpr int kTdetWaves = 8;                             // waves per block
 constexpr uint32_t kTdetChans = kTdetWaves * 4u;          // channels per block
 constexpr uint32_t kTdetResident = 3;                     // blocks per CU: 3 x 40 KiB of LDS, 6 waves per SIMD
 constexpr uint32_t kTdetBuf = 128u + 256u;                // values per channel in LDS
 constexpr uint32_t kTdetLdsBytes = 128u * 16u * 8u + kTdetChans * kTdetBuf * 2u + kTdetChans * 4u;   // table, buffers, the channels' plans
-constexpr int kTdetListWaves = 4;
-struct TdetRoute {
+struct TdetRoute : ListRoute {             // the list: k_tdet_list
     uint32_t grid = 0, threads = 0, lds = 0;
     uint32_t e0 = 0;                       // k_tdet<, E0>: how evaluation 0's window is aligned in LDS (0: n % 8 == 0, 1: n % 4 == 0, 2: else)
-    uint32_t waves = 0;                    // waves of 64 channels: the counts' row
-    uint32_t list_grid = 0;                // k_tdet_list, both passes (0: no list)
-    uint64_t counts_bytes = 0;             // d_work: head + counts, rounded to 16
-    uint64_t work_bytes = 0;               // d_work in all: + the records when d_rec is NULL
 };
-inline uint64_t tdet_counts_bytes(uint32_t C, uint32_t F) { return kLinkWorkHead + (((uint64_t)F * link_waves(C) * 4u + 15u) & ~15ull); }
-inline uint64_t tdet_work_bytes(uint32_t C, uint32_t F, bool with_rec) { return tdet_counts_bytes(C, F) + (with_rec ? 0u : (uint64_t)C * F * 8u); }
+inline uint64_t tdet_work_bytes(uint32_t C, uint32_t F, bool with_rec) { return list_work_bytes(C, F, with_rec, sizeof(igdsp_tdet_rec)); }
 inline TdetRoute tdet_route(uint32_t C, uint32_t F, uint32_t n, bool list, bool with_rec)
 {
     TdetRoute r;
     if ((uint64_t)C * F == 0 || (uint64_t)C * F >= 0xFFFFFFE0ull || n < 2u || n > IGDSP_MAX_PAYLOAD || (n & 1u)) return r;
+    static_cast<ListRoute &>(r) = list_route(C, F, list, with_rec, sizeof(igdsp_tdet_rec));
     r.grid = (uint32_t)(((uint64_t)C + kTdetChans - 1u) / kTdetChans);
     r.threads = kTdetWaves * 64;
     r.lds = kTdetLdsBytes;
     r.e0 = n % 8u == 0u ? 0u : (n % 4u == 0u ? 1u : 2u);
-    r.waves = link_waves(C);
-    if (list) {
-        r.list_grid = (uint32_t)(((uint64_t)F * r.waves + kTdetListWaves - 1u) / kTdetListWaves);
-        r.counts_bytes = tdet_counts_bytes(C, F);
-        r.work_bytes = tdet_work_bytes(C, F, with_rec);
-    }
     return r;
 }
 
@@ -1163,7 +1175,7 @@ inline AgcRoute agc_route(uint32_t C, uint32_t F, uint32_t n, bool g711, bool ya
 // busy, no reduction) and keeps A[k].  A wave is four channels, a block kVadWaves waves.  LDS: the level table times n, per channel the
 // row twice and the rare path's arrays (A, R, a, the payload).  Registers: the route is written for kVadResident blocks per CU (6 waves per SIMD, 80 VGPRs: at 64 the
 // PCM form spills).
-// The list: the records are dense (in d_rec, or in d_work when there is none), counted and stored as igdsp_tone_detect's.
+// The list: ListRoute.
 constexpr int kVadWaves = 4;                              // waves per block
 constexpr uint32_t kVadLanes = 16;                        // lanes per channel
 constexpr uint32_t kVadChans = kVadWaves * 4u;            // channels per block
@@ -1171,52 +1183,45 @@ constexpr uint32_t kVadResident = 6;                      // blocks per CU
 constexpr uint32_t kVadPad = 16;                          // zeros in front of the row: the highest lane's lag is 15
 constexpr uint32_t kVadBuf = kVadPad + 256u + 8u;         // values per channel in LDS: zeros, the row, zeros (the second copy's last pair ends in one)
 constexpr uint32_t kVadLdsBytes = 128u * 8u + kVadChans * (kVadBuf * 2u + 256u * 2u + 3u * 12u * 8u + 16u);   // table; row, its second copy, A, R, a, payload
-constexpr int kVadListWaves = 4;
-struct VadRoute {
+struct VadRoute : ListRoute {              // the list: k_vad_list
     uint32_t grid = 0, threads = 0, lds = 0;
     bool g711 = false, copy = false;       // k_vad<IN_G711, COPY>
     uint32_t pieces = 0;                   // pieces of 8 samples per row: lanes p and p + 16 of the 16 take them in two turns
-    uint32_t waves = 0;                    // waves of 64 channels: the counts' row
-    uint32_t list_grid = 0;                // k_vad_list, both passes (0: no list)
-    uint64_t counts_bytes = 0;             // d_work: head + counts, rounded to 16
-    uint64_t work_bytes = 0;               // d_work in all: + the records when d_rec is NULL
 };
-inline uint64_t vad_counts_bytes(uint32_t C, uint32_t F) { return kLinkWorkHead + (((uint64_t)F * link_waves(C) * 4u + 15u) & ~15ull); }
-inline uint64_t vad_work_bytes(uint32_t C, uint32_t F, bool with_rec) { return vad_counts_bytes(C, F) + (with_rec ? 0u : (uint64_t)C * F * 16u); }
+inline uint64_t vad_work_bytes(uint32_t C, uint32_t F, bool with_rec) { return list_work_bytes(C, F, with_rec, sizeof(igdsp_vad_rec)); }
 inline VadRoute vad_route(uint32_t C, uint32_t F, uint32_t n, bool g711, bool yardstick, bool list, bool with_rec)
 {
     VadRoute r;
     if ((uint64_t)C * F == 0 || (uint64_t)C * F >= 0xFFFFFFE0ull || n < 16u || n > IGDSP_MAX_PAYLOAD || (n & 7u)) return r;
+    static_cast<ListRoute &>(r) = list_route(C, F, list, with_rec, sizeof(igdsp_vad_rec));
     r.grid = (uint32_t)(((uint64_t)C + kVadChans - 1u) / kVadChans);
     r.threads = kVadWaves * 64;
     r.lds = kVadLdsBytes;
     r.g711 = g711;
     r.copy = yardstick;
     r.pieces = n / 8u;
-    r.waves = link_waves(C);
-    if (list) {
-        r.list_grid = (uint32_t)(((uint64_t)F * r.waves + kVadListWaves - 1u) / kVadListWaves);
-        r.counts_bytes = vad_counts_bytes(C, F);
-        r.work_bytes = vad_work_bytes(C, F, with_rec);
-    }
     return r;
 }
 
+// ---- the lane-per-channel tile (k_cng, k_filt): a lane owns a channel, a block is one wave, and the frame's rows lie in LDS as a tile
+// that the wave fills and stores piece by piece (16 bytes of a row; the pieces of a tile are consecutive in memory).  A row is
+// n / 2 + 1 dwords apart (odd: the lanes' dword accesses of one sample pair fall into different banks); behind the rows a byte per
+// row for the stage's own use.  Item i of a pass is row i / P, piece i % P, the division done by the multiplier tile_inv(P): exact
+// below 2^11 items for P <= 32 (on the device: tile_item, tile_piece, igdsp_lanes.h).
+constexpr uint32_t tile_row_dwords(uint32_t n) { return n / 2u + 1u; }
+constexpr uint32_t tile_lds_bytes(uint32_t chans, uint32_t n) { return chans * tile_row_dwords(n) * 4u + chans; }
+constexpr uint32_t tile_inv(uint32_t pieces) { return (1u << 20) / pieces + 1u; }
+
 // ---- igdsp_cng_run (launch_cng): k_cng<IN, COPY>.  A lane owns a channel for the whole launch (the lattice is serial in the sample: the
-// parallelism is across channels); a block is one wave and kCngChans channels.  LDS: the frame's kCngChans rows as a tile, a row
-// n / 2 + 1 dwords apart (odd: the lanes' dword stores of one sample pair fall into different banks), and a byte per row that says
-// who fills it.  The wave fills the voice rows and stores the whole tile piece by piece (16 bytes of a row, pieces of a tile are
-// consecutive in memory); item i of a pass is row i / P, piece i % P, the division done by the multiplier `inv` (exact below 2^11
-// items for P <= 32).  Registers and LDS: the route is written for kCngResident blocks per CU, one wave per SIMD at 65 536 channels
+// parallelism is across channels); a block is one wave and kCngChans channels.  LDS: the frame's kCngChans rows as the lane-per-channel tile above,
+// the row's byte says who fills it.  The wave fills the voice rows and stores the whole tile.  Registers and LDS: the route is written for kCngResident blocks per CU, one wave per SIMD at 65 536 channels
 // (128 VGPRs; 33 088 bytes of LDS at n = 256).
 constexpr uint32_t kCngChans = 64;                        // channels per block: the lanes of its one wave
 constexpr uint32_t kCngResident = 4;                      // blocks per CU
 constexpr uint32_t kCngVgprs = 128;
 constexpr int kCngNone = 0, kCngG711 = 1, kCngPcm = 2;    // k_cng<IN, >: the voice input
-constexpr uint32_t cng_row_dwords(uint32_t n) { return n / 2u + 1u; }
-constexpr uint32_t cng_lds_bytes(uint32_t n) { return kCngChans * cng_row_dwords(n) * 4u + kCngChans; }
-constexpr uint32_t cng_inv(uint32_t pieces) { return (1u << 20) / pieces + 1u; }
-static_assert(kCngResident * cng_lds_bytes(256) <= 160u * 1024u, "the resident blocks' tiles fit a CU's LDS");
+constexpr uint32_t cng_row_dwords(uint32_t n) { return tile_row_dwords(n); }   // the name the route driver checks the tile by
+static_assert(kCngResident * tile_lds_bytes(kCngChans, 256) <= 160u * 1024u, "the resident blocks' tiles fit a CU's LDS");
 struct CngRoute {
     uint32_t grid = 0, threads = 0, lds = 0;
     int in = kCngNone;                     // k_cng<IN, COPY>
@@ -1231,22 +1236,20 @@ inline CngRoute cng_route(uint32_t C, uint32_t F, uint32_t n, bool g711, bool pc
     if ((uint64_t)C * F == 0 || (uint64_t)C * F >= 0xFFFFFFE0ull || n < 16u || n > IGDSP_MAX_PAYLOAD || (n & 7u)) return r;
     r.grid = (uint32_t)(((uint64_t)C + kCngChans - 1u) / kCngChans);
     r.threads = 64;
-    r.lds = cng_lds_bytes(n);
+    r.lds = tile_lds_bytes(kCngChans, n);
     r.in = g711 ? kCngG711 : (pcm ? kCngPcm : kCngNone);
     r.copy = yardstick;
     r.pieces = n / 8u;
     r.passes = (kCngChans * r.pieces + 63u) / 64u;
-    r.inv = cng_inv(r.pieces);
+    r.inv = tile_inv(r.pieces);
     return r;
 }
 
 // ---- igdsp_filt_run (launch_filt): k_filt<IN, S, COPY>.  A lane owns a channel for the whole launch (the recurrence is serial in the
 // sample: the parallelism is across channels); a block is one wave and kFiltChans channels.  S = 1, 2 or 4 sections run per sample: the
 // entry's max_sections rounded up (a channel with fewer runs identity sections, so the lanes of a wave do not diverge); the yardstick
-// runs none and is built once per input form (S = 1).  LDS: the frame's kFiltChans rows as a tile, filtered in place, a row n / 2 + 1
-// dwords apart (odd: the lanes' dword accesses of one sample pair fall into different banks), and a byte per row for its law.  The wave
-// fills the tile and stores it piece by piece (16 bytes of a row; pieces of a tile are consecutive in memory); item i of a pass is
-// row i / P, piece i % P, the division done by the multiplier `inv` as in cng_route.  The NEXT frame's pieces are loaded into
+// runs none and is built once per input form (S = 1).  LDS: the frame's kFiltChans rows as the lane-per-channel tile above,
+// filtered in place, the row's byte its law.  The wave fills the tile and stores it.  The NEXT frame's pieces are loaded into
 // registers before the sample loop and written to the tile behind the store pass: the first kFiltAhead turns of 16 bytes (PCM) or 8
 // (codes) per lane, 64 or 32 VGPRs; a row's turns past those (n > 128) are loaded behind the store pass.  Registers and LDS: the route is written for kFiltResident blocks per CU, one wave per SIMD at
 // 65 536 channels and never more than two (kFiltVgprs = 256 of a SIMD's 512; 33 088 bytes of LDS at n = 256).
@@ -1257,10 +1260,8 @@ constexpr uint32_t kFiltMaxPieces = IGDSP_MAX_PAYLOAD / 8;   // pieces of 8 samp
 constexpr uint32_t kFiltAhead = 16;                       // turns of the next frame held in registers through the sample loop
 static_assert(2u * kFiltAhead == kFiltMaxPieces, "the early and the late turns cover a row");
 constexpr int kFiltG711 = 1, kFiltPcm = 2;                // k_filt<IN, , >
-constexpr uint32_t filt_row_dwords(uint32_t n) { return n / 2u + 1u; }
-constexpr uint32_t filt_lds_bytes(uint32_t n) { return kFiltChans * filt_row_dwords(n) * 4u + kFiltChans; }
-constexpr uint32_t filt_inv(uint32_t pieces) { return (1u << 20) / pieces + 1u; }
-static_assert(kFiltResident * filt_lds_bytes(256) <= 160u * 1024u && 2u * kFiltVgprs <= 512u, "the resident blocks' tiles fit a CU's LDS, two waves a SIMD's registers");
+constexpr uint32_t filt_row_dwords(uint32_t n) { return tile_row_dwords(n); }  // the name the route driver checks the tile by
+static_assert(kFiltResident * tile_lds_bytes(kFiltChans, 256) <= 160u * 1024u && 2u * kFiltVgprs <= 512u, "the resident blocks' tiles fit a CU's LDS, two waves a SIMD's registers");
 struct FiltRoute {
     uint32_t grid = 0, threads = 0, lds = 0;
     int in = 0, sections = 0;              // k_filt<IN, S, COPY>
@@ -1275,13 +1276,13 @@ inline FiltRoute filt_route(uint32_t C, uint32_t F, uint32_t n, bool g711, uint3
     if ((uint64_t)C * F == 0 || (uint64_t)C * F >= 0xFFFFFFE0ull || n < 8u || n > IGDSP_MAX_PAYLOAD || (n & 7u) || max_sections > 4u) return r;
     r.grid = (uint32_t)(((uint64_t)C + kFiltChans - 1u) / kFiltChans);
     r.threads = 64;
-    r.lds = filt_lds_bytes(n);
+    r.lds = tile_lds_bytes(kFiltChans, n);
     r.in = g711 ? kFiltG711 : kFiltPcm;
     r.max_sections = max_sections == 0u ? 4u : max_sections;
     r.sections = yardstick ? 1 : (r.max_sections <= 2u ? (int)r.max_sections : 4);
     r.copy = yardstick;
     r.pieces = n / 8u;
-    r.inv = filt_inv(r.pieces);
+    r.inv = tile_inv(r.pieces);
     return r;
 }
 

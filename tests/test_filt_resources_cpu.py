@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 RESIDENT, VGPRS, CU_LDS = 4, 256, 160 * 1024     # kFiltResident, kFiltVgprs (csrc/igdsp_route.h)
-LDS_MAX = 64 * (256 // 2 + 1) * 4 + 64            # filt_lds_bytes(256): dynamic, asked for by the launcher
+LDS_MAX = 64 * (256 // 2 + 1) * 4 + 64            # tile_lds_bytes(kFiltChans, 256): dynamic, asked for by the launcher
 
 
 @pytest.fixture(scope="module")
