@@ -19,7 +19,7 @@ INCLUDE = os.path.join(ROOT, "include")
 LIB = os.path.join(PKG, "libigdsp.so")
 HOST_LIB = os.path.join(PKG, "libigdsp_host.so")
 
-DEVICE_SOURCES = ["igdsp_k_meter.hip", "igdsp_k_packets.hip", "igdsp_k_codec.hip", "igdsp_k_misc.hip", "igdsp_k_tx.hip", "igdsp_k_txstage.hip", "igdsp_k_conf.hip", "igdsp_k_bss.hip", "igdsp_k_ptt.hip", "igdsp_k_link.hip", "igdsp_k_jb.hip", "igdsp_k_plc.hip", "igdsp_k_snd.hip", "igdsp_k_tone.hip", "igdsp_k_rs.hip", "igdsp_k_dbuf.hip", "igdsp_k_spec.hip", "igdsp_k_tdet.hip", "igdsp_k_ec.hip", "igdsp_k_agc.hip", "igdsp_k_vad.hip", "igdsp_k_cng.hip", "igdsp_k_filt.hip", "igdsp_k_ns.hip", "igdsp_k_srtp.hip", "igdsp_k_rtcp.hip", "igdsp_capi.hip", "igdsp_capi_ctx.hip", "igdsp_capi_tx.hip", "igdsp_capi_bench.hip", "igdsp_capi_snd.hip", "igdsp_capi_tone.hip", "igdsp_capi_rs.hip", "igdsp_capi_dbuf.hip", "igdsp_capi_spec.hip", "igdsp_capi_tdet.hip", "igdsp_capi_ec.hip", "igdsp_capi_agc.hip", "igdsp_capi_vad.hip", "igdsp_capi_cng.hip", "igdsp_capi_filt.hip", "igdsp_capi_ns.hip", "igdsp_capi_srtp.hip", "igdsp_capi_rtcp.hip", "igdsp_io.hip"]
+DEVICE_SOURCES = ["igdsp_k_meter.hip", "igdsp_k_packets.hip", "igdsp_k_codec.hip", "igdsp_k_misc.hip", "igdsp_k_tx.hip", "igdsp_k_txstage.hip", "igdsp_k_conf.hip", "igdsp_k_bss.hip", "igdsp_k_ptt.hip", "igdsp_k_link.hip", "igdsp_k_jb.hip", "igdsp_k_plc.hip", "igdsp_k_snd.hip", "igdsp_k_tone.hip", "igdsp_k_rs.hip", "igdsp_k_dbuf.hip", "igdsp_k_spec.hip", "igdsp_k_tdet.hip", "igdsp_k_ec.hip", "igdsp_k_agc.hip", "igdsp_k_vad.hip", "igdsp_k_cng.hip", "igdsp_k_filt.hip", "igdsp_k_ns.hip", "igdsp_k_srtp.hip", "igdsp_k_rtcp.hip", "igdsp_k_srtp_gcm.hip", "igdsp_capi.hip", "igdsp_capi_ctx.hip", "igdsp_capi_tx.hip", "igdsp_capi_bench.hip", "igdsp_capi_snd.hip", "igdsp_capi_tone.hip", "igdsp_capi_rs.hip", "igdsp_capi_dbuf.hip", "igdsp_capi_spec.hip", "igdsp_capi_tdet.hip", "igdsp_capi_ec.hip", "igdsp_capi_agc.hip", "igdsp_capi_vad.hip", "igdsp_capi_cng.hip", "igdsp_capi_filt.hip", "igdsp_capi_ns.hip", "igdsp_capi_srtp.hip", "igdsp_capi_rtcp.hip", "igdsp_capi_srtp_gcm.hip", "igdsp_io.hip"]
 HOST_SOURCES = ["igdsp_host.cpp"]          # C++ mirror of the reference's adapter/hook interface
 HEADERS = sorted(h for h in os.listdir(CSRC) if h.endswith(".h")) + [os.path.join(INCLUDE, "igdsp.h")]   # every header: none can be forgotten
 

@@ -192,6 +192,14 @@ SRTP_STATE = np.dtype([("tag", "<u4"), ("roc", "<u4"), ("s_l", "<u2"), ("have_s_
                        ("mid_o", "<u4", (5,)), ("reserved2", "<u4", (4,))], align=True)            # igdsp_srtp_state, 288 bytes
 SRTP_REC = np.dtype([("roc_used", "<u4"), ("size_out", "<u2"), ("flags", "u1"), ("reserved", "u1")], align=True)   # igdsp_srtp_rec, 8 bytes
 assert SRTP_STATE.itemsize == 288 and SRTP_REC.itemsize == 8
+# SRTP with AES-GCM (RFC 7714, AEAD_AES_128_GCM / AEAD_AES_256_GCM): igdsp_srtp_gcm_protect / igdsp_srtp_gcm_unprotect / igdsp_srtp_gcm_*_packet;
+# the controls, the record and its flags are SRTP's
+SRTP_GCM_TAG, SRTP_GCM_TAG_LEN = 0x53524700, 16
+SRTP_GCM_STATE = np.dtype([("tag", "<u4"), ("roc", "<u4"), ("s_l", "<u2"), ("have_s_l", "<u2"), ("reserved", "<u4"), ("window", "<u8"), ("n_ok", "<u4"),
+                           ("n_auth_fail", "<u4"), ("n_replay", "<u4"), ("n_malformed", "<u4"), ("rk", "<u4", (60,)), ("salt", "u1", (12,)), ("pad", "<u4"),
+                           ("h", "u1", (16,)), ("reserved2", "<u4", (2,))], align=True)            # igdsp_srtp_gcm_state, 320 bytes
+assert SRTP_GCM_STATE.itemsize == 320 and SRTP_GCM_STATE.fields["rk"][1] == 40 and SRTP_GCM_STATE.fields["salt"][1] == 280 and SRTP_GCM_STATE.fields["h"][1] == 296
+assert all(SRTP_GCM_STATE.fields[k][1] == SRTP_STATE.fields[k][1] for k in SRTP_STATE.names[:10])   # the ten words that move are SRTP's
 CHAN_PROBE = np.dtype([("run", "<u4"), ("alarms", "<u4")], align=True)
 # the jitter buffer (igdsp_jb_receive / igdsp_jb_report)
 JB_STATE = np.dtype(
@@ -431,6 +439,11 @@ PROTOTYPES = [
     ("igdsp_rtcp_parse", _int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp]),
     ("igdsp_srtcp_protect", _int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _u32, _vp, _vp, _vp]),
     ("igdsp_srtcp_unprotect", _int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _u32, _vp, _vp, _vp]),
+    ("igdsp_srtp_gcm_derive", _int, [_vp, _u32, _u32, _vp]),
+    ("igdsp_srtp_gcm_protect_packet", _int, [_vp, _u32, _vp, _u32, _vp, _u32, C.POINTER(_u32), _vp]),
+    ("igdsp_srtp_gcm_unprotect_packet", _int, [_vp, _u32, _vp, _u32, _vp, _u32, C.POINTER(_u32), _vp]),
+    ("igdsp_srtp_gcm_protect", _int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _u32, _vp, _vp, _vp]),
+    ("igdsp_srtp_gcm_unprotect", _int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _u32, _vp, _vp, _vp]),
     ("igdsp_g726_reorder", _int, [_vp, _vp, _vp, _u64, _int, _vp]),
     ("igdsp_gen_uniform", _int, [_vp, _vp, _u64, _u64, _u64, _vp]),
     ("igdsp_dev_alloc", _int, [_vp, C.POINTER(_vp), C.c_size_t]),
@@ -475,7 +488,7 @@ INTERNAL_MORE_TWIN = {"igdsp_internal_dbuf_move": "igdsp_dbuf_run", "igdsp_inter
                       "igdsp_internal_agc_move": "igdsp_agc_run", "igdsp_internal_vad_move": "igdsp_vad_run",
                       "igdsp_internal_cng_move": "igdsp_cng_run", "igdsp_internal_filt_move": "igdsp_filt_run",
                       "igdsp_internal_ns_move": "igdsp_ns_run", "igdsp_internal_srtp_move": "igdsp_srtp_protect",
-                      "igdsp_internal_srtcp_move": "igdsp_srtcp_protect",
+                      "igdsp_internal_srtcp_move": "igdsp_srtcp_protect", "igdsp_internal_srtp_gcm_move": "igdsp_srtp_gcm_protect",
                       "igdsp_internal_rtcp_build_move": "igdsp_rtcp_build", "igdsp_internal_rtcp_parse_move": "igdsp_rtcp_parse"}
 INTERNAL_MORE = {name: _PUBLIC[twin] for name, twin in INTERNAL_MORE_TWIN.items()}
 
@@ -896,6 +909,41 @@ def srtp_packet(state, packet, unprotect: bool = False, ctl: int = SRTP_RUN, cap
             rec.ctypes.data_as(_vp))
     if rc != 0:
         raise IgdspError(rc, "igdsp_srtp_unprotect_packet" if unprotect else "igdsp_srtp_protect_packet")
+    return out, int(size_out.value), rec
+
+
+def srtp_gcm_derive(key_salt, key_bytes: int = None, roc0: int = 0, raw: bool = False):
+    """igdsp_srtp_gcm_derive (host only, no GPU): key_bytes (16 or 32; default: what the length says) of master key and 12 of master salt
+    -> one SRTP_GCM_STATE record (RFC 3711 4.3.1 with AES of the key's size, labels 0 and 2; the key schedule of k_e, k_s, H).  raw: the
+    return code alone."""
+    ks = np.frombuffer(bytes(key_salt), np.uint8).copy()
+    key_bytes = ks.size - 12 if key_bytes is None else int(key_bytes)
+    assert ks.size == key_bytes + 12 or key_bytes not in (16, 32)          # (a key size that is none is refused before a byte is read)
+    out = np.zeros((), SRTP_GCM_STATE)
+    rc = load().igdsp_srtp_gcm_derive(ks.ctypes.data_as(_vp), key_bytes, int(roc0) & 0xFFFFFFFF, out.ctypes.data_as(_vp))
+    if raw:
+        return int(rc)
+    if rc != 0:
+        raise IgdspError(rc, "igdsp_srtp_gcm_derive")
+    return out
+
+
+def srtp_gcm_packet(state, packet, unprotect: bool = False, ctl: int = SRTP_RUN, capacity: int = SRTP_MAX_PACKET, in_place: bool = False, fill: int = 0xA5):
+    """igdsp_srtp_gcm_protect_packet / igdsp_srtp_gcm_unprotect_packet (host only, no GPU): one packet of one leg; state an SRTP_GCM_STATE
+    record updated in place; arguments and return as srtp_packet."""
+    assert state.dtype == SRTP_GCM_STATE and state.flags["C_CONTIGUOUS"] and state.flags["WRITEABLE"]
+    pkt = np.frombuffer(bytes(packet), np.uint8).copy()
+    out = np.full(max(int(capacity), 1), fill, np.uint8)
+    if in_place:
+        assert pkt.size <= capacity
+        out[:pkt.size] = pkt
+    src = out if in_place else (pkt if pkt.size else np.zeros(1, np.uint8))
+    size_out, rec = _u32(0), np.zeros((), SRTP_REC)
+    fn = load().igdsp_srtp_gcm_unprotect_packet if unprotect else load().igdsp_srtp_gcm_protect_packet
+    rc = fn(state.ctypes.data_as(_vp), int(ctl), src.ctypes.data_as(_vp), pkt.size, out.ctypes.data_as(_vp), int(capacity), C.byref(size_out),
+            rec.ctypes.data_as(_vp))
+    if rc != 0:
+        raise IgdspError(rc, "igdsp_srtp_gcm_unprotect_packet" if unprotect else "igdsp_srtp_gcm_protect_packet")
     return out, int(size_out.value), rec
 
 
@@ -1338,6 +1386,16 @@ class Context:
     def srtp_unprotect(self, state, packets, sizes, C_, F_, pkt_stride, out, out_stride, sizes_out, rec=None, ctl=None, stream=None):
         """igdsp_srtp_unprotect: sizes include the tag; a refused packet gets size 0 and its output slot is not written."""
         self.srtp_protect(state, packets, sizes, C_, F_, pkt_stride, out, out_stride, sizes_out, rec=rec, ctl=ctl, unprotect=True, stream=stream)
+
+    def srtp_gcm_protect(self, state, packets, sizes, C_, F_, pkt_stride, out, out_stride, sizes_out, rec=None, ctl=None, unprotect=False, stream=None):
+        """igdsp_srtp_gcm_protect (unprotect: igdsp_srtp_gcm_unprotect): srtp_protect's arguments; state [C] SRTP_GCM_STATE from
+        srtp_gcm_derive, key sizes side by side allowed; a protected packet is 16 bytes longer."""
+        fn, name = (self.L.igdsp_srtp_gcm_unprotect, "igdsp_srtp_gcm_unprotect") if unprotect else (self.L.igdsp_srtp_gcm_protect, "igdsp_srtp_gcm_protect")
+        self._ck(fn(self.h, _ptr(ctl), _ptr(packets), _ptr(sizes), C_, F_, pkt_stride, _ptr(state), _ptr(out), out_stride, _ptr(sizes_out), _ptr(rec), stream), name)
+
+    def srtp_gcm_unprotect(self, state, packets, sizes, C_, F_, pkt_stride, out, out_stride, sizes_out, rec=None, ctl=None, stream=None):
+        """igdsp_srtp_gcm_unprotect: sizes include the tag; a refused packet gets size 0 and its output slot is not written."""
+        self.srtp_gcm_protect(state, packets, sizes, C_, F_, pkt_stride, out, out_stride, sizes_out, rec=rec, ctl=ctl, unprotect=True, stream=stream)
 
     def srtcp_protect(self, state, packets, sizes, C_, F_, pkt_stride, out, out_stride, sizes_out, rec=None, ctl=None, unprotect=False, stream=None):
         """igdsp_srtcp_protect (unprotect: igdsp_srtcp_unprotect): srtp_protect's arguments on RTCP packets; state [C] SRTP_STATE from

@@ -674,7 +674,7 @@ inline Verdict ns_run(P d_g711, P d_codec, P d_pcm, P d_ctl, const igdsp_ns_cfg 
 // ---- SRTP: one rule for igdsp_srtp_protect and igdsp_srtp_unprotect.  The strides are checked whether or not there is work.  In place
 // is the one overlap allowed: d_out == d_packets with equal strides, d_sizes_out == d_sizes
 inline Verdict srtp_run(P d_ctl, P d_packets, P d_sizes, uint32_t C, uint32_t F, uint32_t pkt_stride, P d_state, P d_out, uint32_t out_stride, P d_sizes_out,
-                        P d_rec)
+                        P d_rec, uint64_t state_bytes = sizeof(igdsp_srtp_state))
 {
     if (!stride_ok(pkt_stride, 12u) || !stride_ok(out_stride, 12u)) return kInvalid;
     if (empty(C, F)) return kNothing;
@@ -686,7 +686,7 @@ inline Verdict srtp_run(P d_ctl, P d_packets, P d_sizes, uint32_t C, uint32_t F,
     const uint64_t frames = (uint64_t)C * F;
     struct Buf { P p; uint64_t bytes; };
     const Buf ins[3] = {{d_ctl, frames}, {d_packets, frames * pkt_stride}, {d_sizes, frames * 2u}};
-    const Buf outs[4] = {{d_state, (uint64_t)C * sizeof(igdsp_srtp_state)}, {d_out, frames * out_stride}, {d_sizes_out, frames * 2u},
+    const Buf outs[4] = {{d_state, (uint64_t)C * state_bytes}, {d_out, frames * out_stride}, {d_sizes_out, frames * 2u},
                          {d_rec, frames * sizeof(igdsp_srtp_rec)}};
     for (int i = 0; i < 4; ++i) {
         for (int k = 0; k < 3; ++k) {
@@ -706,6 +706,14 @@ inline Verdict srtcp_run(P d_ctl, P d_packets, P d_sizes, uint32_t C, uint32_t F
                          P d_rec)
 {
     return srtp_run(d_ctl, d_packets, d_sizes, C, F, pkt_stride, d_state, d_out, out_stride, d_sizes_out, d_rec);
+}
+
+// ---- SRTP with AES-GCM: igdsp_srtp_gcm_protect and igdsp_srtp_gcm_unprotect take SRTP's arguments under SRTP's rule; the state is the
+// larger igdsp_srtp_gcm_state
+inline Verdict srtp_gcm_run(P d_ctl, P d_packets, P d_sizes, uint32_t C, uint32_t F, uint32_t pkt_stride, P d_state, P d_out, uint32_t out_stride, P d_sizes_out,
+                            P d_rec)
+{
+    return srtp_run(d_ctl, d_packets, d_sizes, C, F, pkt_stride, d_state, d_out, out_stride, d_sizes_out, d_rec, sizeof(igdsp_srtp_gcm_state));
 }
 
 // ---- RTCP.  The stride is checked whether or not there is work.  Build writes its packets, sizes, records and the state; parse its

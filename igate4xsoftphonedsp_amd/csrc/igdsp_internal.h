@@ -235,6 +235,11 @@ hipError_t launch_srtp(const LaunchCfg &cfg, int dir, const uint8_t *ctl, const 
 hipError_t launch_srtcp(const LaunchCfg &cfg, int dir, const uint8_t *ctl, const uint8_t *packets, const uint16_t *sizes, uint32_t C, uint32_t F,
                         uint32_t pkt_stride, igdsp_srtp_state *state, uint8_t *out, uint32_t out_stride, uint16_t *sizes_out, igdsp_srtp_rec *rec,
                         bool yardstick, hipStream_t s);
+// igdsp_srtp_gcm_protect / igdsp_srtp_gcm_unprotect: launch_srtp's arguments with the GCM state; yardstick as there (the 16 tag bytes go
+// out as zeros)
+hipError_t launch_srtp_gcm(const LaunchCfg &cfg, int dir, const uint8_t *ctl, const uint8_t *packets, const uint16_t *sizes, uint32_t C, uint32_t F,
+                           uint32_t pkt_stride, igdsp_srtp_gcm_state *state, uint8_t *out, uint32_t out_stride, uint16_t *sizes_out, igdsp_srtp_rec *rec,
+                           bool yardstick, hipStream_t s);
 // igdsp_rtcp_build: jb, rec and (together) cname, cname_len may be nullptr.  igdsp_rtcp_parse: rec may be nullptr.  yardstick: the
 // compute-free forms.  Build: the same loads, the size rule, a row of the packet's size filled with one loaded word, the same stores,
 // a record with the size and no flag, the state as read.  Parse: the same loads, tile traffic and row reads; the record is the size's

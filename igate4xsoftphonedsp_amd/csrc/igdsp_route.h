@@ -1370,6 +1370,27 @@ inline SrtpRoute srtcp_route(uint32_t C, uint32_t F, uint32_t pkt_stride, uint32
     return srtp_route(C, F, pkt_stride, out_stride, dir, yardstick);
 }
 
+// ---- igdsp_srtp_gcm_protect / igdsp_srtp_gcm_unprotect (launch_srtp_gcm): k_srtp_gcm<DIR, MOVE> has k_srtp's geometry (a lane a leg, 64
+// legs a wave and block, the 64 x 17-word tile, four turns a piece) and LDS of its own: the AES table, the tile, two words a row and
+// the lanes' round keys as [60][64] words (AES-256's schedule; a leg with a 128-bit key uses 44), and for GHASH the lanes' sixteen
+// multiples of H as [16][4][64] words (Shoup's 4-bit tables, 16 KiB) with sixteen reduction words.  A leg's key size is in its state, not
+// in the launch, so one instantiation per direction serves both.  37 696 bytes a block: kSrtpGcmResident = 4 blocks per CU fit its
+// 160 KiB and a fifth does not, so a SIMD holds one wave, which may take all of its 512 registers (kSrtpGcmVgprs).
+constexpr uint32_t kSrtpGcmResident = 4;
+constexpr uint32_t kSrtpGcmVgprs = 512;
+constexpr uint32_t kSrtpGcmRkWords = 60;
+constexpr uint32_t kSrtpGcmTabWords = 16u * 4u;
+constexpr uint32_t kSrtpGcmLdsBytes = 256u * 4u + kSrtpChans * kSrtpPitch * 4u + 2u * kSrtpChans * 4u + kSrtpGcmRkWords * kSrtpChans * 4u +
+                                      kSrtpGcmTabWords * kSrtpChans * 4u + 16u * 4u;   // table, tile, two words a row, round keys, multiples of H, reduction
+static_assert(kSrtpGcmResident * kSrtpGcmLdsBytes <= 160u * 1024u && (kSrtpGcmResident + 1u) * kSrtpGcmLdsBytes > 160u * 1024u &&
+              ((kSrtpGcmResident + 3u) / 4u) * kSrtpGcmVgprs <= 512u, "the resident blocks fit a CU, and no more do");
+inline SrtpRoute srtp_gcm_route(uint32_t C, uint32_t F, uint32_t pkt_stride, uint32_t out_stride, int dir, bool yardstick)
+{
+    SrtpRoute r = srtp_route(C, F, pkt_stride, out_stride, dir, yardstick);   // the grid, the strides' bounds; max_pieces: the last ciphertext
+    if (r.grid) r.lds = kSrtpGcmLdsBytes;                                     // block's slot may lie a piece behind the data's last
+    return r;
+}
+
 // ---- igdsp_rtcp_build (launch_rtcp_build): k_rtcp_build, and igdsp_rtcp_parse (launch_rtcp_parse): k_rtcp_parse.  A lane owns a leg for
 // the launch (the report's prior and the last SR heard are serial in its ticks); a block is one wave and kRtcpChans = 64 legs.  Build:
 // a row of the LDS tile is a whole packet, kRtcpRowWords = 34 words at a pitch of kRtcpRowPitch = 35 (odd), stored as kRtcpRowItems = 9

@@ -1416,6 +1416,36 @@ int LegSrtp::unprotect(const uint8_t *in, uint32_t size, uint8_t *out, uint32_t 
     return (int)n;
 }
 
+// ---- SRTP with AES-GCM on one leg and direction, no context needed
+LegSrtpGcm::LegSrtpGcm(const uint8_t *key_salt, uint32_t key_bytes, uint32_t roc0) : ctl(IGDSP_SRTP_RUN), resetNext(false)
+{
+    std::memset(&state, 0, sizeof(state));                   // no tag word: NO_KEY until a key is derived
+    std::memset(&last, 0, sizeof(last));
+    ok = key_salt && igdsp_srtp_gcm_derive(key_salt, key_bytes, roc0, &state) == IGDSP_OK;
+}
+
+void LegSrtpGcm::reset() { resetNext = true; }
+
+int LegSrtpGcm::protect(const uint8_t *in, uint32_t size, uint8_t *out, uint32_t out_capacity)
+{
+    if (!ok || !in || !out) return IGDSP_EINVAL;
+    uint32_t n = 0;
+    const uint32_t c = (resetNext && ctl == IGDSP_SRTP_RUN) ? (uint32_t)IGDSP_SRTP_RESET : ctl;
+    if (igdsp_srtp_gcm_protect_packet(&state, c, in, size, out, out_capacity, &n, &last) != IGDSP_OK) return IGDSP_EINVAL;
+    if (c == IGDSP_SRTP_RESET) resetNext = false;
+    return (int)n;
+}
+
+int LegSrtpGcm::unprotect(const uint8_t *in, uint32_t size, uint8_t *out, uint32_t out_capacity)
+{
+    if (!ok || !in || !out) return IGDSP_EINVAL;
+    uint32_t n = 0;
+    const uint32_t c = (resetNext && ctl == IGDSP_SRTP_RUN) ? (uint32_t)IGDSP_SRTP_RESET : ctl;
+    if (igdsp_srtp_gcm_unprotect_packet(&state, c, in, size, out, out_capacity, &n, &last) != IGDSP_OK) return IGDSP_EINVAL;
+    if (c == IGDSP_SRTP_RESET) resetNext = false;
+    return (int)n;
+}
+
 // ---- RTCP on one leg, clear or under SRTCP, no context needed
 LegRtcp::LegRtcp(uint32_t ssrc_, const char *cname_, const uint8_t *key_salt, const uint8_t *peer_key_salt, uint32_t index0)
     : secure(key_salt && peer_key_salt), ssrc(ssrc_), cnameLen(0)
@@ -1513,6 +1543,35 @@ int igdsp_host_srtp_rec(void *v, igdsp_srtp_rec *out)
     return IGDSP_OK;
 }
 void igdsp_host_srtp_reset(void *v) { if (v) static_cast<LegSrtp *>(v)->reset(); }
+
+void *igdsp_host_srtp_gcm_new(const uint8_t *key_salt, uint32_t key_bytes, uint32_t roc0)
+{
+    LegSrtpGcm *e = new (std::nothrow) LegSrtpGcm(key_salt, key_bytes, roc0);
+    if (e && !e->ok) { delete e; e = nullptr; }
+    return e;
+}
+void igdsp_host_srtp_gcm_free(void *v) { delete static_cast<LegSrtpGcm *>(v); }
+int igdsp_host_srtp_gcm_control(void *v, uint32_t ctl)
+{
+    if (!v || ctl > IGDSP_SRTP_BYPASS) return IGDSP_EINVAL;
+    static_cast<LegSrtpGcm *>(v)->ctl = ctl;
+    return IGDSP_OK;
+}
+int igdsp_host_srtp_gcm_protect(void *v, const uint8_t *in, uint32_t size, uint8_t *out, uint32_t out_capacity)
+{
+    return v ? static_cast<LegSrtpGcm *>(v)->protect(in, size, out, out_capacity) : IGDSP_EINVAL;
+}
+int igdsp_host_srtp_gcm_unprotect(void *v, const uint8_t *in, uint32_t size, uint8_t *out, uint32_t out_capacity)
+{
+    return v ? static_cast<LegSrtpGcm *>(v)->unprotect(in, size, out, out_capacity) : IGDSP_EINVAL;
+}
+int igdsp_host_srtp_gcm_rec(void *v, igdsp_srtp_rec *out)
+{
+    if (!v || !out) return IGDSP_EINVAL;
+    *out = static_cast<LegSrtpGcm *>(v)->last;
+    return IGDSP_OK;
+}
+void igdsp_host_srtp_gcm_reset(void *v) { if (v) static_cast<LegSrtpGcm *>(v)->reset(); }
 
 // ---- conference receive levels, no context needed
 void *igdsp_host_levels_new(uint32_t n_channels)

@@ -441,6 +441,26 @@ private:
     bool resetNext;
 };
 
+// LegSrtp for the AEAD suites: one igdsp_srtp_gcm_state through igdsp_srtp_gcm_protect_packet / igdsp_srtp_gcm_unprotect_packet.  RFC 7714,
+// AEAD_AES_128_GCM (key_bytes 16) or AEAD_AES_256_GCM (32), 16-byte tags, RTP only; key_salt is the key_bytes + 12 bytes of
+// pjmedia_srtp_crypto.key.  igdsp_srtp_gcm_protect / igdsp_srtp_gcm_unprotect take the same states for thousands of legs.
+class LegSrtpGcm {
+public:
+    LegSrtpGcm(const uint8_t *key_salt, uint32_t key_bytes, uint32_t roc0 = 0);
+    bool ok;                                 // key_bytes is 16 or 32 and a key was given
+    igdsp_srtp_gcm_state state;
+    igdsp_srtp_rec last;                     // the record of the last packet
+    uint32_t ctl;                            // IGDSP_SRTP_RUN or _BYPASS: what protect() / unprotect() pass
+    void bypass(bool on) { ctl = on ? (uint32_t)IGDSP_SRTP_BYPASS : (uint32_t)IGDSP_SRTP_RUN; }
+    // the output's size, 0 for a packet that is refused (it did not arrive / is not sent), IGDSP_EINVAL for a NULL argument; in == out is allowed
+    int protect(const uint8_t *in, uint32_t size, uint8_t *out, uint32_t out_capacity);
+    int unprotect(const uint8_t *in, uint32_t size, uint8_t *out, uint32_t out_capacity);
+    bool authFailed() const { return (last.flags & IGDSP_SRTP_AUTH_FAIL) != 0; }
+    void reset();                            // roc, s_l and the replay window start over with the next packet; the keys stay
+private:
+    bool resetNext;
+};
+
 // RTCP on one leg, without a context: one igdsp_rtcp_state through igdsp_rtcp_build_packet / igdsp_rtcp_parse_packet and, when a key is
 // given, two SRTCP states (ours to send, the peer's to receive) through igdsp_srtcp_protect_packet / igdsp_srtcp_unprotect_packet: what
 // pjmedia's rtcp session and transport_srtp keep per stream for transport_send_rtcp and transport_rtcp_cb.  igdsp_rtcp_build /
@@ -675,6 +695,15 @@ int   igdsp_host_srtp_protect(void *v, const uint8_t *in, uint32_t size, uint8_t
 int   igdsp_host_srtp_unprotect(void *v, const uint8_t *in, uint32_t size, uint8_t *out, uint32_t out_capacity);
 int   igdsp_host_srtp_rec(void *v, igdsp_srtp_rec *out);
 void  igdsp_host_srtp_reset(void *v);
+// SRTP with AES-GCM on one leg and direction (LegSrtpGcm): igdsp_host_srtp_*'s faces; NULL from _new for a NULL key or a key_bytes that is
+// not 16 or 32
+void *igdsp_host_srtp_gcm_new(const uint8_t *key_salt, uint32_t key_bytes, uint32_t roc0);
+void  igdsp_host_srtp_gcm_free(void *v);
+int   igdsp_host_srtp_gcm_control(void *v, uint32_t ctl);
+int   igdsp_host_srtp_gcm_protect(void *v, const uint8_t *in, uint32_t size, uint8_t *out, uint32_t out_capacity);
+int   igdsp_host_srtp_gcm_unprotect(void *v, const uint8_t *in, uint32_t size, uint8_t *out, uint32_t out_capacity);
+int   igdsp_host_srtp_gcm_rec(void *v, igdsp_srtp_rec *out);
+void  igdsp_host_srtp_gcm_reset(void *v);
 // the spectrum graph without a context (SpectrumGraph): NULL from _new for sizes igdsp_spec_frame rejects; _feed one frame in (1: it
 // computed a spectrum, 0: not, IGDSP_EINVAL for a NULL argument); _real / _iir the two arrays of 512 floats, owned by the handle; _clear
 // is spectClear; _fft_avg is d_fftAvg

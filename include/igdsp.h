@@ -2230,7 +2230,7 @@ int  igdsp_ns_run(igdsp_ctx *ctx, const uint8_t *d_g711 /* [F][C][n] */, const u
  * the same code (csrc/igdsp_srtp.h; independent restatement: tests/srtp_model.py) and give the same bytes, records and states for any
  * split of the frames over launches and at any channel count and position.
  * SCOPE: AES_CM_128_HMAC_SHA1_80 and its _32 tag length, for RTP (SRTCP: the section "RTCP / SRTCP" below).  NOT built: MKI, a non-zero
- * key derivation rate, AES-256, GCM,
+ * key derivation rate, AES-256 in counter mode (RFC 6188; AES-GCM with either key size: the section "SRTP with AES-GCM" below),
  * F8, the NULL cipher, and SDES / DTLS key exchange: the caller brings the 30 bytes of master key and salt that pjmedia keeps in
  * pjmedia_srtp_crypto.key.
  *
@@ -2447,6 +2447,67 @@ int  igdsp_srtcp_unprotect(igdsp_ctx *ctx, const uint8_t *d_ctl /* [F][C], NULL:
                            const uint16_t *d_sizes /* [F][C] */, uint32_t n_channels, uint32_t n_frames, uint32_t pkt_stride,
                            igdsp_srtp_state *d_state /* [C], in and out */, uint8_t *d_out /* [F][C][out_stride] */, uint32_t out_stride,
                            uint16_t *d_sizes_out /* [F][C] */, igdsp_srtp_rec *d_rec /* [F][C] */, void *stream);
+
+/* ---- SRTP with AES-GCM: RFC 7714 protection of the RTP packets, per leg and direction ---------------------------------------------------------
+ * The suites a peer with AEAD support offers ahead of the SHA-1 ones: AEAD_AES_128_GCM (16-byte key, 12-byte salt) and AEAD_AES_256_GCM
+ * (32-byte key, 12-byte salt), both with the 16-byte tag.  igdsp_srtp_gcm_protect / igdsp_srtp_gcm_unprotect stand where
+ * igdsp_srtp_protect / igdsp_srtp_unprotect stand.  Everything not named here is the section "SRTP"'s, word for word: HEADER LENGTH and
+ * its MALFORMED cases, the INDEX estimate, the 64-packet window, OLD / REPLAY, the CONTROL values RUN / BYPASS / RESET, EMPTY, the
+ * counters, the RECORD igdsp_srtp_rec and its flags, in place, "a refused packet gets size 0 and its slot is never written", and the
+ * ARGUMENTS clauses (strides, alignment, range, overlap).  The rule is pinned bit for bit by FIPS-197 and the GCM specification
+ * (tests/golden/srtp_gcm_kat.json holds their known answers and whole packets recorded from OpenSSL); the host entries and the device
+ * entries run the same code (csrc/igdsp_srtp_gcm.h; independent restatement: tests/srtp_gcm_model.py).
+ * SCOPE: RTP only.  NOT built: SRTCP under GCM (RFC 7714 9, 10: a GCM call's RTCP stays on the host), AES_256_CM_HMAC_SHA1_* (RFC 6188),
+ * 8-byte GCM tags, MKI, a key derivation rate, SDES / DTLS key exchange.
+ *
+ * SESSION KEYS.  RFC 3711 4.3.1's AES-CM key derivation with AES of the suite's own key size: label 0 gives the 16 / 32 bytes of k_e,
+ * label 2 the 12 bytes of k_s; there is no k_a.  The 12-byte master salt is used as a 112-bit salt by appending 16 zero bits (RFC 7714
+ * 11).  This clause is UNVERIFIED against RFC 7714's vectors (section 16), which were not at hand; the AES-CM keystream under it is
+ * held against OpenSSL's EVP_aes_128_ctr / EVP_aes_256_ctr.  H = AES_k_e(0^128) is computed at derive time.
+ * IV, 12 bytes: k_s xor (00 00 || SSRC || v || SEQ), big-endian, the packet's own SSRC, v the estimated rollover counter.
+ * COUNTER BLOCKS.  J0 = IV || 00 00 00 01; payload block j (from 0) is XORed with AES_k_e(IV || be32(j + 2)), from byte h on.  An empty
+ * payload is legal.
+ * TAG, 16 bytes, appended: GHASH_H(A, C) xor AES_k_e(J0).  A is the header bytes [0, h), an ED-137 extension included, zero-padded to 16;
+ * C the encrypted payload [h, end), zero-padded; the last block the two 64-bit bit lengths.  GHASH in GCM's convention: a block is a
+ * 128-bit big-endian number, bit 0 the most significant, reduction by 0xE1 || 0^120.
+ * PROTECT.  size_out = size + 16, MALFORMED when that passes the output slot or capacity.  No replay test.
+ * UNPROTECT.  MALFORMED when size < h + 16.  The tag is computed over the ciphertext and all 16 bytes are compared before anything is
+ * decrypted or stored; a mismatch is AUTH_FAIL (a flipped header bit too: the header is the AAD).  size_out = size - 16.
+ * FAIL CLOSED, both ways.  The GCM entries accept a state only when its first word is IGDSP_SRTP_GCM_TAG | 16 or | 32; an
+ * igdsp_srtp_state, an SRTCP state or random bytes give NO_KEY.  A GCM state handed to the SRTP / SRTCP entries is NO_KEY by their rule.
+ * STATE, 320 bytes, 16-byte aligned, from igdsp_srtp_gcm_derive: the first ten words are igdsp_srtp_state's (tag, roc, s_l / have_s_l,
+ * reserved, window, four counters), then the key schedule of k_e (AES-128 uses 44 of the 60 words), k_s and H.  Legs of both key sizes
+ * may stand side by side in one launch.
+ * Host only, no GPU: igdsp_srtp_gcm_derive (key_salt: key_bytes + 12 bytes; key_bytes 16 or 32, anything else IGDSP_EINVAL);
+ * igdsp_srtp_gcm_protect_packet / igdsp_srtp_gcm_unprotect_packet: one packet by the same rule, in == out allowed. */
+#define IGDSP_SRTP_GCM_TAG    0x53524700u /* igdsp_srtp_gcm_state.tag, | key_bytes (16 or 32)         */
+#define IGDSP_SRTP_GCM_TAG_LEN 16
+typedef struct igdsp_srtp_gcm_state {
+    uint32_t tag;                   /* IGDSP_SRTP_GCM_TAG | key_bytes                            */
+    uint32_t roc;
+    uint16_t s_l, have_s_l;
+    uint32_t reserved;
+    uint64_t window;                /* bit i: index top - i was accepted (unprotect)             */
+    uint32_t n_ok, n_auth_fail, n_replay, n_malformed;
+    uint32_t rk[60];                /* AES encryption key schedule of k_e: 44 words (128), 60 (256) */
+    uint8_t  salt[12];              /* k_s                                                       */
+    uint32_t pad;
+    uint8_t  h[16];                 /* H = AES_k_e(0^128)                                        */
+    uint32_t reserved2[2];
+} igdsp_srtp_gcm_state;             /* 320 bytes */
+int  igdsp_srtp_gcm_derive(const uint8_t *key_salt /* [key_bytes + 12] */, uint32_t key_bytes /* 16 | 32 */, uint32_t roc0, igdsp_srtp_gcm_state *out);
+int  igdsp_srtp_gcm_protect_packet(igdsp_srtp_gcm_state *st, uint32_t ctl, const uint8_t *in, uint32_t size, uint8_t *out, uint32_t out_capacity,
+                                   uint32_t *size_out, igdsp_srtp_rec *rec);
+int  igdsp_srtp_gcm_unprotect_packet(igdsp_srtp_gcm_state *st, uint32_t ctl, const uint8_t *in, uint32_t size, uint8_t *out, uint32_t out_capacity,
+                                     uint32_t *size_out, igdsp_srtp_rec *rec);
+int  igdsp_srtp_gcm_protect(igdsp_ctx *ctx, const uint8_t *d_ctl /* [F][C], NULL: RUN */, const uint8_t *d_packets /* [F][C][pkt_stride] */,
+                            const uint16_t *d_sizes /* [F][C] */, uint32_t n_channels, uint32_t n_frames, uint32_t pkt_stride,
+                            igdsp_srtp_gcm_state *d_state /* [C], in and out */, uint8_t *d_out /* [F][C][out_stride] */, uint32_t out_stride,
+                            uint16_t *d_sizes_out /* [F][C] */, igdsp_srtp_rec *d_rec /* [F][C] */, void *stream);
+int  igdsp_srtp_gcm_unprotect(igdsp_ctx *ctx, const uint8_t *d_ctl /* [F][C], NULL: RUN */, const uint8_t *d_packets /* [F][C][pkt_stride] */,
+                              const uint16_t *d_sizes /* [F][C] */, uint32_t n_channels, uint32_t n_frames, uint32_t pkt_stride,
+                              igdsp_srtp_gcm_state *d_state /* [C], in and out */, uint8_t *d_out /* [F][C][out_stride] */, uint32_t out_stride,
+                              uint16_t *d_sizes_out /* [F][C] */, igdsp_srtp_rec *d_rec /* [F][C] */, void *stream);
 
 /* ---- synthetic input generators (device side; SURVEY 8(d) definitions) ---------
  * D-uniform: byte k of global byte index g is
